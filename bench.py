@@ -10,8 +10,10 @@ is bracketed by barrier + synchronize and the MAX over ranks is reported ("weak"
     python bench.py --gpus 1 --steps 10 --warmup 2
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     # + DIR/logits.npy of the last timed step
 
-Rank 0 prints ONE JSON line.  Extra objects:
+--steps is the number of timed steps of every leg (the headline and the side configurations), each after --warmup untimed
+ones; `ms_per_step` is one timed step of the headline.  Rank 0 prints ONE JSON line.  Extra objects:
   roofline     -- the dominant kernel family (fp32 MFMA GEMM / implicit-GEMM conv): algorithmic
                   FLOPs / HIP-event time of its launches inside the timed region, against the
                   157.3 TFLOP/s fp32 matrix peak of gfx950.
@@ -549,7 +551,7 @@ def run_leg(ctx, spec, model=None):
     timed_out = out                                            # (a training leg's loss is reported from the last TIMED step: the steps further
                                                                #  down that skip the collective let the replicas' weights diverge)
     res = {"elapsed": elapsed, "ms_per_step": 1e3 * elapsed / steps, "B": B, "L": L, "T": T, "cfg": cfg, "x": x, "amask": amask,
-           "family": family, "prof": prof if do_prof else {}, "gold_wave": gold_wave, "gold_logits": gold_logits,
+           "timed_out": timed_out, "family": family, "prof": prof if do_prof else {}, "gold_wave": gold_wave, "gold_logits": gold_logits,
            "kernel_launches_per_step": {k: v["kernels"] // steps for k, v in prof.items() if v["kernels"]},
            "op_calls_per_step": {k: v["issued"] // steps for k, v in prof.items() if v["issued"]}}
 
@@ -728,6 +730,26 @@ def measure_alt(ctx, model, x, amask, model_name, B, L, steps, warmup, prec, ref
     return o
 
 
+DUMP_MAX_ELEMS = 8 << 20          # --dump-outputs: at most 32 MiB of float32 per array
+
+
+def dump_outputs(out_dir, mode, timed_out):
+    """--dump-outputs DIR: what a caller of the timed path received from its last timed step, as float32 .npy files in DIR -- the
+    logits (B, T, vocab) of a forward leg, the loss of a training step.  The inputs are seeded, so two builds run with the same
+    arguments can be compared file for file.  An array above DUMP_MAX_ELEMS is replaced by a fixed, seeded sample of its elements
+    (flat; the same positions on every run with the same shape)."""
+    import numpy as np
+    name = "logits" if mode == "forward" else "loss"
+    a = np.asarray(timed_out.detach().float().cpu().numpy(), np.float32)
+    if a.size > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(0).integers(0, a.size, DUMP_MAX_ELEMS))
+        a = a.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, name + ".npy")
+    np.save(path, a)
+    return path
+
+
 COMPACT_LIMIT = 4096              # the driver keeps 8 KB of stdout; the line it parses must stay far below that
 ROOF_KEYS = ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_over_algorithmic", "clock_mhz_under_load",
              "frac_clock_adjusted")
@@ -871,6 +893,9 @@ def main():
     ap.add_argument("--backend", default=os.environ.get("W2V2_BENCH_BACKEND", "nccl"),
                     help="process-group backend: nccl (= RCCL, the default and the only one a result may be quoted on); gloo exists so the "
                          "N > 1 code path can be exercised by two processes on ONE GPU, which RCCL refuses (tests/test_dist_gpu.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0: logits of a forward, loss of a training "
+                         "step) as DIR/<name>.npy in float32, for comparing two builds output for output")
     args = ap.parse_args()
 
     if args.cpu_baseline_only:
@@ -926,6 +951,8 @@ def main():
     spec = {"model": args.model, "precision": args.precision, "mode": args.mode, "B": args.batch, "L": args.samples,
             "steps": args.steps, "warmup": args.warmup, "profile": not args.no_profile}
     res, model, out = run_leg(ctx, spec)
+    if args.dump_outputs and rank == 0:
+        print(f"bench: outputs of the last timed step -> {dump_outputs(args.dump_outputs, args.mode, res['timed_out'])}", file=sys.stderr)
     cfg, B, L, T, x, amask = res["cfg"], res["B"], res["L"], res["T"], res["x"], res["amask"]
     elapsed, prof, logit_err, gold_wave = res["elapsed"], res["prof"], res.get("logit_err"), res["gold_wave"]
     gemm_family = res["family"]
@@ -1009,7 +1036,9 @@ def main():
         del model, out, x, amask, res
         gc.collect()
         k = max(1, args.side_shrink)
-        side_steps, side_warm = (10, 2) if k == 1 else (3, 1)      # (the shrunken legs exist for the multi-process tests: keep them short)
+        # the side legs time --steps steps after --warmup ones, like the headline (the shrunken legs exist for the multi-process tests:
+        # at most 3 + 1 there, to keep them short)
+        side_steps, side_warm = (args.steps, args.warmup) if k == 1 else (min(3, args.steps), min(1, args.warmup))
         legs = [("configs2_train_bf16", {"model": "base", "precision": "bf16", "mode": "train", "B": 32 // k, "L": 246000, "steps": side_steps, "warmup": side_warm},
                  "BASELINE configs[2] per-GPU shard: wav2vec2-base CTC fine-tune step, bf16 contractions (conv stack frozen, dropout 0.1, "
                  "spec-augment, Adam, fp32 variables / optimizer state), 32 x 246000 per GPU (global batch 256 at 8 GPUs)"),

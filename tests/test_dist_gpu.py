@@ -185,33 +185,57 @@ def test_bench_two_ranks_report_every_baseline_config_with_the_collective():
     assert js["configs2_train_bf16"]["allreduce"]["payload_bytes"] == 4 * (90195104 + 768)      # 360.8 MB fp32 for base
 
 
-def test_bench_eight_ranks_over_gloo_is_the_drivers_command():
-    """The driver's own 8-GPU command line (`bench.py --gpus 8`) with eight processes on the one GPU over gloo:
-    the world size the scaling run uses, the base model's 14 gradient buckets all-reduced among eight ranks inside the timed steps,
-    the loss divisor 8 x the per-rank batch -- and the ONE compact stdout line must carry the measured collective of the training
-    leg (`allreduce.exposed_ms`, `standalone_ms`, `busbw_GBps`).  Only configs[2] runs as a side leg here (`--side-legs`): gloo stages
-    every all-reduce through host memory, and the large model's 1.25-GB payload among eight processes takes minutes per step (the
-    two-rank test above runs all three legs).  No number of this run is quotable (one GPU, host-staged collectives) -- it exists so
-    that the driver's first real `--gpus 8` run cannot fail on plumbing or on parsing."""
+def test_bench_four_ranks_over_gloo_is_the_drivers_command():
+    """The driver's multi-GPU command line (`bench.py --gpus N`) with four processes on the one GPU over gloo:
+    the base model's 14 gradient buckets all-reduced among more than two ranks inside the timed steps, the loss divisor N x the
+    per-rank batch -- and the ONE compact stdout line must carry the measured collective of the training leg (`allreduce.exposed_ms`,
+    `standalone_ms`, `busbw_GBps`).  Four ranks, not the scaling run's eight: with this test's own process, no more than six processes
+    may hold the one shared GPU at a time (the eight-rank launch command itself is pinned on CPU, test_host_cpu.py, and the eight-rank
+    gloo reduction in test_dist_cpu.py).  Only configs[2] runs as a side leg here (`--side-legs`): gloo stages every all-reduce through
+    host memory, and the large model's 1.25-GB payload takes minutes per step (the two-rank test above runs all three legs).  No number
+    of this run is quotable (one GPU, host-staged collectives) -- it exists so that the driver's first real `--gpus 8` run cannot fail
+    on plumbing or on parsing."""
     import subprocess
+    world = 4
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None), env.pop("RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--steps", "1", "--warmup", "1",
            "--side-shrink", "16", "--side-legs", "configs2_train_bf16", "--no-cpu-baseline", "--no-alt", "--no-profile"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     compact, js = _bench_objects(r)
-    assert compact["n_gpus"] == 8 and compact["config"]["global_batch"] == 256 and compact["scaling"] == "weak" and compact["value"] > 0
+    assert compact["n_gpus"] == world and compact["config"]["global_batch"] == world * 32 and compact["scaling"] == "weak" and compact["value"] > 0
     ar = compact["configs2_train_bf16"]["allreduce"]
     assert "exposed_ms" in ar and ar["standalone_ms"] > 0 and ar["busbw_GBps"] > 0, compact["configs2_train_bf16"]
     assert "configs3_large_fwd_f32" not in compact and "configs4_large_train_bf16" not in compact
-    assert js["n_gpus"] == 8 and js["comm"]["world_size"] == 8 and js["config"]["global_batch"] == 256 and js["scaling"] == "weak"
+    assert js["n_gpus"] == world and js["comm"]["world_size"] == world and js["config"]["global_batch"] == world * 32 and js["scaling"] == "weak"
     leg = js["configs2_train_bf16"]
     assert "error" not in leg, leg
     ar = leg["allreduce"]
-    assert leg["n_gpus"] == 8 and leg["global_batch"] == 8 * 2 and ar["world_size"] == 8 and ar["buckets"] == 14 and ar["collectives_per_step"] >= 14
+    assert leg["n_gpus"] == world and leg["global_batch"] == world * 2 and ar["world_size"] == world and ar["buckets"] == 14
+    assert ar["collectives_per_step"] >= 14
     assert ar["standalone_ms"] > 0 and np.isfinite(leg["final_loss"]) and ar["engine"].startswith("torch.distributed")
     assert ar["payload_bytes"] == 4 * (90195104 + 768)
+
+
+def test_bench_dump_outputs_same_inputs_same_logits(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the logits of the last timed forward as DIR/logits.npy (float32, (B, T, vocab)); the
+    inputs are seeded, so two runs with the same workload -- here at 2 and at 3 timed steps -- dump the same logits bit for bit
+    (the forward is bitwise reproducible), and `steps` / `ms_per_step` on the line are those of the run."""
+    import subprocess
+    dumps = []
+    for steps in (2, 3):
+        out_dir = tmp_path / f"steps{steps}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--batch", "2",
+               "--samples", "46797", "--no-cpu-baseline", "--no-alt", "--no-side", "--no-profile", "--dump-outputs", str(out_dir)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        compact, _ = _bench_objects(r)
+        assert compact["steps"] == steps and compact["ms_per_step"] > 0
+        assert sorted(os.listdir(out_dir)) == ["logits.npy"]
+        dumps.append(np.load(out_dir / "logits.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (2, 145, 32) and np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 # ---------------------------------------------------------------- the library's own RCCL collective (csrc/comm.hip) ----------

@@ -661,6 +661,33 @@ def test_bench_stdout_line_is_compact_and_parseable():
     assert len(line) < 4096 and json.loads(line)["roofline"]["frac"] and json.loads(line)["cpu_baseline"]["value"] == 1.0
 
 
+def test_bench_dump_outputs_are_float32_within_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last timed step's result as DIR/<name>.npy in float32 -- logits of a forward leg whole, the loss
+    of a training step; an array above the budget becomes a seeded sample of the same positions on every run (<= 64 MB in all)."""
+    import importlib.util
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test4", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    logits = torch.from_numpy(V.hash_normal("bench/dump", 2 * 49 * 32, 0).reshape(2, 49, 32))
+    path = bench.dump_outputs(str(tmp_path / "a"), "forward", logits)
+    assert path == str(tmp_path / "a" / "logits.npy")
+    got = np.load(path)
+    assert got.dtype == np.float32 and got.shape == (2, 49, 32) and np.array_equal(got, logits.numpy())
+    got = np.load(bench.dump_outputs(str(tmp_path / "a"), "train", torch.tensor(3.25, dtype=torch.float64)))
+    assert got.dtype == np.float32 and float(got) == 3.25
+    # over the budget: a sample, identical from run to run, within 64 MB
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    big = torch.arange(50000, dtype=torch.float32).reshape(10, 5000)
+    one = np.load(bench.dump_outputs(str(tmp_path / "b"), "forward", big))
+    two = np.load(bench.dump_outputs(str(tmp_path / "c"), "forward", big))
+    assert one.dtype == np.float32 and one.shape == (1000,) and np.array_equal(one, two)
+    assert np.all(np.diff(one) >= 0) and len(np.unique(one)) > 900
+    monkeypatch.undo()
+    assert bench.DUMP_MAX_ELEMS * 4 <= 64 * 10 ** 6
+
+
 def test_grouped_tile_order_is_a_bijection():
     """csrc/common.h::grouped_tile (round 6: the order in which an XCD's run walks the output tiles of the wide GEMMs -- groups of gm
     tile rows, column-major inside a group).  The same integer arithmetic restated here must visit every tile exactly once for any
