@@ -416,10 +416,17 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 
 thread_local int tl_precision = 0;
+thread_local int tl_ring = -1;      // w2v2_op_gemm_variant: forces the ring route below for one call (-1: by shape)
+
+// The LDS-ring kernels (gemm_f32_sw.hip) for the shapes that took gemm_f32_dma_kernel's 256 x 128 x 16 and 128 x 128 x 32
+// instances: 0 = those instances, 1 = the ring kernels with one tile per block, 2 = the ring kernels with a persistent grid.
+constexpr int RING_DEFAULT = 2;
+int ring_route() { return tl_ring >= 0 ? tl_ring : tune_int("W2V2_GEMM_RING", RING_DEFAULT); }
 
 }  // namespace
 
 void gemm_set_precision(int mode) { tl_precision = mode; }
+void gemm_f32_force_ring(int route) { tl_ring = route; }
 int gemm_get_precision() { return tl_precision; }
 
 int launch_gemm(Profiler* prof, const float* A, int64_t lda, int64_t strideA, const float* B,
@@ -448,6 +455,7 @@ int launch_gemm_ex(Profiler* prof, const float* A, int64_t lda, int64_t strideA,
     ProfScope ps(prof, FAM_GEMM, 2.0 * M * (double)N * K * nbatch,
                  4.0 * nbatch * ((double)M * K + (double)M * N) + 4.0 * (double)K * N, s);
     int cfg = forced_cfg();
+    const bool by_shape = cfg < 0;      // (a forced W2V2_GEMM_CFG names a gemm_f32_dma_kernel / gemm_f32_kernel instance)
     // default: the LDS-DMA 128x128 kernel with 8 waves (2x4, each wave 64x32), 2 blocks per CU = 4 waves
     // per SIMD, whenever the shape allows 16-byte global accesses (every GEMM of the model does).
     // Measured on MI355X, B=32 base shapes (profiles/r01_gemm_tile_study.md): this 118-129 TF; the same
@@ -500,7 +508,14 @@ int launch_gemm_ex(Profiler* prof, const float* A, int64_t lda, int64_t strideA,
             if (main_rows > 0 && main_rows < M) {
                 GemmArgs h = g;
                 h.M = (int)main_rows;
-                if (int e = launch_dma<2, 4, 2>(h, 1, s)) return e;
+                const int ring = by_shape ? ring_route() : 0;
+                if (ring && strideB == 0 && gemm_f32_ring_ok(1, A, lda, strideA, B, ldb, strideB, h.M, N, K)) {
+                    if (int e = launch_gemm_f32_ring(1, ring == 2, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, bias, residual,
+                                                     h.M, N, K, 1, act, s))
+                        return e;
+                } else if (int e = launch_dma<2, 4, 2>(h, 1, s)) {
+                    return e;
+                }
                 GemmArgs t = g;
                 t.A = g.A + main_rows * lda;
                 t.C = g.C + main_rows * ldc;
@@ -525,7 +540,19 @@ int launch_gemm_ex(Profiler* prof, const float* A, int64_t lda, int64_t strideA,
     const int wide_min = tune_int("W2V2_GEMM_WIDE", 1536);      // fewest 256 x 128 tiles that take the wide kernel (0: never)
     if (cfg == 7 && fast && wide_min > 0 && N % 128 == 0) {
         const int64_t tm256 = (M + 255) / 256, tiles256 = tm256 * (N / 128) * nbatch;
-        if (tiles256 >= wide_min && (tm256 * 256 - M) * 40 <= M) return launch_dma<4, 2, 2, 16, 256, 128>(g, nbatch, s);
+        if (tiles256 >= wide_min && (tm256 * 256 - M) * 40 <= M) {
+            const int ring = by_shape ? ring_route() : 0;
+            if (ring && strideB == 0 && gemm_f32_ring_ok(0, A, lda, strideA, B, ldb, strideB, M, N, K))
+                return launch_gemm_f32_ring(0, ring == 2, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, bias, residual, M, N, K,
+                                            nbatch, act, s);
+            return launch_dma<4, 2, 2, 16, 256, 128>(g, nbatch, s);
+        }
+    }
+    if (cfg == 7 && fast) {
+        const int ring = by_shape ? ring_route() : 0;
+        if (ring && strideB == 0 && gemm_f32_ring_ok(1, A, lda, strideA, B, ldb, strideB, M, N, K))
+            return launch_gemm_f32_ring(1, ring == 2, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, bias, residual, M, N, K,
+                                        nbatch, act, s);
     }
     switch (cfg) {
         case 16: if (fast) return launch_dma<2, 2, 2, 32, 64, 64>(g, nbatch, s); return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);

@@ -1080,6 +1080,16 @@ int w2v2_op_gemm(const float* A, int64_t lda, int64_t strideA, const float* B, i
     return launch_gemm(nullptr, A, lda, strideA, B, ldb, C, ldc, strideC, bias, residual, M, N, K, nbatch, act,
                        reinterpret_cast<hipStream_t>(stream));
 }
+int w2v2_op_gemm_variant(const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb, float* C,
+                         int64_t ldc, int64_t strideC, const float* bias, const float* residual, int32_t M,
+                         int32_t N, int32_t K, int32_t nbatch, int32_t act, int32_t variant, void* stream) {
+    W2V2_REQUIRE(variant >= -1 && variant <= 2, "op_gemm_variant: variant %d (-1 by shape, 0 double buffer, 1 ring, 2 persistent ring)", variant);
+    gemm_f32_force_ring(variant);
+    const int e = launch_gemm(nullptr, A, lda, strideA, B, ldb, C, ldc, strideC, bias, residual, M, N, K, nbatch, act,
+                              reinterpret_cast<hipStream_t>(stream));
+    gemm_f32_force_ring(-1);
+    return e;
+}
 int w2v2_op_set_precision(int32_t mode) {
     W2V2_REQUIRE(mode >= W2V2_PRECISION_FP32 && mode <= W2V2_PRECISION_F16X2, "op_set_precision: unknown mode %d", mode);
     gemm_set_precision(mode);

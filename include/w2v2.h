@@ -354,6 +354,14 @@ int w2v2_op_gemm(const float* A_dev, int64_t lda, int64_t strideA,
                  float* C_dev, int64_t ldc, int64_t strideC,
                  const float* bias_dev, const float* residual_dev,
                  int32_t M, int32_t N, int32_t K, int32_t nbatch, int32_t act, void* stream);
+/* w2v2_op_gemm with the fp32 kernel family pinned, for bit-for-bit comparisons: variant -1 by shape (= w2v2_op_gemm),
+ * 0 the double-buffered LDS-DMA kernels only, 1 the LDS-ring kernels where the shape routes to them, 2 the same with a
+ * persistent grid (csrc/gemm_f32_sw.hip). */
+int w2v2_op_gemm_variant(const float* A_dev, int64_t lda, int64_t strideA,
+                         const float* B_dev, int64_t ldb,
+                         float* C_dev, int64_t ldc, int64_t strideC,
+                         const float* bias_dev, const float* residual_dev,
+                         int32_t M, int32_t N, int32_t K, int32_t nbatch, int32_t act, int32_t variant, void* stream);
 
 /* Precision of the w2v2_op_* calls issued by the calling thread from now on (per-kernel tests of the bf16
  * mode); model-level calls take the model's own setting (w2v2_set_precision) and restore this one. */
