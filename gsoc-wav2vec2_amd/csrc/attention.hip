@@ -57,6 +57,7 @@ struct AttnArgs {
     float* ctx;                 // (B, T, H)
     int B, T, H, heads;
     float scale;
+    const SegTile* tiles;       // SEG: one entry per block of queries of a packed utterance (B = 1, T = stream frames)
 };
 
 __device__ __forceinline__ float f4get(const float4& v, int e) {
@@ -74,7 +75,9 @@ __device__ __forceinline__ void dma16(const float* g, float* l) {
 // tile.  The DMA writes LDS lane-linearly, so the K image (read as 16-byte column slices by 16 rows at a
 // time) is XOR-swizzled on the global SOURCE address and again on the read; V is read row-contiguously
 // and needs no swizzle.
-template <int DH, int NW, bool TRAIN = false>
+// SEG: block x = tile `tiles[x]` of a packed utterance; queries, keys and values are that utterance's frames only (a B = 1 run of
+// it alone: the key clamp and the tail mask stop at its last frame, so no tile reads past it)
+template <int DH, int NW, bool TRAIN = false, bool SEG = false>
 __global__ __launch_bounds__(NW * 64) void attention_kernel(AttnArgs a, AttnTrain tr) {
     constexpr int JD = DH / 8;            // 8-wide d blocks for the QK^T contraction
     constexpr int DT = DH / 32;           // 32-wide d tiles of the output
@@ -89,15 +92,23 @@ __global__ __launch_bounds__(NW * 64) void attention_kernel(AttnArgs a, AttnTrai
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // (an SGPR: the DMA's LDS address is then provably wave-uniform)
     const int li = lane & 31, lh = lane >> 5;
     const int head = blockIdx.y, b = blockIdx.z;
-    const int q0 = (blockIdx.x * NW + wave) * 32;
+    int q0 = (blockIdx.x * NW + wave) * 32;
+    int T = a.T;                          // frames of the sequence this block attends within
+    int64_t row0 = (int64_t)b * a.T;      // its first row in qkv / ctx
+    if constexpr (SEG) {
+        const SegTile st = a.tiles[blockIdx.x];
+        q0 = st.t0 + wave * 32;
+        T = st.nf;
+        row0 = st.f0;
+    }
     const int64_t ld = 3 * (int64_t)a.H;
-    const float* __restrict__ base = a.qkv + (int64_t)b * a.T * ld + head * DH;
-    const int flen = a.frame_len ? a.frame_len[b] : a.T;
+    const float* __restrict__ base = a.qkv + row0 * ld + head * DH;
+    const int flen = (!SEG && a.frame_len) ? a.frame_len[b] : T;
 
     // ---- Q fragment (B operand of S^T): lane = (query li, d half lh), pre-scaled (encoder.py:28) ----
     float4 qf[JD];
     {
-        const int qr = min(q0 + li, a.T - 1);
+        const int qr = min(q0 + li, T - 1);
         const float* qp = base + (int64_t)qr * ld + 4 * lh;
 #pragma unroll
         for (int j = 0; j < JD; ++j) {
@@ -122,7 +133,7 @@ __global__ __launch_bounds__(NW * 64) void attention_kernel(AttnArgs a, AttnTrai
             const bool isv = p >= NP;
             const int pp = isv ? p - NP : p;
             const int r = pp * RPP + p_row;                       // row inside the tile
-            const int key = min(k0 + r, a.T - 1);                 // clamp: tail rows are masked / weighted 0
+            const int key = min(k0 + r, T - 1);                   // clamp: tail rows are masked / weighted 0
             const int slot = isv ? p_slot : (p_slot ^ ((r >> SH) & SWM));
             dma16(base + (int64_t)key * ld + (isv ? 2 : 1) * a.H + slot * 4, S + p * 256);
         }
@@ -136,9 +147,9 @@ __global__ __launch_bounds__(NW * 64) void attention_kernel(AttnArgs a, AttnTrai
     float m_run = -INFINITY, l_run = 0.f;
     // dropout hash inputs hoisted out of the tile loop: element index = ((b h + head) T + q) T + key, modulo 2^32
     const uint32_t drop_key = TRAIN ? dropout_key(tr.seed, tr.stream) : 0u, drop_thr = TRAIN ? dropout_threshold(tr.p) : 0u;
-    const uint32_t drop_row = (uint32_t)((((uint64_t)b * a.heads + head) * a.T + (uint64_t)min(q0 + li, a.T - 1)) * attention_drop_stride(a.T));
+    const uint32_t drop_row = (uint32_t)((((uint64_t)b * a.heads + head) * T + (uint64_t)min(q0 + li, T - 1)) * attention_drop_stride(T));
 
-    const int ntiles = (a.T + KT - 1) / KT;
+    const int ntiles = (T + KT - 1) / KT;
     issue_tile(0, 0);
     __syncthreads();                       // carries the vmcnt(0) that retires the DMA
 
@@ -171,7 +182,7 @@ __global__ __launch_bounds__(NW * 64) void attention_kernel(AttnArgs a, AttnTrai
         // ---- mask + online softmax (lane owns query li; keys (r&3) + 8 (r>>2) + 4 lh) ----
         // Per-score VALU work competes with the other waves' MFMA issue, so it is kept minimal: masking only on tiles
         // that touch the valid-length / T boundary (wave-uniform branch), dropout hash inputs hoisted.
-        if (k0 + KT > min(flen, a.T)) {
+        if (k0 + KT > min(flen, T)) {
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -179,7 +190,7 @@ __global__ __launch_bounds__(NW * 64) void attention_kernel(AttnArgs a, AttnTrai
                     const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     float v = s[kt][r];
                     v = key >= flen ? v - 10000.0f : v;       // (1 - mask) * -10000, encoder.py:256-257
-                    v = key >= a.T ? -INFINITY : v;           // tile padding: not a key at all
+                    v = key >= T ? -INFINITY : v;             // tile padding: not a key at all
                     s[kt][r] = v;
                 }
         }
@@ -236,10 +247,10 @@ __global__ __launch_bounds__(NW * 64) void attention_kernel(AttnArgs a, AttnTrai
 
     // ---- normalise and store: O^T rows are d = 32 dt + (r&3) + 8 (r>>2) + 4 lh, column = query ----
     const int q = q0 + li;
-    if (TRAIN && q < a.T && lh == 0) tr.lse[((int64_t)b * a.heads + head) * a.T + q] = m_run + logf(l_run);
-    if (q < a.T) {
+    if (TRAIN && q < T && lh == 0) tr.lse[((int64_t)b * a.heads + head) * T + q] = m_run + logf(l_run);
+    if (q < T) {
         const float inv = ((TRAIN && tr.p > 0.f) ? 1.0f / (1.0f - tr.p) : 1.0f) / l_run;
-        float* op = a.ctx + ((int64_t)b * a.T + q) * a.H + head * DH + 4 * lh;
+        float* op = a.ctx + (row0 + q) * a.H + head * DH + 4 * lh;
 #pragma unroll
         for (int d = 0; d < DT; ++d)
 #pragma unroll
@@ -262,6 +273,24 @@ int launch_attn_nw(const AttnArgs& a, hipStream_t s) {
     const int qb = NW * 32;
     dim3 grid((a.T + qb - 1) / qb, a.heads, a.B), block(NW * 64);
     W2V2_LAUNCH((attention_kernel<DH, NW>), grid, block, lds, s, a, AttnTrain{0.f, 0, 0, nullptr});
+    W2V2_HIP_CHECK(hipGetLastError());
+    return W2V2_OK;
+}
+
+// packed forward: a fixed 8 waves (256 queries) per tile -- the tile table is built by the host before the launch
+constexpr int SEG_NW = 8;
+
+template <int DH>
+int launch_attn_seg(const AttnArgs& a, int ntiles, hipStream_t s) {
+    const size_t lds = (size_t)2 * 2 * KT * DH * sizeof(float);
+    static std::atomic<bool> attr_set{false};
+    if (!attr_set) {
+        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<DH, SEG_NW, false, true>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_set = true;
+    }
+    dim3 grid(ntiles, a.heads, 1), block(SEG_NW * 64);
+    W2V2_LAUNCH((attention_kernel<DH, SEG_NW, false, true>), grid, block, lds, s, a, AttnTrain{0.f, 0, 0, nullptr});
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }
@@ -644,6 +673,25 @@ int launch_attn_bwd(const AttnBwdArgs& a, const AttnTrain& tr, const float* ctx,
 }
 
 }  // namespace
+
+int attention_packed_rows(int) { return SEG_NW * 32; }
+
+int launch_attention_packed(Profiler* prof, const float* qkv, float* ctx, const SegTile* tiles, int ntiles, int64_t frames,
+                            double sum_nf2, int H, int heads, hipStream_t s) {
+    W2V2_REQUIRE(qkv && ctx && tiles, "attention_packed: null operand");
+    W2V2_REQUIRE(ntiles > 0 && frames > 0 && frames < INT32_MAX && heads > 0 && H % heads == 0, "attention_packed: bad sizes");
+    const int dh = H / heads;
+    ProfScope ps(prof, FAM_ATTENTION, 4.0 * heads * sum_nf2 * dh, 4.0 * (double)frames * 4.0 * H, s);
+    AttnArgs a{qkv, nullptr, ctx, 1, (int)frames, H, heads, 1.0f / sqrtf((float)dh), tiles};
+    switch (dh) {
+        case 32: return launch_attn_seg<32>(a, ntiles, s);
+        case 64: return launch_attn_seg<64>(a, ntiles, s);
+        case 128: return launch_attn_seg<128>(a, ntiles, s);
+        default:
+            set_error("attention_packed: head size %d unsupported (32, 64, 128)", dh);
+            return W2V2_EINVAL;
+    }
+}
 
 int launch_attention(Profiler* prof, const float* qkv, const int32_t* frame_len, float* ctx, int B,
                      int T, int H, int heads, hipStream_t s) {

@@ -287,7 +287,36 @@ int launch_layer_norm_x(Profiler* prof, const float* x, float* y, const float* g
                         int C, float eps, int act, uint16_t* y16 /* optional bf16 shadow of y */, hipStream_t s,
                         const PlaneOut* planes = nullptr /* optional planes of y (precision modes bf16x3 / f16x2; C % 4 == 0) */);
 
+// ---- packed variable-length forward (w2v2_forward_packed) --------------------------------------------------------------
+// The utterances sit back to back in one stream.  Utterance i starts at stream sample s0, a multiple of the alignment unit
+// (a multiple of the conv stack's total stride and of conv0's stride x its stats chunk), so its frames at every conv layer
+// start at s0 / (that layer's cumulative stride) and its conv0 rows at a chunk boundary.  Its span, [s0, next s0), holds its
+// samples and then zeros.
+struct PackSeg {
+    int64_t s0, len, src0;        // first stream sample, samples, offset in the caller's dense concatenation
+    int32_t f0, nf, out0, pad;    // first stream frame, frames (w2v2_num_frames(len)), first row of the caller's output
+};
+// one tile of an utterance's frames: rows [t0, t0 + tile rows) of the nf frames that start at stream frame f0
+struct SegTile {
+    int32_t f0, nf, t0, pad;
+};
+// index of the span that holds stream sample `pos` (spans tile the stream; segs sorted by s0)
+__device__ __forceinline__ int pack_seg_of_sample(const PackSeg* segs, int n, int64_t pos) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (segs[mid].s0 <= pos) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
 int64_t conv0_ws_floats(int B, int64_t L, int K, int stride, int C);
+int conv0_chunk_frames();     // conv0 rows per statistics chunk
+// group-norm conv0 over a packed stream of L samples: statistics per utterance over exactly its rows (no padding, no
+// neighbour), applied with that utterance's scale and shift.  ws: conv0_ws_floats(1, L, ...); scale_shift: (nseg, 2, C).
+int launch_conv0_packed(Profiler* prof, const float* wave, const float* kernel, const float* bias, const float* gamma,
+                        const float* beta, float* out, float* ws, float* scale_shift, int64_t L, int K, int stride, int C,
+                        float eps, int act, const PackSeg* segs, int nseg, hipStream_t s);
 int launch_conv0(Profiler* prof, const float* wave, const float* kernel, const float* bias,
                  const float* gamma, const float* beta, float* out, float* ws, int B, int64_t L,
                  int K, int stride, int C, float eps, int norm_mode, int act, hipStream_t s);
@@ -330,6 +359,20 @@ int launch_pos_conv_dw_bf16(Profiler* prof, const float* xz, const float* dc, fl
 
 int launch_attention(Profiler* prof, const float* qkv, const int32_t* frame_len, float* ctx, int B,
                      int T, int H, int heads, hipStream_t s);
+
+// packed forward, fp32: the positional conv over tiles of 128 frames (pos_conv_packed_rows()), each utterance zero-padded at its
+// own edges; attention over tiles of attention_packed_rows() queries, keys restricted to the tile's utterance.  x / y and
+// qkv / ctx are (frames, H) / (frames, 3H) stream buffers; frames and sum_nf2 (sum of squared utterance frames) size the profile.
+int pos_conv_packed_rows();
+int launch_pos_conv_packed(Profiler* prof, const float* x, const float* wg, const float* bias, float* y, const SegTile* tiles,
+                           int ntiles, int64_t frames, int H, int K, int groups, int act, hipStream_t s);
+int attention_packed_rows(int head_size);
+int launch_attention_packed(Profiler* prof, const float* qkv, float* ctx, const SegTile* tiles, int ntiles, int64_t frames,
+                            double sum_nf2, int H, int heads, hipStream_t s);
+// packed.hip: caller's dense concatenation -> aligned stream (gaps zeroed); stream rows -> caller's rows
+int launch_pack_scatter(const float* src, float* stream, int64_t L, const PackSeg* segs, int nseg, hipStream_t s);
+int launch_pack_gather(const float* stream_rows, float* out, int64_t out_rows, int width, const PackSeg* segs, int nseg,
+                       hipStream_t s);
 
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
 enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3 };

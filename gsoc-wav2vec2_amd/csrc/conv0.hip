@@ -42,7 +42,19 @@ struct Conv0Args {
     int64_t L;
     int T0, K, stride, C, nchunks, norm_mode, act;
     float eps;
+    const PackSeg* segs;   // packed stream (launch_conv0_packed) or null: stats rows and scale / shift row per utterance
+    int nseg;
 };
+
+// packed stream: the utterance whose span holds conv0 chunk `chunk`, and how many of the chunk's rows are its frames
+__device__ __forceinline__ int conv0_chunk_seg(const Conv0Args& a, int chunk, int* rows) {
+    const int64_t t0 = (int64_t)chunk * TC;
+    const int i = pack_seg_of_sample(a.segs, a.nseg, t0 * a.stride);
+    const PackSeg sg = a.segs[i];
+    const int64_t T0 = 1 + (sg.len - a.K) / a.stride;
+    *rows = (int)max((int64_t)0, min((int64_t)TC, T0 - (t0 - sg.s0 / a.stride)));
+    return i;
+}
 
 // MODE 0: stats, MODE 1: apply (group norm), MODE 2: plain conv(+bias) write
 template <int MODE, int KT, int ST>
@@ -52,7 +64,13 @@ __global__ __launch_bounds__(256) void conv0_kernel(Conv0Args a) {
     const int S = ST > 0 ? ST : a.stride;
     const int b = blockIdx.y, chunk = blockIdx.x;
     const int t0 = chunk * TC;
-    const int nt = min(TC, a.T0 - t0);
+    int nt = min(TC, a.T0 - t0);
+    int ssrow = b;                              // row of the scale / shift table
+    if (a.segs) {                               // packed: statistics over the utterance's own rows only
+        int rows;
+        ssrow = conv0_chunk_seg(a, chunk, &rows);
+        if (MODE == 0) nt = rows;
+    }
     const int nx = (nt - 1) * S + K;
     const float* __restrict__ wv = a.wave + (int64_t)b * a.L + (int64_t)t0 * S;
     for (int i = threadIdx.x; i < nx; i += 256) xs[i] = wv[i];
@@ -73,8 +91,8 @@ __global__ __launch_bounds__(256) void conv0_kernel(Conv0Args a) {
             bs[j] = (ok && a.bias) ? a.bias[c] : 0.f;
             s1[j] = 0.0; s2[j] = 0.0;
             if (MODE == 1 && ok) {
-                sc[j] = a.scale_shift[((int64_t)b * 2 + 0) * a.C + c];
-                sh[j] = a.scale_shift[((int64_t)b * 2 + 1) * a.C + c];
+                sc[j] = a.scale_shift[((int64_t)ssrow * 2 + 0) * a.C + c];
+                sh[j] = a.scale_shift[((int64_t)ssrow * 2 + 1) * a.C + c];
             } else {
                 sc[j] = 1.f; sh[j] = 0.f;
             }
@@ -199,8 +217,10 @@ __global__ __launch_bounds__(256) void conv0_apply4_kernel(Conv0Args a, int tpr 
     for (int k = 0; k < KT; ++k) w[k] = *reinterpret_cast<const f32x4_c0*>(a.kernel + (int64_t)k * a.C + c);
     if (a.bias) bs = *reinterpret_cast<const f32x4_c0*>(a.bias + c);
     if (MODE == 1) {
-        sc = *reinterpret_cast<const f32x4_c0*>(a.scale_shift + ((int64_t)b * 2 + 0) * a.C + c);
-        sh = *reinterpret_cast<const f32x4_c0*>(a.scale_shift + ((int64_t)b * 2 + 1) * a.C + c);
+        int rows;
+        const int ssrow = a.segs ? conv0_chunk_seg(a, chunk, &rows) : b;     // packed: the utterance's scale / shift
+        sc = *reinterpret_cast<const f32x4_c0*>(a.scale_shift + ((int64_t)ssrow * 2 + 0) * a.C + c);
+        sh = *reinterpret_cast<const f32x4_c0*>(a.scale_shift + ((int64_t)ssrow * 2 + 1) * a.C + c);
     }
     if (MODE == 3) {      // gamma / beta of this lane's channels
         sc = *reinterpret_cast<const f32x4_c0*>(a.gamma + c);
@@ -300,6 +320,30 @@ __global__ void conv0_finalize_kernel(Conv0Args a, int B) {
     const double inv = (double)a.gamma[c] / sqrt(var + (double)a.eps);
     a.scale_shift[((int64_t)b * 2 + 0) * a.C + c] = (float)inv;
     a.scale_shift[((int64_t)b * 2 + 1) * a.C + c] = (float)((double)a.beta[c] - mean * inv);
+}
+
+// packed stream, (utterance, c): the same combine over exactly the utterance's chunks and rows (its first chunk starts at its
+// first row; conv0_kernel<0> counted only its rows in the last one)
+__global__ void conv0_seg_finalize_kernel(Conv0Args a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)a.nseg * a.C) return;
+    const int g = (int)(i / a.C), c = (int)(i % a.C);
+    const PackSeg sg = a.segs[g];
+    const int64_t T0 = 1 + (sg.len - a.K) / a.stride;
+    const int64_t ch0 = sg.s0 / a.stride / TC, nch = (T0 + TC - 1) / TC;
+    double s1 = 0.0, s2 = 0.0;
+    for (int64_t ch = ch0; ch < ch0 + nch; ++ch) {
+        const double* p = a.partial + (ch * 2) * a.C;
+        s1 += p[c];
+        s2 += p[a.C + c];
+    }
+    const double n = (double)T0;
+    const double mean = s1 / n;
+    double var = s2 / n - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    const double inv = (double)a.gamma[c] / sqrt(var + (double)a.eps);
+    a.scale_shift[((int64_t)g * 2 + 0) * a.C + c] = (float)inv;
+    a.scale_shift[((int64_t)g * 2 + 1) * a.C + c] = (float)((double)a.beta[c] - mean * inv);
 }
 
 // ---- GroupNorm statistics without computing the conv (K = 10) ---------------------------------------------------
@@ -443,7 +487,7 @@ int launch_conv0_x(Profiler* prof, const float* wave, const float* kernel, const
     W2V2_REQUIRE(B > 0 && C > 0 && K > 0 && K <= 32 && stride > 0 && L >= K,
                  "conv0: unsupported B=%d C=%d K=%d stride=%d L=%lld", B, C, K, stride, (long long)L);
     W2V2_REQUIRE(norm_mode >= 0 && norm_mode <= 2, "conv0: bad norm_mode %d", norm_mode);
-    Conv0Args a;
+    Conv0Args a{};
     a.wave = wave; a.kernel = kernel; a.bias = bias; a.gamma = gamma; a.beta = beta; a.out = out; a.out16 = out16; a.planes = pl;
     a.L = L; a.K = K; a.stride = stride; a.C = C; a.eps = eps; a.norm_mode = norm_mode; a.act = act;
     a.T0 = (int)(1 + (L - K) / stride);
@@ -514,6 +558,41 @@ int launch_conv0_x(Profiler* prof, const float* wave, const float* kernel, const
     {
         ProfScope ps(prof, FAM_CONV0_APPLY, flops, in_bytes + out_bytes, s);
         launch_mode<1>(a, B, s);
+    }
+    W2V2_HIP_CHECK(hipGetLastError());
+    return W2V2_OK;
+}
+
+int conv0_chunk_frames() { return TC; }
+
+// Packed stream: pass 1 is the per-chunk conv recompute (conv0_kernel<0>), each chunk counting only the rows of the utterance
+// whose span holds it; the finalize combines each utterance's chunks; the apply pass reads the utterance's scale / shift.
+// (The Gram-form statistics of the dense path take 2048-frame blocks, which would straddle utterances.)
+int launch_conv0_packed(Profiler* prof, const float* wave, const float* kernel, const float* bias, const float* gamma,
+                        const float* beta, float* out, float* ws, float* scale_shift, int64_t L, int K, int stride, int C,
+                        float eps, int act, const PackSeg* segs, int nseg, hipStream_t s) {
+    W2V2_REQUIRE(wave && kernel && gamma && beta && out && ws && scale_shift && segs && nseg > 0, "conv0_packed: null operand");
+    W2V2_REQUIRE(C > 0 && K > 0 && K <= 32 && stride > 0 && L >= K, "conv0_packed: unsupported C=%d K=%d stride=%d L=%lld", C, K,
+                 stride, (long long)L);
+    Conv0Args a{};
+    a.wave = wave; a.kernel = kernel; a.bias = bias; a.gamma = gamma; a.beta = beta; a.out = out;
+    a.L = L; a.K = K; a.stride = stride; a.C = C; a.eps = eps; a.norm_mode = 0; a.act = act;
+    a.T0 = (int)(1 + (L - K) / stride);
+    a.nchunks = conv0_nchunks(L, K, stride);
+    a.partial = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(ws) + 7) & ~(uintptr_t)7);
+    a.scale_shift = scale_shift;
+    a.segs = segs;
+    a.nseg = nseg;
+    const double flops = 2.0 * (double)a.T0 * C * K;
+    {
+        ProfScope ps(prof, FAM_CONV0_STATS, flops, 4.0 * (double)L, s);
+        launch_mode<0>(a, 1, s);
+        const int64_t n = (int64_t)nseg * C;
+        W2V2_LAUNCH(conv0_seg_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    }
+    {
+        ProfScope ps(prof, FAM_CONV0_APPLY, flops, 4.0 * (double)L + 4.0 * (double)a.T0 * C, s);
+        launch_mode<1>(a, 1, s);
     }
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;

@@ -43,6 +43,14 @@ struct w2v2_model {
     float *qkv = nullptr, *ctx = nullptr, *t0 = nullptr, *t1 = nullptr, *t2 = nullptr, *t3 = nullptr,
           *ffn = nullptr, *enc_out = nullptr;
     int32_t* frame_len = nullptr;
+    // packed variable-length forward (w2v2_forward_packed): stream buffers allocated with a B = 1 workspace of ws_L samples
+    int64_t pk_L = 0;                        // ws_L the stream buffers were sized for (0: none)
+    int pk_seg_cap = 0, pk_tile_cap = 0;
+    float *pk_wave = nullptr, *pk_scale = nullptr, *pk_out = nullptr;   // stream samples, conv0 scale / shift per utterance, head output
+    void* pk_tab = nullptr;                  // device tables: PackSeg[pk_seg_cap] | SegTile[pk_tile_cap]
+    void* pk_stage = nullptr;                // pinned staging of the tables (outlives the workspace)
+    size_t pk_stage_bytes = 0;
+    hipEvent_t pk_copied = nullptr;          // recorded after the last copy out of pk_stage
     // bf16 shadows (precision mode 1, inference forward; w2v2_api.hip::ensure_shadows).  Weight shadows are the
     // GEMM kernels transposed to (N, K); activation shadows are written by the producing kernels.
     bool sh_ready = false, w16_valid = false;

@@ -66,10 +66,13 @@ struct PosArgs {
     int B, T, H, K, groups, act;
     int pad_left;               // K / 2 forward; K - 1 - K / 2 for the transposed (data-gradient) pass
     int add_residual;           // 1: y = xz + act(conv + bias) (forward); 0: y = act(conv + bias)
+    const SegTile* tiles;       // SEG: one entry per 128-frame tile of a packed utterance (B = 1, T = stream frames)
+    int ntiles;
 };
 
-// CG = channels per group (input == output), a multiple of 16, <= 64
-template <int CG>
+// CG = channels per group (input == output), a multiple of 16, <= 64.  SEG: the block owns tile `tiles[e]` of one packed
+// utterance and sees only that utterance's frames, zero-padded at its own edges -- exactly a B = 1 run of the utterance alone.
+template <int CG, bool SEG = false>
 __global__ __launch_bounds__(256) void pos_conv_kernel(PosArgs a) {
     constexpr int NT = CG / 16;                 // 16-wide output column tiles per wave
     constexpr int KS = CG / 4;                  // 4-deep k steps per tap
@@ -86,7 +89,25 @@ __global__ __launch_bounds__(256) void pos_conv_kernel(PosArgs a) {
     // groups' taps stay resident in its L2, and the frame blocks of one (sample, group) -- which share half their input slab --
     // follow each other on it.
     int t0, g, b;
-    {
+    int T = a.T;                                // frames of the sequence this block works on
+    int64_t row0;                               // its first row in x / y
+    if constexpr (SEG) {
+        const int bid = blockIdx.x;
+        int e;
+        if (a.groups % 8 == 0) {                // (same XCD-to-group ownership as below)
+            const int gpx = a.groups >> 3, xcd = bid & 7, idx = bid >> 3;
+            e = idx % a.ntiles;
+            g = xcd * gpx + idx / a.ntiles;
+        } else {
+            e = bid % a.ntiles;
+            g = bid / a.ntiles;
+        }
+        const SegTile st = a.tiles[e];
+        t0 = st.t0;
+        T = st.nf;
+        row0 = st.f0;
+        b = 0;
+    } else {
         const int tb = (a.T + PBM - 1) / PBM;
         const int bid = blockIdx.x;
         if (a.groups % 8 == 0) {
@@ -100,20 +121,21 @@ __global__ __launch_bounds__(256) void pos_conv_kernel(PosArgs a) {
             g = (bid / tb) % a.groups;
             b = bid / (tb * a.groups);
         }
+        row0 = (int64_t)b * a.T;
     }
     const int pad = a.pad_left;
     const int rows = PBM + a.K - 1;
     float* Xs = smem;                           // rows x XS
     float* Ws = smem + ((rows * XS + 3) & ~3);  // 2 x CG x WS
-    const int flen = a.frame_len ? a.frame_len[b] : a.T;
+    const int flen = (!SEG && a.frame_len) ? a.frame_len[b] : T;
 
     // ---- stage the input slab: frames t0-pad .. t0+PBM+K-2-pad, zero outside [0, min(T, flen)) ----
-    const float* __restrict__ xb = a.x + (int64_t)b * a.T * a.H + g * CG;
+    const float* __restrict__ xb = a.x + row0 * a.H + g * CG;
     for (int i = tid; i < rows * (CG / 4); i += 256) {
         const int r = i / (CG / 4), c4 = (i % (CG / 4)) * 4;
         const int t = t0 - pad + r;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (t >= 0 && t < a.T && t < flen) v = *reinterpret_cast<const float4*>(xb + (int64_t)t * a.H + c4);
+        if (t >= 0 && t < T && t < flen) v = *reinterpret_cast<const float4*>(xb + (int64_t)t * a.H + c4);
         float* d = Xs + r * XS + c4;
         d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
     }
@@ -171,7 +193,7 @@ __global__ __launch_bounds__(256) void pos_conv_kernel(PosArgs a) {
 
     // ---- epilogue: + bias -> GELU -> + xz (residual from the slab) -> store ----
     // 16x16 C/D map: col = lane & 15, row = 4 (lane >> 4) + reg
-    float* __restrict__ yb = a.y + (int64_t)b * a.T * a.H + g * CG;
+    float* __restrict__ yb = a.y + row0 * a.H + g * CG;
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
         const int co = n * 16 + ln;
@@ -182,10 +204,10 @@ __global__ __launch_bounds__(256) void pos_conv_kernel(PosArgs a) {
             for (int r = 0; r < 4; ++r) {
                 const int lr = wave * 32 + m * 16 + lk * 4 + r;
                 const int t = t0 + lr;
-                if (t < a.T) {
+                if (t < T) {
                     const float res = a.add_residual ? Xs[(lr + pad) * XS + co] : 0.0f;
                     const float c = acc[m][n][r] + bv;
-                    if (a.pre_act) a.pre_act[((int64_t)b * a.T + t) * a.H + g * CG + co] = c;
+                    if (a.pre_act) a.pre_act[(row0 + t) * a.H + g * CG + co] = c;
                     yb[(int64_t)t * a.H + co] = res + apply_act(c, a.act);
                 }
             }
@@ -193,7 +215,7 @@ __global__ __launch_bounds__(256) void pos_conv_kernel(PosArgs a) {
     }
 }
 
-template <int CG>
+template <int CG, bool SEG = false>
 int launch_pos(const PosArgs& a, hipStream_t s) {
     constexpr int XS = CG + 2;
     constexpr int WS = (CG % 32 == 0) ? CG + 16 : CG;
@@ -201,13 +223,13 @@ int launch_pos(const PosArgs& a, hipStream_t s) {
     const size_t lds = (size_t)(((rows * XS + 3) & ~3) + 2 * CG * WS) * sizeof(float);
     static std::atomic<bool> attr_set{false};   // (idempotent call; atomic so concurrent host threads agree on the flag)
     if (!attr_set) {
-        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pos_conv_kernel<CG>),
+        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(pos_conv_kernel<CG, SEG>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
     W2V2_REQUIRE(lds <= 160 * 1024, "pos_conv: K=%d needs %zu B of LDS (> 160 KiB)", a.K, lds);
-    dim3 grid((unsigned)(((a.T + PBM - 1) / PBM) * a.groups * a.B)), block(256);
-    W2V2_LAUNCH(pos_conv_kernel<CG>, grid, block, lds, s, a);
+    dim3 grid((unsigned)(SEG ? (int64_t)a.ntiles * a.groups : (int64_t)((a.T + PBM - 1) / PBM) * a.groups * a.B)), block(256);
+    W2V2_LAUNCH((pos_conv_kernel<CG, SEG>), grid, block, lds, s, a);
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }
@@ -406,6 +428,27 @@ int launch_pos_conv_ex(Profiler* prof, const float* x, const float* wg, const fl
         case 64: return launch_pos<64>(a, s);
         default:
             set_error("pos_conv: channels per group = %d unsupported (16, 32, 48, 64)", cg);
+            return W2V2_EINVAL;
+    }
+}
+
+int pos_conv_packed_rows() { return PBM; }
+
+int launch_pos_conv_packed(Profiler* prof, const float* x, const float* wg, const float* bias, float* y, const SegTile* tiles,
+                           int ntiles, int64_t frames, int H, int K, int groups, int act, hipStream_t s) {
+    W2V2_REQUIRE(x && wg && bias && y && tiles, "pos_conv_packed: null operand");
+    W2V2_REQUIRE(ntiles > 0 && frames > 0 && frames < INT32_MAX && K > 0 && groups > 0 && H % groups == 0 && H % 4 == 0,
+                 "pos_conv_packed: bad sizes");
+    const int cg = H / groups;
+    PosArgs a{x, wg, bias, nullptr, y, nullptr, 1, (int)frames, H, K, groups, act, K / 2, 1, tiles, ntiles};
+    ProfScope ps(prof, FAM_POSCONV, 2.0 * (double)frames * H * cg * K, 8.0 * (double)frames * H + 4.0 * K * cg * H, s);
+    switch (cg) {
+        case 16: return launch_pos<16, true>(a, s);
+        case 32: return launch_pos<32, true>(a, s);
+        case 48: return launch_pos<48, true>(a, s);
+        case 64: return launch_pos<64, true>(a, s);
+        default:
+            set_error("pos_conv_packed: channels per group = %d unsupported (16, 32, 48, 64)", cg);
             return W2V2_EINVAL;
     }
 }

@@ -7,6 +7,7 @@
 // FeatureExtractorLayer x7 (feature_extractor.py:54-59) -> FeatureProjection
 // (feature_extractor.py:92-95) -> Wav2Vec2Encoder.call (encoder.py:251-276) ->
 // TransformerLayer.call (encoder.py:111-134) -> lm_head.
+#include <algorithm>
 #include <mutex>
 #include <atomic>
 #include <stdarg.h>
@@ -216,6 +217,10 @@ static void free_workspace(w2v2_model* m) {
     m->hs.clear();
     m->ws_B = 0;
     m->ws_L = 0;
+    m->pk_L = 0;                   // the packed stream buffers live in `allocs`
+    m->pk_wave = m->pk_scale = m->pk_out = nullptr;
+    m->pk_tab = nullptr;
+    m->pk_seg_cap = m->pk_tile_cap = 0;
 }
 
 static int ws_alloc(w2v2_model* m, float** out, int64_t floats) {
@@ -558,6 +563,11 @@ void w2v2_destroy(w2v2_model* m) {
     if (m->range_flag) (void)hipFree(m->range_flag);
     if (m->pos_w16) (void)hipFree(m->pos_w16);
     if (m->shadow_jobs) (void)hipFree(m->shadow_jobs);
+    if (m->pk_copied) {
+        (void)hipEventSynchronize(m->pk_copied);
+        (void)hipEventDestroy(m->pk_copied);
+    }
+    if (m->pk_stage) (void)hipHostFree(m->pk_stage);
     profiler_destroy(m->prof);
     delete m;
 }
@@ -716,20 +726,38 @@ int w2v2_range_overflow(w2v2_model* m, int32_t* flag, void* stream) {
     return W2V2_OK;
 }
 
-int w2v2_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, const int32_t* mask,
-                 float* out, void* stream) {
-    W2V2_REQUIRE(m && wave && out, "forward: null argument");
-    W2V2_REQUIRE(B > 0 && L > 0, "forward: bad batch shape (%d, %lld)", B, (long long)L);
-    if (!m->finalized) {
-        set_error("forward: call w2v2_finalize after setting the variables");
-        return W2V2_ESTATE;
-    }
+// What the packed forward hands the shared forward body: the stream's utterance and tile tables (device) and where the
+// stream-sized head output goes.  The workspace holds at least the stream (ws_B == 1, ws_L >= L).
+struct PackedPlan {
+    const PackSeg* segs;
+    int nseg;
+    const SegTile* pos_tiles;
+    int npos;
+    const SegTile* attn_tiles;
+    int nattn;
+    double sum_nf2;
+    float* head_out;          // (stream frames, vocab) when the model has a head
+};
+
+// The inference forward over (B, L).  pk null: the batched forward (w2v2_forward).  pk set: one stream of packed utterances
+// (B = 1, fp32); the three stages that mix frames -- conv0's GroupNorm statistics, the positional conv and attention -- take
+// their segment-aware forms, everything else runs unchanged over the stream.
+static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, const int32_t* mask, float* out, hipStream_t s,
+                        const PackedPlan* pk) {
     const w2v2_config& c = m->cfg;
     PrecisionScope precision(m->precision);
     const int64_t Tll = w2v2_num_frames(m, L);
     W2V2_REQUIRE(Tll >= 1, "forward: %lld samples are shorter than the conv stack's receptive field", (long long)L);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (int e = w2v2_ensure_workspace(m, B, L)) return e;
+    if (!pk)
+        if (int e = w2v2_ensure_workspace(m, B, L)) return e;
+    W2V2_REQUIRE(m->ws_B == B && m->ws_L >= L, "forward: workspace (%d, %lld) does not hold (%d, %lld)", m->ws_B, (long long)m->ws_L,
+                 B, (long long)L);
+    // frames per conv layer for THIS input (the workspace may be larger: a packed stream runs in a workspace of its capacity)
+    std::vector<int> conv_T(c.num_conv_layers);
+    {
+        int64_t t = L;
+        for (int i = 0; i < c.num_conv_layers; ++i) conv_T[i] = (int)(t = 1 + (t - c.kernal_sizes[i]) / c.strides[i]);
+    }
     Profiler* pf = m->prof;
     const int T = (int)Tll;
     const int H = c.hidden_size, F = c.intermediate_size;
@@ -766,8 +794,8 @@ int w2v2_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, const i
     };
     std::vector<char> cp(NC + 1, 0);             // cp[i]: conv layer i's GEMM streams the planes of conv output i - 1
     for (int i = 1; i < NC; ++i)
-        cp[i] = site(m->conv_T[i], c.filter_sizes[i], c.kernal_sizes[i] * c.filter_sizes[i - 1], B, (int64_t)c.strides[i] * c.filter_sizes[i - 1],
-                     (int64_t)m->conv_T[i - 1] * c.filter_sizes[i - 1]) && c.filter_sizes[i - 1] % 4 == 0;
+        cp[i] = site(conv_T[i], c.filter_sizes[i], c.kernal_sizes[i] * c.filter_sizes[i - 1], B, (int64_t)c.strides[i] * c.filter_sizes[i - 1],
+                     (int64_t)conv_T[i - 1] * c.filter_sizes[i - 1]) && c.filter_sizes[i - 1] % 4 == 0;
     const int C512 = c.filter_sizes[NC - 1];
     const bool p_proj = site(BT, H, C512, 1, C512, 0) && C512 % 4 == 0, p_qkv = site(BT, 3 * H, H, 1, H, 0) && H % 4 == 0, p_out = site(BT, H, H, 1, H, 0),
                p_f1 = site(BT, F, H, 1, H, 0), p_f2 = site(BT, H, F, 1, F, 0) && F % 8 == 0;
@@ -835,7 +863,12 @@ int w2v2_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, const i
     };
     for (int i = 0; i + 1 < NC; ++i)
         if (f32_skipped(i)) m->acts_skipped.push_back("conv" + std::to_string(i));
-    {
+    if (pk && !layer_mode) {     // GroupNorm statistics per utterance, over exactly its rows
+        if (int e = launch_conv0_packed(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr, fe(0, "/layer_norm/gamma"),
+                                        fe(0, "/layer_norm/beta"), m->conv[0], m->conv0_ws, m->pk_scale, L, c.kernal_sizes[0], c.strides[0],
+                                        c.filter_sizes[0], 1e-5f, act_ew, pk->segs, pk->nseg, s))
+            return e;
+    } else {
         const PlaneOut po = fused ? PO(m->conv48[0]) : PlaneOut{};
         const bool f32_too = !(NC > 1 && cp[1]) || keep || !fused;
         if (int e = launch_conv0_x(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr,
@@ -845,12 +878,12 @@ int w2v2_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, const i
                                    c.filter_sizes[0], 1e-5f, layer_mode ? 2 : 0, act_ew, s, fused ? &po : nullptr))      // (layer mode: conv + LayerNorm + GELU in one pass)
             return e;
         if (NC > 1 && cp[1] && !fused)
-            if (int e = launch_split_planes(m->conv[0], m->conv48[0].p, m->conv48[0].plane, (int64_t)B * m->conv_T[0] * c.filter_sizes[0], fmt, m->range_flag, s))
+            if (int e = launch_split_planes(m->conv[0], m->conv48[0].p, m->conv48[0].plane, (int64_t)B * conv_T[0] * c.filter_sizes[0], fmt, m->range_flag, s))
                 return e;
     }
     for (int i = 1; i < NC; ++i) {
         const int cin = c.filter_sizes[i - 1], cout = c.filter_sizes[i];
-        const int Tin = m->conv_T[i - 1], Tout = m->conv_T[i];
+        const int Tin = conv_T[i - 1], Tout = conv_T[i];
         uint16_t* o16 = (sh && i + 1 < NC) ? m->conv16[i] : nullptr;     // the last conv output feeds a LayerNorm
         // strided Conv1D == GEMM over an overlapping window view: lda = stride * C_in < K * C_in
         // planes of this layer's output for the next layer's GEMM: from the GEMM epilogue (group-norm mode: bias + GELU there) or from
@@ -886,7 +919,11 @@ int w2v2_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, const i
         if (int e = launch_frame_lengths(pf, mask, m->frame_len, B, L, c.kernal_sizes, c.strides, c.num_conv_layers, s)) return e;
         flen = m->frame_len;
     }
-    if (w2v2_pos_conv_bf16_ok(m)) {      // precision mode 1: one batched bf16 GEMM over (sample, group); m->t0 is free here
+    if (pk) {                            // each utterance zero-padded at its own edges
+        if (int e = launch_pos_conv_packed(pf, m->proj, m->pos_wg, m->P("encoder/pos_conv_embed/conv/bias"), m->posout, pk->pos_tiles, pk->npos,
+                                           T, H, c.num_conv_pos_embeddings, c.num_conv_pos_embedding_groups, act, s))
+            return e;
+    } else if (w2v2_pos_conv_bf16_ok(m)) {      // precision mode 1: one batched bf16 GEMM over (sample, group); m->t0 is free here
         if (int e = w2v2_ensure_pos16(m, B, T, s)) return e;
         if (int e = launch_pos_conv_bf16(pf, m->proj, m->pos_w16, m->P("encoder/pos_conv_embed/conv/bias"), flen, m->posout, nullptr,
                                          m->pos_pack16, m->t0, B, T, H, c.num_conv_pos_embeddings, c.num_conv_pos_embedding_groups,
@@ -933,9 +970,12 @@ int w2v2_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, const i
         const bool ctx_fused = p_out && attention_split_supported(H / c.num_heads) && H % 4 == 0 && tune_int("W2V2_SPLIT_ATTN", 1) != 0;
         PlaneOut po_flag;                                    // (no planes wanted: the split attention still reports f16x2 saturation)
         po_flag.range_flag = m->range_flag;
-        if (int e = launch_attention_x(pf, attn16 ? nullptr : m->qkv, attn16 ? m->qkv16 : nullptr, flen, (ctx16_only || (ctx_fused && !keep)) ? nullptr : m->ctx, B, T, H,
-                                       c.num_heads, attn16 ? m->ctx16 : nullptr, s, ctx_fused ? &po_ctx : (pm ? &po_flag : nullptr)))
+        if (pk) {                        // queries and keys of one utterance per block
+            if (int e = launch_attention_packed(pf, m->qkv, m->ctx, pk->attn_tiles, pk->nattn, T, pk->sum_nf2, H, c.num_heads, s)) return e;
+        } else if (int e = launch_attention_x(pf, attn16 ? nullptr : m->qkv, attn16 ? m->qkv16 : nullptr, flen, (ctx16_only || (ctx_fused && !keep)) ? nullptr : m->ctx, B, T, H,
+                                              c.num_heads, attn16 ? m->ctx16 : nullptr, s, ctx_fused ? &po_ctx : (pm ? &po_flag : nullptr))) {
             return e;
+        }
         if (p_out && !ctx_fused)
             if (int e = launch_split_planes(m->ctx, m->ctx48.p, m->ctx48.plane, BT * H, fmt, m->range_flag, s)) return e;
         // out projection + residual (encoder.py:31,117-119)
@@ -978,14 +1018,114 @@ int w2v2_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, const i
         head_in16 = sh ? m->enc16 : nullptr;
     }
     // ---- head (modeling.py:253-254) ----
+    // (packed: the stream's rows; w2v2_forward_packed gathers the utterances' frames from them)
     if (c.with_lm_head) {
-        if (int e = gemm(m->enc_out, head_in16, H, 0, m->P("lm_head/kernel"), c.vocab_size, out, nullptr, c.vocab_size, 0,
+        if (int e = gemm(m->enc_out, head_in16, H, 0, m->P("lm_head/kernel"), c.vocab_size, pk ? pk->head_out : out, nullptr, c.vocab_size, 0,
                          m->P("lm_head/bias"), nullptr, (int)BT, c.vocab_size, H, 1, 0))
             return e;
-    } else {
+    } else if (!pk) {
         W2V2_HIP_CHECK(hipMemcpyAsync(out, m->enc_out, (size_t)BT * H * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     return W2V2_OK;
+}
+
+int w2v2_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, const int32_t* mask,
+                 float* out, void* stream) {
+    W2V2_REQUIRE(m && wave && out, "forward: null argument");
+    W2V2_REQUIRE(B > 0 && L > 0, "forward: bad batch shape (%d, %lld)", B, (long long)L);
+    if (!m->finalized) {
+        set_error("forward: call w2v2_finalize after setting the variables");
+        return W2V2_ESTATE;
+    }
+    return forward_impl(m, wave, B, L, mask, out, reinterpret_cast<hipStream_t>(stream), nullptr);
+}
+
+int w2v2_forward_packed(w2v2_model* m, const float* wave, int32_t n, const int64_t* cu_samples, float* out, void* stream) {
+    W2V2_REQUIRE(m && wave && cu_samples && out, "forward_packed: null argument");
+    if (!m->finalized) {
+        set_error("forward_packed: call w2v2_finalize after setting the variables");
+        return W2V2_ESTATE;
+    }
+    static const char* modes[] = {"fp32", "bf16", "bf16x3", "f16x2"};
+    W2V2_REQUIRE(m->precision == W2V2_PRECISION_FP32, "forward_packed: precision mode %s is not supported (fp32 only)",
+                 (m->precision >= 0 && m->precision <= 3) ? modes[m->precision] : "?");
+    W2V2_REQUIRE(n >= 1, "forward_packed: %d utterances (need at least one)", n);
+    W2V2_REQUIRE(cu_samples[0] == 0, "forward_packed: cu_samples[0] = %lld, must be 0", (long long)cu_samples[0]);
+    const w2v2_config& c = m->cfg;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // alignment unit: a multiple of the total stride (whole frames at every layer) and of conv0's stats chunk in samples
+    int64_t A = 1;
+    for (int i = 0; i < c.num_conv_layers; ++i) A *= c.strides[i];
+    const int64_t chunk = (int64_t)c.strides[0] * conv0_chunk_frames();
+    int64_t g = A, r = chunk;
+    while (r) { const int64_t t = g % r; g = r; r = t; }
+    const int64_t U = A / g * chunk;
+    // utterances in the stream, and the tiles of the two stages that work per utterance
+    std::vector<PackSeg> segs((size_t)n);
+    int64_t L = 0, rows = 0;
+    double sum_nf2 = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t len = cu_samples[i + 1] - cu_samples[i];
+        W2V2_REQUIRE(len >= 0, "forward_packed: cu_samples decreases at utterance %d", i);
+        const int64_t nf = w2v2_num_frames(m, len);
+        W2V2_REQUIRE(nf >= 1, "forward_packed: utterance %d has %lld samples, shorter than the conv stack's receptive field", i,
+                     (long long)len);
+        segs[i] = PackSeg{L, len, cu_samples[i], (int32_t)(L / A), (int32_t)nf, (int32_t)rows, 0};
+        L += (len + U - 1) / U * U;
+        rows += nf;
+        sum_nf2 += (double)nf * (double)nf;
+    }
+    const int64_t T = w2v2_num_frames(m, L);
+    W2V2_REQUIRE(T < (1 << 24) && (int64_t)segs.back().f0 + segs.back().nf <= T, "forward_packed: stream of %lld samples out of range",
+                 (long long)L);
+    const int H = c.hidden_size, PR = pos_conv_packed_rows(), AR = attention_packed_rows(H / c.num_heads);
+    std::vector<SegTile> tiles;
+    for (const int rows_per_tile : {PR, AR})
+        for (const PackSeg& sg : segs)
+            for (int t0 = 0; t0 < sg.nf; t0 += rows_per_tile) tiles.push_back(SegTile{sg.f0, sg.nf, t0, 0});
+    int npos = 0;
+    for (const PackSeg& sg : segs) npos += (sg.nf + PR - 1) / PR;
+    const int nattn = (int)tiles.size() - npos;
+
+    // workspace of a B = 1 forward over at least the stream, rounded up so that later streams that fit reuse it
+    if (!(m->ws_B == 1 && m->ws_L >= L))
+        if (int e = w2v2_ensure_workspace(m, 1, (L + 64 * U - 1) / (64 * U) * (64 * U))) return e;
+    if (m->pk_L != m->ws_L) {
+        const int64_t Tcap = w2v2_num_frames(m, m->ws_L);
+        m->pk_seg_cap = (int)(m->ws_L / U);
+        m->pk_tile_cap = (int)(2 * (int64_t)m->pk_seg_cap + Tcap / PR + Tcap / AR);
+        if (int e = ws_alloc(m, &m->pk_wave, m->ws_L)) return e;
+        if (int e = ws_alloc(m, &m->pk_scale, (int64_t)m->pk_seg_cap * 2 * c.filter_sizes[0])) return e;
+        if (int e = ws_alloc(m, &m->pk_out, c.with_lm_head ? Tcap * c.vocab_size : 0)) return e;
+        float* tab = nullptr;
+        if (int e = ws_alloc(m, &tab, ((int64_t)m->pk_seg_cap * sizeof(PackSeg) + (int64_t)m->pk_tile_cap * sizeof(SegTile)) / sizeof(float))) return e;
+        m->pk_tab = tab;
+        m->pk_L = m->ws_L;
+    }
+    W2V2_REQUIRE(n <= m->pk_seg_cap && (int64_t)tiles.size() <= m->pk_tile_cap, "forward_packed: tables exceed their capacity");
+    // tables -> device through pinned staging; the previous call's copy out of it must have completed before it is rewritten
+    const size_t seg_bytes = segs.size() * sizeof(PackSeg), bytes = seg_bytes + tiles.size() * sizeof(SegTile);
+    if (!m->pk_copied) W2V2_HIP_CHECK(hipEventCreateWithFlags(&m->pk_copied, hipEventDisableTiming));
+    W2V2_HIP_CHECK(hipEventSynchronize(m->pk_copied));
+    if (m->pk_stage_bytes < bytes) {
+        if (m->pk_stage) W2V2_HIP_CHECK(hipHostFree(m->pk_stage));
+        m->pk_stage = nullptr;
+        m->pk_stage_bytes = 0;
+        const size_t want = std::max(bytes, (size_t)64 << 10);
+        W2V2_HIP_CHECK(hipHostMalloc(&m->pk_stage, want, hipHostMallocDefault));
+        m->pk_stage_bytes = want;
+    }
+    memcpy(m->pk_stage, segs.data(), seg_bytes);
+    memcpy(static_cast<char*>(m->pk_stage) + seg_bytes, tiles.data(), bytes - seg_bytes);
+    W2V2_HIP_CHECK(hipMemcpyAsync(m->pk_tab, m->pk_stage, bytes, hipMemcpyHostToDevice, s));
+    W2V2_HIP_CHECK(hipEventRecord(m->pk_copied, s));
+    const PackSeg* dsegs = static_cast<const PackSeg*>(m->pk_tab);
+    const SegTile* dtiles = reinterpret_cast<const SegTile*>(static_cast<const char*>(m->pk_tab) + seg_bytes);
+
+    if (int e = launch_pack_scatter(wave, m->pk_wave, L, dsegs, n, s)) return e;
+    const PackedPlan plan{dsegs, n, dtiles, npos, dtiles + npos, nattn, sum_nf2, m->pk_out};
+    if (int e = forward_impl(m, m->pk_wave, 1, L, nullptr, out, s, &plan)) return e;
+    return launch_pack_gather(c.with_lm_head ? m->pk_out : m->enc_out, out, rows, c.with_lm_head ? c.vocab_size : H, dsegs, n, s);
 }
 
 int w2v2_ctc_loss(const float* logits, int32_t B, int32_t T, int32_t V, const int32_t* labels, int32_t U,

@@ -539,6 +539,37 @@ class TFKerasModel(Layer):
     def predict(self, batch, attention_mask=None):
         return self(batch, attention_mask=attention_mask, training=False)
 
+    def predict_packed(self, waveforms):
+        """Inference on utterances of different lengths in one call, each computed exactly as `self(wave[None])` computes it
+        alone: no padding enters any statistic and no frame attends across utterances (w2v2_forward_packed, fp32 only).
+        `waveforms`: a list of 1-D numpy arrays or torch tensors, each already normalised.  Returns a list of
+        (T_i, vocab | hidden) tensors, T_i = num_frames(len_i): views of one packed output."""
+        torch = _require_gpu()
+        if isinstance(waveforms, (np.ndarray, torch.Tensor)) or not len(waveforms):
+            raise ValueError("`waveforms` must be a non-empty list of 1-D waveforms")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        parts, frames = [], []
+        for i, w in enumerate(waveforms):
+            if not isinstance(w, torch.Tensor):
+                w = torch.as_tensor(np.asarray(w, dtype=np.float32))
+            if w.dim() != 1:
+                raise ValueError(f"utterance {i} must be 1-D, got shape {tuple(w.shape)}")
+            T = self.num_frames(w.shape[0])
+            if T < 1:
+                raise ValueError(f"utterance {i} has {w.shape[0]} samples, shorter than the feature extractor's receptive field")
+            parts.append(w.to(device=dev, dtype=torch.float32))
+            frames.append(T)
+        self._finalize()
+        wave = torch.cat(parts).contiguous()
+        cu = np.zeros(len(parts) + 1, dtype=np.int64)
+        cu[1:] = np.cumsum([p.shape[0] for p in parts])
+        width = self.config.vocab_size if self._with_lm_head else self.config.hidden_size
+        out = torch.empty((sum(frames), width), device=dev, dtype=torch.float32)
+        N.check(self._lib.w2v2_forward_packed(self._handle, N.ptr(wave), len(parts), N.ptr(cu), N.ptr(out),
+                                              N.current_stream()), "w2v2_forward_packed")
+        out = DeviceTensor.wrap(out)
+        return list(torch.split(out, frames, dim=0))
+
     # ---- introspection used by the parity tests / bench -----------------------
     def activation(self, name):
         shape = (C.c_int64 * 3)()

@@ -187,6 +187,19 @@ int w2v2_range_overflow(w2v2_model* m, int32_t* flag, void* stream);
 int w2v2_forward(w2v2_model* m, const float* wave_dev, int32_t B, int64_t L,
                  const int32_t* mask_dev, float* out_dev, void* stream);
 
+/* Packed variable-length inference forward (training=False): n utterances in one call, each computed as
+ * w2v2_forward computes it alone (B = 1, no mask).
+ *   wave_dev         (sum len_i) fp32, the utterances back to back, each already normalised
+ *   cu_samples_host  (n + 1) int64 prefix offsets, cu_samples_host[0] = 0
+ *   out_dev          (sum T_i, vocab | hidden), T_i = w2v2_num_frames(len_i); utterance i at row sum_{j<i} T_j
+ * W2V2_PRECISION_FP32 only (W2V2_EINVAL naming the mode otherwise); every len_i must give T_i >= 1.
+ * The utterances run as one stream with each start aligned to the conv stack's total stride; only conv0's GroupNorm
+ * statistics, the positional conv and attention see utterance boundaries.  The workspace is sized from the aligned
+ * stream length, rounded up; a later packed call whose stream fits reuses it.  Synchronises with the previous packed
+ * call's table upload (host-side), otherwise enqueued on `stream`. */
+int w2v2_forward_packed(w2v2_model* m, const float* wave_dev, int32_t n, const int64_t* cu_samples_host,
+                        float* out_dev, void* stream);
+
 /* Replaces CTCLoss.call (losses.py:14-45) = tf.nn.ctc_loss(
  * logits_time_major=False, blank_index=pad_id) with the reference's length
  * convention supplied by the caller:
