@@ -11,17 +11,22 @@ is bracketed by barrier + synchronize and the MAX over ranks is reported ("weak"
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     # + DIR/logits.npy of the last timed step
+    python bench.py --gpus 1 --steps K --warmup W --full                 # + everything measured beside the headline
 
---steps is the number of timed steps of every leg (the headline and the side configurations), each after --warmup untimed
-ones; `ms_per_step` is one timed step of the headline.  Rank 0 prints ONE JSON line.  Extra objects:
+A plain run sets up, runs --warmup untimed and --steps timed steps, writes the --dump-outputs files and prints the line;
+`ms_per_step` is one timed step.  Rank 0 prints ONE JSON line.  Its `roofline` object costs no run of its own:
   roofline     -- the dominant kernel family (fp32 MFMA GEMM / implicit-GEMM conv): algorithmic
                   FLOPs / HIP-event time of its launches inside the timed region, against the
                   157.3 TFLOP/s fp32 matrix peak of gfx950.
+--full adds what takes runs of its own or checks the result (--steps timed steps after --warmup untimed ones per leg):
+  families, clock -- per-family breakdown from two extra instrumented steps; the shader clock under load.
+  bf16x3, f16x2 -- the same forward in the two fp32-grade split modes (N=1 only).
+  configs2_train_bf16, configs3_large_fwd_f32, configs4_large_train_bf16 -- the other BASELINE configurations.
   cpu_baseline -- the CPU oracle (numpy restatement of the reference path; TensorFlow cannot be
                   run here) timed on this box's host cores per BASELINE.md section 3 (B=1 and B=8, best /
                   median of 5, plus an aggregate of concurrent workers), rank 0, N=1 only.
-  max_abs_logit_err -- rows 0-1 of the timed batch are the committed HF fixture's waveforms; the
-                  logits of the timed forward are compared with HF-PyTorch fp64 (bar 1e-3).
+  max_abs_logit_err -- rows 0-1 of the timed batch are the committed HF fixture's waveforms (in every run: the
+                  inputs do not depend on --full); the logits of the timed forward are compared with HF-PyTorch fp64 (bar 1e-3).
 """
 
 import argparse
@@ -488,13 +493,16 @@ def make_labels(B, rank):
 
 def run_leg(ctx, spec, model=None):
     """Time one workload: `warmup` untimed steps, then exactly `steps` steps between barrier + synchronize on both sides, MAX over
-    ranks.  spec: model ("base" | "large-robust"), precision, mode ("forward" | "train"), B (rows per GPU), L, steps, warmup, profile.
-    Returns (numbers, model, last output).  A training leg on more than one rank runs the bucketed RCCL gradient all-reduce inside
-    every timed step (Trainer.step) and is then timed again WITHOUT it to report the exposed communication time."""
+    ranks.  spec: model ("base" | "large-robust"), precision, mode ("forward" | "train"), B (rows per GPU), L, steps, warmup, profile,
+    extras.  Returns (numbers, model, last output).  A training leg on more than one rank runs the bucketed RCCL gradient all-reduce
+    inside every timed step (Trainer.step).  With extras (the default; a plain run's headline leg has it off) the leg also measures
+    what takes steps of its own after the timed ones -- a training leg on more than one rank is timed again WITHOUT the collective to
+    report the exposed communication time; the per-family breakdown; the clock -- and checks the golden rows against HF fp64."""
     torch, D, W, dev, world, rank = ctx["torch"], ctx["D"], ctx["W"], ctx["dev"], ctx["world"], ctx["rank"]
     cfg = W.Wav2Vec2Config() if spec["model"] == "base" else W.RobustWav2Vec2Config()
     B, L, mode, precision = spec["B"], spec["L"], spec["mode"], spec["precision"]
     steps, warmup, do_prof = spec["steps"], spec["warmup"], spec.get("profile", True)
+    extras = spec.get("extras", True)
     T = cfg.num_frames(L)
     if model is None:
         model = W.Wav2Vec2ForCTC(cfg, input_shape=(B, L))       # random-init weights from the seeded generator (seed 0)
@@ -564,7 +572,7 @@ def run_leg(ctx, spec, model=None):
               "backend": ctx["comm"]["backend"], "world_size": world,
               "engine": {"torch": "torch.distributed all_reduce per run (RCCL)", "native": "library: ncclAllReduce per bucket on its own stream (csrc/comm.hip)",
                          "native-rs": "library: ncclReduceScatter + ncclAllGather per bucket on its own stream (csrc/comm.hip)"}[trainer.collective]}
-        if world > 1:
+        if world > 1 and extras:
             for _ in range(1):
                 step(all_reduce=False)
             barrier()
@@ -590,12 +598,12 @@ def run_leg(ctx, spec, model=None):
                        "busbw_GBps": round(payload * 2 * (world - 1) / world / e_ar / 1e9, 3),
                        "algbw_GBps": round(payload / e_ar / 1e9, 3),
                        "busbw_note": "payload x 2 (N - 1) / N / standalone time (ring all-reduce convention); xGMI: 7 links x ~153 GB/s per GPU"})
-        else:
+        elif world == 1:
             ar["note"] = "one rank: no collective is issued (SUM over one replica is the identity); the N > 1 lines carry exposed_ms / busbw"
         res["allreduce"] = ar
 
     # -- per-family breakdown: two extra, untimed steps with every family instrumented
-    if do_prof:
+    if do_prof and extras:
         model.profile(True)
         model.profile_reset()
         for _ in range(2):
@@ -603,7 +611,7 @@ def run_leg(ctx, spec, model=None):
         barrier()
         res["prof_all"] = model.profile_read()
         model.profile(False)
-    if do_prof and rank == 0:
+    if do_prof and extras and rank == 0:
         # the probed window: 40 % of a step, started right after the step's enqueue (long enough to average over many kernels)
         res["clock"] = clock_under_load(ctx, lambda: step(all_reduce=False), max(2000, min(60000, int(400 * res["ms_per_step"]))))
     if mode == "train":
@@ -611,7 +619,7 @@ def run_leg(ctx, spec, model=None):
         res["final_loss"] = round(float(timed_out), 4)
     else:
         assert tuple(out.shape) == (B, T, cfg.vocab_size) and bool(torch.isfinite(out).all())
-    if gold_logits is not None:
+    if gold_logits is not None and extras:
         # `out` is the output of the last TIMED-configuration forward (per-family instrumentation does not change results)
         err = float((out[:2].double().cpu() - torch.from_numpy(gold_logits).double()).abs().max())
         bar = 1e-3 if precision in ("fp32", "bf16x3", "f16x2") else 0.15
@@ -868,15 +876,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32, help="rows per GPU")
     ap.add_argument("--samples", type=int, default=246000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the per-family breakdown and the clock (extra untimed "
+                         "steps), the split modes, the other BASELINE configurations, the CPU baseline, the logits against HF fp64, "
+                         "the exposed collective of a multi-rank training leg.  Off: a plain run times the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="run only the CPU leg (no GPU needed) and print its object")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra bf16x3 measurement printed beside the headline")
+    ap.add_argument("--no-alt", action="store_true", help="(--full) skip the bf16x3 / f16x2 measurements beside the fp32 forwards")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the other BASELINE configurations measured beside the headline (configs[2] bf16 fine-tune step, configs[3] "
-                         "large-robust fp32 forward, configs[4] large bf16 fine-tune step at 480000 samples)")
-    ap.add_argument("--side-shrink", type=int, default=1, help="(tests) divide the side legs' per-GPU batch by this factor")
+                    help="(--full) skip the other BASELINE configurations measured beside the headline (configs[2] bf16 fine-tune step, "
+                         "configs[3] large-robust fp32 forward, configs[4] large bf16 fine-tune step at 480000 samples)")
+    ap.add_argument("--side-shrink", type=int, default=1, help="(--full, tests) divide the side legs' per-GPU batch by this factor")
     ap.add_argument("--side-legs", default="configs2_train_bf16,configs3_large_fwd_f32,configs4_large_train_bf16",
-                    help="(tests) comma-separated subset of the side legs to run")
+                    help="(--full, tests) comma-separated subset of the side legs to run")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
     ap.add_argument("--model", choices=["base", "large-robust"], default="base",
                     help="base = wav2vec2-base (the headline); large-robust = 24L/1024d prenorm, LayerNorm convs, conv bias, "
@@ -949,7 +961,7 @@ def main():
     ctx = {"torch": torch, "D": D, "W": wav2vec2, "dev": dev, "world": world, "rank": rank, "comm": comm, "collective": args.collective}
 
     spec = {"model": args.model, "precision": args.precision, "mode": args.mode, "B": args.batch, "L": args.samples,
-            "steps": args.steps, "warmup": args.warmup, "profile": not args.no_profile}
+            "steps": args.steps, "warmup": args.warmup, "profile": not args.no_profile, "extras": args.full}
     res, model, out = run_leg(ctx, spec)
     if args.dump_outputs and rank == 0:
         print(f"bench: outputs of the last timed step -> {dump_outputs(args.dump_outputs, args.mode, res['timed_out'])}", file=sys.stderr)
@@ -958,7 +970,7 @@ def main():
     gemm_family = res["family"]
 
     alts = {}
-    if world == 1 and args.mode == "forward" and args.precision == "fp32" and not args.no_alt:
+    if args.full and world == 1 and args.mode == "forward" and args.precision == "fp32" and not args.no_alt:
         for prec in ("bf16x3", "f16x2"):
             try:                                               # never let the side measurement cost the headline line
                 alts[prec] = measure_alt(ctx, model, x, amask, args.model, B, L, args.steps, max(1, args.warmup), prec, out, res.get("gold_logits"),
@@ -1001,6 +1013,7 @@ def main():
                 roof["traffic"], roof["traffic_source"] = None, "PMC profiles are kept for the BASELINE batch sizes only"
             add_clock(roof, res.get("clock"))
             line["roofline"] = roof
+        if "prof_all" in res:
             fam, unattr, kernels, flops_step = families_of(res, world, args.steps)
             line["families"] = fam
             line["unattributed_ms"] = unattr
@@ -1021,18 +1034,19 @@ def main():
         if "allreduce" in res:
             line["allreduce"] = res["allreduce"]
 
-    # ---- the other BASELINE configurations, measured by this same command beside the headline (every rank takes part: the two
-    # training legs run the bucketed RCCL gradient all-reduce when N > 1).  Each leg is guarded: a failure is reported in its
+    # ---- with --full, the other BASELINE configurations, measured by this same command beside the headline (every rank takes part:
+    # the two training legs run the bucketed RCCL gradient all-reduce when N > 1).  Each leg is guarded: a failure is reported in its
     # object and never costs the headline line.
-    headline_default = (args.model, args.precision, args.mode, args.batch, args.samples) == ("base", "fp32", "forward", 32, 246000)
-    if headline_default and not args.no_side and rank == 0:
+    side_legs = (args.full and not args.no_side
+                 and (args.model, args.precision, args.mode, args.batch, args.samples) == ("base", "fp32", "forward", 32, 246000))
+    if side_legs and rank == 0:
         try:                                                   # insurance: the headline as measured, on disk before anything else runs
             os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
             with open(os.path.join(ROOT, "gpurun_out", "bench_headline.json"), "w") as f:
                 json.dump(line, f)
         except OSError:
             pass
-    if headline_default and not args.no_side:
+    if side_legs:
         del model, out, x, amask, res
         gc.collect()
         k = max(1, args.side_shrink)
@@ -1091,7 +1105,7 @@ def main():
         gc.collect()
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and args.mode == "forward" and args.model == "base" and args.precision == "fp32":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.mode == "forward" and args.model == "base" and args.precision == "fp32":
             try:
                 line["cpu_baseline"] = cpu_baseline(cfg, V.seeded_weights(cfg, seed=0), L, None if gold_wave is None else gold_wave[0])
                 if line["cpu_baseline"]["value"]:

@@ -149,7 +149,7 @@ def _bench_objects(r):
 
 
 def test_bench_two_ranks_report_every_baseline_config_with_the_collective():
-    """The one command the driver runs, at N = 2: `bench.py --gpus 2` self-launches two ranks under torch.distributed.run and its
+    """The driver's command at N = 2 with `--full`: `bench.py --gpus 2` self-launches two ranks under torch.distributed.run and its
     single JSON line must carry, beside the headline, BASELINE configs[2] / [3] / [4] -- the two training legs with the bucketed
     gradient all-reduce INSIDE their timed steps and the measured `allreduce` object (payload, buckets, step time without the
     collective, exposed time, standalone time, bus bandwidth).  The test box has one GPU and RCCL refuses two ranks on one device, so
@@ -159,7 +159,7 @@ def test_bench_two_ranks_report_every_baseline_config_with_the_collective():
     import subprocess
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None), env.pop("RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--full",
            "--side-shrink", "8", "--no-cpu-baseline", "--no-alt"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -186,7 +186,7 @@ def test_bench_two_ranks_report_every_baseline_config_with_the_collective():
 
 
 def test_bench_four_ranks_over_gloo_is_the_drivers_command():
-    """The driver's multi-GPU command line (`bench.py --gpus N`) with four processes on the one GPU over gloo:
+    """The driver's multi-GPU command line (`bench.py --gpus N --full`) with four processes on the one GPU over gloo:
     the base model's 14 gradient buckets all-reduced among more than two ranks inside the timed steps, the loss divisor N x the
     per-rank batch -- and the ONE compact stdout line must carry the measured collective of the training leg (`allreduce.exposed_ms`,
     `standalone_ms`, `busbw_GBps`).  Four ranks, not the scaling run's eight: with this test's own process, no more than six processes
@@ -199,7 +199,7 @@ def test_bench_four_ranks_over_gloo_is_the_drivers_command():
     world = 4
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None), env.pop("RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--steps", "1", "--warmup", "1", "--full",
            "--side-shrink", "16", "--side-legs", "configs2_train_bf16", "--no-cpu-baseline", "--no-alt", "--no-profile"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -236,6 +236,32 @@ def test_bench_dump_outputs_same_inputs_same_logits(tmp_path):
         dumps.append(np.load(out_dir / "logits.npy"))
     assert dumps[0].dtype == np.float32 and dumps[0].shape == (2, 145, 32) and np.isfinite(dumps[0]).all()
     assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_bench_plain_run_times_the_headline_only_and_full_adds_the_rest(tmp_path):
+    """A plain `bench.py` run sets up, warms up, times its steps, dumps and prints the line: no split modes, no CPU baseline, no
+    per-family steps, no check against HF fp64 -- only the roofline of the timed region, which costs no step of its own.  The same
+    command with `--full` adds them (here at 2 x 246000, so that rows 0-1 are the committed fixture's waveforms and the HF fp64 check
+    runs), and its headline computes the same logits bit for bit."""
+    import subprocess
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2"]
+    runs = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        compact, js = _bench_objects(r)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in compact, (name, k)
+        assert compact["steps"] == 2 and compact["warmup"] == 1 and compact["ms_per_step"] > 0 and compact["roofline"]["frac"] > 0
+        runs[name] = (compact, js, np.load(tmp_path / name / "logits.npy"))
+    plain, full = runs["plain"][1], runs["full"][1]
+    for k in ("bf16x3", "f16x2", "cpu_baseline", "families", "max_abs_logit_err"):
+        assert k not in plain, k
+    assert "clock_mhz_under_load" not in plain["roofline"]
+    for k in ("bf16x3", "f16x2", "families", "max_abs_logit_err"):
+        assert k in full, k
+    assert full["max_abs_logit_err"] < 1e-3 and full["bf16x3"]["ms_per_step"] > 0 and "clock_mhz_under_load" in full["roofline"]
+    assert runs["plain"][2].shape == (2, 768, 32) and np.array_equal(runs["plain"][2], runs["full"][2])
 
 
 # ---------------------------------------------------------------- the library's own RCCL collective (csrc/comm.hip) ----------

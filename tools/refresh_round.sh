@@ -7,12 +7,12 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/final; mkdir -p $O; cd $R
 python -m pytest tests -m gpu -q > $O/gpu_tests.log 2>&1; tail -3 $O/gpu_tests.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -6 $O/smoke.log
-# the driver's own command (headline + the three BASELINE legs beside it), then the same line under the launcher with one rank (RCCL group of 1)
+# the driver's command with --full (headline + the three BASELINE legs beside it), then the same line under the launcher with one rank (RCCL group of 1)
 # every bench line is kept twice: the compact stdout line the driver parses (*.json) and the complete object (*_full.json, from gpurun_out/bench_full.json)
 run() { local name=$1; shift; "$@" > $O/$name.json 2> $O/$name.err; cp gpurun_out/bench_full.json $O/${name}_full.json 2>/dev/null; }
-run bench_n1 python bench.py --steps 20 --warmup 5
-run bench_n1_launched python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline
-S="--no-cpu-baseline --no-side"
+run bench_n1 python bench.py --steps 20 --warmup 5 --full
+run bench_n1_launched python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 5 --warmup 2 --full --no-cpu-baseline
+S="--full --no-cpu-baseline --no-side"
 run bench_bf16_n1 python bench.py --precision bf16 $S
 run bench_bf16x3_n1 python bench.py --precision bf16x3 $S
 run bench_f16x2_n1 python bench.py --precision f16x2 $S
