@@ -49,6 +49,7 @@ struct AttnSplitArgs {
     float scale;
     PlaneOut planes;            // optional planes of ctx for the out-projection GEMM (gemm_split_sw.hip)
     int* range_flag;            // f16x2: sticky saturation flag (may be null)
+    const SegTile* tiles;       // SEG: one entry per block of 256 queries of a packed utterance (B = 1, T = stream frames)
 };
 
 
@@ -110,7 +111,9 @@ template <int FMT> struct Terms;
 template <> struct Terms<PF_BF16X3> { static constexpr int N = 6; static constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0}; };
 template <> struct Terms<PF_F16X2> { static constexpr int N = 3; static constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0}; };
 
-template <int FMT>
+// SEG: block x = tile `tiles[x]` of a packed utterance; queries, keys and values are that utterance's frames only, clamped to its
+// last frame, with no additive mask -- a B = 1 run of the utterance alone, bit for bit (same key order, splits and term order)
+template <int FMT, bool SEG = false>
 __global__ __launch_bounds__(NT, 2) void attention_split_kernel(AttnSplitArgs a) {
     constexpr int NP = plane_count(FMT), STAGE = stage_bytes(FMT), NTERM = Terms<FMT>::N;
     constexpr float OPS = FMT == PF_F16X2 ? F16X2_ACT_SCALE : 1.0f;       // scale of q d^-0.5, k, v before their split
@@ -119,15 +122,23 @@ __global__ __launch_bounds__(NT, 2) void attention_split_kernel(AttnSplitArgs a)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
     const int head = blockIdx.y, b = blockIdx.z;
-    const int q0 = (blockIdx.x * NW + wave) * 32;
+    int q0 = (blockIdx.x * NW + wave) * 32;
+    int T = a.T;                          // frames of the sequence this block attends within
+    int64_t row0 = (int64_t)b * a.T;      // its first row in qkv / ctx
+    if constexpr (SEG) {
+        const SegTile st = a.tiles[blockIdx.x];
+        q0 = st.t0 + wave * 32;
+        T = st.nf;
+        row0 = st.f0;
+    }
     const int64_t ld = 3 * (int64_t)a.H;
-    const float* __restrict__ base = a.qkv + (int64_t)b * a.T * ld + head * DH;
-    const int flen = a.frame_len ? a.frame_len[b] : a.T;
+    const float* __restrict__ base = a.qkv + row0 * ld + head * DH;
+    const int flen = (!SEG && a.frame_len) ? a.frame_len[b] : T;
 
     // ---- Q fragments (B operand of S^T), three planes: lane = (query li, half lh), d = 16 st + 8 lh .. + 7, pre-scaled ----
     u32x4 qf[NP][4];
     {
-        const int qr = min(q0 + li, a.T - 1);
+        const int qr = min(q0 + li, T - 1);
         const float* qp = base + (int64_t)qr * ld + 8 * lh;
         const float qs = a.scale * OPS;
 #pragma unroll
@@ -154,12 +165,12 @@ __global__ __launch_bounds__(NT, 2) void attention_split_kernel(AttnSplitArgs a)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int idx = tid + i * NT, r = idx >> 4, sl = idx & 15;
-            const int key = min(k0 + r, a.T - 1);       // clamp: tail rows are masked out below
+            const int key = min(k0 + r, T - 1);         // clamp: tail rows are masked out below
             rk[i] = *reinterpret_cast<const f32x4*>(base + (int64_t)key * ld + a.H + sl * 4);
         }
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            const int key = min(k0 + 4 * v_c + kk, a.T - 1);
+            const int key = min(k0 + 4 * v_c + kk, T - 1);
             rv[kk] = *reinterpret_cast<const f32x2*>(base + (int64_t)key * ld + 2 * a.H + 2 * v_dp);
         }
     };
@@ -194,7 +205,7 @@ __global__ __launch_bounds__(NT, 2) void attention_split_kernel(AttnSplitArgs a)
         for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
 
-    const int ntiles = (a.T + KT - 1) / KT;
+    const int ntiles = (T + KT - 1) / KT;
     load_tile(0);
     store_tile(0);
     __syncthreads();
@@ -235,7 +246,7 @@ __global__ __launch_bounds__(NT, 2) void attention_split_kernel(AttnSplitArgs a)
                 for (int r = 0; r < 16; ++r) s[kt][r] *= 1.0f / (OPS * OPS);
         }
         // ---- mask + online softmax (lane owns query li; keys (r&3) + 8 (r>>2) + 4 lh) ----
-        if (k0 + KT > min(flen, a.T)) {
+        if (k0 + KT > min(flen, T)) {
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -243,7 +254,7 @@ __global__ __launch_bounds__(NT, 2) void attention_split_kernel(AttnSplitArgs a)
                     const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                     float v = s[kt][r];
                     v = key >= flen ? v - 10000.0f : v;       // (1 - mask) * -10000, encoder.py:256-257
-                    v = key >= a.T ? -INFINITY : v;           // tile padding: not a key at all
+                    v = key >= T ? -INFINITY : v;             // tile padding: not a key at all
                     s[kt][r] = v;
                 }
         }
@@ -317,9 +328,9 @@ __global__ __launch_bounds__(NT, 2) void attention_split_kernel(AttnSplitArgs a)
     const int q = q0 + li;
     report_overflow(a.range_flag, ovf);
     ovf = false;
-    if (q < a.T) {
+    if (q < T) {
         const float inv = (1.0f / l_run) * (FMT == PF_F16X2 ? 1.0f / (P_SCALE * OPS) : 1.0f);      // (f16x2: O carries the scales of P and V)
-        const int64_t off = ((int64_t)b * a.T + q) * a.H + head * DH + 4 * lh;
+        const int64_t off = (row0 + q) * a.H + head * DH + 4 * lh;
 #pragma unroll
         for (int d = 0; d < 2; ++d)
 #pragma unroll
@@ -336,29 +347,65 @@ __global__ __launch_bounds__(NT, 2) void attention_split_kernel(AttnSplitArgs a)
 
 bool attention_split_supported(int head_dim) { return head_dim == DH; }
 
+namespace {
+
+// the four instances share one LDS budget per format: two stages of K and V^T planes
+int set_split_attrs() {
+    static std::atomic<bool> attr_set{false};   // (idempotent call; atomic so concurrent host threads agree on the flag)
+    if (attr_set) return W2V2_OK;
+    W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_split_kernel<PF_BF16X3>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage_bytes(PF_BF16X3)));
+    W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_split_kernel<PF_F16X2>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage_bytes(PF_F16X2)));
+    W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_split_kernel<PF_BF16X3, true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage_bytes(PF_BF16X3)));
+    W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_split_kernel<PF_F16X2, true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage_bytes(PF_F16X2)));
+    attr_set = true;
+    return W2V2_OK;
+}
+
+int check_split_args(const float* qkv, const float* ctx, const PlaneOut& pl, int H, int heads, int fmt) {
+    W2V2_REQUIRE(!pl.p || (pl.plane % 4 == 0 && (reinterpret_cast<uintptr_t>(pl.p) & 7) == 0), "attention_split: unaligned planes");
+    W2V2_REQUIRE(heads > 0 && H % heads == 0 && H / heads == DH, "attention_split: head size %d unsupported (64)", heads > 0 ? H / heads : 0);
+    W2V2_REQUIRE((H % 4) == 0 && (reinterpret_cast<uintptr_t>(qkv) & 15) == 0 && (reinterpret_cast<uintptr_t>(ctx) & 15) == 0,
+                 "attention_split: unaligned buffers");
+    W2V2_REQUIRE(fmt == PF_BF16X3 || fmt == PF_F16X2, "attention_split: unknown plane format %d", fmt);
+    return W2V2_OK;
+}
+
+}  // namespace
+
 int launch_attention_split(const float* qkv, const int32_t* frame_len, float* ctx, int B, int T, int H, int heads,
                            hipStream_t s, const PlaneOut* planes, int fmt, int* range_flag) {
     const PlaneOut pl = planes ? *planes : PlaneOut{};
     W2V2_REQUIRE(qkv && (ctx || pl.p) && B > 0 && T > 0 && heads > 0, "attention_split: bad argument");
-    W2V2_REQUIRE(!pl.p || (pl.plane % 4 == 0 && (reinterpret_cast<uintptr_t>(pl.p) & 7) == 0), "attention_split: unaligned planes");
-    W2V2_REQUIRE(H / heads == DH && H % heads == 0, "attention_split: head size %d unsupported (64)", H / heads);
-    W2V2_REQUIRE((H % 4) == 0 && (reinterpret_cast<uintptr_t>(qkv) & 15) == 0 && (reinterpret_cast<uintptr_t>(ctx) & 15) == 0,
-                 "attention_split: unaligned buffers");
-    W2V2_REQUIRE(fmt == PF_BF16X3 || fmt == PF_F16X2, "attention_split: unknown plane format %d", fmt);
-    AttnSplitArgs a{qkv, frame_len, ctx, B, T, H, heads, 1.0f / sqrtf((float)DH), pl, range_flag};
-    static std::atomic<bool> attr_set{false};   // (idempotent call; atomic so concurrent host threads agree on the flag)
-    if (!attr_set) {
-        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_split_kernel<PF_BF16X3>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage_bytes(PF_BF16X3)));
-        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_split_kernel<PF_F16X2>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage_bytes(PF_F16X2)));
-        attr_set = true;
-    }
+    if (int e = check_split_args(qkv, ctx, pl, H, heads, fmt)) return e;
+    AttnSplitArgs a{qkv, frame_len, ctx, B, T, H, heads, 1.0f / sqrtf((float)DH), pl, range_flag, nullptr};
+    if (int e = set_split_attrs()) return e;
     dim3 grid((T + NW * 32 - 1) / (NW * 32), heads, B), block(NT);
     if (fmt == PF_F16X2)
         W2V2_LAUNCH(attention_split_kernel<PF_F16X2>, grid, block, 2 * stage_bytes(PF_F16X2), s, a);
     else
         W2V2_LAUNCH(attention_split_kernel<PF_BF16X3>, grid, block, 2 * stage_bytes(PF_BF16X3), s, a);
+    W2V2_HIP_CHECK(hipGetLastError());
+    return W2V2_OK;
+}
+
+int launch_attention_split_packed(Profiler* prof, const float* qkv, float* ctx, const SegTile* tiles, int ntiles, int64_t frames,
+                                  double sum_nf2, int H, int heads, hipStream_t s, const PlaneOut* planes, int fmt, int* range_flag) {
+    const PlaneOut pl = planes ? *planes : PlaneOut{};
+    W2V2_REQUIRE(qkv && (ctx || pl.p) && tiles, "attention_split_packed: null operand");
+    W2V2_REQUIRE(ntiles > 0 && frames > 0 && frames < INT32_MAX && heads > 0, "attention_split_packed: bad sizes");
+    if (int e = check_split_args(qkv, ctx, pl, H, heads, fmt)) return e;
+    ProfScope ps(prof, FAM_ATTENTION, 4.0 * heads * sum_nf2 * DH, 4.0 * (double)frames * 4.0 * H, s);
+    AttnSplitArgs a{qkv, nullptr, ctx, 1, (int)frames, H, heads, 1.0f / sqrtf((float)DH), pl, range_flag, tiles};
+    if (int e = set_split_attrs()) return e;
+    dim3 grid(ntiles, heads, 1), block(NT);
+    if (fmt == PF_F16X2)
+        W2V2_LAUNCH((attention_split_kernel<PF_F16X2, true>), grid, block, 2 * stage_bytes(PF_F16X2), s, a);
+    else
+        W2V2_LAUNCH((attention_split_kernel<PF_BF16X3, true>), grid, block, 2 * stage_bytes(PF_BF16X3), s, a);
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }

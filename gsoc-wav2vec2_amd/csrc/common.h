@@ -316,7 +316,8 @@ int conv0_chunk_frames();     // conv0 rows per statistics chunk
 // neighbour), applied with that utterance's scale and shift.  ws: conv0_ws_floats(1, L, ...); scale_shift: (nseg, 2, C).
 int launch_conv0_packed(Profiler* prof, const float* wave, const float* kernel, const float* bias, const float* gamma,
                         const float* beta, float* out, float* ws, float* scale_shift, int64_t L, int K, int stride, int C,
-                        float eps, int act, const PackSeg* segs, int nseg, hipStream_t s);
+                        float eps, int act, const PackSeg* segs, int nseg, hipStream_t s,
+                        const PlaneOut* planes = nullptr /* optional planes of out (K = 10, stride 5, C % 4 == 0; out may then be null) */);
 int launch_conv0(Profiler* prof, const float* wave, const float* kernel, const float* bias,
                  const float* gamma, const float* beta, float* out, float* ws, int B, int64_t L,
                  int K, int stride, int C, float eps, int norm_mode, int act, hipStream_t s);
@@ -373,6 +374,9 @@ int launch_attention_packed(Profiler* prof, const float* qkv, float* ctx, const 
 int launch_pack_scatter(const float* src, float* stream, int64_t L, const PackSeg* segs, int nseg, hipStream_t s);
 int launch_pack_gather(const float* stream_rows, float* out, int64_t out_rows, int width, const PackSeg* segs, int nseg,
                        hipStream_t s);
+// zero the stream rows no utterance owns -- [f0 + nf, next f0) behind each, [f0 + nf, frames) behind the last -- of an fp32
+// (frames, width) buffer (x, may be null) and of its planes (pl, may be null): what the segment kernels never write stays defined
+int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int width, const PackSeg* segs, int nseg, hipStream_t s);
 
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
 enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3 };
@@ -388,6 +392,10 @@ int launch_attention_split(const float* qkv, const int32_t* frame_len, float* ct
                            const PlaneOut* planes = nullptr /* optional planes of ctx; ctx itself may then be null */,
                            int fmt = PF_BF16X3 /* PF_F16X2: two fp16 terms / three products per contraction (precision mode 3) */,
                            int* range_flag = nullptr /* f16x2: sticky flag for q / k / v beyond fp16's scaled range */);
+// packed forward, precision modes 2 / 3: the split kernel over the same 256-query tile table as launch_attention_packed, keys and
+// values restricted to the tile's utterance; each utterance's ctx (and planes) bit-identical to launch_attention_split on it alone
+int launch_attention_split_packed(Profiler* prof, const float* qkv, float* ctx, const SegTile* tiles, int ntiles, int64_t frames,
+                                  double sum_nf2, int H, int heads, hipStream_t s, const PlaneOut* planes, int fmt, int* range_flag);
 // qkv16: optional bf16 shadow of qkv (precision mode 1 with head size 64 reads ONLY it; qkv may then be null.  Without it that
 // kernel rounds qkv into scratch first).  ctx may be null when ctx16 is given.
 int launch_attention_x(Profiler* prof, const float* qkv, const uint16_t* qkv16, const int32_t* frame_len, float* ctx, int B, int T, int H,

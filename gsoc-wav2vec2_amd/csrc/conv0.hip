@@ -570,12 +570,19 @@ int conv0_chunk_frames() { return TC; }
 // (The Gram-form statistics of the dense path take 2048-frame blocks, which would straddle utterances.)
 int launch_conv0_packed(Profiler* prof, const float* wave, const float* kernel, const float* bias, const float* gamma,
                         const float* beta, float* out, float* ws, float* scale_shift, int64_t L, int K, int stride, int C,
-                        float eps, int act, const PackSeg* segs, int nseg, hipStream_t s) {
-    W2V2_REQUIRE(wave && kernel && gamma && beta && out && ws && scale_shift && segs && nseg > 0, "conv0_packed: null operand");
+                        float eps, int act, const PackSeg* segs, int nseg, hipStream_t s, const PlaneOut* planes) {
+    const PlaneOut pl = planes ? *planes : PlaneOut{};
+    W2V2_REQUIRE(wave && kernel && gamma && beta && (out || pl.p) && ws && scale_shift && segs && nseg > 0, "conv0_packed: null operand");
     W2V2_REQUIRE(C > 0 && K > 0 && K <= 32 && stride > 0 && L >= K, "conv0_packed: unsupported C=%d K=%d stride=%d L=%lld", C, K,
                  stride, (long long)L);
+    // (as in launch_conv0_x: only the 16-byte-store apply kernel writes planes, so its geometry and alignment are required up front)
+    W2V2_REQUIRE(!pl.p || (K == 10 && stride == 5 && C % 4 == 0 && C / 4 <= 256 && 256 % (C / 4) == 0 && pl.plane % 4 == 0 &&
+                           (reinterpret_cast<uintptr_t>(pl.p) & 7) == 0 &&
+                           ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(kernel) | reinterpret_cast<uintptr_t>(bias) |
+                             reinterpret_cast<uintptr_t>(scale_shift)) & 15) == 0),
+                 "conv0_packed: plane output needs the K = 10 / stride 5 geometry, C %% 4 == 0 and 16-byte aligned operands");
     Conv0Args a{};
-    a.wave = wave; a.kernel = kernel; a.bias = bias; a.gamma = gamma; a.beta = beta; a.out = out;
+    a.wave = wave; a.kernel = kernel; a.bias = bias; a.gamma = gamma; a.beta = beta; a.out = out; a.planes = pl;
     a.L = L; a.K = K; a.stride = stride; a.C = C; a.eps = eps; a.norm_mode = 0; a.act = act;
     a.T0 = (int)(1 + (L - K) / stride);
     a.nchunks = conv0_nchunks(L, K, stride);
@@ -591,7 +598,8 @@ int launch_conv0_packed(Profiler* prof, const float* wave, const float* kernel, 
         W2V2_LAUNCH(conv0_seg_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
     }
     {
-        ProfScope ps(prof, FAM_CONV0_APPLY, flops, 4.0 * (double)L + 4.0 * (double)a.T0 * C, s);
+        const double out_bytes = ((out ? 4.0 : 0.0) + (pl.p ? 2.0 * plane_count(pl.fmt) : 0.0)) * (double)a.T0 * C;
+        ProfScope ps(prof, FAM_CONV0_APPLY, flops, 4.0 * (double)L + out_bytes, s);
         launch_mode<1>(a, 1, s);
     }
     W2V2_HIP_CHECK(hipGetLastError());

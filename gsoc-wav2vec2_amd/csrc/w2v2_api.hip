@@ -740,8 +740,10 @@ struct PackedPlan {
 };
 
 // The inference forward over (B, L).  pk null: the batched forward (w2v2_forward).  pk set: one stream of packed utterances
-// (B = 1, fp32); the three stages that mix frames -- conv0's GroupNorm statistics, the positional conv and attention -- take
-// their segment-aware forms, everything else runs unchanged over the stream.
+// (B = 1; precision modes fp32, bf16x3, f16x2); the three stages that mix frames -- conv0's GroupNorm statistics, the positional
+// conv and attention -- take their segment-aware forms, everything else runs unchanged over the stream.  The stream rows no
+// utterance owns (1-2 behind each) are zeroed in the two buffers only segment kernels write, posout and ctx, so that every
+// row a plane producer reads is defined by the call's own inputs.
 static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, const int32_t* mask, float* out, hipStream_t s,
                         const PackedPlan* pk) {
     const w2v2_config& c = m->cfg;
@@ -801,8 +803,9 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
                p_f1 = site(BT, F, H, 1, H, 0), p_f2 = site(BT, H, F, 1, F, 0) && F % 8 == 0;
     bool any_planes = p_proj || p_qkv || p_out || p_f1 || p_f2;
     for (int i = 1; i < NC; ++i) any_planes = any_planes || cp[i];
+    // (packed: sized for the workspace's capacity, so that a later packed call whose stream fits reuses them as it reuses the workspace)
     if (any_planes)
-        if (int e = w2v2_ensure_planes(m, B, L, fmt)) return e;
+        if (int e = w2v2_ensure_planes(m, B, pk ? m->ws_L : L, fmt)) return e;
     auto PO = [&](const PlaneBuf& b) {
         PlaneOut o;
         o.p = b.p; o.plane = b.plane; o.fmt = fmt; o.range_flag = m->range_flag;
@@ -850,7 +853,8 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
     m->acts_skipped.clear();
     // (planes: a conv output whose one reader streams its planes is written ONLY as planes, like the bf16-only outputs of mode 1)
     auto planes_only_out = [&](int i) { return i + 1 < NC && cp[i + 1] && !keep; };
-    // the fused plane output needs conv0's 16-byte-store kernel (K = 10, stride 5); other geometries write fp32 and split it
+    // the fused plane output needs conv0's 16-byte-store kernel (K = 10, stride 5); other geometries write fp32 and split it.  (The
+    // packed group-norm pass, launch_conv0_packed, applies through the same kernel and writes exactly what the dense pass writes.)
     const bool fused = NC > 1 && cp[1] && c.kernal_sizes[0] == 10 && c.strides[0] == 5 && 256 % (c.filter_sizes[0] / 4) == 0 && c.filter_sizes[0] / 4 <= 256;
     // "convI" is not readable back exactly when the code below hands its producer a null fp32 destination (this used to be a
     // second, looser predicate): conv0 fused into planes; a plane-fed GEMM whose output also goes out as planes only; a LayerNorm-mode
@@ -863,20 +867,21 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
     };
     for (int i = 0; i + 1 < NC; ++i)
         if (f32_skipped(i)) m->acts_skipped.push_back("conv" + std::to_string(i));
-    if (pk && !layer_mode) {     // GroupNorm statistics per utterance, over exactly its rows
-        if (int e = launch_conv0_packed(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr, fe(0, "/layer_norm/gamma"),
-                                        fe(0, "/layer_norm/beta"), m->conv[0], m->conv0_ws, m->pk_scale, L, c.kernal_sizes[0], c.strides[0],
-                                        c.filter_sizes[0], 1e-5f, act_ew, pk->segs, pk->nseg, s))
-            return e;
-    } else {
+    {
         const PlaneOut po = fused ? PO(m->conv48[0]) : PlaneOut{};
         const bool f32_too = !(NC > 1 && cp[1]) || keep || !fused;
-        if (int e = launch_conv0_x(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr,
-                                   fe(0, "/layer_norm/gamma"), fe(0, "/layer_norm/beta"),
-                                   (w2v2_conv_out_bf16_only(m, 0, sh) || w2v2_conv_ln_bf16_only(m, 0, sh) || !f32_too) ? nullptr : m->conv[0],
-                                   sh ? m->conv16[0] : nullptr, m->conv0_ws, B, L, c.kernal_sizes[0], c.strides[0],
-                                   c.filter_sizes[0], 1e-5f, layer_mode ? 2 : 0, act_ew, s, fused ? &po : nullptr))      // (layer mode: conv + LayerNorm + GELU in one pass)
+        if (pk && !layer_mode) {     // GroupNorm statistics per utterance, over exactly its rows
+            if (int e = launch_conv0_packed(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr, fe(0, "/layer_norm/gamma"),
+                                            fe(0, "/layer_norm/beta"), f32_too ? m->conv[0] : nullptr, m->conv0_ws, m->pk_scale, L, c.kernal_sizes[0],
+                                            c.strides[0], c.filter_sizes[0], 1e-5f, act_ew, pk->segs, pk->nseg, s, fused ? &po : nullptr))
+                return e;
+        } else if (int e = launch_conv0_x(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr,
+                                          fe(0, "/layer_norm/gamma"), fe(0, "/layer_norm/beta"),
+                                          (w2v2_conv_out_bf16_only(m, 0, sh) || w2v2_conv_ln_bf16_only(m, 0, sh) || !f32_too) ? nullptr : m->conv[0],
+                                          sh ? m->conv16[0] : nullptr, m->conv0_ws, B, L, c.kernal_sizes[0], c.strides[0],
+                                          c.filter_sizes[0], 1e-5f, layer_mode ? 2 : 0, act_ew, s, fused ? &po : nullptr)) {    // (layer mode: conv + LayerNorm + GELU in one pass)
             return e;
+        }
         if (NC > 1 && cp[1] && !fused)
             if (int e = launch_split_planes(m->conv[0], m->conv48[0].p, m->conv48[0].plane, (int64_t)B * conv_T[0] * c.filter_sizes[0], fmt, m->range_flag, s))
                 return e;
@@ -919,10 +924,11 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
         if (int e = launch_frame_lengths(pf, mask, m->frame_len, B, L, c.kernal_sizes, c.strides, c.num_conv_layers, s)) return e;
         flen = m->frame_len;
     }
-    if (pk) {                            // each utterance zero-padded at its own edges
+    if (pk) {                            // each utterance zero-padded at its own edges (the fp32 kernel in every mode, as the dense split modes)
         if (int e = launch_pos_conv_packed(pf, m->proj, m->pos_wg, m->P("encoder/pos_conv_embed/conv/bias"), m->posout, pk->pos_tiles, pk->npos,
                                            T, H, c.num_conv_pos_embeddings, c.num_conv_pos_embedding_groups, act, s))
             return e;
+        if (int e = launch_pack_zero_gaps(m->posout, nullptr, T, H, pk->segs, pk->nseg, s)) return e;
     } else if (w2v2_pos_conv_bf16_ok(m)) {      // precision mode 1: one batched bf16 GEMM over (sample, group); m->t0 is free here
         if (int e = w2v2_ensure_pos16(m, B, T, s)) return e;
         if (int e = launch_pos_conv_bf16(pf, m->proj, m->pos_w16, m->P("encoder/pos_conv_embed/conv/bias"), flen, m->posout, nullptr,
@@ -935,6 +941,11 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
     }
     const PlaneOut po_attn = p_qkv ? PO(m->attn_in48) : PlaneOut{}, po_ctx = p_out ? PO(m->ctx48) : PlaneOut{},
                    po_ffn_in = p_f1 ? PO(m->ffn_in48) : PlaneOut{};
+    if (pk)                              // (the attention kernels write only the utterances' rows of ctx and of its planes, in every layer)
+        if (int e = launch_pack_zero_gaps(m->ctx, p_out ? &po_ctx : nullptr, T, H, pk->segs, pk->nseg, s)) return e;
+    // packed, precision modes 2 / 3: the split attention's segment form where the dense forward takes the split kernel
+    const bool split_attn = m->precision >= W2V2_PRECISION_BF16X3 && attention_split_supported(H / c.num_heads) && H % 4 == 0 &&
+                            tune_int("W2V2_SPLIT_ATTN", 1) != 0;
     if (!prenorm)
         if (int e = launch_layer_norm_x(pf, m->posout, m->hs[0], m->P("encoder/layer_norm/gamma"),
                                         m->P("encoder/layer_norm/beta"), BT, H, eps, 0, sh ? m->hs16[0] : nullptr, s, p_qkv ? &po_attn : nullptr))
@@ -970,10 +981,15 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
         const bool ctx_fused = p_out && attention_split_supported(H / c.num_heads) && H % 4 == 0 && tune_int("W2V2_SPLIT_ATTN", 1) != 0;
         PlaneOut po_flag;                                    // (no planes wanted: the split attention still reports f16x2 saturation)
         po_flag.range_flag = m->range_flag;
-        if (pk) {                        // queries and keys of one utterance per block
+        const PlaneOut* attn_pl = ctx_fused ? &po_ctx : (pm ? &po_flag : nullptr);
+        if (pk && split_attn) {          // queries and keys of one utterance per block
+            if (int e = launch_attention_split_packed(pf, m->qkv, (ctx_fused && !keep) ? nullptr : m->ctx, pk->attn_tiles, pk->nattn, T, pk->sum_nf2, H,
+                                                      c.num_heads, s, attn_pl, fmt, attn_pl ? attn_pl->range_flag : nullptr))
+                return e;
+        } else if (pk) {
             if (int e = launch_attention_packed(pf, m->qkv, m->ctx, pk->attn_tiles, pk->nattn, T, pk->sum_nf2, H, c.num_heads, s)) return e;
         } else if (int e = launch_attention_x(pf, attn16 ? nullptr : m->qkv, attn16 ? m->qkv16 : nullptr, flen, (ctx16_only || (ctx_fused && !keep)) ? nullptr : m->ctx, B, T, H,
-                                              c.num_heads, attn16 ? m->ctx16 : nullptr, s, ctx_fused ? &po_ctx : (pm ? &po_flag : nullptr))) {
+                                              c.num_heads, attn16 ? m->ctx16 : nullptr, s, attn_pl)) {
             return e;
         }
         if (p_out && !ctx_fused)
@@ -1047,7 +1063,8 @@ int w2v2_forward_packed(w2v2_model* m, const float* wave, int32_t n, const int64
         return W2V2_ESTATE;
     }
     static const char* modes[] = {"fp32", "bf16", "bf16x3", "f16x2"};
-    W2V2_REQUIRE(m->precision == W2V2_PRECISION_FP32, "forward_packed: precision mode %s is not supported (fp32 only)",
+    W2V2_REQUIRE(m->precision == W2V2_PRECISION_FP32 || m->precision == W2V2_PRECISION_BF16X3 || m->precision == W2V2_PRECISION_F16X2,
+                 "forward_packed: precision mode %s is not supported (fp32, bf16x3, f16x2)",
                  (m->precision >= 0 && m->precision <= 3) ? modes[m->precision] : "?");
     W2V2_REQUIRE(n >= 1, "forward_packed: %d utterances (need at least one)", n);
     W2V2_REQUIRE(cu_samples[0] == 0, "forward_packed: cu_samples[0] = %lld, must be 0", (long long)cu_samples[0]);
@@ -1373,6 +1390,46 @@ int w2v2_op_pos_conv(const float* x, const float* wg, const float* bias, const i
 int w2v2_op_attention(const float* qkv, const int32_t* frame_len, float* ctx, int32_t B, int32_t T,
                       int32_t H, int32_t num_heads, void* stream) {
     return launch_attention(nullptr, qkv, frame_len, ctx, B, T, H, num_heads, reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_attention_packed(const float* qkv, int32_t n, const int32_t* cu_frames, float* ctx, uint16_t* planes, int64_t plane_stride,
+                             int32_t* range_flag, int32_t H, int32_t heads, void* stream) {
+    W2V2_REQUIRE(qkv && cu_frames && (ctx || planes), "op_attention_packed: null operand");
+    W2V2_REQUIRE(n >= 1 && cu_frames[0] == 0, "op_attention_packed: need n >= 1 utterances and cu_frames[0] == 0");
+    W2V2_REQUIRE(heads > 0 && H % heads == 0, "op_attention_packed: bad sizes H=%d heads=%d", H, heads);
+    const int mode = gemm_get_precision();
+    W2V2_REQUIRE(mode != W2V2_PRECISION_BF16, "op_attention_packed: precision mode bf16 is not supported (fp32, bf16x3, f16x2)");
+    const int dh = H / heads, fmt = mode == W2V2_PRECISION_F16X2 ? PF_F16X2 : PF_BF16X3;
+    const bool split = mode >= W2V2_PRECISION_BF16X3 && attention_split_supported(dh) && H % 4 == 0 && tune_int("W2V2_SPLIT_ATTN", 1) != 0;
+    W2V2_REQUIRE(split || ctx, "op_attention_packed: this mode and head size run the fp32 kernel, which needs ctx");
+    W2V2_REQUIRE(!planes || mode >= W2V2_PRECISION_BF16X3, "op_attention_packed: planes are written in precision modes bf16x3 / f16x2 only");
+    // the tile table of the packed forward, utterances back to back
+    const int AR = attention_packed_rows(dh);
+    std::vector<SegTile> tiles;
+    double sum_nf2 = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const int nf = cu_frames[i + 1] - cu_frames[i];
+        W2V2_REQUIRE(nf >= 1, "op_attention_packed: utterance %d has %d frames (need at least one)", i, nf);
+        for (int t0 = 0; t0 < nf; t0 += AR) tiles.push_back(SegTile{cu_frames[i], nf, t0, 0});
+        sum_nf2 += (double)nf * (double)nf;
+    }
+    const int64_t frames = cu_frames[n];
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    SegTile* dt = nullptr;
+    W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dt), tiles.size() * sizeof(SegTile)));
+    int e = hipMemcpyAsync(dt, tiles.data(), tiles.size() * sizeof(SegTile), hipMemcpyHostToDevice, s) == hipSuccess &&
+                    hipStreamSynchronize(s) == hipSuccess ? W2V2_OK : W2V2_EHIP;
+    if (e) set_error("op_attention_packed: staging the tile table failed");
+    PlaneOut pl;
+    pl.p = planes; pl.plane = plane_stride; pl.fmt = fmt; pl.range_flag = range_flag;
+    if (!e && split) {
+        e = launch_attention_split_packed(nullptr, qkv, ctx, dt, (int)tiles.size(), frames, sum_nf2, H, heads, s, planes ? &pl : nullptr, fmt, range_flag);
+    } else if (!e) {      // the fp32 segment kernel, then (modes 2 / 3) the planes of its output, as the packed forward does
+        e = launch_attention_packed(nullptr, qkv, ctx, dt, (int)tiles.size(), frames, sum_nf2, H, heads, s);
+        if (!e && planes) e = launch_split_planes(ctx, planes, plane_stride, frames * H, fmt, range_flag, s);
+    }
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(dt);
+    return e;
 }
 int w2v2_op_frame_lengths(const int32_t* mask, int32_t* frame_len, int32_t B, int64_t L,
                           const int32_t* kernal_sizes, const int32_t* strides, int32_t num_layers, void* stream) {

@@ -124,6 +124,7 @@ PROTOTYPES = {
     "w2v2_op_weight_norm_regroup": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "w2v2_op_pos_conv": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "w2v2_op_attention": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P]),
+    "w2v2_op_attention_packed": (C.c_int, [_P, _I32, _P, _P, _P, _I64, _P, _I32, _I32, _P]),
     "w2v2_op_frame_lengths": (C.c_int, [_P, _P, _I32, _I64, C.POINTER(_I32), C.POINTER(_I32), _I32, _P]),
 }
 

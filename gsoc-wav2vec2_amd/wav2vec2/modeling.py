@@ -541,7 +541,9 @@ class TFKerasModel(Layer):
 
     def predict_packed(self, waveforms):
         """Inference on utterances of different lengths in one call, each computed exactly as `self(wave[None])` computes it
-        alone: no padding enters any statistic and no frame attends across utterances (w2v2_forward_packed, fp32 only).
+        alone: no padding enters any statistic and no frame attends across utterances (w2v2_forward_packed).  Precision modes
+        "fp32", "bf16x3" and "f16x2" (set_precision); "bf16" raises.  In "f16x2" the contract of set_precision holds: poll
+        `range_overflow()` after the calls whose activations are not known to stay in range.
         `waveforms`: a list of 1-D numpy arrays or torch tensors, each already normalised.  Returns a list of
         (T_i, vocab | hidden) tensors, T_i = num_frames(len_i): views of one packed output."""
         torch = _require_gpu()

@@ -192,9 +192,11 @@ int w2v2_forward(w2v2_model* m, const float* wave_dev, int32_t B, int64_t L,
  *   wave_dev         (sum len_i) fp32, the utterances back to back, each already normalised
  *   cu_samples_host  (n + 1) int64 prefix offsets, cu_samples_host[0] = 0
  *   out_dev          (sum T_i, vocab | hidden), T_i = w2v2_num_frames(len_i); utterance i at row sum_{j<i} T_j
- * W2V2_PRECISION_FP32 only (W2V2_EINVAL naming the mode otherwise); every len_i must give T_i >= 1.
+ * Precision modes W2V2_PRECISION_FP32, _BF16X3 and _F16X2; W2V2_PRECISION_BF16 gives W2V2_EINVAL naming the mode.  In
+ * f16x2 the same range contract as w2v2_forward holds: poll w2v2_range_overflow.  Every len_i must give T_i >= 1.
  * The utterances run as one stream with each start aligned to the conv stack's total stride; only conv0's GroupNorm
- * statistics, the positional conv and attention see utterance boundaries.  The workspace is sized from the aligned
+ * statistics, the positional conv and attention see utterance boundaries.  The 1-2 stream rows behind each utterance
+ * are zeroed where only those stages would write them, so nothing of an earlier call is read.  The workspace is sized from the aligned
  * stream length, rounded up; a later packed call whose stream fits reuses it.  Synchronises with the previous packed
  * call's table upload (host-side), otherwise enqueued on `stream`. */
 int w2v2_forward_packed(w2v2_model* m, const float* wave_dev, int32_t n, const int64_t* cu_samples_host,
@@ -507,6 +509,17 @@ int w2v2_op_pos_conv(const float* x_dev, const float* wg_dev, const float* bias_
  *   materialised. */
 int w2v2_op_attention(const float* qkv_dev, const int32_t* frame_len_dev, float* ctx_dev,
                       int32_t B, int32_t T, int32_t H, int32_t num_heads, void* stream);
+
+/* Attention of n packed utterances (the packed forward's segment kernels): utterance i owns rows
+ * [cu_frames_host[i], cu_frames_host[i + 1]) of qkv (rows, 3H) and ctx (rows, H), back to back, and attends only
+ * within them, unmasked -- each as w2v2_op_attention computes it alone (B = 1, T = its frames, no frame_len).
+ * Dispatches on w2v2_op_set_precision: fp32 kernel in mode 0; the split kernel in modes 2 / 3 (head size 64, else the
+ * fp32 kernel and a split of its output); mode 1 (bf16) gives W2V2_EINVAL.  planes_dev (optional, modes 2 / 3):
+ * the planes of ctx, plane_stride elements apart (W2V2_PLANES_* of the mode); ctx_dev may then be null on the split
+ * kernel.  range_flag_dev (optional): f16x2 sticky saturation flag.  Stages its tile table synchronously. */
+int w2v2_op_attention_packed(const float* qkv_dev, int32_t n, const int32_t* cu_frames_host, float* ctx_dev,
+                             uint16_t* planes_dev, int64_t plane_stride, int32_t* range_flag_dev,
+                             int32_t H, int32_t heads, void* stream);
 
 /* frame_len[b] = conv-stack length arithmetic applied to sum(mask[b, :])
  * (modeling.py:201-204). */

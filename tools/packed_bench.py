@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Throughput of three ways to run one set of differently sized utterances through the base fp32 Wav2Vec2ForCTC (seeded weights):
+"""Throughput of three ways to run one set of differently sized utterances through the base Wav2Vec2ForCTC (seeded weights), in
+one precision mode (--precision fp32 | bf16x3 | f16x2, default fp32; the mode holds for all three forms):
 
   packed  one predict_packed call (w2v2_forward_packed): each utterance exact, no padded frame computed;
   b1      a B = 1 loop: exact, one forward per utterance (a new length re-sizes the workspace, as for any caller);
@@ -9,7 +10,7 @@
 The lengths are drawn once from a seed, uniform in [--min-s, --max-s] seconds (default 64 utterances of 1.5-35 s, roughly
 LibriSpeech test-clean's range).  Prints one JSON line: audio-s/s per form, ms per pass, and the padded batch's padding fraction.
 
-    python tools/packed_bench.py [--n 64] [--steps 3] [--warmup 1] [--forms packed,b1,padded]
+    python tools/packed_bench.py [--n 64] [--steps 3] [--warmup 1] [--forms packed,b1,padded] [--precision fp32]
 """
 import argparse
 import json
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--forms", default="packed,b1,padded")
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "f16x2"])
     args = ap.parse_args()
 
     import torch
@@ -43,6 +45,7 @@ def main():
     cfg = wav2vec2.Wav2Vec2Config()
     m = wav2vec2.Wav2Vec2ForCTC(cfg, input_shape=(1, 2048))
     m.set_weights(V.seeded_weights(cfg, seed=1))
+    m.set_precision(args.precision)
     rng = np.random.default_rng(args.seed)
     lens = rng.integers(int(args.min_s * SR), int(args.max_s * SR) + 1, size=args.n)
     waves = [torch.randn(int(n), device="cuda") for n in lens]
@@ -62,7 +65,7 @@ def main():
         m(padded)
 
     forms = {"packed": run_packed, "b1": run_b1, "padded": run_padded}
-    res = {"n": args.n, "audio_s": round(audio_s, 2), "min_len": int(lens.min()), "max_len": Lmax,
+    res = {"precision": args.precision, "n": args.n, "audio_s": round(audio_s, 2), "min_len": int(lens.min()), "max_len": Lmax,
            "padding_fraction": round(1.0 - float(lens.sum()) / (args.n * Lmax), 4),
            "frames": int(sum(m.num_frames(int(n)) for n in lens)), "padded_frames": args.n * m.num_frames(Lmax)}
     for name in args.forms.split(","):
@@ -89,6 +92,8 @@ def main():
         res["packed_over_padded"] = round(res["packed"]["audio_s_per_s"] / res["padded"]["audio_s_per_s"], 3)
     if "packed" in res and "b1" in res:
         res["packed_over_b1"] = round(res["packed"]["audio_s_per_s"] / res["b1"]["audio_s_per_s"], 3)
+    if args.precision == "f16x2":
+        res["range_overflow"] = m.range_overflow()
     print(json.dumps(res))
 
 
