@@ -1,0 +1,378 @@
+// CTC forced alignment: the single best frame-level path (Viterbi) that spells a given label string, for n utterances at once.
+//
+// Definition (tests/align_reference.py implements exactly this).  x_t(v) is the fp32 logit widened to fp64; ext is the label
+// string with blanks interleaved, S = 2U + 1 states, ext[2k] = blank, ext[2k + 1] = l_k.
+//   delta_0(0) = x_0(blank); delta_0(1) = x_0(l_0) if U >= 1; every other state -inf.
+//   t >= 1: delta_t(s) = m + x_t(ext[s]), m and the backpointer bp picked in this order, every comparison a strict `>` done as
+//   compare and select (no fmax: it treats NaN differently):
+//     m = delta_{t-1}(s), bp = 0;
+//     if s >= 1 and delta_{t-1}(s-1) > m:                                          m = delta_{t-1}(s-1), bp = 1;
+//     if s >= 2, ext[s] != blank, ext[s] != ext[s-2] and delta_{t-1}(s-2) > m:     m = delta_{t-1}(s-2), bp = 2.
+//   Ties prefer staying, then advancing by one.  End state: U >= 1: S-1 if delta_{T-1}(S-1) > delta_{T-1}(S-2), else S-2;
+//   U = 0: state 0 (all blank).  The path follows the backpointers down to t = 0.
+// The recursion runs on raw logits (sum_t lse_t is common to every path); every step is one IEEE fp64 compare-select and add in a
+// fixed order, so the decisions are bit-identical to an fp64 numpy loop on every input, ties and NaN included.
+// Outputs per frame (sum T_i, back to back): token[t] = ext[s_t]; label_index[t] = k for state 2k+1, -1 for a blank;
+// frame_logp[t] = x_t(token[t]) - lse_t as fp32, lse_t the fp64 log-sum-exp of the frame (fp32 max, then lane-strided fp64 sums
+// and a fixed butterfly, as ctc_softmax_kernel).  Per utterance: score = delta_{T-1}(s_end) - sum_t lse_t (fp64).
+// An utterance is feasible only if T >= U + R, R = #{k >= 1: l_k = l_{k-1}}: otherwise score = -inf, token = label_index = -1 and
+// frame_logp = NaN.  A label outside [0, V) or equal to the blank (labels are on the device): score = NaN, the same -1 / NaN rows.
+//
+// Structure.  align_lse_kernel: one wave per frame, lse_t into the workspace (fully parallel).  align_viterbi_kernel: one block per
+// utterance.  A thread owns P consecutive state pairs (2k blank, 2k+1 label k) in registers as fp64; per step the only value that
+// crosses threads is the odd state of a thread's last pair, through a double-buffered LDS array behind ONE LDS-only barrier
+// (s_waitcnt lgkmcnt(0); s_barrier -- as ctc.hip: the step's fire-and-forget backpointer stores are not drained).  The P + 1
+// emissions a step needs are loaded PF steps ahead.  Backpointers: 2 bits per state, 4 per pair; a thread collects its 4P bits of
+// G = 8 / P steps in one 32-bit word and stores it (a plain vector store) to the workspace: word (g, tid) of an utterance holds
+// steps 1 + gG .. gG + G, i.e. T S / 4 bytes per utterance, rounded up to the block's thread count.  P comes from the largest U
+// at launch (1, 2, 4 while at most 256 threads suffice, i.e. up to 1023 labels; 8 beyond, up to 1024 threads: 8191 labels).  After
+// the sweep the same block backtracks: the state moves down by at most 2 per step, so the backpointer words of the next C frames lie
+// in a window of C frames x C pairs; the block loads that window into LDS, one lane walks it, and the block writes the C frames'
+// outputs (token, label index, frame_logp) in parallel.  No atomics: two identical calls give identical bits.
+#include "common.h"
+
+#include <algorithm>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <vector>
+
+namespace w2v2 {
+namespace {
+
+constexpr int ALIGN_MAX_THREADS = 1024;
+constexpr int ALIGN_CHUNK = 128;             // frames per backtrace window
+constexpr int ALIGN_WIN_WORDS = 2304;        // >= ((C - 1) / G + 2) ((C - 1) / P + 2) <= 2193 for C = 128, any P
+
+struct AlignSeg {
+    int64_t row0;      // first logits row
+    int64_t label0;    // first label
+    int64_t out0;      // first output frame
+    int64_t bp0;       // first backpointer word
+    int32_t T, U;
+};
+
+struct AlignArgs {
+    const float* logits;
+    const int32_t* labels;
+    const AlignSeg* segs;
+    double* lse;            // (sum T_i), indexed like the outputs
+    uint32_t* bp;           // backpointer words
+    int32_t* token;
+    int32_t* label_index;
+    float* frame_logp;
+    double* score;
+    int V, blank, nt;       // nt: threads per block (= backpointer words per step group)
+};
+
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// lse_t of frame t of utterance blockIdx.y: one wave per frame, grid.x covers the longest utterance
+__global__ __launch_bounds__(256) void align_lse_kernel(AlignArgs a) {
+    const AlignSeg sg = a.segs[blockIdx.y];
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= sg.T) return;
+    const int lane = threadIdx.x & 63;
+    const float* __restrict__ r = a.logits + (sg.row0 + t) * a.V;
+    float m = -INFINITY;
+    for (int v = lane; v < a.V; v += 64) m = fmaxf(m, r[v]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    double acc = 0.0;
+    for (int v = lane; v < a.V; v += 64) acc += exp((double)r[v] - (double)m);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane == 0) a.lse[sg.out0 + t] = (double)m + log(acc);
+}
+
+// number of threads of the block for which pred holds (wave ballots, then the waves in order)
+__device__ __forceinline__ int block_count(bool pred, int* red) {
+    const unsigned long long b = __ballot(pred);
+    __syncthreads();                                    // (red may still be read by the previous call)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = __popcll(b);
+    __syncthreads();
+    int c = 0;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) c += red[i];
+    return c;
+}
+
+template <int P>
+__global__ __launch_bounds__(P == 8 ? ALIGN_MAX_THREADS : 256) void align_viterbi_kernel(AlignArgs a) {
+    constexpr int G = 8 / P;                 // steps per backpointer word
+    constexpr int PF = P == 8 ? 2 : 8;       // steps the emissions are loaded ahead (a multiple of G; P = 8: registers)
+    constexpr double NEG = -__builtin_inf();
+    __shared__ double xv[2][ALIGN_MAX_THREADS + 1];      // exchange: entry i + 1 = thread i's last odd state; entry 0 = "state -1"
+    __shared__ uint32_t win[ALIGN_WIN_WORDS];            // backtrace window of backpointer words
+    __shared__ int path[ALIGN_CHUNK + 1];
+    __shared__ int red[ALIGN_MAX_THREADS / 64];
+    __shared__ double fin[2];
+    __shared__ int s_cur;
+
+    const AlignSeg sg = a.segs[blockIdx.x];
+    const int tid = threadIdx.x, NT = a.nt, T = sg.T, U = sg.U, V = a.V, blank = a.blank;
+    const float* __restrict__ lg = a.logits + sg.row0 * V;
+    const int32_t* __restrict__ lab = a.labels + sg.label0;
+    const int k0 = tid * P;                  // this thread's pairs: k0 .. k0 + P - 1
+
+    // labels of the thread's pairs (the blank past U), the skip flags, and the two per-utterance checks
+    int lj[P];
+    unsigned skipm = 0;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const int k = k0 + j;
+        lj[j] = blank;
+        if (k < U) {
+            const int l = lab[k];
+            bad |= l < 0 || l >= V || l == blank;
+            if (k >= 1 && l != lab[k - 1]) skipm |= 1u << j;
+            lj[j] = l;
+        }
+    }
+    const int nbad = block_count(bad, red);
+    int R = 0;                                           // repeats l_k = l_{k-1}
+#pragma unroll
+    for (int j = 0; j < P; ++j) R += block_count(k0 + j >= 1 && k0 + j < U && !(skipm >> j & 1u), red);
+    if (nbad || T < U + R) {
+        const double sc = nbad ? __builtin_nan("") : NEG;
+        for (int t = tid; t < T; t += NT) {
+            a.token[sg.out0 + t] = -1;
+            a.label_index[sg.out0 + t] = -1;
+            a.frame_logp[sg.out0 + t] = __builtin_nanf("");
+        }
+        if (tid == 0) a.score[blockIdx.x] = sc;
+        return;                                          // (block-uniform)
+    }
+
+    // ---- sweep ----
+    double ev[P], od[P];                                 // delta(2k), delta(2k + 1) of the thread's pairs
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        ev[j] = NEG;
+        od[j] = NEG;
+    }
+    if (tid == 0) {
+        ev[0] = (double)lg[blank];
+        if (U >= 1) od[0] = (double)lg[lj[0]];
+    }
+    for (int i = tid; i < 2 * (ALIGN_MAX_THREADS + 1); i += NT) (&xv[0][0])[i] = NEG;
+    __syncthreads();
+    xv[0][tid + 1] = od[P - 1];
+    uint32_t* __restrict__ bpw = a.bp + sg.bp0 + tid;
+    float qb[PF], ql[PF][P];                             // x_t(blank), x_t(l_k) of the next PF steps
+#pragma unroll
+    for (int i = 0; i < PF; ++i) {
+        const float* __restrict__ row = lg + (int64_t)min(1 + i, T - 1) * V;
+        qb[i] = row[blank];
+#pragma unroll
+        for (int j = 0; j < P; ++j) ql[i][j] = row[lj[j]];
+    }
+    uint32_t word = 0;
+    auto step = [&](int t, float yb, const float* yl, int slot) {
+        lds_barrier();
+        const double nb = xv[(t - 1) & 1][tid];          // delta_{t-1}(2 k0 - 1)
+        const double xb = (double)yb;
+        uint32_t bits = 0;
+#pragma unroll
+        for (int j = P - 1; j >= 0; --j) {               // downwards: od[j - 1] is still the previous step's
+            const double po = j ? od[j - 1] : nb;
+            double me = ev[j];
+            uint32_t be = 0;
+            if (po > me) { me = po; be = 1; }
+            double mo = od[j];
+            uint32_t bo = 0;
+            if (ev[j] > mo) { mo = ev[j]; bo = 1; }
+            if ((skipm >> j & 1u) && po > mo) { mo = po; bo = 2; }
+            const int k = k0 + j;
+            od[j] = k < U ? mo + (double)yl[j] : NEG;
+            ev[j] = k <= U ? me + xb : NEG;
+            bits |= (be | bo << 2) << (4 * j);
+        }
+        xv[t & 1][tid + 1] = od[P - 1];
+        word |= bits << (slot * 4 * P);
+    };
+    // whole groups of PF steps without a branch between them (the compiler's wait counts then stay exact), then the tail
+    int t0 = 1;
+    for (; t0 + PF <= T; t0 += PF) {
+#pragma unroll
+        for (int i = 0; i < PF; ++i) {
+            step(t0 + i, qb[i], ql[i], i % G);
+            if (i % G == G - 1) {
+                bpw[(int64_t)((t0 + i - 1) / G) * NT] = word;
+                word = 0;
+            }
+            const float* __restrict__ row = lg + (int64_t)min(t0 + i + PF, T - 1) * V;      // (block-uniform row, per-lane column)
+            qb[i] = row[blank];
+#pragma unroll
+            for (int j = 0; j < P; ++j) ql[i][j] = row[lj[j]];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < PF; ++i) {
+        if (t0 + i < T) {                                // (block-uniform)
+            step(t0 + i, qb[i], ql[i], i % G);
+            if (i % G == G - 1 || t0 + i == T - 1) {
+                bpw[(int64_t)((t0 + i - 1) / G) * NT] = word;
+                word = 0;
+            }
+        }
+    }
+    // end state
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        if (k0 + j == U) fin[0] = ev[j];                 // delta(S - 1)
+        if (k0 + j + 1 == U) fin[1] = od[j];             // delta(S - 2)
+    }
+    __syncthreads();                                     // (also makes the backpointer stores visible to the block)
+    const bool last_odd = U >= 1 && !(fin[0] > fin[1]);
+    const double dend = last_odd ? fin[1] : fin[0];
+    if (tid == 0) s_cur = last_odd ? 2 * U - 1 : 2 * U;
+
+    // score: sum_t lse_t by wave 0 in a fixed order (lane l: frames l, l + 64, ...; then a butterfly), independent of P and NT
+    if (tid < 64) {
+        const double* __restrict__ ls = a.lse + sg.out0;
+        double acc = 0.0;
+#pragma unroll 8
+        for (int t = tid; t < T; t += 64) acc += ls[t];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        if (tid == 0) a.score[blockIdx.x] = dend - acc;
+    }
+
+    // ---- backtrace, ALIGN_CHUNK frames per window ----
+    const uint32_t* __restrict__ bpg = a.bp + sg.bp0;
+    int t_hi = T - 1;
+    __syncthreads();
+    while (true) {
+        const int t_lo = max(0, t_hi - ALIGN_CHUNK);
+        const int s_hi = s_cur;
+        // frames (t_lo, t_hi] read the words of step groups (t - 1) / G and of pairs (s_hi >> 1) - C + 1 .. s_hi >> 1
+        const int ph = s_hi >> 1, pl = max(0, ph - ALIGN_CHUNK + 1);
+        const int w_lo = pl / P, ncol = ph / P - w_lo + 1;
+        const int g_lo = t_lo / G, nrow = t_hi > t_lo ? (t_hi - 1) / G - g_lo + 1 : 0;
+        for (int i = tid; i < nrow * ncol; i += NT) {
+            const int r = i / ncol, c = i - r * ncol;
+            win[i] = bpg[(int64_t)(g_lo + r) * NT + w_lo + c];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int s = s_hi;
+            for (int t = t_hi; t > t_lo; --t) {
+                path[t - t_lo] = s;
+                const int p = s >> 1, g = (t - 1) / G;
+                const uint32_t w = win[(g - g_lo) * ncol + p / P - w_lo];
+                s -= (int)(w >> (((t - 1) % G) * 4 * P + 4 * (p % P) + 2 * (s & 1)) & 3u);
+            }
+            path[0] = s;
+            s_cur = s;
+        }
+        __syncthreads();
+        for (int t = t_lo + (t_lo > 0) + tid; t <= t_hi; t += NT) {
+            const int s = path[t - t_lo];
+            const int tok = (s & 1) ? lab[s >> 1] : blank;
+            const int64_t o = sg.out0 + t;
+            a.token[o] = tok;
+            a.label_index[o] = (s & 1) ? (s >> 1) : -1;
+            a.frame_logp[o] = (float)((double)lg[(int64_t)t * V + tok] - a.lse[o]);
+        }
+        if (t_lo == 0) break;
+        t_hi = t_lo;
+    }
+}
+
+// pinned staging of the per-utterance table, per device; the previous call's copy out of it completes before it is rewritten
+struct Stage {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipEvent_t copied = nullptr;
+};
+std::mutex g_stage_mu;
+std::map<int, Stage> g_stage;
+
+template <int P>
+void launch_viterbi(const AlignArgs& a, int n, hipStream_t s) {
+    W2V2_LAUNCH(align_viterbi_kernel<P>, dim3((unsigned)n), dim3((unsigned)a.nt), 0, s, a);
+}
+
+}  // namespace
+
+int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
+                     const int64_t* label0, const int32_t* nlabels, int blank, int32_t* token, int32_t* label_index,
+                     float* frame_logp, double* score, hipStream_t s) {
+    W2V2_REQUIRE(logits && row0 && frames && labels && label0 && nlabels && token && label_index && frame_logp && score,
+                 "ctc_align: null argument");
+    W2V2_REQUIRE(n >= 1, "ctc_align: %d utterances (need at least one)", n);
+    W2V2_REQUIRE(V >= 1, "ctc_align: vocabulary of %d entries", V);
+    W2V2_REQUIRE(blank >= 0 && blank < V, "ctc_align: blank index %d outside vocabulary %d", blank, V);
+    int Umax = 0, Tmax = 0;
+    for (int i = 0; i < n; ++i) {
+        W2V2_REQUIRE(frames[i] >= 1, "ctc_align: utterance %d has %d frames (need at least one)", i, frames[i]);
+        W2V2_REQUIRE(row0[i] >= 0 && label0[i] >= 0, "ctc_align: utterance %d has a negative offset", i);
+        W2V2_REQUIRE(nlabels[i] >= 0, "ctc_align: utterance %d has %d labels", i, nlabels[i]);
+        W2V2_REQUIRE(nlabels[i] <= W2V2_ALIGN_MAX_LABELS, "ctc_align: utterance %d has %d labels; at most %d per utterance", i,
+                     nlabels[i], W2V2_ALIGN_MAX_LABELS);
+        Umax = std::max(Umax, (int)nlabels[i]);
+        Tmax = std::max(Tmax, (int)frames[i]);
+    }
+    // pairs per thread from the largest label count: the fewest that need at most 256 threads, else 8 (up to 1024 threads)
+    const int pairs = Umax + 1;
+    const int P = pairs <= 256 ? 1 : pairs <= 512 ? 2 : pairs <= 1024 ? 4 : 8, G = 8 / P;
+    const int nt = (((pairs + P - 1) / P + 63) / 64) * 64;
+    std::vector<AlignSeg> segs((size_t)n);
+    int64_t out = 0, words = 0;
+    for (int i = 0; i < n; ++i) {
+        segs[i] = AlignSeg{row0[i], label0[i], out, words, frames[i], nlabels[i]};
+        out += frames[i];
+        words += (int64_t)((frames[i] - 1 + G - 1) / G) * nt;
+    }
+    // workspace: the table | lse (fp64, sum T_i) | backpointer words
+    const size_t tab_bytes = ((size_t)n * sizeof(AlignSeg) + 255) & ~(size_t)255;
+    const size_t lse_bytes = ((size_t)out * sizeof(double) + 255) & ~(size_t)255;
+    void* raw = nullptr;
+    if (int e = stream_scratch(SCRATCH_ALIGN, s, tab_bytes + lse_bytes + (size_t)std::max<int64_t>(words, 1) * sizeof(uint32_t), &raw))
+        return e;
+    AlignArgs a;
+    a.logits = logits;
+    a.labels = labels;
+    a.segs = static_cast<const AlignSeg*>(raw);
+    a.lse = reinterpret_cast<double*>(static_cast<char*>(raw) + tab_bytes);
+    a.bp = reinterpret_cast<uint32_t*>(static_cast<char*>(raw) + tab_bytes + lse_bytes);
+    a.token = token;
+    a.label_index = label_index;
+    a.frame_logp = frame_logp;
+    a.score = score;
+    a.V = V;
+    a.blank = blank;
+    a.nt = nt;
+    {
+        int dev = 0;
+        W2V2_HIP_CHECK(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lock(g_stage_mu);
+        Stage& st = g_stage[dev];
+        const size_t bytes = (size_t)n * sizeof(AlignSeg);
+        if (!st.copied) W2V2_HIP_CHECK(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+        W2V2_HIP_CHECK(hipEventSynchronize(st.copied));
+        if (st.bytes < bytes) {
+            if (st.p) W2V2_HIP_CHECK(hipHostFree(st.p));
+            st.p = nullptr;
+            st.bytes = 0;
+            const size_t want = std::max(bytes, (size_t)16 << 10);
+            W2V2_HIP_CHECK(hipHostMalloc(&st.p, want, hipHostMallocDefault));
+            st.bytes = want;
+        }
+        memcpy(st.p, segs.data(), bytes);
+        W2V2_HIP_CHECK(hipMemcpyAsync(raw, st.p, bytes, hipMemcpyHostToDevice, s));
+        W2V2_HIP_CHECK(hipEventRecord(st.copied, s));
+    }
+    // (work for the profile: the sweep's ~12 fp64 operations per state and step; the logits read once by the lse pass)
+    ProfScope ps(nullptr, FAM_CTC, 12.0 * (double)out * (2.0 * Umax + 1.0), 4.0 * (double)out * V, s);
+    W2V2_LAUNCH(align_lse_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);
+    if (P == 1) launch_viterbi<1>(a, n, s);
+    else if (P == 2) launch_viterbi<2>(a, n, s);
+    else if (P == 4) launch_viterbi<4>(a, n, s);
+    else launch_viterbi<8>(a, n, s);
+    W2V2_HIP_CHECK(hipGetLastError());
+    return W2V2_OK;
+}
+
+}  // namespace w2v2

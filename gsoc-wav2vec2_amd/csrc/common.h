@@ -379,7 +379,7 @@ int launch_pack_gather(const float* stream_rows, float* out, int64_t out_rows, i
 int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int width, const PackSeg* segs, int nseg, hipStream_t s);
 
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
-enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3 };
+enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4 };
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out);
 int stream_scratch_release();       // frees the calling device's scratch buffers
 // one layer's q | k | v projections <-> the packed (H, 3H) kernel and (3H) bias (shadow.hip); unpack skips null targets
@@ -413,6 +413,11 @@ int launch_ctc(Profiler* prof, const float* logits, int B, int T, int V, const i
 // scalar) = sum_b nll[b] / grad_div.  One call, no host-side tensor arithmetic around it.
 int launch_ctc_x(Profiler* prof, const float* logits, int B, int T, int V, const int32_t* labels, int U, const int32_t* label_len,
                  const int32_t* logit_len, int uniform_len, int blank, float grad_div, float* nll, float* grad, float* loss_sum, hipStream_t s);
+// CTC forced alignment (align.hip; w2v2_ctc_align): utterance i = logits rows [row0_i, row0_i + frames_i), labels
+// [label0_i, label0_i + nlabels_i); per-frame outputs back to back, one score per utterance
+int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
+                     const int64_t* label0, const int32_t* nlabels, int blank, int32_t* token, int32_t* label_index,
+                     float* frame_logp, double* score, hipStream_t s);
 
 // ---- device helpers ---------------------------------------------------------
 #ifdef __HIPCC__

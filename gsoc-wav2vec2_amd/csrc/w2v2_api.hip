@@ -1160,6 +1160,13 @@ int w2v2_ctc_loss_fused(const float* logits, int32_t B, int32_t T, int32_t V, co
                         reinterpret_cast<hipStream_t>(stream));
 }
 
+int w2v2_ctc_align(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
+                   const int64_t* label0, const int32_t* nlabels, int32_t blank, int32_t* token, int32_t* label_index, float* frame_logp,
+                   double* score, void* stream) {
+    return launch_ctc_align(logits, V, n, row0, frames, labels, label0, nlabels, blank, token, label_index, frame_logp, score,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
 int w2v2_activation_info(const w2v2_model* m, const char* name, int64_t shape[3]) {
     W2V2_REQUIRE(m && name && shape, "activation_info: null argument");
     auto it = m->acts.find(name);

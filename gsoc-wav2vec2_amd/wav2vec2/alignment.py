@@ -1,0 +1,183 @@
+"""CTC forced alignment on the GPU (w2v2_ctc_align, csrc/align.hip).
+
+``forced_align`` finds, per utterance, the single best frame-level CTC path (Viterbi) that spells a given label sequence;
+``token_spans`` and ``word_spans`` turn a path into per-token frame spans and per-word time spans.  The path and its
+per-frame log-probabilities are computed by HIP kernels; the span helpers are host code over the (short) per-frame arrays.
+"""
+
+from dataclasses import dataclass
+from typing import NamedTuple
+
+import numpy as np
+
+from . import _native as N
+
+
+@dataclass
+class Alignment:
+    """One utterance's best path.  ``token`` (T,) int32: the path's token per frame (the blank or a label);
+    ``label_index`` (T,) int32: k where the frame sits on label k, -1 on a blank; ``frame_logp`` (T,) fp32:
+    log_softmax(logits[t])[token[t]]; ``score``: log-probability of the whole path (fp64).  Device tensors
+    as returned by ``forced_align``."""
+    token: object
+    label_index: object
+    frame_logp: object
+    score: float
+
+
+class TokenSpan(NamedTuple):
+    token: int
+    start: int      # first frame
+    end: int        # one past the last frame
+    score: float    # mean of exp(frame_logp) over the span
+
+
+class WordSpan(NamedTuple):
+    text: object    # the word's characters (or its token ids when no vocabulary is given)
+    start_s: float
+    end_s: float
+    score: float    # mean of exp(frame_logp) over the frames of the word's tokens
+
+
+def _host(x):
+    return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+
+def _logits_base(logits, frame_lengths):
+    """(base tensor (rows, V), row offset and frame count per utterance): no copy when the list is row-contiguous views of one
+    storage (what predict_packed returns) or a (B, T, V) tensor; otherwise one concatenation."""
+    import torch
+    if isinstance(logits, torch.Tensor):
+        if logits.dim() != 3:
+            raise ValueError(f"`logits` must be a list of (T_i, V) tensors or a (B, T, V) tensor, got shape {tuple(logits.shape)}")
+        B, T, V = logits.shape
+        lens = [T] * B if frame_lengths is None else [int(n) for n in frame_lengths]
+        if len(lens) != B:
+            raise ValueError(f"frame_lengths has {len(lens)} entries for a batch of {B}")
+        for i, n in enumerate(lens):
+            if not 1 <= n <= T:
+                raise ValueError(f"utterance {i}: frame length {n} outside [1, {T}]")
+        base = logits.detach()
+        if base.dtype != torch.float32 or not base.is_cuda or not base.is_contiguous():
+            base = base.to(device="cuda", dtype=torch.float32).contiguous()
+        return base.reshape(B * T, V), [b * T for b in range(B)], lens
+    if frame_lengths is not None:
+        raise ValueError("frame_lengths goes with a (B, T, V) tensor; a list of (T_i, V) tensors carries its own lengths")
+    parts = list(logits)
+    if not parts:
+        raise ValueError("`logits` is an empty list")
+    for i, p in enumerate(parts):
+        if not isinstance(p, torch.Tensor) or p.dim() != 2:
+            raise ValueError(f"utterance {i}: logits must be a 2-D (T_i, V) tensor")
+        if p.shape[1] != parts[0].shape[1]:
+            raise ValueError(f"utterance {i}: vocabulary {p.shape[1]} differs from utterance 0's {parts[0].shape[1]}")
+        if p.shape[0] < 1:
+            raise ValueError(f"utterance {i} has no frames")
+    V = int(parts[0].shape[1])
+    lens = [int(p.shape[0]) for p in parts]
+    first = parts[0]
+    same = all(p.dtype == torch.float32 and p.is_cuda and p.is_contiguous() and p.device == first.device
+               and p.untyped_storage().data_ptr() == first.untyped_storage().data_ptr() for p in parts)
+    if same:
+        lo = min(p.data_ptr() for p in parts)
+        offs = [p.data_ptr() - lo for p in parts]
+        if all(o % (4 * V) == 0 for o in offs):
+            start = min(range(len(parts)), key=lambda i: parts[i].data_ptr())
+            rows = max(o // (4 * V) + n for o, n in zip(offs, lens))
+            base = parts[start].detach().as_strided((rows, V), (V, 1))
+            return base, [o // (4 * V) for o in offs], lens
+    base = torch.cat([p.detach().to(device="cuda", dtype=torch.float32) for p in parts]).contiguous()
+    return base, list(np.cumsum([0] + lens[:-1]).tolist()), lens
+
+
+def _check_labels(labels, lens, V, blank):
+    out = []
+    for i, lab in enumerate(labels):
+        a = np.asarray(_host(lab) if hasattr(lab, "cpu") else list(lab), dtype=np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() >= V):
+            raise ValueError(f"utterance {i}: labels must lie in [0, {V}), got [{a.min()}, {a.max()}]")
+        if a.size and (a == blank).any():
+            raise ValueError(f"utterance {i}: label {blank} is the blank")
+        if a.size > N.ALIGN_MAX_LABELS:
+            raise ValueError(f"utterance {i}: {a.size} labels; at most {N.ALIGN_MAX_LABELS} per utterance")
+        repeats = int((a[1:] == a[:-1]).sum()) if a.size > 1 else 0
+        if lens[i] < a.size + repeats:
+            raise ValueError(f"utterance {i}: {lens[i]} frames cannot hold {a.size} labels with {repeats} repeats "
+                             f"(a CTC path needs at least {a.size + repeats})")
+        out.append(a.astype(np.int32))
+    return out
+
+
+def forced_align(logits, labels, blank=0, frame_lengths=None):
+    """Best CTC path of each utterance's labels through its logits; one ``Alignment`` per utterance.
+
+    ``logits``: a list of (T_i, V) tensors -- views of one storage, as ``predict_packed`` returns them, are read in place --
+    or a (B, T, V) tensor with ``frame_lengths`` (default: T for every row).  ``labels``: one id sequence per utterance,
+    none of them the blank.  Raises ValueError, naming the utterance, for a label outside the vocabulary, a blank label, or
+    too few frames for the labels (T_i < U_i + repeated neighbours)."""
+    import torch
+    base, row0, lens = _logits_base(logits, frame_lengths)
+    n, V = len(lens), int(base.shape[1])
+    if len(labels) != n:
+        raise ValueError(f"{len(labels)} label sequences for {n} utterances")
+    if not 0 <= blank < V:
+        raise ValueError(f"blank {blank} outside the vocabulary [0, {V})")
+    labs = _check_labels(labels, lens, V, blank)
+    dev = base.device
+    flat = np.concatenate(labs + [np.zeros(1, np.int32)])      # (one spare entry: never an empty buffer)
+    label0 = np.cumsum([0] + [a.size for a in labs[:-1]]).astype(np.int64)
+    labels_dev = torch.from_numpy(flat).to(dev)
+    total = sum(lens)
+    token = torch.empty(total, dtype=torch.int32, device=dev)
+    label_index = torch.empty(total, dtype=torch.int32, device=dev)
+    frame_logp = torch.empty(total, dtype=torch.float32, device=dev)
+    score = torch.empty(n, dtype=torch.float64, device=dev)
+    row0_h = np.asarray(row0, np.int64)
+    frames_h = np.asarray(lens, np.int32)
+    nlab_h = np.asarray([a.size for a in labs], np.int32)
+    lib = N.load()
+    N.check(lib.w2v2_ctc_align(N.ptr(base), V, n, N.ptr(row0_h), N.ptr(frames_h), N.ptr(labels_dev), N.ptr(label0),
+                               N.ptr(nlab_h), int(blank), N.ptr(token), N.ptr(label_index), N.ptr(frame_logp), N.ptr(score),
+                               N.current_stream()), "w2v2_ctc_align")
+    scores = score.cpu().numpy()
+    return [Alignment(tk, li, fl, float(sc)) for tk, li, fl, sc in
+            zip(torch.split(token, lens), torch.split(label_index, lens), torch.split(frame_logp, lens), scores)]
+
+
+def token_spans(alignment):
+    """The U labels of an alignment as ``TokenSpan(token, start, end, score)`` in frames, ``end`` exclusive, in label
+    order; ``score`` is the mean of exp(frame_logp) over the span.  An alignment without a path (-1 rows) has none."""
+    li = _host(alignment.label_index).astype(np.int64)
+    tok = _host(alignment.token)
+    p = np.exp(_host(alignment.frame_logp).astype(np.float64))
+    if li.size == 0:
+        return []
+    cut = np.flatnonzero(li[1:] != li[:-1]) + 1
+    starts = np.concatenate(([0], cut))
+    ends = np.concatenate((cut, [li.size]))
+    return [TokenSpan(int(tok[s]), int(s), int(e), float(p[s:e].mean())) for s, e in zip(starts, ends) if li[s] >= 0]
+
+
+def word_spans(spans, delimiter_id, seconds_per_frame, vocab=None):
+    """Words of a token-span list: the maximal runs of spans whose token is not ``delimiter_id`` (leading, trailing and
+    doubled delimiters make no empty word).  ``WordSpan(text, start_s, end_s, score)``: the first span's start and the last
+    span's end times ``seconds_per_frame``; ``score`` the mean of exp(frame_logp) over the frames of the word's spans;
+    ``text`` the characters ``vocab`` gives the ids (a mapping or a sequence id -> string), or the tuple of ids."""
+    words, cur = [], []
+
+    def close():
+        if cur:
+            nf = sum(s.end - s.start for s in cur)
+            score = sum(s.score * (s.end - s.start) for s in cur) / nf
+            ids = tuple(s.token for s in cur)
+            text = "".join(vocab[i] for i in ids) if vocab is not None else ids
+            words.append(WordSpan(text, cur[0].start * seconds_per_frame, cur[-1].end * seconds_per_frame, score))
+            cur.clear()
+
+    for s in spans:
+        if s.token == delimiter_id:
+            close()
+        else:
+            cur.append(s)
+    close()
+    return words

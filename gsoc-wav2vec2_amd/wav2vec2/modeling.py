@@ -666,3 +666,33 @@ class Wav2Vec2ForCTC(TFKerasModel):
         return self._forward(batch, attention_mask, training, self.config.vocab_size)
 
     call = __call__
+
+    def align(self, waveforms, transcripts, tokenizer=None, delimiter_id=None):
+        """Word timestamps: `predict_packed(waveforms)`, then the CTC forced alignment of each transcript on the packed logits
+        in place (wav2vec2.alignment: forced_align, token_spans, word_spans; blank = config.pad_id).  A transcript is text,
+        encoded with `tokenizer` (a Wav2Vec2Processor(is_tokenizer=True)), or a sequence of ids, used as it is.  Frame f lies at
+        f * prod(strides) / 16000 s.  The word delimiter is the tokenizer's "|" unless `delimiter_id` is given.  Returns one list
+        of WordSpan(text, start_s, end_s, score) per utterance.  Runs in the precision modes predict_packed accepts."""
+        from .alignment import forced_align, token_spans, word_spans
+        from .processor import WORD_DELIMITER
+        if isinstance(transcripts, str) or len(transcripts) != len(waveforms):
+            raise ValueError("one transcript per waveform")
+        ids = []
+        for i, tr in enumerate(transcripts):
+            if isinstance(tr, str):
+                if tokenizer is None:
+                    raise ValueError(f"transcript {i} is text: pass the tokenizer that encodes it")
+                ids.append(list(tokenizer(tr)))
+            else:
+                ids.append([int(x) for x in tr])
+        vocab = None
+        if tokenizer is not None:
+            tokens = tokenizer.get_vocab()
+            vocab = {i: (" " if t == WORD_DELIMITER else t) for t, i in tokens.items()}
+            if delimiter_id is None:
+                delimiter_id = tokens[WORD_DELIMITER]
+        if delimiter_id is None:
+            raise ValueError("ids without a tokenizer: pass delimiter_id")
+        seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
+        alignments = forced_align(self.predict_packed(waveforms), ids, blank=self.config.pad_id)
+        return [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab) for a in alignments]

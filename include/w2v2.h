@@ -225,6 +225,23 @@ int w2v2_ctc_loss_fused(const float* logits_dev, int32_t B, int32_t T, int32_t V
                         int32_t logit_length_all, int32_t blank, float division_factor, float* nll_dev, float* grad_logits_dev,
                         float* loss_sum_dev, void* stream);
 
+/* CTC forced alignment (Viterbi; DESIGN.md §11, exact definition in csrc/align.hip): the single best frame-level path that spells
+ * each utterance's labels.  Model-free, like w2v2_ctc_loss; asynchronous on `stream`.
+ *   utterance i: logits_dev rows [row0_host[i], row0_host[i] + frames_host[i]) (rows of V fp32: the packed output of
+ *                w2v2_forward_packed back to back, or a padded (B, T, V) batch with row0 = b T), labels
+ *                labels_dev[label0_host[i] .. label0_host[i] + nlabels_host[i]) (int32, on the device)
+ *   token_dev, label_index_dev, frame_logp_dev  (sum_i frames_i), utterance after utterance: the path's token (blank or label),
+ *                the label's index k (-1 on a blank), log_softmax(logits[t])[token] (fp32)
+ *   score_dev    (n) fp64 log-probability of the path
+ * frames_i >= 1, 0 <= nlabels_i <= W2V2_ALIGN_MAX_LABELS, blank in [0, V): otherwise W2V2_EINVAL.  Per utterance, with its neighbours
+ * unaffected: frames_i < nlabels_i + (count of labels equal to the one before) gives score -inf; a label outside [0, V) or equal to
+ * the blank gives score NaN; both with token = label_index = -1 and frame_logp NaN.  Synchronises with the previous call's table
+ * upload (host-side), otherwise enqueued on `stream`. */
+#define W2V2_ALIGN_MAX_LABELS 8191
+int w2v2_ctc_align(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host,
+                   const int32_t* labels_dev, const int64_t* label0_host, const int32_t* nlabels_host, int32_t blank,
+                   int32_t* token_dev, int32_t* label_index_dev, float* frame_logp_dev, double* score_dev, void* stream);
+
 /* ---- the training step (reference src/main.py:136-259) --------
  * Replaces what Keras' train_step does around the forward: training-mode forward, backward of every
  * trainable variable, Adam.  Postnorm (base) and prenorm (robust / xlsr) transformers; the conv feature
