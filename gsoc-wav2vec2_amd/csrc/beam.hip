@@ -1,0 +1,581 @@
+// CTC prefix beam search: the n best transcripts of each of n utterances with their log-probabilities, optionally fused with a
+// character n-gram language model held as a dense table on the device.  Model-free, like ctc.hip and align.hip.
+//
+// Definition (tests/beam_reference.py implements exactly this).  x_t(v) is the fp32 logit widened to fp64, lp_t(v) = x_t(v) - lse_t
+// (lse_t reduced as align_lse_kernel reduces it), lse2(a, b) = max + log1p(exp(-|a - b|)) with -inf neutral.  A beam entry is a
+// prefix p (labels, no blanks) with pb, pnb (log-probability of the frame paths so far that collapse to p and end in a blank / a
+// non-blank) and lm(p).  Start: the empty prefix, pb = 0, pnb = -inf, lm = 0.  Per frame, from every entry, tot = lse2(pb, pnb):
+//   stay    p     : pb'  = tot + lp(blank);  pnb' = pnb + lp(p[-1]) if p is not empty
+//   extend  p + c : pnb' = (pb if c == p[-1] else tot) + lp(c);  lm(p + c) = (lm(p) + alpha table[ctx(p), c]) + beta   (c != blank)
+// If p + c is itself in the beam (entry q), the extension is no candidate of its own: q gets pnb' = lse2(pnb', that term).  Candidate
+// index j V + blank for the prefix already at rank j, j V + c for a new one made from rank j.  Key = lse2(pb', pnb') + lm; -inf keys
+// drop; the W largest keys form the next beam in key order, equal keys by ascending index.  Result: the first nbest entries after
+// the last frame: labels, length, score = lse2(pb, pnb) (the CTC log-probability over the frame paths the beam kept: a LOWER
+// bound of the exact value, equal to it when nothing was pruned), total = score + lm.  ctx(p): the last order - 1 labels of p as
+// digits base V, oldest first, blank-filled.  An utterance with a non-finite lse_t (a NaN or +inf logit, a frame of -inf only)
+// has no hypothesis: every length -1, score = total = NaN.
+//
+// Structure.  beam_lse_kernel: one wave per frame (as align_lse_kernel).  beam_search_kernel: one block of 256 threads (one wave
+// per SIMD) per utterance, every score fp64.  Why 256: the W V <= 4096 candidate keys of a step live in registers, 16 per thread at
+// the limits (32 VGPRs for the keys); more waves would only add to every barrier of a step that is latency-, not throughput-bound.
+//  * Prefixes are nodes (parent, label) of a per-utterance trie in the workspace, one 8-byte plain store per NEW survivor; node
+//    1 + t W + rank, so T W + 1 nodes bound it and no counter is needed.  A prefix that was pruned and is made again gets a second
+//    node, so node identity alone does not answer "is p + c in the beam".  Each entry carries a 64-bit hash of its prefix and of its
+//    parent prefix and its length: an entry q is p + c iff len(q) = len(p) + 1, hash(parent of q) = hash(p) and the prefixes are
+//    equal -- the last is known when q's parent node IS p's node, and otherwise (rare) decided exactly by walking both chains
+//    (same_prefix), after which q is re-pointed at p's node.  Hashes only ever save that walk; they decide nothing.
+//  * Per step: (1) the W x W match, 4 lanes per entry, gives each entry the rank of its parent (mi) and each entry the set of its
+//    children's labels (a 64-bit mask: V <= 64); (2) every thread computes the keys of its candidates (index k 256 + tid) while wave
+//    0 computes the <= W "stay" candidates, the only ones that need lse2 (two in a row: the step's serial floor); (3) an exact
+//    radix select, 8 bits per pass, on the 80-bit composite (order-preserving image of the key, then 0xffff - index): a 256-bin
+//    LDS histogram (integer ds_add: counts do not depend on arrival order -- the only atomics in the file), every wave scanning it
+//    redundantly so that a pass costs ONE barrier; it stops as soon as the boundary bin holds exactly what is still needed (3-4
+//    passes on distinct keys; the index passes run only on keys that are bit-equal at the boundary); (4) the survivors are compacted
+//    by ballots (slots fixed by their indices alone), ranked by a W x W count of larger composites (4 lanes per survivor) and written to the other beam
+//    buffer.  Barriers are LDS-only (s_waitcnt lgkmcnt(0); s_barrier) except the one that ends a step, which also drains the
+//    node stores so that same_prefix may read them.
+//  * LDS: beam state as structure-of-arrays of 64 (doubles and ints: consecutive lanes on consecutive banks; the match reads one
+//    entry per 4 lanes, a broadcast); the log-probabilities of 8 frames ahead in a double-buffered ring, loaded one step and
+//    written at its end; the language model row values are loaded at the top of a step, used after the match.
+//  * After the sweep nbest lanes walk their node chains back to the root and write the labels with plain stores (the rest of each
+//    row is -1).  Two identical calls give identical bits; neighbours, order and repetition have no influence.
+#include "common.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <vector>
+
+namespace w2v2 {
+namespace {
+
+constexpr int BEAM_NT = 256;
+constexpr int BEAM_W = W2V2_BEAM_MAX_WIDTH;
+constexpr int BEAM_V = W2V2_BEAM_MAX_VOCAB;
+constexpr int BEAM_KMAX = BEAM_W * BEAM_V / BEAM_NT;        // candidate keys per thread at the limits
+constexpr int BEAM_RING = 8;                                  // frames of log-probabilities per ring half
+static_assert(BEAM_W == 64 && BEAM_V == 64, "beam.hip: one 64-bit child mask per entry, 4 lanes per entry in 256 threads");
+
+typedef unsigned long long u64;
+
+struct BeamSeg {
+    int64_t row0;      // first logits row
+    int64_t lse0;      // first lse entry
+    int64_t node0;     // first trie node
+    int32_t T, pad;
+};
+
+struct BeamArgs {
+    const float* logits;
+    const BeamSeg* segs;
+    double* lse;
+    u64* nodes;             // (parent << 32) | label
+    const float* lm;        // (ctxmod, V) or null
+    int32_t* labels;
+    int32_t* length;
+    double* score;
+    double* total;
+    double alpha, beta;
+    int V, blank, W, nbest, max_len, ctxmod;
+};
+
+struct BeamBuf {
+    double pb[BEAM_W], pnb[BEAM_W], tot[BEAM_W], lm[BEAM_W];
+    u64 h[BEAM_W], hp[BEAM_W];                  // hash of the prefix, of its parent prefix
+    int node[BEAM_W], pn[BEAM_W];               // trie node, parent's node
+    int len[BEAM_W], last[BEAM_W], ctx[BEAM_W];
+    int mi[BEAM_W];                             // rank of the entry that is this prefix without its last label, or -1
+};
+
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+__global__ __launch_bounds__(256) void beam_lse_kernel(BeamArgs a) {
+    const BeamSeg sg = a.segs[blockIdx.y];
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= sg.T) return;
+    const int lane = threadIdx.x & 63;
+    const float* __restrict__ r = a.logits + (sg.row0 + t) * a.V;
+    float m = -INFINITY;
+    for (int v = lane; v < a.V; v += 64) m = fmaxf(m, r[v]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    double acc = 0.0;
+    for (int v = lane; v < a.V; v += 64) acc += exp((double)r[v] - (double)m);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane == 0) a.lse[sg.lse0 + t] = (double)m + log(acc);
+}
+
+__device__ __forceinline__ double lse2(double a, double b) {
+    constexpr double NEG = -__builtin_inf();
+    if (a == NEG) return b;
+    if (b == NEG) return a;
+    return (a > b ? a : b) + log1p(exp(-fabs(a - b)));
+}
+
+// order-preserving image of a double that is neither NaN nor -0.0
+__device__ __forceinline__ u64 key_image(double k) {
+    const u64 b = (u64)__double_as_longlong(k);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+__device__ __forceinline__ u64 hash_step(u64 h, int c) {
+    h = (h ^ (u64)(c + 1)) * 0x9E3779B97F4A7C15ull;
+    return h ^ (h >> 29);
+}
+
+// a node as the whole block sees it (past this CU's vector cache: the walk may have cached a neighbour of a later node)
+__device__ __forceinline__ u64 node_load(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// do nodes x and y, of equal depth, spell the same prefix?
+__device__ __forceinline__ bool same_prefix(const u64* __restrict__ nodes, int x, int y) {
+    while (x != y) {
+        if (x <= 0 || y <= 0) return false;
+        const u64 vx = node_load(nodes + x), vy = node_load(nodes + y);
+        if ((uint32_t)vx != (uint32_t)vy) return false;
+        x = (int)(vx >> 32);
+        y = (int)(vy >> 32);
+    }
+    return true;
+}
+
+__device__ __forceinline__ int select_digit(u64 img, int idx, int pass) {
+    if (pass < 8) return (int)(img >> (56 - 8 * pass)) & 255;
+    const int inv = 0xffff - idx;
+    return pass == 8 ? inv >> 8 : inv & 255;
+}
+
+__global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamArgs a) {
+    constexpr double NEG = -__builtin_inf();
+    __shared__ BeamBuf buf[2];
+    __shared__ double lpr[2][BEAM_RING][BEAM_V];            // lp of frames 8 (t / 8) + r, half (t / 8) & 1
+    __shared__ u64 childmask[BEAM_W];
+    __shared__ double spb[BEAM_W], spnb[BEAM_W], stot[BEAM_W], skey[BEAM_W];      // the stay candidates of a step
+    __shared__ u64 s_img[BEAM_W];                           // the survivors of a step, compacted (not yet in key order)
+    __shared__ int s_idx[BEAM_W];
+    __shared__ double s_pb[BEAM_W], s_pnb[BEAM_W], s_tot[BEAM_W], s_lm[BEAM_W];
+    __shared__ __attribute__((aligned(16))) int hist[3][256];
+    __shared__ int wtot[BEAM_NT / 64];
+
+    const BeamSeg sg = a.segs[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int V = a.V, W = a.W, blank = a.blank, T = sg.T, nbest = a.nbest;
+    const float* __restrict__ lg = a.logits + sg.row0 * V;
+    const double* __restrict__ ls = a.lse + sg.lse0;
+    u64* __restrict__ nodes = a.nodes + sg.node0;
+    const float* __restrict__ lmt = a.lm;
+    const double alpha = a.alpha, beta = a.beta;
+    int32_t* __restrict__ out_lab = a.labels + (int64_t)blockIdx.x * nbest * a.max_len;
+    const int64_t out0 = (int64_t)blockIdx.x * nbest;
+
+    bool bad = false;
+    for (int t = tid; t < T; t += BEAM_NT) bad |= !(fabs(ls[t]) <= 1.7976931348623157e308);
+    const int anybad = __syncthreads_or(bad);
+    for (int i = tid; i < nbest * a.max_len; i += BEAM_NT) out_lab[i] = -1;
+    if (anybad) {                                           // (block-uniform)
+        if (tid < nbest) {
+            a.length[out0 + tid] = -1;
+            a.score[out0 + tid] = __builtin_nan("");
+            a.total[out0 + tid] = __builtin_nan("");
+        }
+        return;
+    }
+
+    // this thread's candidates: index k 256 + tid = j V + c, packed j << 8 | c; its elements of a ring half: e = q 256 + tid = r V + c
+    int jc[BEAM_KMAX];
+#pragma unroll
+    for (int k = 0; k < BEAM_KMAX; ++k) {
+        const int idx = k * BEAM_NT + tid, j = idx / V;
+        jc[k] = j << 8 | (idx - j * V);
+    }
+    int er[2], ec[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int e = q * BEAM_NT + tid;
+        er[q] = e / V;
+        ec[q] = e - er[q] * V;
+    }
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+        if (er[q] < BEAM_RING && er[q] < T) lpr[0][er[q]][ec[q]] = (double)lg[(int64_t)er[q] * V + ec[q]] - ls[er[q]];
+    if (tid == 0) {
+        BeamBuf& B = buf[0];
+        B.pb[0] = 0.0;
+        B.pnb[0] = NEG;
+        B.tot[0] = 0.0;
+        B.lm[0] = 0.0;
+        B.h[0] = 0x243F6A8885A308D3ull;
+        B.hp[0] = 0;
+        B.node[0] = 0;
+        B.pn[0] = -1;
+        B.len[0] = 0;
+        B.last[0] = -1;
+        int ctx = 0;
+        for (int m = 1; m < a.ctxmod; m *= V) ctx = ctx * V + blank;
+        B.ctx[0] = ctx;
+        B.mi[0] = -1;
+    }
+    int nb = 1;
+    __syncthreads();
+
+    for (int t = 0; t < T; ++t) {
+        BeamBuf& B = buf[t & 1];
+        BeamBuf& N = buf[(t & 1) ^ 1];
+        const double* lp = lpr[(t >> 3) & 1][t & 7];
+        const int nk = (nb * V + BEAM_NT - 1) / BEAM_NT;
+
+        // the ring half of the next 8 frames: loaded now, written at the end of this step
+        float pfx[2] = {0.f, 0.f};
+        double pfl[2] = {0.0, 0.0};
+        const bool fill = (t & 7) == 0;
+        if (fill) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int tt = t + BEAM_RING + er[q];
+                if (er[q] < BEAM_RING && tt < T) {
+                    pfx[q] = lg[(int64_t)tt * V + ec[q]];
+                    pfl[q] = ls[tt];
+                }
+            }
+        }
+        // the language model's values of this thread's candidates
+        float lmv[BEAM_KMAX];
+#pragma unroll
+        for (int k = 0; k < BEAM_KMAX; ++k) {
+            lmv[k] = 0.f;
+            if (lmt && k < nk) {
+                const int j = jc[k] >> 8, c = jc[k] & 255;
+                if (j < nb && c != blank) lmv[k] = lmt[(int64_t)B.ctx[j] * V + c];
+            }
+        }
+        hist[0][tid] = 0;
+
+        // (1) match: entry i against every entry j; j is a child of i iff its prefix is i's plus one label
+        {
+            const int i = tid >> 2, part = tid & 3;
+            u64 mask = 0;
+            if (i < nb) {
+                const u64 hi = B.h[i];
+                const int li = B.len[i] + 1, ni = B.node[i];
+                for (int j = part; j < nb; j += 4) {
+                    if (B.len[j] == li && B.hp[j] == hi) {
+                        bool ok = B.pn[j] == ni;
+                        if (!ok) {
+                            ok = same_prefix(nodes, B.pn[j], ni);
+                            if (ok) B.pn[j] = ni;
+                        }
+                        if (ok) {
+                            B.mi[j] = i;
+                            mask |= 1ull << B.last[j];
+                        }
+                    }
+                }
+            }
+            mask |= __shfl_xor(mask, 1, 64);
+            mask |= __shfl_xor(mask, 2, 64);
+            if (part == 0) childmask[i] = mask;
+        }
+        lds_barrier();
+
+        // (2) keys: the extensions by every thread, the stays by wave 0
+        u64 img[BEAM_KMAX];
+        unsigned valid = 0;
+#pragma unroll
+        for (int k = 0; k < BEAM_KMAX; ++k) {
+            img[k] = 0;
+            if (k < nk) {
+                const int j = jc[k] >> 8, c = jc[k] & 255;
+                if (j < nb && c != blank && !((childmask[j] >> c) & 1ull)) {
+                    const double base = c == B.last[j] ? B.pb[j] : B.tot[j];
+                    const double pnbn = base + lp[c];
+                    const double lmn = __dadd_rn(__dadd_rn(B.lm[j], __dmul_rn(alpha, (double)lmv[k])), beta);
+                    const double key = (pnbn + lmn) + 0.0;
+                    if (key > NEG) {
+                        img[k] = key_image(key);
+                        valid |= 1u << k;
+                    }
+                }
+            }
+        }
+        if (tid < nb) {
+            const int j = tid, last = B.last[j], i = B.mi[j];
+            const double pbn = B.tot[j] + lp[blank];
+            double pnbn = last >= 0 ? B.pnb[j] + lp[last] : NEG;
+            if (i >= 0) pnbn = lse2(pnbn, (last == B.last[i] ? B.pb[i] : B.tot[i]) + lp[last]);
+            const double totn = lse2(pbn, pnbn);
+            spb[j] = pbn;
+            spnb[j] = pnbn;
+            stot[j] = totn;
+            skey[j] = (totn + B.lm[j]) + 0.0;
+        }
+        lds_barrier();
+#pragma unroll
+        for (int k = 0; k < BEAM_KMAX; ++k) {
+            if (k < nk) {
+                const int j = jc[k] >> 8, c = jc[k] & 255;
+                if (j < nb && c == blank) {
+                    const double key = skey[j];
+                    if (key > NEG) {
+                        img[k] = key_image(key);
+                        valid |= 1u << k;
+                    }
+                }
+            }
+        }
+
+        // (3) exact radix select of the min(W, valid) largest composites (image, 0xffff - index)
+        unsigned active = valid, acc = 0;
+        int need = 0, nsel = 0;
+        for (int pass = 0; pass < 10; ++pass) {
+            int* H = hist[pass % 3];
+            hist[(pass + 1) % 3][tid] = 0;
+#pragma unroll
+            for (int k = 0; k < BEAM_KMAX; ++k)
+                if (active >> k & 1u) atomicAdd(&H[select_digit(img[k], k * BEAM_NT + tid, pass)], 1);
+            lds_barrier();
+            const int4 hv = reinterpret_cast<const int4*>(H)[lane];      // bins 4 lane .. 4 lane + 3
+            const int s = hv.x + hv.y + hv.z + hv.w;
+            int suf = s;                                                  // sum over the lanes >= this one
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int v = __shfl_down(suf, off, 64);
+                if (lane + off < 64) suf += v;
+            }
+            if (pass == 0) {
+                need = min(W, __shfl(suf, 0, 64));
+                nsel = need;
+            }
+            if (need == 0) break;                                         // (block-uniform)
+            const int above = suf - s;
+            const int L = __ffsll((long long)__ballot(above < need && need <= suf)) - 1;      // exactly one lane
+            const int h3 = __shfl(hv.w, L, 64), h2 = __shfl(hv.z, L, 64), h1 = __shfl(hv.y, L, 64), h0 = __shfl(hv.x, L, 64);
+            int cum = __shfl(above, L, 64), d, hd;
+            if (cum + h3 >= need) { d = 4 * L + 3; hd = h3; }
+            else if (cum + h3 + h2 >= need) { cum += h3; d = 4 * L + 2; hd = h2; }
+            else if (cum + h3 + h2 + h1 >= need) { cum += h3 + h2; d = 4 * L + 1; hd = h1; }
+            else { cum += h3 + h2 + h1; d = 4 * L; hd = h0; }
+            need -= cum;
+            const bool all = hd == need;                                  // the boundary bin is taken whole: done
+#pragma unroll
+            for (int k = 0; k < BEAM_KMAX; ++k) {
+                if (active >> k & 1u) {
+                    const int dg = select_digit(img[k], k * BEAM_NT + tid, pass);
+                    if (dg > d || (dg == d && all)) acc |= 1u << k;
+                    if (dg != d || all) active &= ~(1u << k);
+                }
+            }
+            if (all) break;                                               // (block-uniform)
+        }
+
+        // (4) the survivors compacted, then their ranks, then the next beam
+        {
+            int mine = 0;
+#pragma unroll
+            for (int k = 0; k < BEAM_KMAX; ++k) mine += __popcll(__ballot(acc >> k & 1u));
+            if (lane == 0) wtot[wave] = mine;
+        }
+        lds_barrier();
+        {
+            // distinct slots 0 .. nsel - 1, fixed by the indices alone; the ranks below put them in key order
+            int before_k = 0;
+#pragma unroll
+            for (int k = 0; k < BEAM_KMAX; ++k) {
+                if (k < nk) {                                             // (block-uniform)
+                    const bool f = acc >> k & 1u;
+                    const u64 bl = __ballot(f);
+                    if (f) {                                              // (wave w fills the slots behind the earlier waves')
+                        int slot = before_k + __popcll(bl & ((1ull << lane) - 1ull));
+                        for (int w = 0; w < wave; ++w) slot += wtot[w];
+                        slot = min(slot, BEAM_W - 1);
+                        const int j = jc[k] >> 8, c = jc[k] & 255;
+                        s_img[slot] = img[k];
+                        s_idx[slot] = k * BEAM_NT + tid;
+                        if (c == blank) {
+                            s_pb[slot] = spb[j];
+                            s_pnb[slot] = spnb[j];
+                            s_tot[slot] = stot[j];
+                            s_lm[slot] = B.lm[j];
+                        } else {
+                            const double pnbn = (c == B.last[j] ? B.pb[j] : B.tot[j]) + lp[c];
+                            s_pb[slot] = NEG;
+                            s_pnb[slot] = pnbn;
+                            s_tot[slot] = pnbn;
+                            s_lm[slot] = __dadd_rn(__dadd_rn(B.lm[j], __dmul_rn(alpha, (double)lmv[k])), beta);
+                        }
+                    }
+                    before_k += __popcll(bl);
+                }
+            }
+        }
+        lds_barrier();
+        {
+            const int r = tid >> 2, part = tid & 3;
+            int cnt = 0;
+            if (r < nsel) {
+                const u64 my = s_img[r];
+                const int myi = s_idx[r];
+                for (int q = part; q < nsel; q += 4) {
+                    const u64 o = s_img[q];
+                    cnt += (o > my || (o == my && s_idx[q] < myi)) ? 1 : 0;
+                }
+            }
+            cnt += __shfl_xor(cnt, 1, 64);
+            cnt += __shfl_xor(cnt, 2, 64);
+            if (part == 0 && r < nsel) {
+                const int idx = s_idx[r], j = idx / V, c = idx - j * V;
+                N.pb[cnt] = s_pb[r];
+                N.pnb[cnt] = s_pnb[r];
+                N.tot[cnt] = s_tot[r];
+                N.lm[cnt] = s_lm[r];
+                N.mi[cnt] = -1;
+                if (c == blank) {
+                    N.h[cnt] = B.h[j];
+                    N.hp[cnt] = B.hp[j];
+                    N.node[cnt] = B.node[j];
+                    N.pn[cnt] = B.pn[j];
+                    N.len[cnt] = B.len[j];
+                    N.last[cnt] = B.last[j];
+                    N.ctx[cnt] = B.ctx[j];
+                } else {
+                    const int node = 1 + t * W + cnt;
+                    nodes[node] = (u64)(uint32_t)B.node[j] << 32 | (u64)(uint32_t)c;
+                    N.h[cnt] = hash_step(B.h[j], c);
+                    N.hp[cnt] = B.h[j];
+                    N.node[cnt] = node;
+                    N.pn[cnt] = B.node[j];
+                    N.len[cnt] = B.len[j] + 1;
+                    N.last[cnt] = c;
+                    N.ctx[cnt] = (B.ctx[j] * V + c) % a.ctxmod;
+                }
+            }
+        }
+        if (fill) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int tt = t + BEAM_RING + er[q];
+                if (er[q] < BEAM_RING && tt < T) lpr[((t >> 3) + 1) & 1][er[q]][ec[q]] = (double)pfx[q] - pfl[q];
+            }
+        }
+        nb = nsel;
+        __syncthreads();                                    // (also drains this step's node stores)
+    }
+
+    // results: the first nbest entries, their labels walked back to the root
+    if (tid < nbest) {
+        const BeamBuf& B = buf[T & 1];
+        if (tid < nb) {
+            const int len = B.len[tid];
+            a.length[out0 + tid] = len;
+            a.score[out0 + tid] = B.tot[tid];
+            a.total[out0 + tid] = B.tot[tid] + B.lm[tid];
+            int n = B.node[tid];
+            for (int k = len - 1; k >= 0 && n > 0; --k) {
+                const u64 v = node_load(nodes + n);
+                out_lab[(int64_t)tid * a.max_len + k] = (int32_t)(uint32_t)v;
+                n = (int)(v >> 32);
+            }
+        } else {
+            a.length[out0 + tid] = -1;
+            a.score[out0 + tid] = __builtin_nan("");
+            a.total[out0 + tid] = __builtin_nan("");
+        }
+    }
+}
+
+// pinned staging of the per-utterance table, per device; the previous call's copy out of it completes before it is rewritten
+struct Stage {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipEvent_t copied = nullptr;
+};
+std::mutex g_stage_mu;
+std::map<int, Stage> g_stage;
+
+}  // namespace
+
+int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int beam_width,
+                           int nbest, const float* lm_table, int lm_order, float lm_alpha, float lm_beta, int max_len,
+                           int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s) {
+    W2V2_REQUIRE(logits && row0 && frames && labels_out && length && score && total, "ctc_beam_search: null argument");
+    W2V2_REQUIRE(n >= 1, "ctc_beam_search: %d utterances (need at least one)", n);
+    W2V2_REQUIRE(V >= 1 && V <= W2V2_BEAM_MAX_VOCAB, "ctc_beam_search: vocabulary of %d entries; 1 to %d", V, W2V2_BEAM_MAX_VOCAB);
+    W2V2_REQUIRE(blank >= 0 && blank < V, "ctc_beam_search: blank index %d outside vocabulary %d", blank, V);
+    W2V2_REQUIRE(beam_width >= 1 && beam_width <= W2V2_BEAM_MAX_WIDTH, "ctc_beam_search: beam width %d; 1 to %d", beam_width,
+                 W2V2_BEAM_MAX_WIDTH);
+    W2V2_REQUIRE(nbest >= 1 && nbest <= beam_width, "ctc_beam_search: nbest %d outside [1, beam width %d]", nbest, beam_width);
+    W2V2_REQUIRE(lm_order >= 1 && lm_order <= 4, "ctc_beam_search: language model order %d; 1 to 4", lm_order);
+    W2V2_REQUIRE(std::isfinite(lm_alpha) && std::isfinite(lm_beta), "ctc_beam_search: language model weights must be finite");
+    int Tmax = 0;
+    for (int i = 0; i < n; ++i) {
+        W2V2_REQUIRE(frames[i] >= 1, "ctc_beam_search: utterance %d has %d frames (need at least one)", i, frames[i]);
+        W2V2_REQUIRE(row0[i] >= 0, "ctc_beam_search: utterance %d has a negative offset", i);
+        W2V2_REQUIRE((int64_t)frames[i] * beam_width < ((int64_t)1 << 31) - 1, "ctc_beam_search: utterance %d has too many frames (%d)",
+                     i, frames[i]);
+        Tmax = std::max(Tmax, (int)frames[i]);
+    }
+    W2V2_REQUIRE(max_len >= Tmax, "ctc_beam_search: max_len %d below the longest utterance's %d frames", max_len, Tmax);
+    W2V2_REQUIRE((int64_t)nbest * max_len < ((int64_t)1 << 31), "ctc_beam_search: nbest * max_len = %d * %d does not fit 31 bits", nbest,
+                 max_len);
+    std::vector<BeamSeg> segs((size_t)n);
+    int64_t out = 0, nn = 0;
+    for (int i = 0; i < n; ++i) {
+        segs[i] = BeamSeg{row0[i], out, nn, frames[i], 0};
+        out += frames[i];
+        nn += (int64_t)frames[i] * beam_width + 1;
+    }
+    // workspace: the table | lse (fp64, sum T_i) | trie nodes (sum T_i W + 1)
+    const size_t tab_bytes = ((size_t)n * sizeof(BeamSeg) + 255) & ~(size_t)255;
+    const size_t lse_bytes = ((size_t)out * sizeof(double) + 255) & ~(size_t)255;
+    void* raw = nullptr;
+    if (int e = stream_scratch(SCRATCH_BEAM, s, tab_bytes + lse_bytes + (size_t)nn * sizeof(u64), &raw)) return e;
+    BeamArgs a;
+    a.logits = logits;
+    a.segs = static_cast<const BeamSeg*>(raw);
+    a.lse = reinterpret_cast<double*>(static_cast<char*>(raw) + tab_bytes);
+    a.nodes = reinterpret_cast<u64*>(static_cast<char*>(raw) + tab_bytes + lse_bytes);
+    a.lm = lm_table;
+    a.labels = labels_out;
+    a.length = length;
+    a.score = score;
+    a.total = total;
+    a.alpha = (double)lm_alpha;
+    a.beta = (double)lm_beta;
+    a.V = V;
+    a.blank = blank;
+    a.W = beam_width;
+    a.nbest = nbest;
+    a.max_len = max_len;
+    a.ctxmod = 1;
+    if (lm_table)
+        for (int k = 1; k < lm_order; ++k) a.ctxmod *= V;
+    {
+        int dev = 0;
+        W2V2_HIP_CHECK(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lock(g_stage_mu);
+        Stage& st = g_stage[dev];
+        const size_t bytes = (size_t)n * sizeof(BeamSeg);
+        if (!st.copied) W2V2_HIP_CHECK(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+        W2V2_HIP_CHECK(hipEventSynchronize(st.copied));
+        if (st.bytes < bytes) {
+            if (st.p) W2V2_HIP_CHECK(hipHostFree(st.p));
+            st.p = nullptr;
+            st.bytes = 0;
+            const size_t want = std::max(bytes, (size_t)16 << 10);
+            W2V2_HIP_CHECK(hipHostMalloc(&st.p, want, hipHostMallocDefault));
+            st.bytes = want;
+        }
+        memcpy(st.p, segs.data(), bytes);
+        W2V2_HIP_CHECK(hipMemcpyAsync(raw, st.p, bytes, hipMemcpyHostToDevice, s));
+        W2V2_HIP_CHECK(hipEventRecord(st.copied, s));
+    }
+    // (work for the profile: about 4 fp64 operations per candidate and step; the logits read once by the lse pass)
+    ProfScope ps(nullptr, FAM_CTC, 4.0 * (double)out * beam_width * V, 4.0 * (double)out * V, s);
+    W2V2_LAUNCH(beam_lse_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);
+    W2V2_LAUNCH(beam_search_kernel, dim3((unsigned)n), dim3(BEAM_NT), 0, s, a);
+    W2V2_HIP_CHECK(hipGetLastError());
+    return W2V2_OK;
+}
+
+}  // namespace w2v2

@@ -379,7 +379,7 @@ int launch_pack_gather(const float* stream_rows, float* out, int64_t out_rows, i
 int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int width, const PackSeg* segs, int nseg, hipStream_t s);
 
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
-enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4 };
+enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4, SCRATCH_BEAM = 5 };
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out);
 int stream_scratch_release();       // frees the calling device's scratch buffers
 // one layer's q | k | v projections <-> the packed (H, 3H) kernel and (3H) bias (shadow.hip); unpack skips null targets
@@ -418,6 +418,11 @@ int launch_ctc_x(Profiler* prof, const float* logits, int B, int T, int V, const
 int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
                      const int64_t* label0, const int32_t* nlabels, int blank, int32_t* token, int32_t* label_index,
                      float* frame_logp, double* score, hipStream_t s);
+// CTC prefix beam search (beam.hip; w2v2_ctc_beam_search): the same addressing of the logits; per utterance nbest rows of max_len
+// labels, their lengths (-1: no such hypothesis), score (CTC log-probability over the kept paths) and total (score + LM)
+int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int beam_width,
+                           int nbest, const float* lm_table, int lm_order, float lm_alpha, float lm_beta, int max_len,
+                           int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s);
 
 // ---- device helpers ---------------------------------------------------------
 #ifdef __HIPCC__

@@ -1167,6 +1167,13 @@ int w2v2_ctc_align(const float* logits, int32_t V, int32_t n, const int64_t* row
                             reinterpret_cast<hipStream_t>(stream));
 }
 
+int w2v2_ctc_beam_search(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t blank,
+                         int32_t beam_width, int32_t nbest, const float* lm_table, int32_t lm_order, float lm_alpha, float lm_beta,
+                         int32_t max_len, int32_t* labels_out, int32_t* length, double* score, double* total, void* stream) {
+    return launch_ctc_beam_search(logits, V, n, row0, frames, blank, beam_width, nbest, lm_table, lm_order, lm_alpha, lm_beta, max_len,
+                                  labels_out, length, score, total, reinterpret_cast<hipStream_t>(stream));
+}
+
 int w2v2_activation_info(const w2v2_model* m, const char* name, int64_t shape[3]) {
     W2V2_REQUIRE(m && name && shape, "activation_info: null argument");
     auto it = m->acts.find(name);

@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_PKG_ROOT, "lib", "libw2v2.so")
 
 MAX_CONV_LAYERS = 16
 ALIGN_MAX_LABELS = 8191          # W2V2_ALIGN_MAX_LABELS: labels per utterance of w2v2_ctc_align
+BEAM_MAX_WIDTH = 64              # W2V2_BEAM_MAX_WIDTH, W2V2_BEAM_MAX_VOCAB: limits of w2v2_ctc_beam_search
+BEAM_MAX_VOCAB = 64
 
 
 class W2V2Config(C.Structure):
@@ -64,6 +66,7 @@ PROTOTYPES = {
     "w2v2_ctc_loss": (C.c_int, [_P, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P]),
     "w2v2_ctc_loss_fused": (C.c_int, [_P, _I32, _I32, _I32, _P, _I32, _I32, _I32, C.c_float, _P, _P, _P, _P]),
     "w2v2_ctc_align": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    "w2v2_ctc_beam_search": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_float, C.c_float, _I32, _P, _P, _P, _P, _P]),
     "w2v2_set_trainable": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "w2v2_set_trainable_flags": (C.c_int, [_P, _P, _I32]),
     "w2v2_set_option": (C.c_int, [_P, _I32, _I32]),

@@ -696,3 +696,43 @@ class Wav2Vec2ForCTC(TFKerasModel):
         seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
         alignments = forced_align(self.predict_packed(waveforms), ids, blank=self.config.pad_id)
         return [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab) for a in alignments]
+
+    def transcribe(self, waveforms, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False):
+        """Text: `predict_packed(waveforms)`, then the CTC prefix beam search on the packed logits in place
+        (wav2vec2.decoding.beam_search; blank = config.pad_id), ids -> text with `tokenizer` (a Wav2Vec2Processor(is_tokenizer=True);
+        "|" -> space, as its `decode`).  `lm`: a wav2vec2.decoding.CharNgramLM or None.  `beam_width=None` is the greedy path for
+        comparison: the argmax of every frame on the device, then `tokenizer.decode`.  With `timestamps=True` the best hypothesis
+        of each utterance goes through the forced alignment (wav2vec2.alignment) and the result carries its WordSpans (none for
+        an empty transcript).  Returns one wav2vec2.decoding.Transcript(text, hypotheses, texts, words) per utterance; see
+        `beam_search` for what a hypothesis' score means.  Runs in the precision modes predict_packed accepts."""
+        from .alignment import forced_align, token_spans, word_spans
+        from .decoding import Hypothesis, Transcript, beam_search
+        from .processor import WORD_DELIMITER
+        blank = self.config.pad_id
+        logits = self.predict_packed(waveforms)
+        if beam_width is None:
+            if lm is not None:
+                raise ValueError("the greedy path takes no language model")
+            hyps = []
+            for l in logits:
+                path = l.argmax(dim=1).cpu().numpy()
+                keep = np.flatnonzero((path != blank) & (np.concatenate(([True], path[1:] != path[:-1]))))
+                hyps.append([Hypothesis(tuple(int(v) for v in path[keep]), float("nan"), float("nan"))])
+        else:
+            hyps = beam_search(logits, beam_width=beam_width, nbest=nbest, blank=blank, lm=lm)
+        words = [None] * len(hyps)
+        if timestamps:
+            tokens = tokenizer.get_vocab()
+            vocab = {i: (" " if t == WORD_DELIMITER else t) for t, i in tokens.items()}
+            seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
+            have = [i for i, h in enumerate(hyps) if h and h[0].ids]
+            words = [[] for _ in hyps]
+            if have:
+                alignments = forced_align([logits[i] for i in have], [list(hyps[i][0].ids) for i in have], blank=blank)
+                for i, a in zip(have, alignments):
+                    words[i] = word_spans(token_spans(a), tokens[WORD_DELIMITER], seconds_per_frame, vocab)
+        out = []
+        for h, w in zip(hyps, words):
+            texts = [x.text(tokenizer) for x in h]
+            out.append(Transcript(texts[0] if texts else "", h, texts, w))
+        return out

@@ -242,6 +242,28 @@ int w2v2_ctc_align(const float* logits_dev, int32_t V, int32_t n, const int64_t*
                    const int32_t* labels_dev, const int64_t* label0_host, const int32_t* nlabels_host, int32_t blank,
                    int32_t* token_dev, int32_t* label_index_dev, float* frame_logp_dev, double* score_dev, void* stream);
 
+/* CTC prefix beam search (exact definition in csrc/beam.hip): the nbest most probable transcripts of each utterance,
+ * optionally fused with a character n-gram language model.  Model-free, like w2v2_ctc_align, and with the same addressing:
+ *   utterance i: logits_dev rows [row0_host[i], row0_host[i] + frames_host[i]) of V fp32
+ *   lm_table_dev  NULL (every table value 0), or (V^(lm_order - 1), V) fp32 log-probabilities: row = the last lm_order - 1 labels of
+ *                 the prefix as digits base V, oldest first, missing history filled with the blank; a new label c adds
+ *                 lm_alpha * table[row][c] + lm_beta to the hypothesis' LM score.  The table must be finite (not checked here).
+ *   labels_out_dev (n, nbest, max_len) int32, -1 behind each hypothesis; length_dev (n, nbest), -1 where the utterance has fewer
+ *                 hypotheses; score_dev (n, nbest) fp64: the CTC log-probability of the transcript summed over the frame paths whose
+ *                 prefixes stayed in the beam at every step -- a LOWER bound of the exact value, equal to it when nothing was
+ *                 pruned; total_dev = score + LM score, the ranking key; hypotheses in descending total.
+ * 1 <= beam_width <= W2V2_BEAM_MAX_WIDTH, 1 <= nbest <= beam_width, 1 <= V <= W2V2_BEAM_MAX_VOCAB, blank in [0, V), lm_order 1..4,
+ * finite lm_alpha / lm_beta, frames_i >= 1, max_len >= max_i frames_i: otherwise W2V2_EINVAL.  An utterance with a NaN or +inf logit
+ * (or a frame of -inf only) has no hypothesis (every length -1, score = total = NaN); -inf logits are legal; neighbours are
+ * unaffected.  Results do not depend on the other utterances of the call, their order, or repetition.  Synchronises with the
+ * previous call's table upload (host-side), otherwise enqueued on `stream`. */
+#define W2V2_BEAM_MAX_WIDTH 64
+#define W2V2_BEAM_MAX_VOCAB 64
+int w2v2_ctc_beam_search(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host,
+                         int32_t blank, int32_t beam_width, int32_t nbest, const float* lm_table_dev, int32_t lm_order,
+                         float lm_alpha, float lm_beta, int32_t max_len, int32_t* labels_out_dev, int32_t* length_dev,
+                         double* score_dev, double* total_dev, void* stream);
+
 /* ---- the training step (reference src/main.py:136-259) --------
  * Replaces what Keras' train_step does around the forward: training-mode forward, backward of every
  * trainable variable, Adam.  Postnorm (base) and prenorm (robust / xlsr) transformers; the conv feature
