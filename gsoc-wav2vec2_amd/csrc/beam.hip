@@ -1,5 +1,6 @@
 // CTC prefix beam search: the n best transcripts of each of n utterances with their log-probabilities, optionally fused with a
-// character n-gram language model held as a dense table on the device.  Model-free, like ctc.hip and align.hip.
+// character n-gram language model held as a dense table on the device, or with a word n-gram model and a lexicon (second part of
+// this header).  Model-free, like ctc.hip and align.hip.
 //
 // Definition (tests/beam_reference.py implements exactly this).  x_t(v) is the fp32 logit widened to fp64, lp_t(v) = x_t(v) - lse_t
 // (lse_t reduced as align_lse_kernel reduces it), lse2(a, b) = max + log1p(exp(-|a - b|)) with -inf neutral.  A beam entry is a
@@ -39,6 +40,31 @@
 //    written at its end; the language model row values are loaded at the top of a step, used after the match.
 //  * After the sweep nbest lanes walk their node chains back to the root and write the labels with plain stores (the rest of each
 //    row is -1).  Two identical calls give identical bits; neighbours, order and repetition have no influence.
+//
+// Word n-gram language model with a lexicon (w2v2_ctc_beam_search_words; tests/wordlm_reference.py implements exactly
+// this from the prefix alone).  One label d is the word delimiter; a prefix is split into words at d, empty words do not exist.
+//  * Compiled model (host, from an ARPA model): words 0 .. NW - 1 with `unk` and `eos` (or -1); one state per context of 0 to
+//    order - 1 words, state 0 the empty context, the start state the context <s> if the model has it; per state a backoff weight
+//    bo[s] and a backoff state bstate[s] (the context without its oldest word), and arcs (word, logp, next_state) sorted by word,
+//    next_state = the longest suffix of h w that is a state.  fp32 values, widened to fp64.  State 0 holds every word, in order.
+//    lookup(s, w): acc = 0; search w among the arcs of s; hit: (acc + logp, next_state); miss: acc = acc + bo[s], s = bstate[s], again.
+//  * Lexicon: a trie over labels, child[node, c] dense (n_nodes, V), -1 no child; word_at[node] a word or -1; node 0 the root.
+//  * Every entry carries (wnode, lmstate) beside lm, functions of the prefix alone; wnode -2 = left the lexicon.  Extension by c:
+//      c != d          : wnode' = child[wnode, c] (-2 stays -2); no child: dropped (key -inf) when unk_penalty = -inf (CONSTRAINED
+//                        mode), else wnode' = -2.  lm' = lm, lmstate' = lmstate.
+//      c == d, wnode 0 : nothing changes (no word ended).
+//      c == d, w = word_at[wnode] >= 0 : (lpw, s') = lookup(lmstate, w); lm' = (lm + alpha lpw) + beta; wnode' = 0, lmstate' = s'.
+//      c == d otherwise: constrained: dropped; else (lpu, s') = lookup(lmstate, unk); lm' = (lm + alpha (lpu + unk_penalty)) + beta;
+//                        wnode' = 0, lmstate' = s'.
+//    pb, pnb, the key, the tie rule, the -inf drop and bad rows are the search's above.
+//  * Finalisation, per entry in beam order: fin = lm if wnode = 0, else the lm' of the c == d rule (the entry is removed where that
+//    rule drops it); with an eos word and score_eos: fin = fin + alpha lookup(state after that word, eos).logp (no beta);
+//    total = score + fin; the entries in descending total, equal totals by beam rank; the first nbest are returned, labels as
+//    searched (no delimiter appended).  Nothing left: no hypothesis (length -1, NaN).
+//  * In the kernel (beam_search_kernel<true>): the child lookups of a step's candidates replace the table loads at the top of the
+//    step; the c == d rule of an entry is evaluated ONCE, by the lane that writes the entry into the next beam, and kept with it
+//    (dlm, dstate; dstate -1 = dropped), so a step's delimiter candidates and the finalisation only read it; an entry that stays
+//    copies it.  lookup is a binary search per backoff level, state 0 indexed directly.  No barrier is added to a step.
 #include "common.h"
 
 #include <algorithm>
@@ -46,6 +72,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace w2v2 {
@@ -81,12 +108,24 @@ struct BeamArgs {
     int V, blank, W, nbest, max_len, ctxmod;
 };
 
+// the device arrays of a compiled word model and lexicon (w2v2_word_lm) and the search's scalars
+struct BeamWordArgs : BeamArgs {
+    w2v2_word_lm w;
+    double unk_penalty;
+    int delim, constrained, score_eos;
+};
+
 struct BeamBuf {
     double pb[BEAM_W], pnb[BEAM_W], tot[BEAM_W], lm[BEAM_W];
     u64 h[BEAM_W], hp[BEAM_W];                  // hash of the prefix, of its parent prefix
     int node[BEAM_W], pn[BEAM_W];               // trie node, parent's node
     int len[BEAM_W], last[BEAM_W], ctx[BEAM_W];
     int mi[BEAM_W];                             // rank of the entry that is this prefix without its last label, or -1
+};
+
+struct BeamBufWord : BeamBuf {
+    double dlm[BEAM_W];                         // lm and lmstate of this prefix + d (the c == d rule); dstate -1: dropped
+    int wnode[BEAM_W], lmstate[BEAM_W], dstate[BEAM_W];
 };
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -147,9 +186,54 @@ __device__ __forceinline__ int select_digit(u64 img, int idx, int pass) {
     return pass == 8 ? inv >> 8 : inv & 255;
 }
 
-__global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamArgs a) {
+// lookup(s, w) of the compiled word model: log P(w | context s) with the backoff weights added in order, and the next state
+__device__ __forceinline__ double word_lookup(const w2v2_word_lm& L, int s, int w, int* next) {
+    double acc = 0.0;
+    for (int hop = 0; hop < W2V2_WORDLM_MAX_ORDER && s != 0; ++hop) {          // (a context has at most order - 1 words)
+        int lo = L.arc0_dev[s], hi = L.arc0_dev[s + 1];
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1, aw = L.arc_word_dev[mid];
+            if (aw == w) {
+                *next = L.arc_next_dev[mid];
+                return __dadd_rn(acc, (double)L.arc_logp_dev[mid]);
+            }
+            if (aw < w) lo = mid + 1;
+            else hi = mid;
+        }
+        acc = __dadd_rn(acc, (double)L.bo_dev[s]);
+        s = L.bstate_dev[s];
+    }
+    const int i = L.arc0_dev[0] + w;                                            // state 0 holds every word, in order
+    *next = L.arc_next_dev[i];
+    return __dadd_rn(acc, (double)L.arc_logp_dev[i]);
+}
+
+// the c == d rule for an entry (wnode, lmstate, lm): lm and lmstate of the prefix + d; state -1: dropped
+__device__ __forceinline__ void word_end(const BeamWordArgs& a, int wn, int st, double lm, double* lmo, int* sto) {
+    *lmo = lm;
+    *sto = st;
+    if (wn == 0) return;
+    int w = wn > 0 ? a.w.word_at_dev[wn] : -1;
+    const bool unk = w < 0;
+    if (unk) {
+        if (a.constrained) {
+            *sto = -1;
+            return;
+        }
+        w = a.w.unk;
+    }
+    double lp = word_lookup(a.w, st, w, sto);
+    if (unk) lp = __dadd_rn(lp, a.unk_penalty);
+    *lmo = __dadd_rn(__dadd_rn(lm, __dmul_rn(a.alpha, lp)), a.beta);
+}
+
+// WORD: the word n-gram model with a lexicon in place of the character table (the header's second part)
+template <bool WORD>
+__global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t<WORD, BeamWordArgs, BeamArgs> a) {
     constexpr double NEG = -__builtin_inf();
-    __shared__ BeamBuf buf[2];
+    using Buf = std::conditional_t<WORD, BeamBufWord, BeamBuf>;
+    __shared__ Buf buf[2];
+    __shared__ int s_wn[WORD ? BEAM_W : 1], s_st[WORD ? BEAM_W : 1];      // (WORD) wnode and lmstate of the survivors
     __shared__ double lpr[2][BEAM_RING][BEAM_V];            // lp of frames 8 (t / 8) + r, half (t / 8) & 1
     __shared__ u64 childmask[BEAM_W];
     __shared__ double spb[BEAM_W], spnb[BEAM_W], stot[BEAM_W], skey[BEAM_W];      // the stay candidates of a step
@@ -201,7 +285,7 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamArgs a) {
     for (int q = 0; q < 2; ++q)
         if (er[q] < BEAM_RING && er[q] < T) lpr[0][er[q]][ec[q]] = (double)lg[(int64_t)er[q] * V + ec[q]] - ls[er[q]];
     if (tid == 0) {
-        BeamBuf& B = buf[0];
+        Buf& B = buf[0];
         B.pb[0] = 0.0;
         B.pnb[0] = NEG;
         B.tot[0] = 0.0;
@@ -216,13 +300,19 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamArgs a) {
         for (int m = 1; m < a.ctxmod; m *= V) ctx = ctx * V + blank;
         B.ctx[0] = ctx;
         B.mi[0] = -1;
+        if constexpr (WORD) {
+            B.wnode[0] = 0;
+            B.lmstate[0] = a.w.start_state;
+            B.dlm[0] = 0.0;
+            B.dstate[0] = a.w.start_state;
+        }
     }
     int nb = 1;
     __syncthreads();
 
     for (int t = 0; t < T; ++t) {
-        BeamBuf& B = buf[t & 1];
-        BeamBuf& N = buf[(t & 1) ^ 1];
+        Buf& B = buf[t & 1];
+        Buf& N = buf[(t & 1) ^ 1];
         const double* lp = lpr[(t >> 3) & 1][t & 7];
         const int nk = (nb * V + BEAM_NT - 1) / BEAM_NT;
 
@@ -241,11 +331,25 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamArgs a) {
             }
         }
         // the language model's values of this thread's candidates
+        // (WORD: their lexicon nodes: the child of the entry's node, -2 outside the lexicon, -1 dropped)
         float lmv[BEAM_KMAX];
+        int wch[BEAM_KMAX];
 #pragma unroll
         for (int k = 0; k < BEAM_KMAX; ++k) {
             lmv[k] = 0.f;
-            if (lmt && k < nk) {
+            wch[k] = -2;
+            if constexpr (WORD) {
+                if (k < nk) {
+                    const int j = jc[k] >> 8, c = jc[k] & 255;
+                    if (j < nb && c != blank && c != a.delim) {
+                        const int wn = B.wnode[j];
+                        if (wn >= 0) {
+                            const int ch = a.w.child_dev[(int64_t)wn * V + c];
+                            wch[k] = ch >= 0 ? ch : a.constrained ? -1 : -2;
+                        }
+                    }
+                }
+            } else if (lmt && k < nk) {
                 const int j = jc[k] >> 8, c = jc[k] & 255;
                 if (j < nb && c != blank) lmv[k] = lmt[(int64_t)B.ctx[j] * V + c];
             }
@@ -290,9 +394,21 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamArgs a) {
                 if (j < nb && c != blank && !((childmask[j] >> c) & 1ull)) {
                     const double base = c == B.last[j] ? B.pb[j] : B.tot[j];
                     const double pnbn = base + lp[c];
-                    const double lmn = __dadd_rn(__dadd_rn(B.lm[j], __dmul_rn(alpha, (double)lmv[k])), beta);
+                    double lmn;
+                    bool keep = true;
+                    if constexpr (WORD) {
+                        if (c == a.delim) {
+                            lmn = B.dlm[j];
+                            keep = B.dstate[j] >= 0;
+                        } else {
+                            lmn = B.lm[j];
+                            keep = wch[k] != -1;
+                        }
+                    } else {
+                        lmn = __dadd_rn(__dadd_rn(B.lm[j], __dmul_rn(alpha, (double)lmv[k])), beta);
+                    }
                     const double key = (pnbn + lmn) + 0.0;
-                    if (key > NEG) {
+                    if (key > NEG && keep) {
                         img[k] = key_image(key);
                         valid |= 1u << k;
                     }
@@ -402,7 +518,14 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamArgs a) {
                             s_pb[slot] = NEG;
                             s_pnb[slot] = pnbn;
                             s_tot[slot] = pnbn;
-                            s_lm[slot] = __dadd_rn(__dadd_rn(B.lm[j], __dmul_rn(alpha, (double)lmv[k])), beta);
+                            if constexpr (WORD) {
+                                const bool ends = c == a.delim;
+                                s_lm[slot] = ends ? B.dlm[j] : B.lm[j];
+                                s_wn[slot] = ends ? 0 : wch[k];
+                                s_st[slot] = ends ? B.dstate[j] : B.lmstate[j];
+                            } else {
+                                s_lm[slot] = __dadd_rn(__dadd_rn(B.lm[j], __dmul_rn(alpha, (double)lmv[k])), beta);
+                            }
                         }
                     }
                     before_k += __popcll(bl);
@@ -438,6 +561,12 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamArgs a) {
                     N.len[cnt] = B.len[j];
                     N.last[cnt] = B.last[j];
                     N.ctx[cnt] = B.ctx[j];
+                    if constexpr (WORD) {
+                        N.wnode[cnt] = B.wnode[j];
+                        N.lmstate[cnt] = B.lmstate[j];
+                        N.dlm[cnt] = B.dlm[j];
+                        N.dstate[cnt] = B.dstate[j];
+                    }
                 } else {
                     const int node = 1 + t * W + cnt;
                     nodes[node] = (u64)(uint32_t)B.node[j] << 32 | (u64)(uint32_t)c;
@@ -448,6 +577,15 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamArgs a) {
                     N.len[cnt] = B.len[j] + 1;
                     N.last[cnt] = c;
                     N.ctx[cnt] = (B.ctx[j] * V + c) % a.ctxmod;
+                    if constexpr (WORD) {                     // the word-end rule of the new prefix, once (see the header)
+                        double dl;
+                        int ds;
+                        word_end(a, s_wn[r], s_st[r], s_lm[r], &dl, &ds);
+                        N.wnode[cnt] = s_wn[r];
+                        N.lmstate[cnt] = s_st[r];
+                        N.dlm[cnt] = dl;
+                        N.dstate[cnt] = ds;
+                    }
                 }
             }
         }
@@ -462,9 +600,49 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamArgs a) {
         __syncthreads();                                    // (also drains this step's node stores)
     }
 
+    if constexpr (WORD) {
+        // finalisation (wave 0: W <= 64): the open word ended, eos, then the entries in descending total, equal totals by beam rank
+        if (wave != 0) return;
+        const Buf& B = buf[T & 1];
+        bool ok = lane < nb && B.dstate[lane] >= 0;
+        double tot = 0.0;
+        if (ok) {
+            double fin = B.dlm[lane];
+            if (a.score_eos && a.w.eos >= 0) {
+                int nx;
+                fin = __dadd_rn(fin, __dmul_rn(alpha, word_lookup(a.w, B.dstate[lane], a.w.eos, &nx)));
+            }
+            tot = B.tot[lane] + fin;
+        }
+        int rank = 0;
+        for (int q = 0; q < nb; ++q) {
+            const double tq = __shfl(tot, q, 64);
+            const int okq = __shfl((int)ok, q, 64);
+            rank += (okq && (tq > tot || (tq == tot && q < lane))) ? 1 : 0;
+        }
+        const int nfin = __popcll(__ballot(ok));
+        if (ok && rank < nbest) {
+            const int len = B.len[lane];
+            a.length[out0 + rank] = len;
+            a.score[out0 + rank] = B.tot[lane];
+            a.total[out0 + rank] = tot;
+            int n = B.node[lane];
+            for (int k = len - 1; k >= 0 && n > 0; --k) {
+                const u64 v = node_load(nodes + n);
+                out_lab[(int64_t)rank * a.max_len + k] = (int32_t)(uint32_t)v;
+                n = (int)(v >> 32);
+            }
+        }
+        if (lane >= nfin && lane < nbest) {
+            a.length[out0 + lane] = -1;
+            a.score[out0 + lane] = __builtin_nan("");
+            a.total[out0 + lane] = __builtin_nan("");
+        }
+        return;
+    }
     // results: the first nbest entries, their labels walked back to the root
     if (tid < nbest) {
-        const BeamBuf& B = buf[T & 1];
+        const Buf& B = buf[T & 1];
         if (tid < nb) {
             const int len = B.len[tid];
             a.length[out0 + tid] = len;
@@ -493,11 +671,10 @@ struct Stage {
 std::mutex g_stage_mu;
 std::map<int, Stage> g_stage;
 
-}  // namespace
-
-int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int beam_width,
-                           int nbest, const float* lm_table, int lm_order, float lm_alpha, float lm_beta, int max_len,
-                           int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s) {
+// the checks, the workspace and the launches both entries share; `a` arrives with its language model fields set
+int beam_run(BeamWordArgs& a, bool word, const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank,
+             int beam_width, int nbest, float lm_alpha, float lm_beta, int max_len, int32_t* labels_out, int32_t* length, double* score,
+             double* total, hipStream_t s) {
     W2V2_REQUIRE(logits && row0 && frames && labels_out && length && score && total, "ctc_beam_search: null argument");
     W2V2_REQUIRE(n >= 1, "ctc_beam_search: %d utterances (need at least one)", n);
     W2V2_REQUIRE(V >= 1 && V <= W2V2_BEAM_MAX_VOCAB, "ctc_beam_search: vocabulary of %d entries; 1 to %d", V, W2V2_BEAM_MAX_VOCAB);
@@ -505,7 +682,6 @@ int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row
     W2V2_REQUIRE(beam_width >= 1 && beam_width <= W2V2_BEAM_MAX_WIDTH, "ctc_beam_search: beam width %d; 1 to %d", beam_width,
                  W2V2_BEAM_MAX_WIDTH);
     W2V2_REQUIRE(nbest >= 1 && nbest <= beam_width, "ctc_beam_search: nbest %d outside [1, beam width %d]", nbest, beam_width);
-    W2V2_REQUIRE(lm_order >= 1 && lm_order <= 4, "ctc_beam_search: language model order %d; 1 to 4", lm_order);
     W2V2_REQUIRE(std::isfinite(lm_alpha) && std::isfinite(lm_beta), "ctc_beam_search: language model weights must be finite");
     int Tmax = 0;
     for (int i = 0; i < n; ++i) {
@@ -530,12 +706,10 @@ int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row
     const size_t lse_bytes = ((size_t)out * sizeof(double) + 255) & ~(size_t)255;
     void* raw = nullptr;
     if (int e = stream_scratch(SCRATCH_BEAM, s, tab_bytes + lse_bytes + (size_t)nn * sizeof(u64), &raw)) return e;
-    BeamArgs a;
     a.logits = logits;
     a.segs = static_cast<const BeamSeg*>(raw);
     a.lse = reinterpret_cast<double*>(static_cast<char*>(raw) + tab_bytes);
     a.nodes = reinterpret_cast<u64*>(static_cast<char*>(raw) + tab_bytes + lse_bytes);
-    a.lm = lm_table;
     a.labels = labels_out;
     a.length = length;
     a.score = score;
@@ -547,9 +721,6 @@ int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row
     a.W = beam_width;
     a.nbest = nbest;
     a.max_len = max_len;
-    a.ctxmod = 1;
-    if (lm_table)
-        for (int k = 1; k < lm_order; ++k) a.ctxmod *= V;
     {
         int dev = 0;
         W2V2_HIP_CHECK(hipGetDevice(&dev));
@@ -573,9 +744,58 @@ int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row
     // (work for the profile: about 4 fp64 operations per candidate and step; the logits read once by the lse pass)
     ProfScope ps(nullptr, FAM_CTC, 4.0 * (double)out * beam_width * V, 4.0 * (double)out * V, s);
     W2V2_LAUNCH(beam_lse_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);
-    W2V2_LAUNCH(beam_search_kernel, dim3((unsigned)n), dim3(BEAM_NT), 0, s, a);
+    if (word) W2V2_LAUNCH(beam_search_kernel<true>, dim3((unsigned)n), dim3(BEAM_NT), 0, s, a);
+    else W2V2_LAUNCH(beam_search_kernel<false>, dim3((unsigned)n), dim3(BEAM_NT), 0, s, static_cast<const BeamArgs&>(a));
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
+}
+
+}  // namespace
+
+int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int beam_width,
+                           int nbest, const float* lm_table, int lm_order, float lm_alpha, float lm_beta, int max_len,
+                           int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s) {
+    W2V2_REQUIRE(lm_order >= 1 && lm_order <= 4, "ctc_beam_search: language model order %d; 1 to 4", lm_order);
+    BeamWordArgs a{};
+    a.lm = lm_table;
+    a.ctxmod = 1;
+    if (lm_table && V >= 1 && V <= W2V2_BEAM_MAX_VOCAB)
+        for (int k = 1; k < lm_order; ++k) a.ctxmod *= V;
+    return beam_run(a, false, logits, V, n, row0, frames, blank, beam_width, nbest, lm_alpha, lm_beta, max_len, labels_out, length, score,
+                    total, s);
+}
+
+int launch_ctc_beam_search_words(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank,
+                                 int beam_width, int nbest, const w2v2_word_lm* lm, int delim, float lm_alpha, float lm_beta,
+                                 float unk_penalty, int score_eos, int max_len, int32_t* labels_out, int32_t* length, double* score,
+                                 double* total, hipStream_t s) {
+    W2V2_REQUIRE(lm, "ctc_beam_search_words: null language model");
+    W2V2_REQUIRE(lm->child_dev && lm->word_at_dev && lm->arc0_dev && lm->arc_word_dev && lm->arc_logp_dev && lm->arc_next_dev &&
+                     lm->bo_dev && lm->bstate_dev, "ctc_beam_search_words: null language model array");
+    W2V2_REQUIRE(lm->n_nodes >= 1 && lm->n_states >= 1 && lm->n_arcs >= 1 && lm->n_words >= 1,
+                 "ctc_beam_search_words: language model sizes must be positive (nodes %d, states %d, arcs %d, words %d)", lm->n_nodes,
+                 lm->n_states, lm->n_arcs, lm->n_words);
+    W2V2_REQUIRE(lm->order >= 1 && lm->order <= W2V2_WORDLM_MAX_ORDER, "ctc_beam_search_words: language model order %d; 1 to %d",
+                 lm->order, W2V2_WORDLM_MAX_ORDER);
+    W2V2_REQUIRE(V < 1 || (int64_t)lm->n_nodes * V < ((int64_t)1 << 31), "ctc_beam_search_words: lexicon of %d nodes times %d labels does not fit 31 bits",
+                 lm->n_nodes, V);
+    W2V2_REQUIRE(lm->start_state >= 0 && lm->start_state < lm->n_states, "ctc_beam_search_words: start state %d outside [0, %d)",
+                 lm->start_state, lm->n_states);
+    W2V2_REQUIRE(lm->unk >= 0 && lm->unk < lm->n_words, "ctc_beam_search_words: unk word %d outside [0, %d)", lm->unk, lm->n_words);
+    W2V2_REQUIRE(lm->eos >= -1 && lm->eos < lm->n_words, "ctc_beam_search_words: eos word %d outside [-1, %d)", lm->eos, lm->n_words);
+    W2V2_REQUIRE(lm->n_arcs >= lm->n_words, "ctc_beam_search_words: %d arcs cannot hold the %d words of state 0", lm->n_arcs, lm->n_words);
+    W2V2_REQUIRE(delim >= 0 && delim < V && delim != blank, "ctc_beam_search_words: word delimiter %d outside vocabulary %d or the blank", delim, V);
+    W2V2_REQUIRE(!(unk_penalty != unk_penalty) && unk_penalty <= 0.f, "ctc_beam_search_words: unk_penalty must be <= 0 or -inf, not NaN");
+    BeamWordArgs a{};
+    a.lm = nullptr;
+    a.ctxmod = 1;
+    a.w = *lm;
+    a.constrained = std::isinf(unk_penalty) ? 1 : 0;
+    a.unk_penalty = a.constrained ? 0.0 : (double)unk_penalty;
+    a.delim = delim;
+    a.score_eos = score_eos ? 1 : 0;
+    return beam_run(a, true, logits, V, n, row0, frames, blank, beam_width, nbest, lm_alpha, lm_beta, max_len, labels_out, length, score,
+                    total, s);
 }
 
 }  // namespace w2v2

@@ -423,6 +423,11 @@ int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, con
 int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int beam_width,
                            int nbest, const float* lm_table, int lm_order, float lm_alpha, float lm_beta, int max_len,
                            int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s);
+// the same search with a word n-gram model and a lexicon in place of the table (w2v2_ctc_beam_search_words)
+int launch_ctc_beam_search_words(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank,
+                                 int beam_width, int nbest, const w2v2_word_lm* lm, int delim, float lm_alpha, float lm_beta,
+                                 float unk_penalty, int score_eos, int max_len, int32_t* labels_out, int32_t* length, double* score,
+                                 double* total, hipStream_t s);
 
 // ---- device helpers ---------------------------------------------------------
 #ifdef __HIPCC__

@@ -1174,6 +1174,14 @@ int w2v2_ctc_beam_search(const float* logits, int32_t V, int32_t n, const int64_
                                   labels_out, length, score, total, reinterpret_cast<hipStream_t>(stream));
 }
 
+int w2v2_ctc_beam_search_words(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t blank,
+                               int32_t beam_width, int32_t nbest, const w2v2_word_lm* lm, int32_t delim, float lm_alpha, float lm_beta,
+                               float unk_penalty, int32_t score_eos, int32_t max_len, int32_t* labels_out, int32_t* length,
+                               double* score, double* total, void* stream) {
+    return launch_ctc_beam_search_words(logits, V, n, row0, frames, blank, beam_width, nbest, lm, delim, lm_alpha, lm_beta, unk_penalty,
+                                        score_eos, max_len, labels_out, length, score, total, reinterpret_cast<hipStream_t>(stream));
+}
+
 int w2v2_activation_info(const w2v2_model* m, const char* name, int64_t shape[3]) {
     W2V2_REQUIRE(m && name && shape, "activation_info: null argument");
     auto it = m->acts.find(name);

@@ -17,6 +17,7 @@ MAX_CONV_LAYERS = 16
 ALIGN_MAX_LABELS = 8191          # W2V2_ALIGN_MAX_LABELS: labels per utterance of w2v2_ctc_align
 BEAM_MAX_WIDTH = 64              # W2V2_BEAM_MAX_WIDTH, W2V2_BEAM_MAX_VOCAB: limits of w2v2_ctc_beam_search
 BEAM_MAX_VOCAB = 64
+WORDLM_MAX_ORDER = 5             # W2V2_WORDLM_MAX_ORDER: order of the word n-gram model of w2v2_ctc_beam_search_words
 
 
 class W2V2Config(C.Structure):
@@ -43,6 +44,12 @@ class W2V2Config(C.Structure):
     ]
 
 
+class W2V2WordLM(C.Structure):
+    """struct w2v2_word_lm (include/w2v2.h): device arrays and sizes of a compiled word n-gram model and its lexicon."""
+    _fields_ = [(k, C.c_void_p) for k in ("child", "word_at", "arc0", "arc_word", "arc_logp", "arc_next", "bo", "bstate")] + \
+               [(k, C.c_int32) for k in ("n_nodes", "n_states", "n_arcs", "n_words", "order", "start_state", "unk", "eos")]
+
+
 # name -> (restype, argtypes); every symbol declared in include/w2v2.h
 _P = C.c_void_p
 _I32 = C.c_int32
@@ -67,6 +74,8 @@ PROTOTYPES = {
     "w2v2_ctc_loss_fused": (C.c_int, [_P, _I32, _I32, _I32, _P, _I32, _I32, _I32, C.c_float, _P, _P, _P, _P]),
     "w2v2_ctc_align": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "w2v2_ctc_beam_search": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_float, C.c_float, _I32, _P, _P, _P, _P, _P]),
+    "w2v2_ctc_beam_search_words": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, C.POINTER(W2V2WordLM), _I32, C.c_float, C.c_float,
+                                             C.c_float, _I32, _I32, _P, _P, _P, _P, _P]),
     "w2v2_set_trainable": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "w2v2_set_trainable_flags": (C.c_int, [_P, _P, _I32]),
     "w2v2_set_option": (C.c_int, [_P, _I32, _I32]),

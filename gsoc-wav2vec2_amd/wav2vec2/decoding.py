@@ -3,8 +3,13 @@
 ``beam_search`` returns, per utterance, the n most probable transcripts with their log-probabilities; ``CharNgramLM`` is an
 optional character n-gram language model, a dense table of log-probabilities that the kernel reads on the device.  The search
 is a HIP kernel; the table is counted and smoothed on the host (it is built once) and uploaded on first use.
+
+``WordNgramLM`` is the other kind of language model: a word-level backoff n-gram (read from an ARPA file or counted from text)
+with a lexicon that spells its words in the model's labels (w2v2_ctc_beam_search_words).
 """
 
+import math
+import os
 from typing import NamedTuple
 
 import numpy as np
@@ -98,6 +103,413 @@ class CharNgramLM:
         return cls.from_ids([tokenizer(t) for t in texts], max(vocab.values()) + 1, vocab[PAD_TOKEN], order, add_k, alpha, beta)
 
 
+BOS, EOS, UNK = "<s>", "</s>", "<unk>"
+_LN10 = math.log(10.0)
+
+
+def _ln32(log10_value):
+    """an ARPA log10 value as the model holds it: natural log in fp64, rounded to fp32 once"""
+    return float(np.float32(np.float64(log10_value) * np.float64(_LN10)))
+
+
+class WordNgramLM:
+    """Word n-gram backoff language model with a lexicon, for ``beam_search`` / ``Wav2Vec2ForCTC.transcribe``.
+
+    The search splits a hypothesis into words at the label ``delimiter``.  A word that ends adds ``alpha * ln P(word | the
+    order - 1 words before it) + beta`` to the hypothesis' language-model score, P by the usual backoff recursion; a label
+    string that is no word of the lexicon is scored as ``<unk>`` with ``unk_penalty`` (<= 0) added to its log-probability -- or,
+    with ``unk_penalty = -inf`` (the CONSTRAINED mode), a hypothesis that leaves the lexicon is dropped on the spot.  After the
+    last frame the open word is ended, ``alpha * ln P(</s> | .)`` is added (``score_eos``, where the model has ``</s>``) and the
+    final beam is ordered by that total.  In constrained mode an utterance can end with no hypothesis at all (every entry of
+    the final beam inside an unfinished word): ``beam_search`` then returns an empty list for it, ``transcribe`` an empty text.
+
+    ``ngrams``: {tuple of words: log10 P(last | the others)}, ``backoffs``: {tuple of words: log10 backoff weight} -- the
+    contents of an ARPA file, with ``<s>``, ``</s>``, ``<unk>`` as there.  Every n-gram's context must itself be an n-gram and
+    every word a unigram.  Without an ``<unk>`` unigram one is added with ``unk_logp`` (log10; required then).
+    ``lexicon``: {word: label ids}, the words unigrams of the model, the ids in [0, vocab_size) without the delimiter; two words
+    may not share a spelling.  Words of the model outside the lexicon can still be contexts but are never recognised.
+
+    The model is compiled on the host into a state machine (one state per context; ``states``, ``arc0``, ``arc_word``,
+    ``arc_logp``, ``arc_next``, ``bo``, ``bstate``: numpy) and the lexicon into a trie (``child`` (n_nodes, V), ``word_at``);
+    ``logp`` / ``backoff`` keep the n-gram dictionary in natural log (the fp32 values).  Uploaded on first use per device."""
+
+    MAX_ORDER = N.WORDLM_MAX_ORDER
+
+    def __init__(self, ngrams, backoffs, lexicon, vocab_size, delimiter, alpha=1.0, beta=0.0, unk_penalty=-10.0, unk_logp=None,
+                 score_eos=True):
+        V, delim = int(vocab_size), int(delimiter)
+        if not 2 <= V <= N.BEAM_MAX_VOCAB:
+            raise ValueError(f"vocabulary {V}; 2 to {N.BEAM_MAX_VOCAB}")
+        if not 0 <= delim < V:
+            raise ValueError(f"word delimiter {delim} outside the vocabulary [0, {V})")
+        if not (np.isfinite(alpha) and np.isfinite(beta)):
+            raise ValueError("alpha and beta must be finite")
+        if math.isnan(unk_penalty) or unk_penalty > 0 or unk_penalty == math.inf:
+            raise ValueError(f"unk_penalty {unk_penalty}: a value <= 0, or -inf for the constrained mode")
+        ngrams = {tuple(g): float(v) for g, v in ngrams.items()}
+        backoffs = {tuple(g): float(v) for g, v in backoffs.items()}
+        if not ngrams or any(len(g) < 1 for g in ngrams):
+            raise ValueError("the model has no n-grams (or an empty one)")
+        order = max(len(g) for g in ngrams)
+        if not 1 <= order <= self.MAX_ORDER:
+            raise ValueError(f"language model order {order}; 1 to {self.MAX_ORDER}")
+        if (UNK,) not in ngrams:
+            if unk_logp is None:
+                raise ValueError("the model has no <unk> unigram: pass unk_logp (log10)")
+            ngrams[(UNK,)] = float(unk_logp)
+        for g, v in ngrams.items():
+            if not math.isfinite(v):
+                raise ValueError(f"n-gram {' '.join(g)}: log-probability {v} is not finite")
+            if len(g) > 1 and g[:-1] not in ngrams:
+                raise ValueError(f"n-gram {' '.join(g)}: its context {' '.join(g[:-1])} is no n-gram of the model")
+            if (g[-1],) not in ngrams:
+                raise ValueError(f"n-gram {' '.join(g)}: the word {g[-1]} is no unigram of the model")
+        for g, v in backoffs.items():
+            if not math.isfinite(v):
+                raise ValueError(f"backoff weight of {' '.join(g)} is not finite")
+            if g not in ngrams:
+                raise ValueError(f"backoff weight of {' '.join(g)}, which is no n-gram of the model")
+        self.ngrams, self.backoffs = ngrams, backoffs
+        self.order, self.vocab_size, self.delimiter = order, V, delim
+        self.alpha, self.beta, self.unk_penalty, self.score_eos = float(alpha), float(beta), float(unk_penalty), bool(score_eos)
+        self.logp = {g: _ln32(v) for g, v in ngrams.items()}
+        self.backoff = {g: _ln32(v) for g, v in backoffs.items()}
+        self.lexicon = {}
+        spelled = {}
+        for w in sorted(lexicon):
+            ids = tuple(int(c) for c in lexicon[w])
+            if w in (BOS, EOS, UNK) or (w,) not in ngrams:
+                raise ValueError(f"lexicon word {w} is no word of the model")
+            if not ids or any(not 0 <= c < V or c == delim for c in ids):
+                raise ValueError(f"lexicon word {w}: spelling {ids} is empty, holds the delimiter or leaves [0, {V})")
+            if ids in spelled:
+                raise ValueError(f"lexicon words {spelled[ids]} and {w} share the spelling {ids}")
+            spelled[ids] = w
+            self.lexicon[w] = ids
+        if not self.lexicon:
+            raise ValueError("the lexicon is empty")
+        self.skipped = 0            # words of the model the tokenizer could not spell (from_arpa / from_text)
+        self._dev = {}
+        self._compile()
+        self.validate()
+
+    # ---- compilation -----------------------------------------------------------------------------------------------------------
+    def _compile(self):
+        order, V = self.order, self.vocab_size
+        self.words = sorted(g[0] for g in self.logp if len(g) == 1 and g[0] != BOS)
+        self.word_id = {w: i for i, w in enumerate(self.words)}
+        self.unk = self.word_id[UNK]
+        self.eos = self.word_id.get(EOS, -1)
+        ctx = {()}
+        for g in self.logp:
+            ctx.add(g[:-1])
+            if len(g) < order and g[-1] != EOS:
+                ctx.add(g)
+        self.states = sorted(ctx, key=lambda h: (len(h), h))
+        sid = {h: i for i, h in enumerate(self.states)}
+
+        def longest_suffix(h):
+            while h not in sid:
+                h = h[1:]
+            return sid[h]
+
+        arcs = [[] for _ in self.states]
+        for g, v in self.logp.items():
+            if g[-1] == BOS:
+                continue
+            h = g[:-1]
+            arcs[sid[h]].append((self.word_id[g[-1]], v, longest_suffix(g[-(order - 1):] if order > 1 else ())))
+        self.arc0 = np.zeros(len(self.states) + 1, np.int32)
+        for i, a in enumerate(arcs):
+            a.sort()
+            self.arc0[i + 1] = self.arc0[i] + len(a)
+        flat = [x for a in arcs for x in a]
+        self.arc_word = np.array([x[0] for x in flat], np.int32)
+        self.arc_logp = np.array([x[1] for x in flat], np.float32)
+        self.arc_next = np.array([x[2] for x in flat], np.int32)
+        self.bo = np.array([self.backoff.get(h, 0.0) for h in self.states], np.float32)
+        self.bstate = np.array([longest_suffix(h[1:]) if h else 0 for h in self.states], np.int32)
+        self.start_state = sid.get((BOS,), 0)
+        # the lexicon trie
+        child, word_at = [[-1] * V], [-1]
+        for w, ids in self.lexicon.items():
+            node = 0
+            for c in ids:
+                if child[node][c] < 0:
+                    child[node][c] = len(child)
+                    child.append([-1] * V)
+                    word_at.append(-1)
+                node = child[node][c]
+            word_at[node] = self.word_id[w]
+        self.child = np.array(child, np.int32).reshape(-1, V)
+        self.word_at = np.array(word_at, np.int32)
+
+    def validate(self):
+        """The compiled arrays are what the kernel trusts: check them (ValueError)."""
+        ns, na, nw, nn, V = len(self.bo), len(self.arc_word), len(self.words), len(self.word_at), self.vocab_size
+        a0 = self.arc0
+        if self.child.shape != (nn, V) or nn * V >= 2 ** 31:
+            raise ValueError(f"the lexicon's child table has shape {self.child.shape}; ({nn}, {V}) with fewer than 2^31 entries")
+        if len(a0) != ns + 1 or a0[0] != 0 or a0[-1] != na or (np.diff(a0) < 0).any() or len(self.bstate) != ns:
+            raise ValueError("the arc offsets do not partition the arcs")
+        if len(self.arc_logp) != na or len(self.arc_next) != na:
+            raise ValueError("the arc arrays differ in length")
+        if not (np.isfinite(self.arc_logp).all() and np.isfinite(self.bo).all()):
+            raise ValueError("the model holds a non-finite value")
+        if na and (self.arc_word.min() < 0 or self.arc_word.max() >= nw):
+            raise ValueError("an arc's word id is out of range")
+        if na and (self.arc_next.min() < 0 or self.arc_next.max() >= ns):
+            raise ValueError("an arc's next state is out of range")
+        if (self.bstate < 0).any() or (self.bstate >= np.maximum(np.arange(ns), 1)).any():
+            raise ValueError("a backoff state does not precede its state")          # (states are sorted by context length)
+        inner = np.ones(na, bool)
+        inner[a0[1:-1][a0[1:-1] < na]] = False
+        inner[0] = False
+        if (np.diff(self.arc_word)[inner[1:]] <= 0).any():
+            raise ValueError("the arcs of a state are not sorted by word id")
+        if a0[1] != nw or not np.array_equal(self.arc_word[:nw], np.arange(nw)):
+            raise ValueError("state 0 does not hold every word in order")
+        if not (0 <= self.start_state < ns and 0 <= self.unk < nw and -1 <= self.eos < nw):
+            raise ValueError("start state, unk or eos out of range")
+        c = self.child
+        if (c < -1).any() or (c >= nn).any() or (c[:, self.delimiter] >= 0).any() or (c == 0).any():
+            raise ValueError("the lexicon's child table holds a bad node")
+        if (self.word_at < -1).any() or (self.word_at >= nw).any() or self.word_at[0] != -1:
+            raise ValueError("the lexicon's word table holds a bad word id")
+
+    # ---- lookups on the host (tests, tools) ------------------------------------------------------------------------------------
+    def lookup(self, state, word):
+        """(ln P(word id | state) with the backoff weights added in order, next state): what the kernel computes"""
+        acc, s = 0.0, int(state)
+        while True:
+            lo, hi = int(self.arc0[s]), int(self.arc0[s + 1])
+            k = lo + int(np.searchsorted(self.arc_word[lo:hi], word))
+            if k < hi and self.arc_word[k] == word:
+                return acc + float(self.arc_logp[k]), int(self.arc_next[k])
+            acc = acc + float(self.bo[s])
+            s = int(self.bstate[s])
+
+    def uses_label(self, c):
+        return bool((self.child[:, int(c)] >= 0).any())
+
+    def device_arrays(self, device):
+        """(struct w2v2_word_lm, the tensors it points to) on ``device`` (uploaded on first use, then kept)"""
+        import torch
+        key = str(device)
+        if key not in self._dev:
+            self.validate()
+            t = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device)
+                 for k in ("child", "word_at", "arc0", "arc_word", "arc_logp", "arc_next", "bo", "bstate")}
+            st = N.W2V2WordLM()
+            for k, v in t.items():
+                setattr(st, k, v.data_ptr())
+            st.n_nodes, st.n_states, st.n_arcs, st.n_words = len(self.word_at), len(self.bo), len(self.arc_word), len(self.words)
+            st.order, st.start_state, st.unk, st.eos = self.order, self.start_state, self.unk, self.eos
+            self._dev[key] = (st, t)
+        return self._dev[key]
+
+    # ---- ARPA ------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def read_arpa(path_or_text):
+        """(ngrams, backoffs) of an ARPA file (a path, or the text itself when it holds a line break): the \\data\\ header with
+        its counts, one \\N-grams: section per order (log10 probability, N words, optional log10 backoff weight), \\end\\.
+        ValueError naming the line on malformed input, a count mismatch, or an n-gram whose context is missing."""
+        text = path_or_text
+        if "\n" not in text:
+            with open(os.fspath(path_or_text), "r", encoding="utf-8") as f:
+                text = f.read()
+        ngrams, backoffs, counts, seen = {}, {}, {}, {}
+        section, ended, header = None, False, False
+
+        def close(ln):
+            if section and seen.get(section, 0) != counts[section]:
+                raise ValueError(f"line {ln}: the {section}-grams section holds {seen.get(section, 0)} n-grams, the header says "
+                                 f"{counts[section]}")
+
+        ln = 0
+        for ln, raw in enumerate(text.split("\n"), 1):
+            line = raw.strip()
+            if not line:
+                continue
+            if ended:
+                raise ValueError(f"line {ln}: text after \\end\\")
+            if line == "\\data\\":
+                if header:
+                    raise ValueError(f"line {ln}: a second \\data\\ header")
+                header = True
+            elif not header:
+                raise ValueError(f"line {ln}: expected \\data\\, got `{line}`")
+            elif line.startswith("ngram ") and section is None:
+                try:
+                    n, c = line[6:].split("=")
+                    n, c = int(n), int(c)
+                except ValueError:
+                    raise ValueError(f"line {ln}: malformed count line `{line}`") from None
+                if n != len(counts) + 1 or c < 0:
+                    raise ValueError(f"line {ln}: count of order {n} out of sequence, or negative")
+                counts[n] = c
+            elif line == "\\end\\":
+                close(ln)
+                if section != len(counts) or not counts:
+                    raise ValueError(f"line {ln}: \\end\\ before the {len(counts)}-grams section")
+                ended = True
+            elif line.startswith("\\") and line.endswith("-grams:"):
+                close(ln)
+                try:
+                    n = int(line[1:-7])
+                except ValueError:
+                    raise ValueError(f"line {ln}: malformed section header `{line}`") from None
+                if n != (section or 0) + 1 or n not in counts:
+                    raise ValueError(f"line {ln}: section {n}-grams out of sequence or missing from the header")
+                section = n
+            elif section is None:
+                raise ValueError(f"line {ln}: expected a count or a section, got `{line}`")
+            else:
+                f = line.split()
+                if len(f) not in (section + 1, section + 2):
+                    raise ValueError(f"line {ln}: a {section}-gram line has {section + 1} or {section + 2} fields, got {len(f)}")
+                try:
+                    p = float(f[0])
+                    b = float(f[section + 1]) if len(f) == section + 2 else None
+                except ValueError:
+                    raise ValueError(f"line {ln}: `{line}` holds a number that does not parse") from None
+                if not math.isfinite(p) or (b is not None and not math.isfinite(b)):
+                    raise ValueError(f"line {ln}: non-finite value")
+                g = tuple(f[1:section + 1])
+                if g in ngrams:
+                    raise ValueError(f"line {ln}: n-gram `{' '.join(g)}` occurs twice")
+                if section > 1 and g[:-1] not in ngrams:
+                    raise ValueError(f"line {ln}: the context `{' '.join(g[:-1])}` of `{' '.join(g)}` is no n-gram")
+                if section > 1 and (g[-1],) not in ngrams:
+                    raise ValueError(f"line {ln}: the word `{g[-1]}` of `{' '.join(g)}` is no unigram")
+                ngrams[g] = p
+                if b is not None:
+                    backoffs[g] = b
+                seen[section] = seen.get(section, 0) + 1
+        if not ended:
+            raise ValueError(f"line {ln}: the file ends without \\end\\")
+        return ngrams, backoffs
+
+    @staticmethod
+    def spell(word, tokenizer):
+        """the label ids of a word, or None where the tokenizer cannot spell it (a character it drops, maps to <unk> or to the
+        word delimiter)"""
+        from .processor import PAD_TOKEN, UNK_TOKEN, WORD_DELIMITER
+        vocab = tokenizer.get_vocab()
+        ids = tuple(int(c) for c in tokenizer(word))
+        bad = (vocab[PAD_TOKEN], vocab[UNK_TOKEN], vocab[WORD_DELIMITER])
+        return ids if ids and len(ids) == len(word) and not any(c in bad for c in ids) else None
+
+    @classmethod
+    def _with_tokenizer(cls, ngrams, backoffs, tokenizer, lexicon, **kw):
+        from .processor import WORD_DELIMITER
+        vocab = tokenizer.get_vocab()
+        words = sorted(g[0] for g in ngrams if len(g) == 1) if lexicon is None else list(lexicon)
+        lex, spelled, skipped = {}, set(), 0
+        for w in words:
+            if w in (BOS, EOS, UNK):
+                continue
+            ids = lexicon[w] if isinstance(lexicon, dict) else cls.spell(w, tokenizer)
+            if ids is None or tuple(ids) in spelled:             # unspellable, or spelled as an earlier word (case): skipped, counted
+                skipped += 1
+                continue
+            spelled.add(tuple(ids))
+            lex[w] = tuple(ids)
+        lm = cls(ngrams, backoffs, lex, max(vocab.values()) + 1, vocab[WORD_DELIMITER], **kw)
+        lm.skipped = skipped
+        return lm
+
+    @classmethod
+    def from_arpa(cls, path_or_text, tokenizer, alpha=1.0, beta=0.0, unk_penalty=-10.0, unk_logp=None, lexicon=None, score_eos=True):
+        """The model of an ARPA file (``read_arpa``).  ``lexicon``: None = the model's unigrams without <s>, </s>, <unk>, spelled
+        by ``tokenizer``; or a list of words to spell; or {word: ids}.  Words the tokenizer cannot spell are skipped and counted
+        (``skipped``).  ``unk_logp`` (log10): the <unk> unigram to add where the file has none."""
+        ngrams, backoffs = cls.read_arpa(path_or_text)
+        return cls._with_tokenizer(ngrams, backoffs, tokenizer, lexicon, alpha=alpha, beta=beta, unk_penalty=unk_penalty,
+                                   unk_logp=unk_logp, score_eos=score_eos)
+
+    @staticmethod
+    def count_ngrams(sentences, order, discount=0.75):
+        """(ngrams, backoffs), log10, of word sequences by absolute discounting with backoff.  With c the counts over
+        <s> w1 .. wn </s>: P(w | h) = (c(h w) - D) / c(h) for a seen h w; the mass D |seen(h)| / c(h) left over goes to the
+        unseen words in proportion to P(w | h without its oldest word), i.e. bo(h) = that mass / (1 - sum over seen w of
+        P(w | shorter h)).  Unigrams: the left-over mass is <unk>'s.  So sum_w P(w | h) = 1 for every context, <unk> included."""
+        order = int(order)
+        if not 1 <= order <= WordNgramLM.MAX_ORDER:
+            raise ValueError(f"language model order {order}; 1 to {WordNgramLM.MAX_ORDER}")
+        if not 0 < discount < 1:
+            raise ValueError(f"discount {discount} outside (0, 1)")
+        c = {}
+        for sent in sentences:
+            seq = [BOS] + list(sent) + [EOS]
+            for w in sent:
+                if w in (BOS, EOS, UNK) or not w or any(ch.isspace() for ch in w):
+                    raise ValueError(f"`{w}` cannot be a word of the text")
+            for i in range(1, len(seq)):
+                for n in range(1, order + 1):
+                    if i - n + 1 >= 0:
+                        g = tuple(seq[i - n + 1:i + 1])
+                        c[g] = c.get(g, 0) + 1
+        if not any(len(g) == 1 and g[0] != EOS for g in c):
+            raise ValueError("the text holds no word")
+        by_ctx = {}
+        for g, k in c.items():
+            by_ctx.setdefault(g[:-1], {})[g[-1]] = k
+        P, BO = {}, {}
+
+        def prob(h, w):
+            while True:
+                if h + (w,) in P:
+                    return P[h + (w,)]
+                if not h:
+                    return P[(UNK,)] if (w,) not in P else P[(w,)]
+                return BO.get(h, 1.0) * prob(h[1:], w)
+
+        for h in sorted(by_ctx, key=len):
+            seen = by_ctx[h]
+            tot = float(sum(seen.values()))
+            for w, k in seen.items():
+                P[h + (w,)] = (k - discount) / tot
+            left = discount * len(seen) / tot
+            if not h:
+                P[(UNK,)] = left
+            else:
+                BO[h] = left / (1.0 - sum(prob(h[1:], w) for w in seen))
+        ngrams = {g: math.log10(p) for g, p in P.items()}
+        ngrams[(BOS,)] = -99.0
+        backoffs = {h: math.log10(b) for h, b in BO.items()}
+        return ngrams, backoffs
+
+    @classmethod
+    def from_text(cls, texts, tokenizer, order, discount=0.75, alpha=1.0, beta=0.0, unk_penalty=-10.0, lexicon=None, score_eos=True):
+        """Count the word n-grams of ``texts`` (one sentence each; upper-cased, split at blanks and hyphens, as the tokenizer
+        reads them) and smooth them with ``count_ngrams``; the lexicon as in ``from_arpa``."""
+        sents = [t.upper().replace("-", " ").split() for t in texts]
+        ngrams, backoffs = cls.count_ngrams(sents, order, discount)
+        return cls._with_tokenizer(ngrams, backoffs, tokenizer, lexicon, alpha=alpha, beta=beta, unk_penalty=unk_penalty,
+                                   score_eos=score_eos)
+
+    def to_arpa(self, path=None):
+        """The model as ARPA text (written to ``path`` if given): values in log10 with every digit, so that reading it back
+        gives the same model."""
+        out = ["\\data\\"]
+        by_n = [sorted(g for g in self.ngrams if len(g) == n) for n in range(1, self.order + 1)]
+        out += [f"ngram {n}={len(gs)}" for n, gs in enumerate(by_n, 1)]
+        for n, gs in enumerate(by_n, 1):
+            out += ["", f"\\{n}-grams:"]
+            for g in gs:
+                line = f"{self.ngrams[g]!r}\t{' '.join(g)}"
+                if g in self.backoffs:
+                    line += f"\t{self.backoffs[g]!r}"
+                out.append(line)
+        out += ["", "\\end\\", ""]
+        text = "\n".join(out)
+        if path is not None:
+            with open(os.fspath(path), "w", encoding="utf-8") as f:
+                f.write(text)
+        return text
+
+
 def _check_args(V, beam_width, nbest, blank, lm):
     if not 1 <= V <= N.BEAM_MAX_VOCAB:
         raise ValueError(f"vocabulary {V}; the beam search takes at most {N.BEAM_MAX_VOCAB}")
@@ -107,9 +519,14 @@ def _check_args(V, beam_width, nbest, blank, lm):
         raise ValueError(f"nbest {nbest} outside [1, beam_width {beam_width}]")
     if not 0 <= blank < V:
         raise ValueError(f"blank {blank} outside the vocabulary [0, {V})")
-    if lm is not None:
+    if isinstance(lm, WordNgramLM):
+        if lm.vocab_size != V:
+            raise ValueError(f"the language model has vocabulary {lm.vocab_size}, the logits {V}")
+        if lm.delimiter == blank or lm.uses_label(blank):
+            raise ValueError(f"blank {blank} is the language model's word delimiter or a letter of its lexicon")
+    elif lm is not None:
         if not isinstance(lm, CharNgramLM):
-            raise ValueError("`lm` must be a CharNgramLM")
+            raise ValueError("`lm` must be a CharNgramLM or a WordNgramLM")
         if lm.vocab_size != V:
             raise ValueError(f"the language model has vocabulary {lm.vocab_size}, the logits {V}")
 
@@ -118,7 +535,9 @@ def beam_search(logits, beam_width=16, nbest=1, blank=0, frame_lengths=None, lm=
     """CTC prefix beam search; per utterance a list of at most ``nbest`` ``Hypothesis(ids, score, total)``, best first.
 
     ``logits``: what ``forced_align`` accepts -- a list of (T_i, V) tensors (views of one storage, as ``predict_packed``
-    returns them, are read in place) or a (B, T, V) tensor with ``frame_lengths``.  ``lm``: a ``CharNgramLM`` or None.
+    returns them, are read in place) or a (B, T, V) tensor with ``frame_lengths``.  ``lm``: a ``CharNgramLM``, a
+    ``WordNgramLM`` (whose word delimiter and weights are the object's; see there for the constrained mode, in which an
+    utterance may return an empty list) or None.
 
     ``score`` is the log of the summed probability of the frame paths that spell the transcript AND whose prefixes stayed in
     the beam at every frame: a LOWER bound of the transcript's exact CTC log-probability (``-ctc_loss``), equal to it only
@@ -140,12 +559,24 @@ def beam_search(logits, beam_width=16, nbest=1, blank=0, frame_lengths=None, lm=
     total = torch.empty((n, nbest), dtype=torch.float64, device=dev)
     row0_h = np.asarray(row0, np.int64)
     frames_h = np.asarray(lens, np.int32)
-    table = lm.device_table(dev) if lm is not None else None
     lib = N.load()
+    if isinstance(lm, WordNgramLM):
+        import ctypes
+        st, _keep = lm.device_arrays(dev)
+        N.check(lib.w2v2_ctc_beam_search_words(N.ptr(base), V, n, N.ptr(row0_h), N.ptr(frames_h), blank, beam_width, nbest,
+                                               ctypes.byref(st), lm.delimiter, lm.alpha, lm.beta, lm.unk_penalty, int(lm.score_eos),
+                                               max_len, N.ptr(labels), N.ptr(length), N.ptr(score), N.ptr(total), N.current_stream()),
+                "w2v2_ctc_beam_search_words")
+        return _hypotheses(n, nbest, labels, length, score, total)
+    table = lm.device_table(dev) if lm is not None else None
     N.check(lib.w2v2_ctc_beam_search(N.ptr(base), V, n, N.ptr(row0_h), N.ptr(frames_h), blank, beam_width, nbest, N.ptr(table),
                                      lm.order if lm is not None else 1, lm.alpha if lm is not None else 0.0,
                                      lm.beta if lm is not None else 0.0, max_len, N.ptr(labels), N.ptr(length), N.ptr(score),
                                      N.ptr(total), N.current_stream()), "w2v2_ctc_beam_search")
+    return _hypotheses(n, nbest, labels, length, score, total)
+
+
+def _hypotheses(n, nbest, labels, length, score, total):
     length_h = length.cpu().numpy()
     labels_h = labels.cpu().numpy()
     score_h, total_h = score.cpu().numpy(), total.cpu().numpy()

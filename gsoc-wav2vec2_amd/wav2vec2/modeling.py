@@ -700,8 +700,9 @@ class Wav2Vec2ForCTC(TFKerasModel):
     def transcribe(self, waveforms, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False):
         """Text: `predict_packed(waveforms)`, then the CTC prefix beam search on the packed logits in place
         (wav2vec2.decoding.beam_search; blank = config.pad_id), ids -> text with `tokenizer` (a Wav2Vec2Processor(is_tokenizer=True);
-        "|" -> space, as its `decode`).  `lm`: a wav2vec2.decoding.CharNgramLM or None.  `beam_width=None` is the greedy path for
-        comparison: the argmax of every frame on the device, then `tokenizer.decode`.  With `timestamps=True` the best hypothesis
+        "|" -> space, as its `decode`).  `lm`: a wav2vec2.decoding.CharNgramLM, a wav2vec2.decoding.WordNgramLM (a word n-gram model
+        with a lexicon; in its constrained mode an utterance can end without a hypothesis: an empty text) or None.
+        `beam_width=None` is the greedy path for comparison: the argmax of every frame on the device, then `tokenizer.decode`.  With `timestamps=True` the best hypothesis
         of each utterance goes through the forced alignment (wav2vec2.alignment) and the result carries its WordSpans (none for
         an empty transcript).  Returns one wav2vec2.decoding.Transcript(text, hypotheses, texts, words) per utterance; see
         `beam_search` for what a hypothesis' score means.  Runs in the precision modes predict_packed accepts."""

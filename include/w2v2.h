@@ -264,6 +264,43 @@ int w2v2_ctc_beam_search(const float* logits_dev, int32_t V, int32_t n, const in
                          float lm_alpha, float lm_beta, int32_t max_len, int32_t* labels_out_dev, int32_t* length_dev,
                          double* score_dev, double* total_dev, void* stream);
 
+/* The same search with a WORD n-gram language model and a lexicon in place of the character table (exact definition
+ * in csrc/beam.hip).  Label `delim` is the word delimiter: a prefix is split into words at it.  The lexicon is a trie over labels
+ * (node 0 the root); the model is a backoff n-gram compiled into states (one per context, state 0 the empty context) with sorted
+ * arcs.  Everything is built on the host (wav2vec2.decoding.WordNgramLM compiles an ARPA model) and lives on the device:
+ *   child_dev     (n_nodes, V) int32: the child of a node by a label, -1 none;  word_at_dev (n_nodes): the word a node spells, -1 none
+ *   arc0_dev      (n_states + 1): the arcs of state s are arc0[s] .. arc0[s + 1], sorted by word; state 0 holds the n_words words
+ *                 0 .. n_words - 1 in order;  arc_word_dev / arc_logp_dev / arc_next_dev (n_arcs): word, ln P(word | context) fp32,
+ *                 the state after it (the longest suffix of context + word that is a state)
+ *   bo_dev        (n_states) fp32 ln backoff weight;  bstate_dev (n_states): the context without its oldest word
+ *   start_state   the context <s> (or 0);  unk: the word scored for a string outside the lexicon;  eos: </s> or -1
+ * A word w that ends in state s adds lm_alpha * lookup(s, w) + lm_beta to the hypothesis' LM score, lookup walking the backoff
+ * chain (miss: add bo[s], go to bstate[s]).  unk_penalty <= 0 is added to ln P(unk | .) for a string that is no word; -INFINITY
+ * is the CONSTRAINED mode: a hypothesis may not leave the lexicon (such candidates are dropped).  After the last frame the open
+ * word is ended, lm_alpha * ln P(eos | .) is added where score_eos != 0 and eos >= 0, and the entries of the final beam are
+ * re-ordered by that total; an entry whose open word is dropped is removed, so an utterance can have no hypothesis at all.
+ * Outputs, addressing, limits and the treatment of bad logits are w2v2_ctc_beam_search's.  W2V2_EINVAL with a message: a null
+ * pointer, delim outside [0, V) or equal to the blank, a size <= 0, order outside 1..W2V2_WORDLM_MAX_ORDER, n_nodes * V >= 2^31,
+ * non-finite lm_alpha / lm_beta, unk_penalty NaN or > 0, start_state / unk / eos out of range.  The CONTENTS of the arrays are
+ * trusted (the Python class validates them). */
+#define W2V2_WORDLM_MAX_ORDER 5
+typedef struct w2v2_word_lm {
+    const int32_t* child_dev;
+    const int32_t* word_at_dev;
+    const int32_t* arc0_dev;
+    const int32_t* arc_word_dev;
+    const float* arc_logp_dev;
+    const int32_t* arc_next_dev;
+    const float* bo_dev;
+    const int32_t* bstate_dev;
+    int32_t n_nodes, n_states, n_arcs, n_words;
+    int32_t order, start_state, unk, eos;
+} w2v2_word_lm;
+int w2v2_ctc_beam_search_words(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host,
+                               int32_t blank, int32_t beam_width, int32_t nbest, const w2v2_word_lm* lm, int32_t delim,
+                               float lm_alpha, float lm_beta, float unk_penalty, int32_t score_eos, int32_t max_len,
+                               int32_t* labels_out_dev, int32_t* length_dev, double* score_dev, double* total_dev, void* stream);
+
 /* ---- the training step (reference src/main.py:136-259) --------
  * Replaces what Keras' train_step does around the forward: training-mode forward, backward of every
  * trainable variable, Adam.  Postnorm (base) and prenorm (robust / xlsr) transformers; the conv feature
