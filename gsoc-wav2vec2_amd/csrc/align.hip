@@ -281,13 +281,8 @@ __global__ __launch_bounds__(P == 8 ? ALIGN_MAX_THREADS : 256) void align_viterb
 }
 
 // pinned staging of the per-utterance table, per device; the previous call's copy out of it completes before it is rewritten
-struct Stage {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipEvent_t copied = nullptr;
-};
 std::mutex g_stage_mu;
-std::map<int, Stage> g_stage;
+std::map<int, PinnedStage> g_stage;
 
 template <int P>
 void launch_viterbi(const AlignArgs& a, int n, hipStream_t s) {
@@ -348,21 +343,11 @@ int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, con
         int dev = 0;
         W2V2_HIP_CHECK(hipGetDevice(&dev));
         std::lock_guard<std::mutex> lock(g_stage_mu);
-        Stage& st = g_stage[dev];
+        PinnedStage& st = g_stage[dev];
         const size_t bytes = (size_t)n * sizeof(AlignSeg);
-        if (!st.copied) W2V2_HIP_CHECK(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
-        W2V2_HIP_CHECK(hipEventSynchronize(st.copied));
-        if (st.bytes < bytes) {
-            if (st.p) W2V2_HIP_CHECK(hipHostFree(st.p));
-            st.p = nullptr;
-            st.bytes = 0;
-            const size_t want = std::max(bytes, (size_t)16 << 10);
-            W2V2_HIP_CHECK(hipHostMalloc(&st.p, want, hipHostMallocDefault));
-            st.bytes = want;
-        }
+        if (int e = pinned_stage_begin(st, bytes, (size_t)16 << 10)) return e;
         memcpy(st.p, segs.data(), bytes);
-        W2V2_HIP_CHECK(hipMemcpyAsync(raw, st.p, bytes, hipMemcpyHostToDevice, s));
-        W2V2_HIP_CHECK(hipEventRecord(st.copied, s));
+        if (int e = pinned_stage_upload(st, raw, bytes, s)) return e;
     }
     // (work for the profile: the sweep's ~12 fp64 operations per state and step; the logits read once by the lse pass)
     ProfScope ps(nullptr, FAM_CTC, 12.0 * (double)out * (2.0 * Umax + 1.0), 4.0 * (double)out * V, s);

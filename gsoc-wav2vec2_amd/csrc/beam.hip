@@ -663,13 +663,8 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t
 }
 
 // pinned staging of the per-utterance table, per device; the previous call's copy out of it completes before it is rewritten
-struct Stage {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipEvent_t copied = nullptr;
-};
 std::mutex g_stage_mu;
-std::map<int, Stage> g_stage;
+std::map<int, PinnedStage> g_stage;
 
 // the checks, the workspace and the launches both entries share; `a` arrives with its language model fields set
 int beam_run(BeamWordArgs& a, bool word, const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank,
@@ -725,21 +720,11 @@ int beam_run(BeamWordArgs& a, bool word, const float* logits, int V, int n, cons
         int dev = 0;
         W2V2_HIP_CHECK(hipGetDevice(&dev));
         std::lock_guard<std::mutex> lock(g_stage_mu);
-        Stage& st = g_stage[dev];
+        PinnedStage& st = g_stage[dev];
         const size_t bytes = (size_t)n * sizeof(BeamSeg);
-        if (!st.copied) W2V2_HIP_CHECK(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
-        W2V2_HIP_CHECK(hipEventSynchronize(st.copied));
-        if (st.bytes < bytes) {
-            if (st.p) W2V2_HIP_CHECK(hipHostFree(st.p));
-            st.p = nullptr;
-            st.bytes = 0;
-            const size_t want = std::max(bytes, (size_t)16 << 10);
-            W2V2_HIP_CHECK(hipHostMalloc(&st.p, want, hipHostMallocDefault));
-            st.bytes = want;
-        }
+        if (int e = pinned_stage_begin(st, bytes, (size_t)16 << 10)) return e;
         memcpy(st.p, segs.data(), bytes);
-        W2V2_HIP_CHECK(hipMemcpyAsync(raw, st.p, bytes, hipMemcpyHostToDevice, s));
-        W2V2_HIP_CHECK(hipEventRecord(st.copied, s));
+        if (int e = pinned_stage_upload(st, raw, bytes, s)) return e;
     }
     // (work for the profile: about 4 fp64 operations per candidate and step; the logits read once by the lse pass)
     ProfScope ps(nullptr, FAM_CTC, 4.0 * (double)out * beam_width * V, 4.0 * (double)out * V, s);

@@ -263,6 +263,7 @@ int launch_gemm_bf16_sw(const uint16_t* A16, int64_t lda, int64_t strideA, const
 bool gemm_bf16_swtr_ok(int M, int N, int K, int64_t lda, int64_t ldb, int64_t strideA, int64_t strideB);
 int launch_gemm_bf16_swtr(const uint16_t* A16, int64_t lda, int64_t strideA, const uint16_t* B16, int64_t ldb, int64_t strideB, float* C,
                           int64_t ldc, int64_t strideC, int M, int N, int K, int nbatch, hipStream_t s, int kextra = 0, int krag = 0);
+bool gemm_bf16_streams_a16(int K, int64_t lda, int64_t strideA);     // launch_gemm_bf16_x streams A's shadow for this shape (gemm_bf16.hip)
 int launch_gemm_bf16_x(Profiler* prof, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb,
                        int64_t strideB, float* C, int64_t ldc, int64_t strideC, const float* bias,
                        const float* residual, int M, int N, int K, int nbatch, int act, const GemmShadows& x,
@@ -382,6 +383,16 @@ int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int widt
 enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4, SCRATCH_BEAM = 5 };
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out);
 int stream_scratch_release();       // frees the calling device's scratch buffers
+// pinned staging of a small host table on its way to the device (shadow.hip): grow-only, and the previous upload out of it has
+// completed before it is rewritten.  One per owner, who serialises its users: a model; a device's entry of a library-wide map, under that map's lock.
+struct PinnedStage {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipEvent_t copied = nullptr;     // recorded behind the last upload out of p
+};
+int pinned_stage_begin(PinnedStage& st, size_t bytes, size_t min_bytes);             // waits for the previous upload; st.p then holds >= bytes (a new buffer: >= min_bytes)
+int pinned_stage_upload(PinnedStage& st, void* dst, size_t bytes, hipStream_t s);    // dst <- st.p[0, bytes) on s
+void pinned_stage_free(PinnedStage& st);
 // one layer's q | k | v projections <-> the packed (H, 3H) kernel and (3H) bias (shadow.hip); unpack skips null targets
 int launch_qkv_pack(float* packed_w, float* packed_b, const float* const w[3], const float* const b[3], int H, hipStream_t s);
 int launch_qkv_pack_layers(float* const* packed_w, float* const* packed_b, const float* const* w, const float* const* b, int layers, int H, hipStream_t s);

@@ -803,6 +803,11 @@ int launch_gemm_bf16(Profiler* prof, const float* A, int64_t lda, int64_t stride
                               GemmShadows{}, s);
 }
 
+// The shape part of "this GEMM streams the bf16 shadow of A": whole 64-wide K tiles, and rows / batch strides that keep every
+// 16-byte piece aligned.  The launcher below adds the run-time part (a shadow was passed, its pointer is 16-byte aligned); the forward
+// plan asks this before the launch to decide which tensors need no fp32 copy.
+bool gemm_bf16_streams_a16(int K, int64_t lda, int64_t strideA) { return K % BK == 0 && lda % 8 == 0 && strideA % 8 == 0; }
+
 int launch_gemm_bf16_x(Profiler* prof, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb,
                        int64_t strideB, float* C, int64_t ldc, int64_t strideC, const float* bias,
                        const float* residual, int M, int N, int K, int nbatch, int act, const GemmShadows& x,
@@ -834,7 +839,7 @@ int launch_gemm_bf16_x(Profiler* prof, const float* A, int64_t lda, int64_t stri
     const bool kfast = K % BK == 0;
     const bool a32 = A && (lda % 4 == 0) && (strideA % 4 == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);
     const bool b32 = B && (N % 4 == 0) && (ldb % 4 == 0) && (strideB % 4 == 0) && ((reinterpret_cast<uintptr_t>(B) & 15) == 0);
-    const bool a16 = x.A16 && kfast && (lda % 8 == 0) && (strideA % 8 == 0) && ((reinterpret_cast<uintptr_t>(x.A16) & 15) == 0);
+    const bool a16 = x.A16 && gemm_bf16_streams_a16(K, lda, strideA) && ((reinterpret_cast<uintptr_t>(x.A16) & 15) == 0);
     const bool b16 = x.B16 && kfast && strideB == 0 && (g.ldb16 % 8 == 0) && ((reinterpret_cast<uintptr_t>(x.B16) & 15) == 0);
     int src;
     // tuning knob: 0 = register-staged shadows (595 TF on the forward mix), 1 = LDS-DMA, 2 stages, 2 blocks/CU (617, default),

@@ -1,4 +1,5 @@
-// Model state shared by the forward (w2v2_api.hip) and training (w2v2_train.hip) translation units.
+// Model state and the forward plan shared by the C ABI (w2v2_api.hip), the inference forward (forward.hip) and training
+// (w2v2_train.hip).
 #pragma once
 
 #include <map>
@@ -48,10 +49,8 @@ struct w2v2_model {
     int pk_seg_cap = 0, pk_tile_cap = 0;
     float *pk_wave = nullptr, *pk_scale = nullptr, *pk_out = nullptr;   // stream samples, conv0 scale / shift per utterance, head output
     void* pk_tab = nullptr;                  // device tables: PackSeg[pk_seg_cap] | SegTile[pk_tile_cap]
-    void* pk_stage = nullptr;                // pinned staging of the tables (outlives the workspace)
-    size_t pk_stage_bytes = 0;
-    hipEvent_t pk_copied = nullptr;          // recorded after the last copy out of pk_stage
-    // bf16 shadows (precision mode 1, inference forward; w2v2_api.hip::ensure_shadows).  Weight shadows are the
+    w2v2::PinnedStage pk_stage;              // pinned staging of the tables (outlives the workspace)
+    // bf16 shadows (precision mode 1, inference forward; forward.hip::w2v2_ensure_shadows).  Weight shadows are the
     // GEMM kernels transposed to (N, K); activation shadows are written by the producing kernels.
     bool sh_ready = false, w16_valid = false;
     std::unordered_map<const float*, uint16_t*> w16;      // (N, K): forward GEMMs
@@ -70,7 +69,7 @@ struct w2v2_model {
     struct SplitPlanes { uint16_t* p = nullptr; int64_t elems = 0; uint64_t epoch = 0; };
     std::unordered_map<const float*, SplitPlanes> w48;     // keyed by the fp32 matrix (a variable, or a transposed copy)
     uint64_t w48_epoch = 1;                                 // bumped whenever the variables change: entries re-split lazily
-    // precision modes 2 / 3 on the plane-fed GEMM (gemm_split_sw.hip; w2v2_api.hip::w2v2_ensure_planes): the planes of every GEMM
+    // precision modes 2 / 3 on the plane-fed GEMM (gemm_split_sw.hip; forward.hip::w2v2_ensure_planes): the planes of every GEMM
     // operand, written by its producer (three bf16 planes or two fp16 planes per element: PlaneFmt), and the weights as that kernel's
     // LDS images, built on first use and re-split lazily after the variables change (w48_epoch).  Stream order lets one buffer serve
     // every layer: attention input | ctx | FFN input | FFN hidden.
@@ -97,15 +96,74 @@ struct w2v2_model {
 };
 
 
+// ---- the forward plan (forward.hip; the table of every tensor's forms is in DESIGN.md, "The forward plan") ------------------------
+// where a producer leaves the planes of its output; converts to the launchers' optional `const PlaneOut*` (null = none)
+struct PlaneDst {
+    w2v2::PlaneOut o;
+    bool on = false;
+    operator const w2v2::PlaneOut*() const { return on ? &o : nullptr; }
+};
+
+struct ForwardPlan {
+    using PlaneBuf = w2v2_model::PlaneBuf;
+    // The forms a tensor can be stored in.  Which of them a forward writes is decided ONCE, in w2v2_plan_forward, before the first
+    // launch: producers take their destinations and consumers their sources from the same field, through the helpers below.
+    enum Form : unsigned { F32 = 1, B16 = 2 /* nearest-even bf16 shadow (precision mode bf16) */, PLANES = 4 /* operand planes (bf16x3 / f16x2) */ };
+    // sizes and modes
+    int B = 0, T = 0, NC = 0;
+    int64_t L = 0, BT = 0;
+    std::vector<int> conv_T;                 // frames per conv layer for THIS input (a packed stream runs in a larger workspace)
+    bool sh = false, attn16 = false;         // precision mode bf16 with shadows; ... and the bf16 attention kernels (q|k|v, ctx as bf16)
+    bool pm = false;                         // precision modes bf16x3 / f16x2 with operand planes
+    int fmt = w2v2::PF_BF16X3;
+    bool keep = false;                       // W2V2_OPT_KEEP_ACTIVATIONS
+    bool layer_mode = false, prenorm = false;
+    int act = 1, act_ew = 1;                 // GELU form of the GEMM epilogues / of the element-wise kernels
+    bool fused = false;                      // conv0's kernel writes the planes of its output itself
+    bool split_attn = false;                 // the split attention kernel runs (the packed forward picks its launcher by this)
+    bool ctx_fused = false;                  // ... and writes ctx's planes itself
+    bool ctx16_only = false, ffn_sh_only = false;      // mode bf16: ctx / the FFN hidden exist only as bf16 (both ignore `keep`)
+    bool pos16 = false;                      // the bf16 positional conv (needs w2v2_ensure_pos16)
+    // plane-fed GEMM call sites: cp[i] = conv layer i's GEMM (1 .. NC-1) streams the planes of conv output i - 1
+    std::vector<char> cp;
+    bool p_proj = false, p_qkv = false, p_out = false, p_f1 = false, p_f2 = false, any_planes = false;
+    // forms written in this forward, per tensor.  conv[i] is the value behind LN + GELU in LayerNorm mode; conv0_kernel / attn_kernel
+    // are the forms those two kernels write themselves (the planes of conv[0] / ctx are otherwise split off the fp32 copy behind them)
+    std::vector<unsigned> conv;
+    unsigned conv0_kernel = F32, ln512 = F32, proj = F32, hidden = F32, attn_in = F32, qkv = F32, ctx = F32, attn_kernel = F32,
+             ffn_in = F32, ffn = F32, head_in = F32;
+
+    // the GEMM behind conv layer i writes conv[i] itself, or (LayerNorm mode) the fp32 input of the LN + GELU pass that does
+    unsigned conv_gemm_out(int i) const { return layer_mode ? (unsigned)F32 : conv[i]; }
+    // a producer's destinations / a consumer's sources: the buffer when the form is written in this forward, else null
+    static float* f32(unsigned forms, float* p) { return (forms & F32) ? p : nullptr; }
+    static uint16_t* b16(unsigned forms, uint16_t* p) { return (forms & B16) ? p : nullptr; }
+    static uint16_t* b16(unsigned forms, const std::vector<uint16_t*>& v, int i) { return (forms & B16) ? v[i] : nullptr; }
+    static const PlaneBuf* planes(unsigned forms, const PlaneBuf& b) { return (forms & PLANES) ? &b : nullptr; }
+    static const PlaneBuf* planes(unsigned forms, const std::vector<PlaneBuf>& v, int i) { return (forms & PLANES) ? &v[i] : nullptr; }
+    PlaneDst plane_out(const PlaneBuf* b, int* range_flag) const {
+        PlaneDst d;
+        if (b) { d.o.p = b->p; d.o.plane = b->plane; d.o.fmt = fmt; d.o.range_flag = range_flag; d.on = true; }
+        return d;
+    }
+};
+struct PackedPlan;      // forward.hip: the tables of a packed stream
+
 // implemented in w2v2_api.hip
-bool w2v2_shadows_enabled(const w2v2_model* m);                            // W2V2_OPT_BF16_SHADOWS (default on)
-bool w2v2_conv_out_bf16_only(const w2v2_model* m, int i, bool sh);         // conv-stack output i is written only as bf16 this forward
-bool w2v2_conv_ln_bf16_only(const w2v2_model* m, int i, bool sh);          // LayerNorm-mode extractor: LN + GELU output i only as bf16
-bool w2v2_keep_activations(const w2v2_model* m);                           // W2V2_OPT_KEEP_ACTIVATIONS: also write the fp32 copies nothing reads
-int w2v2_ensure_shadows(w2v2_model* m, int B, int T, hipStream_t s);
-bool w2v2_pos_conv_bf16_ok(const w2v2_model* m);                          // precision 1 and a supported group shape
-int w2v2_ensure_pos16(w2v2_model* m, int B, int T, hipStream_t s);       // kernel shadow + pack scratch     // allocate activation shadows, (re)build weight shadows
 int w2v2_ensure_workspace(w2v2_model* m, int B, int64_t L);
+int w2v2_ws_alloc(w2v2_model* m, float** out, int64_t floats);           // a buffer that lives as long as the workspace
+void w2v2_free_planes(w2v2_model* m);
+// implemented in forward.hip
+// conv-stack output i (behind LN + GELU in LayerNorm mode) is written only as bf16: shadows on, no `keep`, and layer i + 1's GEMM streams the shadow
+bool w2v2_conv_bf16_only(const w2v2_model* m, int i, bool sh);
+// the plan of a forward over (B, L) in the model's precision mode and options; `planes` false (training) keeps every GEMM off the plane-fed route.
+// Needs the workspace (w2v2_ensure_workspace) in place.
+ForwardPlan w2v2_plan_forward(const w2v2_model* m, int B, int64_t L, bool planes, bool packed);
+// conv0, conv 1 .. NC-1, the projection LayerNorm and the projection GEMM (-> m->proj) as the plan says; sets m->acts_skipped.  pk: the packed stream, or null
+int w2v2_forward_frontend(w2v2_model* m, const ForwardPlan& plan, const float* wave, const PackedPlan* pk, hipStream_t s);
+int w2v2_ensure_shadows(w2v2_model* m, int B, int T, hipStream_t s);      // allocate activation shadows, (re)build weight shadows
+bool w2v2_pos_conv_bf16_ok(const w2v2_model* m);                          // precision 1 and a supported group shape
+int w2v2_ensure_pos16(w2v2_model* m, int B, int T, hipStream_t s);        // kernel shadow + pack scratch
 // precision mode 2: the LDS-image bf16 planes of the (K, N) fp32 matrix `W` (built / refreshed on demand; gemm_split.hip)
 int w2v2_split_planes(w2v2_model* m, const float* W, int K, int N, hipStream_t s, const uint16_t** planes);
 // whether GEMM (M, N, K) x nbatch with this A should take the split kernel in the model's current precision mode

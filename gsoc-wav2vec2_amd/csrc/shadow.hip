@@ -230,6 +230,35 @@ int stream_scratch_release() {
     return W2V2_OK;
 }
 
+int pinned_stage_begin(PinnedStage& st, size_t bytes, size_t min_bytes) {
+    if (!st.copied) W2V2_HIP_CHECK(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+    W2V2_HIP_CHECK(hipEventSynchronize(st.copied));
+    if (st.bytes < bytes) {
+        if (st.p) W2V2_HIP_CHECK(hipHostFree(st.p));
+        st.p = nullptr;
+        st.bytes = 0;
+        const size_t want = bytes > min_bytes ? bytes : min_bytes;
+        W2V2_HIP_CHECK(hipHostMalloc(&st.p, want, hipHostMallocDefault));
+        st.bytes = want;
+    }
+    return W2V2_OK;
+}
+
+int pinned_stage_upload(PinnedStage& st, void* dst, size_t bytes, hipStream_t s) {
+    W2V2_HIP_CHECK(hipMemcpyAsync(dst, st.p, bytes, hipMemcpyHostToDevice, s));
+    W2V2_HIP_CHECK(hipEventRecord(st.copied, s));
+    return W2V2_OK;
+}
+
+void pinned_stage_free(PinnedStage& st) {
+    if (st.copied) {
+        (void)hipEventSynchronize(st.copied);
+        (void)hipEventDestroy(st.copied);
+    }
+    if (st.p) (void)hipHostFree(st.p);
+    st = PinnedStage{};
+}
+
 int launch_to_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t s) {
     W2V2_REQUIRE(x && y && n > 0, "to_bf16: bad argument");
     W2V2_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0, "to_bf16: unaligned buffer");

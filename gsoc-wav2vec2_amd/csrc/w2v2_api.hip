@@ -1,12 +1,6 @@
-// C ABI (include/w2v2.h): model lifetime, variable I/O, the forward orchestration,
-// profiling and the single-operator entry points.  Host code only; the kernels
-// live in the sibling .hip files.
-//
-// Forward order follows the reference exactly: Wav2Vec2ForCTC.call
-// (modeling.py:239-255) -> Wav2Vec2Model.call (modeling.py:169-209) ->
-// FeatureExtractorLayer x7 (feature_extractor.py:54-59) -> FeatureProjection
-// (feature_extractor.py:92-95) -> Wav2Vec2Encoder.call (encoder.py:251-276) ->
-// TransformerLayer.call (encoder.py:111-134) -> lm_head.
+// C ABI (include/w2v2.h): model lifetime, variable I/O, the activation workspace, options,
+// profiling and the single-operator entry points.  Host code only; the forward is in
+// forward.hip, training in w2v2_train.hip and the kernels in the sibling .hip files.
 #include <algorithm>
 #include <mutex>
 #include <atomic>
@@ -191,7 +185,7 @@ static void build_inventory(w2v2_model* m) {
     }
 }
 
-static void free_planes(w2v2_model* m) {
+void w2v2_free_planes(w2v2_model* m) {
     for (void* p : m->pl_allocs) (void)hipFree(p);
     m->pl_allocs.clear();
     m->conv48.clear();
@@ -202,7 +196,7 @@ static void free_planes(w2v2_model* m) {
 }
 
 static void free_workspace(w2v2_model* m) {
-    free_planes(m);
+    w2v2_free_planes(m);
     for (void* p : m->allocs) (void)hipFree(p);
     m->allocs.clear();
     for (void* p : m->sh_allocs) (void)hipFree(p);
@@ -223,7 +217,7 @@ static void free_workspace(w2v2_model* m) {
     m->pk_seg_cap = m->pk_tile_cap = 0;
 }
 
-static int ws_alloc(w2v2_model* m, float** out, int64_t floats) {
+int w2v2_ws_alloc(w2v2_model* m, float** out, int64_t floats) {
     void* p = nullptr;
     W2V2_HIP_CHECK(hipMalloc(&p, (size_t)(floats > 0 ? floats : 1) * sizeof(float)));
     m->allocs.push_back(p);
@@ -240,58 +234,48 @@ int w2v2_ensure_workspace(w2v2_model* m, int B, int64_t L) {
     for (int i = 0; i < c.num_conv_layers; ++i) {
         T = 1 + (T - c.kernal_sizes[i]) / c.strides[i];
         float* p = nullptr;
-        if (int e = ws_alloc(m, &p, (int64_t)B * T * c.filter_sizes[i])) return e;
+        if (int e = w2v2_ws_alloc(m, &p, (int64_t)B * T * c.filter_sizes[i])) return e;
         m->conv.push_back(p);
         m->conv_T.push_back((int)T);
         m->acts["conv" + std::to_string(i)] = Act{p, {B, T, c.filter_sizes[i]}};
     }
     const int64_t C = c.filter_sizes[c.num_conv_layers - 1];
     const int64_t BT = (int64_t)B * T;
-    if (int e = ws_alloc(m, &m->conv0_ws, conv0_ws_floats(B, L, c.kernal_sizes[0], c.strides[0], c.filter_sizes[0]))) return e;
-    if (int e = ws_alloc(m, &m->ln512, BT * C)) return e;
-    if (int e = ws_alloc(m, &m->proj, BT * H)) return e;
-    if (int e = ws_alloc(m, &m->posout, BT * H)) return e;
+    if (int e = w2v2_ws_alloc(m, &m->conv0_ws, conv0_ws_floats(B, L, c.kernal_sizes[0], c.strides[0], c.filter_sizes[0]))) return e;
+    if (int e = w2v2_ws_alloc(m, &m->ln512, BT * C)) return e;
+    if (int e = w2v2_ws_alloc(m, &m->proj, BT * H)) return e;
+    if (int e = w2v2_ws_alloc(m, &m->posout, BT * H)) return e;
     m->acts["projection"] = Act{m->proj, {B, T, H}};
     for (int i = 0; i <= c.num_layers; ++i) {
         float* p = nullptr;
         if (c.attention_norm_type == 1 && i == 0) {
             p = m->posout;           // prenorm: encoder_in IS x + pos_conv(x)
-        } else if (int e = ws_alloc(m, &p, BT * H)) {
+        } else if (int e = w2v2_ws_alloc(m, &p, BT * H)) {
             return e;
         }
         m->hs.push_back(p);
         m->acts[i == 0 ? std::string("encoder_in") : "layer" + std::to_string(i - 1)] = Act{p, {B, T, H}};
     }
-    if (int e = ws_alloc(m, &m->qkv, BT * 3 * H)) return e;
-    if (int e = ws_alloc(m, &m->ctx, BT * H)) return e;
-    if (int e = ws_alloc(m, &m->t0, BT * H)) return e;
-    if (int e = ws_alloc(m, &m->t1, BT * H)) return e;
-    if (int e = ws_alloc(m, &m->t2, BT * H)) return e;
-    if (int e = ws_alloc(m, &m->t3, BT * H)) return e;
-    if (int e = ws_alloc(m, &m->ffn, BT * F)) return e;
+    if (int e = w2v2_ws_alloc(m, &m->qkv, BT * 3 * H)) return e;
+    if (int e = w2v2_ws_alloc(m, &m->ctx, BT * H)) return e;
+    if (int e = w2v2_ws_alloc(m, &m->t0, BT * H)) return e;
+    if (int e = w2v2_ws_alloc(m, &m->t1, BT * H)) return e;
+    if (int e = w2v2_ws_alloc(m, &m->t2, BT * H)) return e;
+    if (int e = w2v2_ws_alloc(m, &m->t3, BT * H)) return e;
+    if (int e = w2v2_ws_alloc(m, &m->ffn, BT * F)) return e;
     if (c.attention_norm_type == 1) {
-        if (int e = ws_alloc(m, &m->enc_out, BT * H)) return e;
+        if (int e = w2v2_ws_alloc(m, &m->enc_out, BT * H)) return e;
     } else {
         m->enc_out = m->hs[c.num_layers];
     }
     m->acts["encoder_out"] = Act{m->enc_out, {B, T, H}};
     float* fl = nullptr;
-    if (int e = ws_alloc(m, &fl, B + 4)) return e;
+    if (int e = w2v2_ws_alloc(m, &fl, B + 4)) return e;
     m->frame_len = reinterpret_cast<int32_t*>(fl);
     m->ws_B = B;
     m->ws_L = L;
     return W2V2_OK;
 }
-
-// ---- bf16 shadows for the inference forward in precision mode 1 ------------------------------------------
-// w2v2_set_option(m, W2V2_OPT_BF16_SHADOWS, 0) turns them off (every GEMM then rounds its fp32 operands itself): same
-// results bit for bit, used by the tests to prove exactly that.
-bool w2v2_shadows_enabled(const w2v2_model* m) { return m->opt_shadows; }
-
-// Precision mode 1 with shadows: a conv-stack output whose only consumer is the next layer's GEMM (reading the bf16 shadow)
-// is written ONLY as bf16 -- 6.3 GB of fp32 stores per B = 32 x 246000 forward that nothing would read.  Stage taps of
-// those tensors (w2v2_copy_activation) then report an error; w2v2_set_option(m, W2V2_OPT_KEEP_ACTIVATIONS, 1) keeps the fp32 copies.
-bool w2v2_keep_activations(const w2v2_model* m) { return m->opt_keep_acts; }
 
 #ifdef W2V2_TUNING
 namespace w2v2 {
@@ -301,208 +285,6 @@ int tune_int(const char* name, int dflt) {
 }
 }  // namespace w2v2
 #endif
-
-// Whether conv-stack output i (0 .. NC-2) may be written ONLY as bf16 in the coming forward: group-norm mode with shadows,
-// and layer i+1's GEMM is certain to take the bf16 shadow as its A operand (gemm_bf16.hip: K % 64 == 0 and 16-byte
-// aligned rows / batch strides) -- otherwise that GEMM reads the fp32 tensor and it must exist.
-bool w2v2_conv_out_bf16_only(const w2v2_model* m, int i, bool sh) {
-    const w2v2_config& c = m->cfg;
-    if (!sh || c.feature_extractor_norm_type == 1 || i + 1 >= c.num_conv_layers || w2v2_keep_activations(m)) return false;
-    const int64_t cin = c.filter_sizes[i], K = (int64_t)c.kernal_sizes[i + 1] * cin, lda = (int64_t)c.strides[i + 1] * cin;
-    const int64_t strideA = (int64_t)m->conv_T[i] * cin;
-    return K % 64 == 0 && lda % 8 == 0 && strideA % 8 == 0;
-}
-
-// LayerNorm-mode extractor (robust / xlsr): conv i's LayerNorm + GELU output is written ONLY as bf16 when its one consumer, conv
-// i + 1's GEMM, streams the shadow (same alignment conditions as above; the GEMM's own fp32 output is the LayerNorm's input and stays)
-bool w2v2_conv_ln_bf16_only(const w2v2_model* m, int i, bool sh) {
-    const w2v2_config& c = m->cfg;
-    if (!sh || c.feature_extractor_norm_type != 1 || i + 1 >= c.num_conv_layers || w2v2_keep_activations(m)) return false;
-    const int64_t cin = c.filter_sizes[i], K = (int64_t)c.kernal_sizes[i + 1] * cin, lda = (int64_t)c.strides[i + 1] * cin;
-    const int64_t strideA = (int64_t)m->conv_T[i] * cin;
-    return K % 64 == 0 && lda % 8 == 0 && strideA % 8 == 0;
-}
-
-static int sh_alloc(std::vector<void*>& pool, uint16_t** out, int64_t n) {
-    void* p = nullptr;
-    W2V2_HIP_CHECK(hipMalloc(&p, (size_t)(n > 0 ? n : 1) * sizeof(uint16_t)));
-    pool.push_back(p);
-    *out = reinterpret_cast<uint16_t*>(p);
-    return W2V2_OK;
-}
-
-int w2v2_ensure_shadows(w2v2_model* m, int B, int T, hipStream_t s) {
-    const w2v2_config& c = m->cfg;
-    const int64_t H = c.hidden_size, F = c.intermediate_size, BT = (int64_t)B * T;
-    if (!m->sh_ready) {
-        for (int i = 0; i + 1 < c.num_conv_layers; ++i) {       // the last conv output feeds a LayerNorm, not a GEMM
-            uint16_t* p = nullptr;
-            if (int e = sh_alloc(m->sh_allocs, &p, (int64_t)B * m->conv_T[i] * c.filter_sizes[i])) return e;
-            m->conv16.push_back(p);
-        }
-        if (int e = sh_alloc(m->sh_allocs, &m->ln512_16, BT * c.filter_sizes[c.num_conv_layers - 1])) return e;
-        for (int i = 0; i <= c.num_layers; ++i) {
-            uint16_t* p = nullptr;
-            if (int e = sh_alloc(m->sh_allocs, &p, BT * H)) return e;
-            m->hs16.push_back(p);
-        }
-        if (int e = sh_alloc(m->sh_allocs, &m->ctx16, BT * H)) return e;
-        if (int e = sh_alloc(m->sh_allocs, &m->qkv16, BT * 3 * H)) return e;
-        if (int e = sh_alloc(m->sh_allocs, &m->t0_16, BT * H)) return e;
-        if (int e = sh_alloc(m->sh_allocs, &m->t2_16, BT * H)) return e;
-        if (int e = sh_alloc(m->sh_allocs, &m->ffn16, BT * F)) return e;
-        if (int e = sh_alloc(m->sh_allocs, &m->enc16, BT * H)) return e;
-        m->sh_ready = true;
-    }
-    if (!m->w16_valid) {
-        // (re)build the job table when it does not exist yet or the plain copies have become necessary (training started)
-        const bool want_plain = m->train != nullptr;
-        if (!m->shadow_jobs || (want_plain && !m->shadow_jobs_train)) {
-            std::vector<ShadowJob> jobs;
-            auto shadow = [&](const float* w, int K, int N) -> int {
-                uint16_t*& dst = m->w16[w];
-                if (!dst)
-                    if (int e = sh_alloc(m->w16_allocs, &dst, (int64_t)K * N)) return e;
-                uint16_t* plain = nullptr;
-                if (want_plain && N % 64 == 0 && (K * (int64_t)N) % 4 == 0) {     // training: the backward's dX GEMM contracts over N
-                    uint16_t*& dp = m->w16p[w];
-                    if (!dp)
-                        if (int e = sh_alloc(m->w16_allocs, &dp, (int64_t)K * N)) return e;
-                    plain = dp;
-                }
-                for (int k0 = 0; k0 < K; k0 += 64)
-                    for (int n0 = 0; n0 < N; n0 += 64) jobs.push_back(ShadowJob{w, dst, plain, K, N, k0, n0});
-                return W2V2_OK;
-            };
-            for (int i = 1; i < c.num_conv_layers; ++i)
-                if (int e = shadow(m->P("feature_extractor/conv_layers/" + std::to_string(i) + "/conv/kernel"),
-                                   c.kernal_sizes[i] * c.filter_sizes[i - 1], c.filter_sizes[i]))
-                    return e;
-            if (int e = shadow(m->P("feature_projection/projection/kernel"), c.filter_sizes[c.num_conv_layers - 1], (int)H)) return e;
-            for (int i = 0; i < c.num_layers; ++i) {
-                const std::string b = "encoder/layers/" + std::to_string(i);
-                if (int e = shadow(m->qkv_w[i], (int)H, 3 * (int)H)) return e;
-                if (int e = shadow(m->P(b + "/attention/out_proj/kernel"), (int)H, (int)H)) return e;
-                if (int e = shadow(m->P(b + "/feed_forward/intermediate_dense/kernel"), (int)H, (int)F)) return e;
-                if (int e = shadow(m->P(b + "/feed_forward/output_dense/kernel"), (int)F, (int)H)) return e;
-            }
-            if (c.with_lm_head)
-                if (int e = shadow(m->P("lm_head/kernel"), (int)H, c.vocab_size)) return e;
-            if (m->shadow_jobs) W2V2_HIP_CHECK(hipFree(m->shadow_jobs));
-            m->shadow_jobs = nullptr;
-            W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->shadow_jobs), jobs.size() * sizeof(ShadowJob)));
-            W2V2_HIP_CHECK(hipMemcpy(m->shadow_jobs, jobs.data(), jobs.size() * sizeof(ShadowJob), hipMemcpyHostToDevice));
-            m->shadow_njobs = (int)jobs.size();
-            m->shadow_jobs_train = want_plain;
-        }
-        if (int e = launch_weight_shadows_multi(m->shadow_jobs, m->shadow_njobs, s)) return e;
-        m->w16_valid = true;
-    }
-    return W2V2_OK;
-}
-
-// ---- precision modes 2 / 3: operand planes (gemm_split_sw.hip) ----------------------------------------------------------------
-int w2v2_ensure_planes(w2v2_model* m, int B, int64_t L, int fmt) {
-    if (m->pl_fmt == fmt && m->pl_B == B && m->pl_L == L) return W2V2_OK;
-    free_planes(m);
-    const w2v2_config& c = m->cfg;
-    const int np = plane_count(fmt);
-    auto alloc = [&](w2v2_model::PlaneBuf& b, int64_t elems) -> int {
-        b.plane = (elems + 7) & ~(int64_t)7;                 // 16-byte aligned planes
-        void* p = nullptr;
-        W2V2_HIP_CHECK(hipMalloc(&p, (size_t)b.plane * np * sizeof(uint16_t)));
-        m->pl_allocs.push_back(p);
-        b.p = reinterpret_cast<uint16_t*>(p);
-        return W2V2_OK;
-    };
-    const int NC = c.num_conv_layers;
-    m->conv48.resize(NC > 1 ? NC - 1 : 0);
-    for (int i = 0; i + 1 < NC; ++i)
-        if (int e = alloc(m->conv48[i], (int64_t)B * m->conv_T[i] * c.filter_sizes[i])) return e;
-    const int64_t BT = (int64_t)B * m->conv_T[NC - 1], H = c.hidden_size;
-    if (int e = alloc(m->ln512_48, BT * c.filter_sizes[NC - 1])) return e;
-    if (int e = alloc(m->attn_in48, BT * H)) return e;
-    if (int e = alloc(m->ctx48, BT * H)) return e;
-    if (int e = alloc(m->ffn_in48, BT * H)) return e;
-    if (int e = alloc(m->ffn48, BT * c.intermediate_size)) return e;
-    if (!m->range_flag) {
-        W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->range_flag), sizeof(int)));
-        W2V2_HIP_CHECK(hipMemset(m->range_flag, 0, sizeof(int)));
-    }
-    m->pl_fmt = fmt;
-    m->pl_B = B;
-    m->pl_L = L;
-    return W2V2_OK;
-}
-
-int w2v2_split_images(w2v2_model* m, const float* W, int K, int N, int fmt, hipStream_t s, const uint16_t** img, const float** out_scale) {
-    W2V2_REQUIRE(W && (fmt == PF_BF16X3 || fmt == PF_F16X2), "split_images: bad argument");
-    w2v2_model::SplitImages& e = m->wimg[fmt][W];
-    const int64_t elems = (int64_t)plane_count(fmt) * K * N;
-    if (!e.img || e.elems != elems) {
-        if (e.img) (void)hipFree(e.img);
-        e.img = nullptr;
-        W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e.img), (size_t)elems * sizeof(uint16_t)));
-        if (!e.scale_ws) W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e.scale_ws), 2 * sizeof(float)));
-        e.elems = elems;
-        e.epoch = 0;
-    }
-    if (e.epoch != m->w48_epoch) {
-        if (int err = launch_split_weight_sw(W, e.img, K, N, fmt, e.scale_ws, s)) return err;
-        e.epoch = m->w48_epoch;
-    }
-    *img = e.img;
-    *out_scale = fmt == PF_F16X2 ? e.scale_ws + 1 : nullptr;
-    return W2V2_OK;
-}
-
-bool w2v2_use_split_gemm(const w2v2_model* m, const float* A, int64_t lda, int64_t strideA, int64_t ldb, int M, int N, int K, int nbatch) {
-    // (precision mode 3 falls back to this six-product kernel for the shapes / call sites its plane-fed kernel does not serve)
-    if (m->precision < W2V2_PRECISION_BF16X3 || ldb != N || N % 256 != 0) return false;
-    if (tune_int("W2V2_SPLIT_GEMM", 1) == 0) return false;      // (tools-only: tools/nll_drift_probe.py separates the GEMMs from the attention)
-    // (below ~half a wave of 128 x 256 tiles the fp32 path's small tiles and split-K serve a single utterance better)
-    const int64_t split_tiles = (int64_t)((M + 127) / 128) * (N / 256) * nbatch;
-    return split_tiles >= 128 && gemm_split_supported(A, lda, strideA, M, N, K);
-}
-
-int w2v2_split_planes(w2v2_model* m, const float* W, int K, int N, hipStream_t s, const uint16_t** planes) {
-    w2v2_model::SplitPlanes& e = m->w48[W];
-    const int64_t need = 3 * (int64_t)K * N;
-    if (!e.p || e.elems != need) {
-        if (e.p) W2V2_HIP_CHECK(hipFree(e.p));
-        e.p = nullptr;
-        W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e.p), (size_t)need * sizeof(uint16_t)));
-        e.elems = need;
-        e.epoch = 0;
-    }
-    if (e.epoch != m->w48_epoch) {
-        if (int err = launch_split_weight(W, e.p, K, N, s)) return err;
-        e.epoch = m->w48_epoch;
-    }
-    *planes = e.p;
-    return W2V2_OK;
-}
-
-bool w2v2_pos_conv_bf16_ok(const w2v2_model* m) {
-    const int cg = m->cfg.hidden_size / m->cfg.num_conv_pos_embedding_groups;
-    return m->precision == 1 && cg % 8 == 0 && cg <= 64 && (m->cfg.num_conv_pos_embeddings * cg) % 64 == 0;
-}
-
-int w2v2_ensure_pos16(w2v2_model* m, int B, int T, hipStream_t s) {
-    const w2v2_config& c = m->cfg;
-    const int H = c.hidden_size, K = c.num_conv_pos_embeddings, G = c.num_conv_pos_embedding_groups, cg = H / G;
-    if (!m->pos_w16) W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->pos_w16), (size_t)K * cg * H * sizeof(uint16_t)));
-    if (!m->pos16_valid) {
-        if (int e = launch_pos_conv_weight_shadow(m->pos_wg, m->pos_w16, K, cg, G, s)) return e;
-        m->pos16_valid = true;
-    }
-    if (!m->pos_pack16) {
-        float* p = nullptr;
-        if (int e = ws_alloc(m, &p, (pos_conv_bf16_pack_elems(B, T, H, K) + 1) / 2 + 4)) return e;
-        m->pos_pack16 = reinterpret_cast<uint16_t*>(p);
-    }
-    return W2V2_OK;
-}
 
 extern "C" {
 
@@ -563,11 +345,7 @@ void w2v2_destroy(w2v2_model* m) {
     if (m->range_flag) (void)hipFree(m->range_flag);
     if (m->pos_w16) (void)hipFree(m->pos_w16);
     if (m->shadow_jobs) (void)hipFree(m->shadow_jobs);
-    if (m->pk_copied) {
-        (void)hipEventSynchronize(m->pk_copied);
-        (void)hipEventDestroy(m->pk_copied);
-    }
-    if (m->pk_stage) (void)hipHostFree(m->pk_stage);
+    pinned_stage_free(m->pk_stage);
     profiler_destroy(m->prof);
     delete m;
 }
@@ -724,425 +502,6 @@ int w2v2_range_overflow(w2v2_model* m, int32_t* flag, void* stream) {
     if (v) W2V2_HIP_CHECK(hipMemsetAsync(m->range_flag, 0, sizeof(int), s));
     *flag = v != 0;
     return W2V2_OK;
-}
-
-// What the packed forward hands the shared forward body: the stream's utterance and tile tables (device) and where the
-// stream-sized head output goes.  The workspace holds at least the stream (ws_B == 1, ws_L >= L).
-struct PackedPlan {
-    const PackSeg* segs;
-    int nseg;
-    const SegTile* pos_tiles;
-    int npos;
-    const SegTile* attn_tiles;
-    int nattn;
-    double sum_nf2;
-    float* head_out;          // (stream frames, vocab) when the model has a head
-};
-
-// The inference forward over (B, L).  pk null: the batched forward (w2v2_forward).  pk set: one stream of packed utterances
-// (B = 1; precision modes fp32, bf16x3, f16x2); the three stages that mix frames -- conv0's GroupNorm statistics, the positional
-// conv and attention -- take their segment-aware forms, everything else runs unchanged over the stream.  The stream rows no
-// utterance owns (1-2 behind each) are zeroed in the two buffers only segment kernels write, posout and ctx, so that every
-// row a plane producer reads is defined by the call's own inputs.
-static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, const int32_t* mask, float* out, hipStream_t s,
-                        const PackedPlan* pk) {
-    const w2v2_config& c = m->cfg;
-    PrecisionScope precision(m->precision);
-    const int64_t Tll = w2v2_num_frames(m, L);
-    W2V2_REQUIRE(Tll >= 1, "forward: %lld samples are shorter than the conv stack's receptive field", (long long)L);
-    if (!pk)
-        if (int e = w2v2_ensure_workspace(m, B, L)) return e;
-    W2V2_REQUIRE(m->ws_B == B && m->ws_L >= L, "forward: workspace (%d, %lld) does not hold (%d, %lld)", m->ws_B, (long long)m->ws_L,
-                 B, (long long)L);
-    // frames per conv layer for THIS input (the workspace may be larger: a packed stream runs in a workspace of its capacity)
-    std::vector<int> conv_T(c.num_conv_layers);
-    {
-        int64_t t = L;
-        for (int i = 0; i < c.num_conv_layers; ++i) conv_T[i] = (int)(t = 1 + (t - c.kernal_sizes[i]) / c.strides[i]);
-    }
-    Profiler* pf = m->prof;
-    const int T = (int)Tll;
-    const int H = c.hidden_size, F = c.intermediate_size;
-    const int64_t BT = (int64_t)B * T;
-    const int act = c.is_gelu_approx ? 2 : 1;
-    // element-wise kernels in precision mode 1 evaluate exact GELU through the 5-term erf the bf16 GEMM epilogue uses (act 3)
-    const int act_ew = (act == 1 && m->precision == 1) ? 3 : act;
-    const bool layer_mode = c.feature_extractor_norm_type == 1;
-    const bool prenorm = c.attention_norm_type == 1;
-    const float eps = c.layer_norm_eps;
-    auto fe = [&](int i, const char* leaf) { return m->P("feature_extractor/conv_layers/" + std::to_string(i) + leaf); };
-
-    // Precision mode 1 with bf16 shadows: every producer of a GEMM operand also writes its nearest-even bf16 copy, the
-    // GEMMs stream those (2 bytes per element, no conversion) and the weights come from (N, K) bf16 shadows.  `sh`
-    // false = plain pointers everywhere: the GEMMs then round their fp32 operands themselves, with identical results.
-    const bool sh = m->precision == 1 && w2v2_shadows_enabled(m);
-    if (sh)
-        if (int e = w2v2_ensure_shadows(m, B, T, s)) return e;
-    const bool attn16 = sh && attention_bf16_supported(H / c.num_heads);
-    auto W16 = [&](const float* w) -> const uint16_t* { return sh ? m->w16[w] : nullptr; };
-    // Precision mode 2: fp32 operands, each an exact sum of three bf16 terms, six MFMA products (gemm_split.hip).  The
-    // weight planes are built on first use; shapes the split kernel does not take (lm_head: N = 32) stay on the fp32 MFMA.
-    // Precision modes 2 / 3 with operand planes (W2V2_OPT_SPLIT_PLANES, default): every producer of a GEMM operand writes its planes
-    // -- three bf16 terms (bf16x3) or two fp16 terms (f16x2) per element -- and the GEMM streams them (gemm_split_sw.hip).  Whether a
-    // call site does is decided here from its shape, so that the producer knows: whole 256-column tiles, K % 64 == 0, 16-byte aligned
-    // rows, and enough tiles to fill the chip (below that the fp32 path's small tiles serve a single utterance better).
-    using PlaneBuf = w2v2_model::PlaneBuf;
-    const int NC = c.num_conv_layers;
-    const bool pm = m->precision >= W2V2_PRECISION_BF16X3 && m->opt_planes;
-    const int fmt = m->precision == W2V2_PRECISION_F16X2 ? PF_F16X2 : PF_BF16X3;
-    const bool keep = w2v2_keep_activations(m);
-    auto site = [&](int64_t M_, int N_, int K_, int nb, int64_t lda_, int64_t sA_) {
-        return pm && N_ % 256 == 0 && K_ % 64 == 0 && lda_ % 8 == 0 && sA_ % 8 == 0 && 128 * lda_ < (1 << 29) && ((M_ + 127) / 128) * (N_ / 256) * nb >= 128;
-    };
-    std::vector<char> cp(NC + 1, 0);             // cp[i]: conv layer i's GEMM streams the planes of conv output i - 1
-    for (int i = 1; i < NC; ++i)
-        cp[i] = site(conv_T[i], c.filter_sizes[i], c.kernal_sizes[i] * c.filter_sizes[i - 1], B, (int64_t)c.strides[i] * c.filter_sizes[i - 1],
-                     (int64_t)conv_T[i - 1] * c.filter_sizes[i - 1]) && c.filter_sizes[i - 1] % 4 == 0;
-    const int C512 = c.filter_sizes[NC - 1];
-    const bool p_proj = site(BT, H, C512, 1, C512, 0) && C512 % 4 == 0, p_qkv = site(BT, 3 * H, H, 1, H, 0) && H % 4 == 0, p_out = site(BT, H, H, 1, H, 0),
-               p_f1 = site(BT, F, H, 1, H, 0), p_f2 = site(BT, H, F, 1, F, 0) && F % 8 == 0;
-    bool any_planes = p_proj || p_qkv || p_out || p_f1 || p_f2;
-    for (int i = 1; i < NC; ++i) any_planes = any_planes || cp[i];
-    // (packed: sized for the workspace's capacity, so that a later packed call whose stream fits reuses them as it reuses the workspace)
-    if (any_planes)
-        if (int e = w2v2_ensure_planes(m, B, pk ? m->ws_L : L, fmt)) return e;
-    auto PO = [&](const PlaneBuf& b) {
-        PlaneOut o;
-        o.p = b.p; o.plane = b.plane; o.fmt = fmt; o.range_flag = m->range_flag;
-        return o;
-    };
-    // Apl: the planes of A (the call site was decided above), Cpl: where the planes of the result go, need_f32: the fp32 result is
-    // wanted as well (a tap under W2V2_OPT_KEEP_ACTIVATIONS) -- the plane epilogue writes one or the other, so it is then split off C.
-    auto gemm = [&](const float* A, const uint16_t* A16, int64_t lda, int64_t strideA, const float* Bw, int64_t ldb, float* Cc,
-                    uint16_t* C16, int64_t ldc, int64_t strideC, const float* bias, const float* res, int M, int N, int K,
-                    int nbatch, int act_, const PlaneBuf* Apl = nullptr, const PlaneBuf* Cpl = nullptr, bool need_f32 = true) -> int {
-        auto split_out = [&]() -> int {
-            W2V2_REQUIRE(Cc && ldc == N && (nbatch == 1 || strideC == (int64_t)M * N), "forward: plane output of a strided result");
-            return launch_split_planes(Cc, Cpl->p, Cpl->plane, (int64_t)nbatch * M * N, fmt, m->range_flag, s);
-        };
-        if (Apl) {
-            const uint16_t* img = nullptr;
-            const float* sc = nullptr;
-            if (int e = w2v2_split_images(m, Bw, K, N, fmt, s, &img, &sc)) return e;
-            const bool planes_only = Cpl && !need_f32;
-            if (int e = launch_gemm_split_sw(pf, fmt, Apl->p, Apl->plane, lda, strideA, img, sc, planes_only ? nullptr : Cc, planes_only ? Cpl->p : nullptr,
-                                             planes_only ? Cpl->plane : 0, ldc, strideC, bias, res, M, N, K, nbatch, act_, m->range_flag, s))
-                return e;
-            return (Cpl && !planes_only) ? split_out() : W2V2_OK;
-        }
-        int e;
-        if (w2v2_use_split_gemm(m, A, lda, strideA, ldb, M, N, K, nbatch)) {
-            const uint16_t* planes = nullptr;
-            if (int e2 = w2v2_split_planes(m, Bw, K, N, s, &planes)) return e2;
-            e = launch_gemm_split(pf, A, lda, strideA, planes, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, s);
-        } else if (!sh) {
-            e = launch_gemm(pf, A, lda, strideA, Bw, ldb, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, s);
-        } else {
-            GemmShadows x;
-            x.A16 = A16; x.B16 = W16(Bw); x.C16 = C16; x.ldb16 = K;
-            e = launch_gemm_bf16_x(pf, A, lda, strideA, Bw, ldb, 0, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, x, s);
-        }
-        if (e) return e;
-        return Cpl ? split_out() : W2V2_OK;
-    };
-    const bool ffn_sh_only = sh && F % 64 == 0;      // the output dense can then always take the shadow (K = F)
-
-    // ---- feature extractor (feature_extractor.py:54-59) ----
-    // group-norm mode with shadows: conv0 .. conv(NC-2) feed only the next layer's GEMM; where that GEMM reads the bf16 shadow
-    // the fp32 copy is not written at all (w2v2_conv_out_bf16_only)
-    m->acts_skipped.clear();
-    // (planes: a conv output whose one reader streams its planes is written ONLY as planes, like the bf16-only outputs of mode 1)
-    auto planes_only_out = [&](int i) { return i + 1 < NC && cp[i + 1] && !keep; };
-    // the fused plane output needs conv0's 16-byte-store kernel (K = 10, stride 5); other geometries write fp32 and split it.  (The
-    // packed group-norm pass, launch_conv0_packed, applies through the same kernel and writes exactly what the dense pass writes.)
-    const bool fused = NC > 1 && cp[1] && c.kernal_sizes[0] == 10 && c.strides[0] == 5 && 256 % (c.filter_sizes[0] / 4) == 0 && c.filter_sizes[0] / 4 <= 256;
-    // "convI" is not readable back exactly when the code below hands its producer a null fp32 destination (this used to be a
-    // second, looser predicate): conv0 fused into planes; a plane-fed GEMM whose output also goes out as planes only; a LayerNorm-mode
-    // layer whose LN + GELU pass writes bf16 / planes only (conv[i] then holds the pre-norm values); the bf16-only outputs of mode 1
-    auto f32_skipped = [&](int i) {
-        if (w2v2_conv_out_bf16_only(m, i, sh) || w2v2_conv_ln_bf16_only(m, i, sh)) return true;
-        if (i == 0) return NC > 1 && cp[1] && !keep && fused;
-        if (layer_mode) return planes_only_out(i);
-        return cp[i] && i + 1 < NC && cp[i + 1] && !keep;
-    };
-    for (int i = 0; i + 1 < NC; ++i)
-        if (f32_skipped(i)) m->acts_skipped.push_back("conv" + std::to_string(i));
-    {
-        const PlaneOut po = fused ? PO(m->conv48[0]) : PlaneOut{};
-        const bool f32_too = !(NC > 1 && cp[1]) || keep || !fused;
-        if (pk && !layer_mode) {     // GroupNorm statistics per utterance, over exactly its rows
-            if (int e = launch_conv0_packed(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr, fe(0, "/layer_norm/gamma"),
-                                            fe(0, "/layer_norm/beta"), f32_too ? m->conv[0] : nullptr, m->conv0_ws, m->pk_scale, L, c.kernal_sizes[0],
-                                            c.strides[0], c.filter_sizes[0], 1e-5f, act_ew, pk->segs, pk->nseg, s, fused ? &po : nullptr))
-                return e;
-        } else if (int e = launch_conv0_x(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr,
-                                          fe(0, "/layer_norm/gamma"), fe(0, "/layer_norm/beta"),
-                                          (w2v2_conv_out_bf16_only(m, 0, sh) || w2v2_conv_ln_bf16_only(m, 0, sh) || !f32_too) ? nullptr : m->conv[0],
-                                          sh ? m->conv16[0] : nullptr, m->conv0_ws, B, L, c.kernal_sizes[0], c.strides[0],
-                                          c.filter_sizes[0], 1e-5f, layer_mode ? 2 : 0, act_ew, s, fused ? &po : nullptr)) {    // (layer mode: conv + LayerNorm + GELU in one pass)
-            return e;
-        }
-        if (NC > 1 && cp[1] && !fused)
-            if (int e = launch_split_planes(m->conv[0], m->conv48[0].p, m->conv48[0].plane, (int64_t)B * conv_T[0] * c.filter_sizes[0], fmt, m->range_flag, s))
-                return e;
-    }
-    for (int i = 1; i < NC; ++i) {
-        const int cin = c.filter_sizes[i - 1], cout = c.filter_sizes[i];
-        const int Tin = conv_T[i - 1], Tout = conv_T[i];
-        uint16_t* o16 = (sh && i + 1 < NC) ? m->conv16[i] : nullptr;     // the last conv output feeds a LayerNorm
-        // strided Conv1D == GEMM over an overlapping window view: lda = stride * C_in < K * C_in
-        // planes of this layer's output for the next layer's GEMM: from the GEMM epilogue (group-norm mode: bias + GELU there) or from
-        // the LayerNorm + GELU pass behind it (layer-norm mode: the GEMM output is that pass's fp32 input)
-        const bool out_pl = i + 1 < NC && cp[i + 1];
-        const PlaneBuf* opl = out_pl ? &m->conv48[i] : nullptr;
-        if (int e = gemm(m->conv[i - 1], sh ? m->conv16[i - 1] : nullptr, (int64_t)c.strides[i] * cin, (int64_t)Tin * cin,
-                         fe(i, "/conv/kernel"), cout, w2v2_conv_out_bf16_only(m, i, sh) ? nullptr : m->conv[i], layer_mode ? nullptr : o16, cout,
-                         (int64_t)Tout * cout, c.conv_bias ? fe(i, "/conv/bias") : nullptr, nullptr, Tout, cout, c.kernal_sizes[i] * cin, B,
-                         layer_mode ? 0 : act, cp[i] ? &m->conv48[i - 1] : nullptr, layer_mode ? nullptr : opl, keep))
-            return e;
-        if (layer_mode) {
-            const PlaneOut po = out_pl ? PO(*opl) : PlaneOut{};
-            if (int e = launch_layer_norm_x(pf, m->conv[i], (w2v2_conv_ln_bf16_only(m, i, sh) || planes_only_out(i)) ? nullptr : m->conv[i], fe(i, "/layer_norm/gamma"),
-                                            fe(i, "/layer_norm/beta"), (int64_t)B * Tout, cout, 1e-5f, act_ew, o16, s, out_pl ? &po : nullptr))
-                return e;
-        }
-    }
-    // ---- feature projection (feature_extractor.py:92-95) ----
-    const int C = c.filter_sizes[NC - 1];
-    {
-        const PlaneOut po = p_proj ? PO(m->ln512_48) : PlaneOut{};
-        if (int e = launch_layer_norm_x(pf, m->conv[NC - 1], (p_proj && !keep) ? nullptr : m->ln512, m->P("feature_projection/layer_norm/gamma"),
-                                        m->P("feature_projection/layer_norm/beta"), BT, C, eps, 0, sh ? m->ln512_16 : nullptr, s, p_proj ? &po : nullptr))
-            return e;
-    }
-    if (int e = gemm(m->ln512, sh ? m->ln512_16 : nullptr, C, 0, m->P("feature_projection/projection/kernel"), H, m->proj, nullptr,
-                     H, 0, m->P("feature_projection/projection/bias"), nullptr, (int)BT, H, C, 1, 0, p_proj ? &m->ln512_48 : nullptr))
-        return e;
-    // ---- encoder (encoder.py:251-276) ----
-    const int32_t* flen = nullptr;
-    if (mask) {
-        if (int e = launch_frame_lengths(pf, mask, m->frame_len, B, L, c.kernal_sizes, c.strides, c.num_conv_layers, s)) return e;
-        flen = m->frame_len;
-    }
-    if (pk) {                            // each utterance zero-padded at its own edges (the fp32 kernel in every mode, as the dense split modes)
-        if (int e = launch_pos_conv_packed(pf, m->proj, m->pos_wg, m->P("encoder/pos_conv_embed/conv/bias"), m->posout, pk->pos_tiles, pk->npos,
-                                           T, H, c.num_conv_pos_embeddings, c.num_conv_pos_embedding_groups, act, s))
-            return e;
-        if (int e = launch_pack_zero_gaps(m->posout, nullptr, T, H, pk->segs, pk->nseg, s)) return e;
-    } else if (w2v2_pos_conv_bf16_ok(m)) {      // precision mode 1: one batched bf16 GEMM over (sample, group); m->t0 is free here
-        if (int e = w2v2_ensure_pos16(m, B, T, s)) return e;
-        if (int e = launch_pos_conv_bf16(pf, m->proj, m->pos_w16, m->P("encoder/pos_conv_embed/conv/bias"), flen, m->posout, nullptr,
-                                         m->pos_pack16, m->t0, B, T, H, c.num_conv_pos_embeddings, c.num_conv_pos_embedding_groups,
-                                         act, c.num_conv_pos_embeddings / 2, 1, s))
-            return e;
-    } else if (int e = launch_pos_conv(pf, m->proj, m->pos_wg, m->P("encoder/pos_conv_embed/conv/bias"), flen, m->posout, B, T,
-                                       H, c.num_conv_pos_embeddings, c.num_conv_pos_embedding_groups, act, s)) {
-        return e;
-    }
-    const PlaneOut po_attn = p_qkv ? PO(m->attn_in48) : PlaneOut{}, po_ctx = p_out ? PO(m->ctx48) : PlaneOut{},
-                   po_ffn_in = p_f1 ? PO(m->ffn_in48) : PlaneOut{};
-    if (pk)                              // (the attention kernels write only the utterances' rows of ctx and of its planes, in every layer)
-        if (int e = launch_pack_zero_gaps(m->ctx, p_out ? &po_ctx : nullptr, T, H, pk->segs, pk->nseg, s)) return e;
-    // packed, precision modes 2 / 3: the split attention's segment form where the dense forward takes the split kernel
-    const bool split_attn = m->precision >= W2V2_PRECISION_BF16X3 && attention_split_supported(H / c.num_heads) && H % 4 == 0 &&
-                            tune_int("W2V2_SPLIT_ATTN", 1) != 0;
-    if (!prenorm)
-        if (int e = launch_layer_norm_x(pf, m->posout, m->hs[0], m->P("encoder/layer_norm/gamma"),
-                                        m->P("encoder/layer_norm/beta"), BT, H, eps, 0, sh ? m->hs16[0] : nullptr, s, p_qkv ? &po_attn : nullptr))
-            return e;
-    for (int i = 0; i < c.num_layers; ++i) {
-        const std::string b = "encoder/layers/" + std::to_string(i);
-        const float* x = m->hs[i];
-        const float* attn_in = x;
-        const uint16_t* attn_in16 = sh ? m->hs16[i] : nullptr;       // postnorm: the previous LayerNorm wrote it
-        // (prenorm, bf16 shadows: the two in-layer LayerNorm outputs feed one GEMM each; when that GEMM is certain to stream the shadow -- K = H a
-        //  multiple of 64 and a weight shadow, as for the attention output below -- the fp32 copy is not written: 2 x 98 MB per layer at 16 x 480000)
-        auto shadow_certain = [&](const float* w) {
-            const auto it = m->w16.find(w);
-            return sh && !keep && H % 64 == 0 && it != m->w16.end() && it->second != nullptr;
-        };
-        if (prenorm) {
-            const bool a16_only = shadow_certain(m->qkv_w[i]);
-            if (int e = launch_layer_norm_x(pf, x, ((p_qkv && !keep) || a16_only) ? nullptr : m->t0, m->P(b + "/layer_norm/gamma"), m->P(b + "/layer_norm/beta"), BT, H, eps, 0,
-                                            sh ? m->t0_16 : nullptr, s, p_qkv ? &po_attn : nullptr))
-                return e;
-            attn_in = m->t0;
-            attn_in16 = sh ? m->t0_16 : nullptr;
-        }
-        // the bf16 attention kernels read q | k | v only as bf16: the projection then writes just that shadow
-        if (int e = gemm(attn_in, attn_in16, H, 0, m->qkv_w[i], 3 * H, attn16 ? nullptr : m->qkv, attn16 ? m->qkv16 : nullptr, 3 * H, 0, m->qkv_b[i],
-                         nullptr, (int)BT, 3 * H, H, 1, 0, p_qkv ? &m->attn_in48 : nullptr))
-            return e;
-        // (the attention output's one reader is the out-projection GEMM; when that is certain to stream the bf16 shadow -- K = H a
-        //  multiple of 64, rows 16-byte aligned: gemm_bf16.hip -- the fp32 copy is not written: 75 MB per layer at B = 32)
-        const auto wo16 = m->w16.find(m->P(b + "/attention/out_proj/kernel"));
-        const bool ctx16_only = attn16 && H % 64 == 0 && wo16 != m->w16.end() && wo16->second != nullptr;
-        // (planes: the split attention kernel writes the planes of ctx itself; any other attention kernel leaves fp32 to be split)
-        const bool ctx_fused = p_out && attention_split_supported(H / c.num_heads) && H % 4 == 0 && tune_int("W2V2_SPLIT_ATTN", 1) != 0;
-        PlaneOut po_flag;                                    // (no planes wanted: the split attention still reports f16x2 saturation)
-        po_flag.range_flag = m->range_flag;
-        const PlaneOut* attn_pl = ctx_fused ? &po_ctx : (pm ? &po_flag : nullptr);
-        if (pk && split_attn) {          // queries and keys of one utterance per block
-            if (int e = launch_attention_split_packed(pf, m->qkv, (ctx_fused && !keep) ? nullptr : m->ctx, pk->attn_tiles, pk->nattn, T, pk->sum_nf2, H,
-                                                      c.num_heads, s, attn_pl, fmt, attn_pl ? attn_pl->range_flag : nullptr))
-                return e;
-        } else if (pk) {
-            if (int e = launch_attention_packed(pf, m->qkv, m->ctx, pk->attn_tiles, pk->nattn, T, pk->sum_nf2, H, c.num_heads, s)) return e;
-        } else if (int e = launch_attention_x(pf, attn16 ? nullptr : m->qkv, attn16 ? m->qkv16 : nullptr, flen, (ctx16_only || (ctx_fused && !keep)) ? nullptr : m->ctx, B, T, H,
-                                              c.num_heads, attn16 ? m->ctx16 : nullptr, s, attn_pl)) {
-            return e;
-        }
-        if (p_out && !ctx_fused)
-            if (int e = launch_split_planes(m->ctx, m->ctx48.p, m->ctx48.plane, BT * H, fmt, m->range_flag, s)) return e;
-        // out projection + residual (encoder.py:31,117-119)
-        if (int e = gemm(m->ctx, attn16 ? m->ctx16 : nullptr, H, 0, m->P(b + "/attention/out_proj/kernel"), H, m->t1, nullptr, H, 0,
-                         m->P(b + "/attention/out_proj/bias"), x, (int)BT, H, H, 1, 0, p_out ? &m->ctx48 : nullptr))
-            return e;
-        const float* ffn_res = m->t1;
-        if (!prenorm) {
-            if (int e = launch_layer_norm_x(pf, m->t1, m->t2, m->P(b + "/layer_norm/gamma"), m->P(b + "/layer_norm/beta"), BT, H, eps, 0,
-                                            sh ? m->t2_16 : nullptr, s, p_f1 ? &po_ffn_in : nullptr))
-                return e;
-            ffn_res = m->t2;
-        } else {
-            const bool t2_16_only = shadow_certain(m->P(b + "/feed_forward/intermediate_dense/kernel"));
-            if (int e = launch_layer_norm_x(pf, m->t1, ((p_f1 && !keep) || t2_16_only) ? nullptr : m->t2, m->P(b + "/final_layer_norm/gamma"), m->P(b + "/final_layer_norm/beta"), BT, H,
-                                            eps, 0, sh ? m->t2_16 : nullptr, s, p_f1 ? &po_ffn_in : nullptr))
-                return e;
-        }
-        // the FFN intermediate has one consumer: with shadows only its bf16 form is written (302 MB of fp32 stores saved)
-        if (int e = gemm(m->t2, sh ? m->t2_16 : nullptr, H, 0, m->P(b + "/feed_forward/intermediate_dense/kernel"), F,
-                         ffn_sh_only ? nullptr : m->ffn, sh ? m->ffn16 : nullptr, F, 0, m->P(b + "/feed_forward/intermediate_dense/bias"),
-                         nullptr, (int)BT, F, H, 1, act, p_f1 ? &m->ffn_in48 : nullptr, p_f2 ? &m->ffn48 : nullptr, keep))
-            return e;
-        // output dense + residual; StochasticDepth at inference is a plain add (tensorflow_addons.py:386-390)
-        float* dst = prenorm ? m->hs[i + 1] : m->t3;
-        if (int e = gemm(m->ffn, sh ? m->ffn16 : nullptr, F, 0, m->P(b + "/feed_forward/output_dense/kernel"), H, dst, nullptr, H, 0,
-                         m->P(b + "/feed_forward/output_dense/bias"), ffn_res, (int)BT, H, F, 1, 0, p_f2 ? &m->ffn48 : nullptr))
-            return e;
-        if (!prenorm)       // (its planes are the next layer's attention input)
-            if (int e = launch_layer_norm_x(pf, m->t3, m->hs[i + 1], m->P(b + "/final_layer_norm/gamma"),
-                                            m->P(b + "/final_layer_norm/beta"), BT, H, eps, 0, sh ? m->hs16[i + 1] : nullptr, s,
-                                            (p_qkv && i + 1 < c.num_layers) ? &po_attn : nullptr))
-                return e;
-    }
-    const uint16_t* head_in16 = sh && !prenorm ? m->hs16[c.num_layers] : nullptr;
-    if (prenorm) {
-        if (int e = launch_layer_norm_x(pf, m->hs[c.num_layers], m->enc_out, m->P("encoder/layer_norm/gamma"),
-                                        m->P("encoder/layer_norm/beta"), BT, H, eps, 0, sh ? m->enc16 : nullptr, s))
-            return e;
-        head_in16 = sh ? m->enc16 : nullptr;
-    }
-    // ---- head (modeling.py:253-254) ----
-    // (packed: the stream's rows; w2v2_forward_packed gathers the utterances' frames from them)
-    if (c.with_lm_head) {
-        if (int e = gemm(m->enc_out, head_in16, H, 0, m->P("lm_head/kernel"), c.vocab_size, pk ? pk->head_out : out, nullptr, c.vocab_size, 0,
-                         m->P("lm_head/bias"), nullptr, (int)BT, c.vocab_size, H, 1, 0))
-            return e;
-    } else if (!pk) {
-        W2V2_HIP_CHECK(hipMemcpyAsync(out, m->enc_out, (size_t)BT * H * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    return W2V2_OK;
-}
-
-int w2v2_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, const int32_t* mask,
-                 float* out, void* stream) {
-    W2V2_REQUIRE(m && wave && out, "forward: null argument");
-    W2V2_REQUIRE(B > 0 && L > 0, "forward: bad batch shape (%d, %lld)", B, (long long)L);
-    if (!m->finalized) {
-        set_error("forward: call w2v2_finalize after setting the variables");
-        return W2V2_ESTATE;
-    }
-    return forward_impl(m, wave, B, L, mask, out, reinterpret_cast<hipStream_t>(stream), nullptr);
-}
-
-int w2v2_forward_packed(w2v2_model* m, const float* wave, int32_t n, const int64_t* cu_samples, float* out, void* stream) {
-    W2V2_REQUIRE(m && wave && cu_samples && out, "forward_packed: null argument");
-    if (!m->finalized) {
-        set_error("forward_packed: call w2v2_finalize after setting the variables");
-        return W2V2_ESTATE;
-    }
-    static const char* modes[] = {"fp32", "bf16", "bf16x3", "f16x2"};
-    W2V2_REQUIRE(m->precision == W2V2_PRECISION_FP32 || m->precision == W2V2_PRECISION_BF16X3 || m->precision == W2V2_PRECISION_F16X2,
-                 "forward_packed: precision mode %s is not supported (fp32, bf16x3, f16x2)",
-                 (m->precision >= 0 && m->precision <= 3) ? modes[m->precision] : "?");
-    W2V2_REQUIRE(n >= 1, "forward_packed: %d utterances (need at least one)", n);
-    W2V2_REQUIRE(cu_samples[0] == 0, "forward_packed: cu_samples[0] = %lld, must be 0", (long long)cu_samples[0]);
-    const w2v2_config& c = m->cfg;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    // alignment unit: a multiple of the total stride (whole frames at every layer) and of conv0's stats chunk in samples
-    int64_t A = 1;
-    for (int i = 0; i < c.num_conv_layers; ++i) A *= c.strides[i];
-    const int64_t chunk = (int64_t)c.strides[0] * conv0_chunk_frames();
-    int64_t g = A, r = chunk;
-    while (r) { const int64_t t = g % r; g = r; r = t; }
-    const int64_t U = A / g * chunk;
-    // utterances in the stream, and the tiles of the two stages that work per utterance
-    std::vector<PackSeg> segs((size_t)n);
-    int64_t L = 0, rows = 0;
-    double sum_nf2 = 0.0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t len = cu_samples[i + 1] - cu_samples[i];
-        W2V2_REQUIRE(len >= 0, "forward_packed: cu_samples decreases at utterance %d", i);
-        const int64_t nf = w2v2_num_frames(m, len);
-        W2V2_REQUIRE(nf >= 1, "forward_packed: utterance %d has %lld samples, shorter than the conv stack's receptive field", i,
-                     (long long)len);
-        segs[i] = PackSeg{L, len, cu_samples[i], (int32_t)(L / A), (int32_t)nf, (int32_t)rows, 0};
-        L += (len + U - 1) / U * U;
-        rows += nf;
-        sum_nf2 += (double)nf * (double)nf;
-    }
-    const int64_t T = w2v2_num_frames(m, L);
-    W2V2_REQUIRE(T < (1 << 24) && (int64_t)segs.back().f0 + segs.back().nf <= T, "forward_packed: stream of %lld samples out of range",
-                 (long long)L);
-    const int H = c.hidden_size, PR = pos_conv_packed_rows(), AR = attention_packed_rows(H / c.num_heads);
-    std::vector<SegTile> tiles;
-    for (const int rows_per_tile : {PR, AR})
-        for (const PackSeg& sg : segs)
-            for (int t0 = 0; t0 < sg.nf; t0 += rows_per_tile) tiles.push_back(SegTile{sg.f0, sg.nf, t0, 0});
-    int npos = 0;
-    for (const PackSeg& sg : segs) npos += (sg.nf + PR - 1) / PR;
-    const int nattn = (int)tiles.size() - npos;
-
-    // workspace of a B = 1 forward over at least the stream, rounded up so that later streams that fit reuse it
-    if (!(m->ws_B == 1 && m->ws_L >= L))
-        if (int e = w2v2_ensure_workspace(m, 1, (L + 64 * U - 1) / (64 * U) * (64 * U))) return e;
-    if (m->pk_L != m->ws_L) {
-        const int64_t Tcap = w2v2_num_frames(m, m->ws_L);
-        m->pk_seg_cap = (int)(m->ws_L / U);
-        m->pk_tile_cap = (int)(2 * (int64_t)m->pk_seg_cap + Tcap / PR + Tcap / AR);
-        if (int e = ws_alloc(m, &m->pk_wave, m->ws_L)) return e;
-        if (int e = ws_alloc(m, &m->pk_scale, (int64_t)m->pk_seg_cap * 2 * c.filter_sizes[0])) return e;
-        if (int e = ws_alloc(m, &m->pk_out, c.with_lm_head ? Tcap * c.vocab_size : 0)) return e;
-        float* tab = nullptr;
-        if (int e = ws_alloc(m, &tab, ((int64_t)m->pk_seg_cap * sizeof(PackSeg) + (int64_t)m->pk_tile_cap * sizeof(SegTile)) / sizeof(float))) return e;
-        m->pk_tab = tab;
-        m->pk_L = m->ws_L;
-    }
-    W2V2_REQUIRE(n <= m->pk_seg_cap && (int64_t)tiles.size() <= m->pk_tile_cap, "forward_packed: tables exceed their capacity");
-    // tables -> device through pinned staging; the previous call's copy out of it must have completed before it is rewritten
-    const size_t seg_bytes = segs.size() * sizeof(PackSeg), bytes = seg_bytes + tiles.size() * sizeof(SegTile);
-    if (!m->pk_copied) W2V2_HIP_CHECK(hipEventCreateWithFlags(&m->pk_copied, hipEventDisableTiming));
-    W2V2_HIP_CHECK(hipEventSynchronize(m->pk_copied));
-    if (m->pk_stage_bytes < bytes) {
-        if (m->pk_stage) W2V2_HIP_CHECK(hipHostFree(m->pk_stage));
-        m->pk_stage = nullptr;
-        m->pk_stage_bytes = 0;
-        const size_t want = std::max(bytes, (size_t)64 << 10);
-        W2V2_HIP_CHECK(hipHostMalloc(&m->pk_stage, want, hipHostMallocDefault));
-        m->pk_stage_bytes = want;
-    }
-    memcpy(m->pk_stage, segs.data(), seg_bytes);
-    memcpy(static_cast<char*>(m->pk_stage) + seg_bytes, tiles.data(), bytes - seg_bytes);
-    W2V2_HIP_CHECK(hipMemcpyAsync(m->pk_tab, m->pk_stage, bytes, hipMemcpyHostToDevice, s));
-    W2V2_HIP_CHECK(hipEventRecord(m->pk_copied, s));
-    const PackSeg* dsegs = static_cast<const PackSeg*>(m->pk_tab);
-    const SegTile* dtiles = reinterpret_cast<const SegTile*>(static_cast<const char*>(m->pk_tab) + seg_bytes);
-
-    if (int e = launch_pack_scatter(wave, m->pk_wave, L, dsegs, n, s)) return e;
-    const PackedPlan plan{dsegs, n, dtiles, npos, dtiles + npos, nattn, sum_nf2, m->pk_out};
-    if (int e = forward_impl(m, m->pk_wave, 1, L, nullptr, out, s, &plan)) return e;
-    return launch_pack_gather(c.with_lm_head ? m->pk_out : m->enc_out, out, rows, c.with_lm_head ? c.vocab_size : H, dsegs, n, s);
 }
 
 int w2v2_ctc_loss(const float* logits, int32_t B, int32_t T, int32_t V, const int32_t* labels, int32_t U,

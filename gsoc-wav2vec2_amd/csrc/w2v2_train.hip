@@ -357,7 +357,7 @@ static int refresh_transposes(w2v2_model* m, hipStream_t s) {
     // never read: only lm_head's (N = 32: no shadow) and the flipped positional kernel are needed.  `transposes_full`
     // remembers whether the fp32 copies are current, for a later switch back to fp32 / bf16x3 on the same model.
     const w2v2_config& c = m->cfg;
-    bool need_full = !(m->precision == 1 && w2v2_shadows_enabled(m) && m->w16_valid);
+    bool need_full = !(m->precision == 1 && m->opt_shadows && m->w16_valid);
     if (!need_full) {      // every kernel whose fp32 copy is skipped must really have its bf16 stand-in (shapes with N % 64 != 0 do not)
         auto has = [&](const float* w) { return m->w16p.find(w) != m->w16p.end(); };
         need_full = !has(m->P("feature_projection/projection/kernel"));
@@ -628,11 +628,11 @@ int w2v2_train_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, c
     const int T = (int)Tll;
     const int H = c.hidden_size, F = c.intermediate_size;
     const int64_t BT = (int64_t)B * T;
-    // Precision mode 1: the same bf16 shadows as the inference forward (w2v2_api.hip).  Every producer of a forward GEMM
+    // Precision mode 1: the same bf16 shadows as the inference forward (forward.hip).  Every producer of a forward GEMM
     // operand -- conv0, GEMM epilogues, LayerNorm, dropout, attention -- also writes the nearest-even bf16 copy, so the
     // forward GEMMs stream 2-byte operands by LDS-DMA instead of converting fp32 in registers.  The shadow buffers are
     // transient scratch (the backward works from the saved fp32 activations); results are bit-identical either way.
-    const bool sh = m->precision == 1 && w2v2_shadows_enabled(m);
+    const bool sh = m->precision == 1 && m->opt_shadows;
     if (sh)       // (also refreshes the bf16 weight shadows after an optimizer step: m->w16_valid, which the decisions below read)
         if (int e = w2v2_ensure_shadows(m, B, T, s)) return e;
     const bool attn16 = sh && attention_bf16_supported(H / c.num_heads);
@@ -660,12 +660,9 @@ int w2v2_train_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, c
     const int act = c.is_gelu_approx ? 2 : 1;
     // element-wise kernels in precision mode 1 evaluate exact GELU / GELU' through the 5-term erf the bf16 GEMM epilogue uses (act 3)
     const int act_ew = (act == 1 && m->precision == 1) ? 3 : act;
-    const bool layer_mode = c.feature_extractor_norm_type == 1;
     const float eps = c.layer_norm_eps, p = dropout_p;
     t->p = p;
     t->seed = seed;
-    auto fe = [&](int i, const char* leaf) { return m->P("feature_extractor/conv_layers/" + std::to_string(i) + leaf); };
-
     auto gemm = [&](const float* A, const uint16_t* A16, int64_t lda, int64_t strideA, const float* Bw, int64_t ldb, float* Cc,
                     uint16_t* C16, int64_t ldc, int64_t strideC, const float* bias, const float* res, int M, int N, int K,
                     int nbatch, int act_) -> int {
@@ -680,41 +677,11 @@ int w2v2_train_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, c
         return launch_gemm_bf16_x(pf, A, lda, strideA, Bw, ldb, 0, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, x, s);
     };
     auto S16 = [&](uint16_t* p16) -> uint16_t* { return sh ? p16 : nullptr; };
-    const int NC = c.num_conv_layers;
 
-    // ---- frozen feature extractor: identical to inference (no dropout inside, feature_extractor.py:54-59) ----
-    m->acts_skipped.clear();                   // conv outputs written only as bf16: see w2v2_api.hip::w2v2_conv_out_bf16_only
-    for (int i = 0; i + 1 < NC; ++i)
-        if (w2v2_conv_out_bf16_only(m, i, sh) || w2v2_conv_ln_bf16_only(m, i, sh)) m->acts_skipped.push_back("conv" + std::to_string(i));
-    if (int e = launch_conv0_x(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr,
-                               fe(0, "/layer_norm/gamma"), fe(0, "/layer_norm/beta"),
-                               (w2v2_conv_out_bf16_only(m, 0, sh) || w2v2_conv_ln_bf16_only(m, 0, sh)) ? nullptr : m->conv[0],
-                               sh ? m->conv16[0] : nullptr, m->conv0_ws, B, L, c.kernal_sizes[0], c.strides[0],
-                               c.filter_sizes[0], 1e-5f, layer_mode ? 2 : 0, act_ew, s))      // (layer mode: conv + LayerNorm + GELU in one pass)
-        return e;
-    for (int i = 1; i < NC; ++i) {
-        const int cin = c.filter_sizes[i - 1], cout = c.filter_sizes[i];
-        const int Tin = m->conv_T[i - 1], Tout = m->conv_T[i];
-        uint16_t* o16 = (sh && i + 1 < NC) ? m->conv16[i] : nullptr;
-        if (int e = gemm(m->conv[i - 1], sh ? m->conv16[i - 1] : nullptr, (int64_t)c.strides[i] * cin, (int64_t)Tin * cin,
-                         fe(i, "/conv/kernel"), cout, w2v2_conv_out_bf16_only(m, i, sh) ? nullptr : m->conv[i], layer_mode ? nullptr : o16, cout,
-                         (int64_t)Tout * cout, c.conv_bias ? fe(i, "/conv/bias") : nullptr, nullptr, Tout, cout, c.kernal_sizes[i] * cin, B,
-                         layer_mode ? 0 : act))
-            return e;
-        if (layer_mode)
-            if (int e = launch_layer_norm_x(pf, m->conv[i], w2v2_conv_ln_bf16_only(m, i, sh) ? nullptr : m->conv[i], fe(i, "/layer_norm/gamma"), fe(i, "/layer_norm/beta"),
-                                            (int64_t)B * Tout, cout, 1e-5f, act_ew, o16, s))
-                return e;
-    }
-    // ---- feature projection: LN -> Dense -> Dropout (feature_extractor.py:92-95) ----
-    const int C = c.filter_sizes[NC - 1];
-    const float* conv_out = m->conv[NC - 1];
-    if (int e = launch_layer_norm_x(pf, conv_out, m->ln512, m->P("feature_projection/layer_norm/gamma"),
-                                    m->P("feature_projection/layer_norm/beta"), BT, C, eps, 0, S16(m->ln512_16), s))
-        return e;
-    if (int e = gemm(m->ln512, S16(m->ln512_16), C, 0, m->P("feature_projection/projection/kernel"), H, m->proj, nullptr, H, 0,
-                     m->P("feature_projection/projection/bias"), nullptr, (int)BT, H, C, 1, 0))
-        return e;
+    // ---- frozen feature extractor and feature projection LN -> Dense: the inference forward's stage (no dropout inside,
+    // feature_extractor.py:54-59,92-95), planned without operand planes: the bf16x3 conv GEMMs stay on the six-product kernel ----
+    if (int e = w2v2_forward_frontend(m, w2v2_plan_forward(m, B, L, false, false), wave, nullptr, s)) return e;
+    // ---- Dropout behind the projection (feature_extractor.py:95) ----
     if (int e = launch_dropout_fwd(m->proj, nullptr, t->hd, BT * H, 0, p, seed, DS_FEATURE_PROJECTION, s)) return e;
     // ---- spec-augment: masked frames <- masked_spec_embed (modeling.py:193-199, spec_augment.py:119-127) ----
     t->have_spec = spec_mask_host != nullptr;
@@ -864,7 +831,7 @@ int w2v2_train_backward(w2v2_model* m, const float* dlogits, void* stream) {
     StepProfScope step_prof(m->prof);          // the training-only kernels' launchers find the profiler here (common.h)
     // dX = dY W^T reads the fp32 transposed copy WT ([out][in]) as its B operand; in precision mode 1 with shadows the bf16
     // copy of W itself ([in][out] = (N, K) for this GEMM) is the B shadow -- no transpose needed.  Bit-identical results.
-    const bool shb = m->precision == 1 && w2v2_shadows_enabled(m) && m->w16_valid;
+    const bool shb = m->precision == 1 && m->opt_shadows && m->w16_valid;
     // A16: the producer's bf16 shadow of A (or null): with it both operands stream by LDS-DMA (gemm_bf16.hip source 5)
     auto gemm_dx = [&](const float* A, const uint16_t* A16, int64_t lda, const float* WT, const float* W, float* Cc, int64_t ldc,
                        const float* res, int M, int N, int K, hipStream_t st, uint16_t* C16 = nullptr) -> int {

@@ -186,6 +186,41 @@ def test_bf16_shadows_do_not_change_results(torch_mod, name):
     assert np.array_equal(m.activation(f"conv{len(cfg.kernal_sizes) - 1}"), res["1"][f"conv{len(cfg.kernal_sizes) - 1}"])
 
 
+@pytest.mark.parametrize("precision", ["fp32", "bf16", "bf16x3", "f16x2"])
+@pytest.mark.parametrize("name,copies", [("tiny_base", 1), ("tiny_robust", 1), ("base_sample_padded", 8)])
+def test_taps_are_never_stale(torch_mod, name, copies, precision):
+    """Every precision mode skips the fp32 copy of an activation whose readers take another form of it (the forward plan).
+    With default options a stage tap then either says so or returns exactly the bits the same forward leaves with the option
+    "keep_activations" on -- never what an earlier forward left in the buffer -- and the logits do not depend on the option.  Eight
+    copies of the BASELINE-length fixture are the batch at which every GEMM call site of the split modes streams operand planes."""
+    g = H.golden(name)
+    m, cfg = build(name)
+    m.set_precision(precision)
+    wave = np.concatenate([g["wave"]] * copies, 0)
+    mask = g.get("attention_mask")
+    mask = None if mask is None else np.concatenate([mask.astype(np.int32)] * copies, 0)
+    taps = [f"conv{i}" for i in range(len(cfg.kernal_sizes))] + ["projection", "encoder_in"] + \
+           [f"layer{i}" for i in range(cfg.num_layers)] + ["encoder_out"]
+    m.set_option("keep_activations", True)
+    kept_logits = m(wave, attention_mask=mask).numpy()
+    kept = {tap: m.activation(tap) for tap in taps}
+    # a forward of other data (seeded noise) in between: a tap that is not written below would now return THIS forward's values
+    m(np.random.default_rng(7).standard_normal(wave.shape).astype(np.float32), attention_mask=mask)
+    m.set_option("keep_activations", False)
+    logits = m(wave, attention_mask=mask).numpy()
+    assert np.array_equal(logits, kept_logits)
+    raised = []
+    for tap in taps:
+        try:
+            got = m.activation(tap)
+        except RuntimeError:
+            raised.append(tap)
+            continue
+        assert np.array_equal(got, kept[tap]), f"{name}/{precision}/{tap}: stale or different, max diff {H.max_err(got, kept[tap]):.3e}"
+    print(f"{name} x{copies} {precision}: taps without an fp32 copy: {raised}")
+    assert all(tap.startswith("conv") for tap in raised), raised      # only conv-stack outputs are ever skipped
+
+
 @pytest.mark.parametrize("mode", ["bf16x3", "f16x2"])
 @pytest.mark.parametrize("name", ["tiny_base", "base_sample_unpadded", "base_sample_padded", "robust_masked"])
 def test_bf16x3_precision_is_fp32_grade(torch_mod, name, mode):
