@@ -295,7 +295,8 @@ int launch_layer_norm_x(Profiler* prof, const float* x, float* y, const float* g
 // samples and then zeros.
 struct PackSeg {
     int64_t s0, len, src0;        // first stream sample, samples, offset in the caller's dense concatenation
-    int32_t f0, nf, out0, pad;    // first stream frame, frames (w2v2_num_frames(len)), first row of the caller's output
+    int32_t f0, nf, out0, keep0;  // first stream frame, frames (w2v2_num_frames(len)), first row of the caller's output, first of
+                                  // the utterance's frames that goes there (w2v2_forward_windows; the rows up to the next out0)
 };
 // one tile of an utterance's frames: rows [t0, t0 + tile rows) of the nf frames that start at stream frame f0
 struct SegTile {
@@ -318,7 +319,10 @@ int conv0_chunk_frames();     // conv0 rows per statistics chunk
 int launch_conv0_packed(Profiler* prof, const float* wave, const float* kernel, const float* bias, const float* gamma,
                         const float* beta, float* out, float* ws, float* scale_shift, int64_t L, int K, int stride, int C,
                         float eps, int act, const PackSeg* segs, int nseg, hipStream_t s,
-                        const PlaneOut* planes = nullptr /* optional planes of out (K = 10, stride 5, C % 4 == 0; out may then be null) */);
+                        const PlaneOut* planes = nullptr /* optional planes of out (K = 10, stride 5, C % 4 == 0; out may then be null) */,
+                        double* gram_ws = nullptr /* conv0_gram_ws_doubles(): statistics in the dense pass's form, as each utterance alone */,
+                        int max_seg_frames = 0 /* with gram_ws: conv0 rows of the longest utterance */);
+int64_t conv0_gram_ws_doubles(int64_t L, int stride, int nseg);
 int launch_conv0(Profiler* prof, const float* wave, const float* kernel, const float* bias,
                  const float* gamma, const float* beta, float* out, float* ws, int B, int64_t L,
                  int K, int stride, int C, float eps, int norm_mode, int act, hipStream_t s);
@@ -371,8 +375,11 @@ int launch_pos_conv_packed(Profiler* prof, const float* x, const float* wg, cons
 int attention_packed_rows(int head_size);
 int launch_attention_packed(Profiler* prof, const float* qkv, float* ctx, const SegTile* tiles, int ntiles, int64_t frames,
                             double sum_nf2, int H, int heads, hipStream_t s);
-// packed.hip: caller's dense concatenation -> aligned stream (gaps zeroed); stream rows -> caller's rows
-int launch_pack_scatter(const float* src, float* stream, int64_t L, const PackSeg* segs, int nseg, hipStream_t s);
+// packed.hip: caller's samples (from src0 on, per utterance) -> aligned stream (gaps zeroed); stream rows -> caller's rows.
+// stats: null (a copy), or launch_pack_stats' (nseg, 2) fp64 (mean, sqrt(var + eps)): (x - mean) / that, formed in fp64
+int launch_pack_scatter(const float* src, float* stream, int64_t L, const PackSeg* segs, int nseg, hipStream_t s,
+                        const double* stats = nullptr);
+int launch_pack_stats(const float* src, const PackSeg* segs, int nseg, double eps, double* stats, hipStream_t s);
 int launch_pack_gather(const float* stream_rows, float* out, int64_t out_rows, int width, const PackSeg* segs, int nseg,
                        hipStream_t s);
 // zero the stream rows no utterance owns -- [f0 + nf, next f0) behind each, [f0 + nf, frames) behind the last -- of an fp32
@@ -380,7 +387,8 @@ int launch_pack_gather(const float* stream_rows, float* out, int64_t out_rows, i
 int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int width, const PackSeg* segs, int nseg, hipStream_t s);
 
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
-enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4, SCRATCH_BEAM = 5 };
+enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4, SCRATCH_BEAM = 5, SCRATCH_WINDOWS = 6,
+                   SCRATCH_CUTS = 7 };
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out);
 int stream_scratch_release();       // frees the calling device's scratch buffers
 // pinned staging of a small host table on its way to the device (shadow.hip): grow-only, and the previous upload out of it has
@@ -434,6 +442,10 @@ int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, con
 int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int beam_width,
                            int nbest, const float* lm_table, int lm_order, float lm_alpha, float lm_beta, int max_len,
                            int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s);
+// pause cuts of CTC logits (segment.hip; w2v2_ctc_pause_cuts): the same addressing of the logits; per utterance max_cuts slots of
+// cuts and pause lengths (-1 behind the last) and the true count
+int launch_ctc_pause_cuts(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int delim,
+                          float margin, int min_pause, int max_cuts, int32_t* cut, int32_t* pause, int32_t* count, hipStream_t s);
 // the same search with a word n-gram model and a lexicon in place of the table (w2v2_ctc_beam_search_words)
 int launch_ctc_beam_search_words(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank,
                                  int beam_width, int nbest, const w2v2_word_lm* lm, int delim, float lm_alpha, float lm_beta,

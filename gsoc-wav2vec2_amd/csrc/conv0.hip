@@ -357,12 +357,11 @@ __global__ void conv0_seg_finalize_kernel(Conv0Args a) {
 constexpr int GK = 10, GN = GK + GK * (GK + 1) / 2;   // 65
 constexpr int GFR = 2048;                              // frames per block
 
-__global__ __launch_bounds__(256) void conv0_gram_kernel(Conv0Args a, int nblk) {
+// one block of up to GFR frames: wv = the first frame's first sample; 65 fp64 sums to dst
+__device__ __forceinline__ void conv0_gram_block(const float* __restrict__ wv, int nt, int S, double* __restrict__ dst) {
     extern __shared__ __attribute__((aligned(16))) float xs[];
     __shared__ double red[4][GN];
-    const int b = blockIdx.y, blk = blockIdx.x, S = a.stride;
-    const int t0 = blk * GFR, nt = min(GFR, a.T0 - t0), nx = (nt - 1) * S + GK;
-    const float* __restrict__ wv = a.wave + (int64_t)b * a.L + (int64_t)t0 * S;
+    const int nx = (nt - 1) * S + GK;
     for (int i = threadIdx.x; i < nx; i += 256) xs[i] = wv[i];
     __syncthreads();
     float acc[GN];
@@ -392,22 +391,19 @@ __global__ __launch_bounds__(256) void conv0_gram_kernel(Conv0Args a, int nblk) 
         if (lane == 0) red[wave][i] = v;
     }
     __syncthreads();
-    if (threadIdx.x < GN)
-        a.partial[((int64_t)b * nblk + blk) * GN + threadIdx.x] =
-            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    if (threadIdx.x < GN) dst[threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// one block per sample: combine the Gram partials, then every channel evaluates its two forms in fp64
-__global__ __launch_bounds__(256) void conv0_gram_finalize_kernel(Conv0Args a, int nblk) {
+// combine nblk Gram partials, then every channel evaluates its two forms in fp64 -> its scale / shift over n frames
+__device__ __forceinline__ void conv0_gram_combine(const Conv0Args& a, const double* __restrict__ part, int nblk, double n,
+                                                   float* __restrict__ scale_shift) {
     __shared__ double g[GN];
-    const int b = blockIdx.x;
     if (threadIdx.x < GN) {
         double v = 0.0;
-        for (int i = 0; i < nblk; ++i) v += a.partial[((int64_t)b * nblk + i) * GN + threadIdx.x];
+        for (int i = 0; i < nblk; ++i) v += part[(int64_t)i * GN + threadIdx.x];
         g[threadIdx.x] = v;
     }
     __syncthreads();
-    const double n = (double)a.T0;
     for (int c = threadIdx.x; c < a.C; c += 256) {
         double w[GK];
 #pragma unroll
@@ -426,9 +422,44 @@ __global__ __launch_bounds__(256) void conv0_gram_finalize_kernel(Conv0Args a, i
         double var = s2 / n - mean * mean;
         var = var > 0.0 ? var : 0.0;
         const double inv = (double)a.gamma[c] / sqrt(var + (double)a.eps);
-        a.scale_shift[((int64_t)b * 2 + 0) * a.C + c] = (float)inv;
-        a.scale_shift[((int64_t)b * 2 + 1) * a.C + c] = (float)((double)a.beta[c] - mean * inv);
+        scale_shift[c] = (float)inv;
+        scale_shift[a.C + c] = (float)((double)a.beta[c] - mean * inv);
     }
+}
+
+__global__ __launch_bounds__(256) void conv0_gram_kernel(Conv0Args a, int nblk) {
+    const int b = blockIdx.y, blk = blockIdx.x, t0 = blk * GFR;
+    conv0_gram_block(a.wave + (int64_t)b * a.L + (int64_t)t0 * a.stride, min(GFR, a.T0 - t0), a.stride,
+                     a.partial + ((int64_t)b * nblk + blk) * GN);
+}
+
+// one block per sample
+__global__ __launch_bounds__(256) void conv0_gram_finalize_kernel(Conv0Args a, int nblk) {
+    const int b = blockIdx.x;
+    conv0_gram_combine(a, a.partial + (int64_t)b * nblk * GN, nblk, (double)a.T0, a.scale_shift + (int64_t)b * 2 * a.C);
+}
+
+// The same statistics per utterance of a packed stream (w2v2_forward_windows): blocks of GFR frames counted from the utterance's
+// own first frame and folded in the same order, so an utterance's scale / shift carry the bits the dense pass gives it alone.
+// Utterance i keeps its partials in slots [slot0, slot0 + its blocks), slot0 = (its first conv0 row) / GFR + i: disjoint, since
+// the next utterance starts at least this one's rows further on.
+__device__ __forceinline__ int64_t conv0_gram_seg_slot(const PackSeg& sg, int i, int stride) { return sg.s0 / stride / GFR + i; }
+
+__global__ __launch_bounds__(256) void conv0_gram_seg_kernel(Conv0Args a) {
+    const int i = blockIdx.y, t0 = blockIdx.x * GFR;
+    const PackSeg sg = a.segs[i];
+    const int64_t T0 = 1 + (sg.len - a.K) / a.stride;
+    if (t0 >= T0) return;
+    conv0_gram_block(a.wave + sg.s0 + (int64_t)t0 * a.stride, (int)min((int64_t)GFR, T0 - t0), a.stride,
+                     a.partial + (conv0_gram_seg_slot(sg, i, a.stride) + blockIdx.x) * GN);
+}
+
+__global__ __launch_bounds__(256) void conv0_gram_seg_finalize_kernel(Conv0Args a) {
+    const int i = blockIdx.x;
+    const PackSeg sg = a.segs[i];
+    const int64_t T0 = 1 + (sg.len - a.K) / a.stride;
+    conv0_gram_combine(a, a.partial + conv0_gram_seg_slot(sg, i, a.stride) * GN, (int)((T0 + GFR - 1) / GFR), (double)T0,
+                       a.scale_shift + (int64_t)i * 2 * a.C);
 }
 
 template <int MODE>
@@ -568,9 +599,15 @@ int conv0_chunk_frames() { return TC; }
 // Packed stream: pass 1 is the per-chunk conv recompute (conv0_kernel<0>), each chunk counting only the rows of the utterance
 // whose span holds it; the finalize combines each utterance's chunks; the apply pass reads the utterance's scale / shift.
 // (The Gram-form statistics of the dense path take 2048-frame blocks, which would straddle utterances.)
+// gram_ws (w2v2_forward_windows; conv0_gram_ws_doubles): the statistics in the dense pass's Gram form instead, per utterance in
+// blocks counted from its own start -- bit for bit what launch_conv0_x gives the utterance alone; max_seg_frames: the longest
+// utterance's conv0 rows.
+int64_t conv0_gram_ws_doubles(int64_t L, int stride, int nseg) { return (L / stride / GFR + nseg + 2) * GN; }
+
 int launch_conv0_packed(Profiler* prof, const float* wave, const float* kernel, const float* bias, const float* gamma,
                         const float* beta, float* out, float* ws, float* scale_shift, int64_t L, int K, int stride, int C,
-                        float eps, int act, const PackSeg* segs, int nseg, hipStream_t s, const PlaneOut* planes) {
+                        float eps, int act, const PackSeg* segs, int nseg, hipStream_t s, const PlaneOut* planes, double* gram_ws,
+                        int max_seg_frames) {
     const PlaneOut pl = planes ? *planes : PlaneOut{};
     W2V2_REQUIRE(wave && kernel && gamma && beta && (out || pl.p) && ws && scale_shift && segs && nseg > 0, "conv0_packed: null operand");
     W2V2_REQUIRE(C > 0 && K > 0 && K <= 32 && stride > 0 && L >= K, "conv0_packed: unsupported C=%d K=%d stride=%d L=%lld", C, K,
@@ -593,9 +630,16 @@ int launch_conv0_packed(Profiler* prof, const float* wave, const float* kernel, 
     const double flops = 2.0 * (double)a.T0 * C * K;
     {
         ProfScope ps(prof, FAM_CONV0_STATS, flops, 4.0 * (double)L, s);
-        launch_mode<0>(a, 1, s);
-        const int64_t n = (int64_t)nseg * C;
-        W2V2_LAUNCH(conv0_seg_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+        const size_t gram_lds = ((size_t)(GFR - 1) * stride + GK + 4) * sizeof(float);
+        if (gram_ws && K == GK && gram_lds <= 60 * 1024) {      // (the dense pass's own choice: launch_conv0_x)
+            a.partial = gram_ws;
+            W2V2_LAUNCH(conv0_gram_seg_kernel, dim3((unsigned)((max_seg_frames + GFR - 1) / GFR), (unsigned)nseg), dim3(256), gram_lds, s, a);
+            W2V2_LAUNCH(conv0_gram_seg_finalize_kernel, dim3((unsigned)nseg), dim3(256), 0, s, a);
+        } else {
+            launch_mode<0>(a, 1, s);
+            const int64_t n = (int64_t)nseg * C;
+            W2V2_LAUNCH(conv0_seg_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+        }
     }
     {
         const double out_bytes = ((out ? 4.0 : 0.0) + (pl.p ? 2.0 * plane_count(pl.fmt) : 0.0)) * (double)a.T0 * C;

@@ -1,5 +1,5 @@
-// The inference forward (w2v2_forward, w2v2_forward_packed): the forward plan, the extractor + projection stage it shares with
-// the training forward, and the buffers / weight images its precision modes need.  Host code only.
+// The inference forward (w2v2_forward, w2v2_forward_packed, w2v2_forward_windows): the forward plan, the extractor + projection
+// stage it shares with the training forward, and the buffers / weight images its precision modes need.  Host code only.
 //
 // Forward order follows the reference exactly: Wav2Vec2ForCTC.call
 // (modeling.py:239-255) -> Wav2Vec2Model.call (modeling.py:169-209) ->
@@ -7,6 +7,8 @@
 // (feature_extractor.py:92-95) -> Wav2Vec2Encoder.call (encoder.py:251-276) ->
 // TransformerLayer.call (encoder.py:111-134) -> lm_head.
 #include <algorithm>
+#include <map>
+#include <mutex>
 #include <string.h>
 
 #include <string>
@@ -384,6 +386,8 @@ struct PackedPlan {
     int nattn;
     double sum_nf2;
     float* head_out;          // (stream frames, vocab) when the model has a head
+    double* gram_ws;          // w2v2_forward_windows: conv0's GroupNorm statistics as the dense forward takes them, or null
+    int max_conv0_rows;       // conv0 rows of the longest utterance
 };
 
 // ---- feature extractor (feature_extractor.py:54-59) and feature projection (feature_extractor.py:92-95) ---------------------------
@@ -408,7 +412,8 @@ int w2v2_forward_frontend(w2v2_model* m, const ForwardPlan& plan, const float* w
         if (pk && !plan.layer_mode) {     // GroupNorm statistics per utterance, over exactly its rows
             if (int e = launch_conv0_packed(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr, fe(0, "/layer_norm/gamma"),
                                             fe(0, "/layer_norm/beta"), ForwardPlan::f32(k, m->conv[0]), m->conv0_ws, m->pk_scale, L, c.kernal_sizes[0],
-                                            c.strides[0], c.filter_sizes[0], 1e-5f, plan.act_ew, pk->segs, pk->nseg, s, po))
+                                            c.strides[0], c.filter_sizes[0], 1e-5f, plan.act_ew, pk->segs, pk->nseg, s, po, pk->gram_ws,
+                                            pk->max_conv0_rows))
                 return e;
         } else if (int e = launch_conv0_x(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr,
                                           fe(0, "/layer_norm/gamma"), fe(0, "/layer_norm/beta"), ForwardPlan::f32(k, m->conv[0]),
@@ -591,33 +596,41 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
     return W2V2_OK;
 }
 
-extern "C" {
+// eps of Wav2Vec2Processor._normalize (processor.py: (x - mean) / sqrt(var + 1e-5))
+constexpr double kWaveNormEps = 1e-5;
 
-int w2v2_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, const int32_t* mask,
-                 float* out, void* stream) {
-    W2V2_REQUIRE(m && wave && out, "forward: null argument");
-    W2V2_REQUIRE(B > 0 && L > 0, "forward: bad batch shape (%d, %lld)", B, (long long)L);
-    if (!m->finalized) {
-        set_error("forward: call w2v2_finalize after setting the variables");
-        return W2V2_ESTATE;
-    }
-    return forward_impl(m, wave, B, L, mask, out, reinterpret_cast<hipStream_t>(stream), nullptr);
-}
+// pinned staging of w2v2_op_normalize_windows' table, per device (as beam.hip's)
+static std::mutex g_norm_stage_mu;
+static std::map<int, PinnedStage> g_norm_stage;
 
-int w2v2_forward_packed(w2v2_model* m, const float* wave, int32_t n, const int64_t* cu_samples, float* out, void* stream) {
-    W2V2_REQUIRE(m && wave && cu_samples && out, "forward_packed: null argument");
+// one piece of a packed stream: samples [src0, src0 + len) of the caller's buffer, computed as an utterance of its own; rows
+// [keep0, keep0 + keepn) of its frames go to the caller's output
+struct StreamPiece {
+    int64_t src0, len;
+    int32_t keep0, keepn;
+};
+
+static int stream_forward_ready(w2v2_model* m, const char* who) {
     if (!m->finalized) {
-        set_error("forward_packed: call w2v2_finalize after setting the variables");
+        set_error("%s: call w2v2_finalize after setting the variables", who);
         return W2V2_ESTATE;
     }
     static const char* modes[] = {"fp32", "bf16", "bf16x3", "f16x2"};
     W2V2_REQUIRE(m->precision == W2V2_PRECISION_FP32 || m->precision == W2V2_PRECISION_BF16X3 || m->precision == W2V2_PRECISION_F16X2,
-                 "forward_packed: precision mode %s is not supported (fp32, bf16x3, f16x2)",
+                 "%s: precision mode %s is not supported (fp32, bf16x3, f16x2)", who,
                  (m->precision >= 0 && m->precision <= 3) ? modes[m->precision] : "?");
-    W2V2_REQUIRE(n >= 1, "forward_packed: %d utterances (need at least one)", n);
-    W2V2_REQUIRE(cu_samples[0] == 0, "forward_packed: cu_samples[0] = %lld, must be 0", (long long)cu_samples[0]);
+    return W2V2_OK;
+}
+
+// The body of w2v2_forward_packed and w2v2_forward_windows: the (checked) pieces into the aligned stream, one B = 1 forward over
+// it with the three segment-aware stages, the kept rows out.  normalize: each piece's samples as Wav2Vec2Processor._normalize
+// gives them, on the device (packed.hip: pack_stats_kernel, pack_scatter_kernel).  dense_stats: conv0's GroupNorm statistics of
+// each piece in the dense forward's Gram form (conv0.hip), so that a piece carries the bits w2v2_forward gives it alone; the
+// packed entry keeps the chunk partials it has always used, and its bits.
+static int forward_stream(w2v2_model* m, const char* who, const float* wave, const std::vector<StreamPiece>& pieces, int normalize,
+                          bool dense_stats, float* out, hipStream_t s) {
     const w2v2_config& c = m->cfg;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int n = (int)pieces.size();
     // alignment unit: a multiple of the total stride (whole frames at every layer) and of conv0's stats chunk in samples
     int64_t A = 1;
     for (int i = 0; i < c.num_conv_layers; ++i) A *= c.strides[i];
@@ -628,20 +641,18 @@ int w2v2_forward_packed(w2v2_model* m, const float* wave, int32_t n, const int64
     // utterances in the stream, and the tiles of the two stages that work per utterance
     std::vector<PackSeg> segs((size_t)n);
     int64_t L = 0, rows = 0;
+    int max_rows0 = 0;
     double sum_nf2 = 0.0;
     for (int i = 0; i < n; ++i) {
-        const int64_t len = cu_samples[i + 1] - cu_samples[i];
-        W2V2_REQUIRE(len >= 0, "forward_packed: cu_samples decreases at utterance %d", i);
-        const int64_t nf = w2v2_num_frames(m, len);
-        W2V2_REQUIRE(nf >= 1, "forward_packed: utterance %d has %lld samples, shorter than the conv stack's receptive field", i,
-                     (long long)len);
-        segs[i] = PackSeg{L, len, cu_samples[i], (int32_t)(L / A), (int32_t)nf, (int32_t)rows, 0};
+        const int64_t len = pieces[i].len, nf = w2v2_num_frames(m, len);
+        max_rows0 = std::max(max_rows0, (int)(1 + (len - c.kernal_sizes[0]) / c.strides[0]));
+        segs[i] = PackSeg{L, len, pieces[i].src0, (int32_t)(L / A), (int32_t)nf, (int32_t)rows, pieces[i].keep0};
         L += (len + U - 1) / U * U;
-        rows += nf;
+        rows += pieces[i].keepn;
         sum_nf2 += (double)nf * (double)nf;
     }
     const int64_t T = w2v2_num_frames(m, L);
-    W2V2_REQUIRE(T < (1 << 24) && (int64_t)segs.back().f0 + segs.back().nf <= T, "forward_packed: stream of %lld samples out of range",
+    W2V2_REQUIRE(T < (1 << 24) && (int64_t)segs.back().f0 + segs.back().nf <= T, "%s: stream of %lld samples out of range", who,
                  (long long)L);
     const int H = c.hidden_size, PR = pos_conv_packed_rows(), AR = attention_packed_rows(H / c.num_heads);
     std::vector<SegTile> tiles;
@@ -665,9 +676,15 @@ int w2v2_forward_packed(w2v2_model* m, const float* wave, int32_t n, const int64
         float* tab = nullptr;
         if (int e = w2v2_ws_alloc(m, &tab, ((int64_t)m->pk_seg_cap * sizeof(PackSeg) + (int64_t)m->pk_tile_cap * sizeof(SegTile)) / sizeof(float))) return e;
         m->pk_tab = tab;
+        float* stats = nullptr;
+        if (int e = w2v2_ws_alloc(m, &stats, (int64_t)m->pk_seg_cap * 2 * (sizeof(double) / sizeof(float)))) return e;
+        m->pk_stats = reinterpret_cast<double*>(stats);
+        float* gram = nullptr;
+        if (int e = w2v2_ws_alloc(m, &gram, conv0_gram_ws_doubles(m->ws_L, c.strides[0], m->pk_seg_cap) * (sizeof(double) / sizeof(float)))) return e;
+        m->pk_gram = reinterpret_cast<double*>(gram);
         m->pk_L = m->ws_L;
     }
-    W2V2_REQUIRE(n <= m->pk_seg_cap && (int64_t)tiles.size() <= m->pk_tile_cap, "forward_packed: tables exceed their capacity");
+    W2V2_REQUIRE(n <= m->pk_seg_cap && (int64_t)tiles.size() <= m->pk_tile_cap, "%s: tables exceed their capacity", who);
     // tables -> device through pinned staging; the previous call's copy out of it must have completed before it is rewritten
     const size_t seg_bytes = segs.size() * sizeof(PackSeg), bytes = seg_bytes + tiles.size() * sizeof(SegTile);
     if (int e = pinned_stage_begin(m->pk_stage, bytes, (size_t)64 << 10)) return e;
@@ -677,9 +694,98 @@ int w2v2_forward_packed(w2v2_model* m, const float* wave, int32_t n, const int64
     const PackSeg* dsegs = static_cast<const PackSeg*>(m->pk_tab);
     const SegTile* dtiles = reinterpret_cast<const SegTile*>(static_cast<const char*>(m->pk_tab) + seg_bytes);
 
-    if (int e = launch_pack_scatter(wave, m->pk_wave, L, dsegs, n, s)) return e;
-    const PackedPlan plan{dsegs, n, dtiles, npos, dtiles + npos, nattn, sum_nf2, m->pk_out};
+    if (normalize)
+        if (int e = launch_pack_stats(wave, dsegs, n, kWaveNormEps, m->pk_stats, s)) return e;
+    if (int e = launch_pack_scatter(wave, m->pk_wave, L, dsegs, n, s, normalize ? m->pk_stats : nullptr)) return e;
+    const PackedPlan plan{dsegs, n, dtiles, npos, dtiles + npos, nattn, sum_nf2, m->pk_out, dense_stats ? m->pk_gram : nullptr, max_rows0};
     if (int e = forward_impl(m, m->pk_wave, 1, L, nullptr, out, s, &plan)) return e;
     return launch_pack_gather(c.with_lm_head ? m->pk_out : m->enc_out, out, rows, c.with_lm_head ? c.vocab_size : H, dsegs, n, s);
+}
+
+extern "C" {
+
+int w2v2_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, const int32_t* mask,
+                 float* out, void* stream) {
+    W2V2_REQUIRE(m && wave && out, "forward: null argument");
+    W2V2_REQUIRE(B > 0 && L > 0, "forward: bad batch shape (%d, %lld)", B, (long long)L);
+    if (!m->finalized) {
+        set_error("forward: call w2v2_finalize after setting the variables");
+        return W2V2_ESTATE;
+    }
+    return forward_impl(m, wave, B, L, mask, out, reinterpret_cast<hipStream_t>(stream), nullptr);
+}
+
+int w2v2_forward_packed(w2v2_model* m, const float* wave, int32_t n, const int64_t* cu_samples, float* out, void* stream) {
+    W2V2_REQUIRE(m && wave && cu_samples && out, "forward_packed: null argument");
+    if (int e = stream_forward_ready(m, "forward_packed")) return e;
+    W2V2_REQUIRE(n >= 1, "forward_packed: %d utterances (need at least one)", n);
+    W2V2_REQUIRE(cu_samples[0] == 0, "forward_packed: cu_samples[0] = %lld, must be 0", (long long)cu_samples[0]);
+    // the special case of w2v2_forward_windows: utterance i from cu[i] on, every frame kept, no normalisation
+    std::vector<StreamPiece> pieces((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int64_t len = cu_samples[i + 1] - cu_samples[i];
+        W2V2_REQUIRE(len >= 0, "forward_packed: cu_samples decreases at utterance %d", i);
+        const int64_t nf = w2v2_num_frames(m, len);
+        W2V2_REQUIRE(nf >= 1, "forward_packed: utterance %d has %lld samples, shorter than the conv stack's receptive field", i,
+                     (long long)len);
+        pieces[i] = StreamPiece{cu_samples[i], len, 0, (int32_t)nf};
+    }
+    return forward_stream(m, "forward_packed", wave, pieces, 0, false, out, reinterpret_cast<hipStream_t>(stream));
+}
+
+int w2v2_forward_windows(w2v2_model* m, const float* wave, int64_t wave_samples, int32_t n, const int64_t* sample0,
+                         const int64_t* samples, const int32_t* keep0, const int32_t* keepn, int32_t normalize, float* out,
+                         void* stream) {
+    W2V2_REQUIRE(m && wave && sample0 && samples && keep0 && keepn && out, "forward_windows: null argument");
+    if (int e = stream_forward_ready(m, "forward_windows")) return e;
+    W2V2_REQUIRE(n >= 1, "forward_windows: %d windows (need at least one)", n);
+    W2V2_REQUIRE(wave_samples >= 1, "forward_windows: a recording of %lld samples", (long long)wave_samples);
+    W2V2_REQUIRE(normalize == 0 || normalize == 1, "forward_windows: normalize = %d, must be 0 or 1", normalize);
+    std::vector<StreamPiece> pieces((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        W2V2_REQUIRE(sample0[i] >= 0 && samples[i] >= 0 && samples[i] <= wave_samples && sample0[i] <= wave_samples - samples[i],
+                     "forward_windows: window %d, samples [%lld, %lld + %lld), lies outside the recording's [0, %lld)", i,
+                     (long long)sample0[i], (long long)sample0[i], (long long)samples[i], (long long)wave_samples);
+        const int64_t nf = w2v2_num_frames(m, samples[i]);
+        W2V2_REQUIRE(nf >= 1, "forward_windows: window %d has %lld samples, shorter than the conv stack's receptive field", i,
+                     (long long)samples[i]);
+        W2V2_REQUIRE(keepn[i] != 0, "forward_windows: window %d keeps no frame", i);
+        W2V2_REQUIRE(keep0[i] >= 0 && keepn[i] > 0 && keep0[i] <= nf - keepn[i],
+                     "forward_windows: window %d keeps frames [%d, %d + %d) of its %lld", i, keep0[i], keep0[i], keepn[i], (long long)nf);
+        pieces[i] = StreamPiece{sample0[i], samples[i], keep0[i], keepn[i]};
+    }
+    return forward_stream(m, "forward_windows", wave, pieces, normalize, true, out, reinterpret_cast<hipStream_t>(stream));
+}
+
+int w2v2_op_normalize_windows(const float* wave, int32_t n, const int64_t* sample0, const int64_t* samples, float* out, void* stream) {
+    W2V2_REQUIRE(wave && sample0 && samples && out, "op_normalize_windows: null argument");
+    W2V2_REQUIRE(n >= 1, "op_normalize_windows: %d windows (need at least one)", n);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // the windows back to back as the "stream": no alignment, no gaps
+    std::vector<PackSeg> segs((size_t)n);
+    int64_t L = 0;
+    for (int i = 0; i < n; ++i) {
+        W2V2_REQUIRE(sample0[i] >= 0 && samples[i] >= 1, "op_normalize_windows: window %d is [%lld, %lld + %lld)", i, (long long)sample0[i],
+                     (long long)sample0[i], (long long)samples[i]);
+        segs[i] = PackSeg{L, samples[i], sample0[i], 0, 0, 0, 0};
+        L += samples[i];
+    }
+    const size_t tab_bytes = ((size_t)n * sizeof(PackSeg) + 255) & ~(size_t)255;
+    void* raw = nullptr;
+    if (int e = stream_scratch(SCRATCH_WINDOWS, s, tab_bytes + (size_t)n * 2 * sizeof(double), &raw)) return e;
+    double* stats = reinterpret_cast<double*>(static_cast<char*>(raw) + tab_bytes);
+    {
+        int dev = 0;
+        W2V2_HIP_CHECK(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lock(g_norm_stage_mu);
+        PinnedStage& st = g_norm_stage[dev];
+        const size_t bytes = (size_t)n * sizeof(PackSeg);
+        if (int e = pinned_stage_begin(st, bytes, (size_t)16 << 10)) return e;
+        memcpy(st.p, segs.data(), bytes);
+        if (int e = pinned_stage_upload(st, raw, bytes, s)) return e;
+    }
+    const PackSeg* dsegs = static_cast<const PackSeg*>(raw);
+    if (int e = launch_pack_stats(wave, dsegs, n, kWaveNormEps, stats, s)) return e;
+    return launch_pack_scatter(wave, out, L, dsegs, n, s, stats);
 }
 }  // extern "C"

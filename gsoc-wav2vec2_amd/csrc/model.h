@@ -49,6 +49,8 @@ struct w2v2_model {
     int pk_seg_cap = 0, pk_tile_cap = 0;
     float *pk_wave = nullptr, *pk_scale = nullptr, *pk_out = nullptr;   // stream samples, conv0 scale / shift per utterance, head output
     void* pk_tab = nullptr;                  // device tables: PackSeg[pk_seg_cap] | SegTile[pk_tile_cap]
+    double* pk_gram = nullptr;               // Gram partials of conv0's GroupNorm statistics per window (w2v2_forward_windows)
+    double* pk_stats = nullptr;              // (pk_seg_cap, 2) mean, sqrt(var + eps) per window (w2v2_forward_windows, normalize)
     w2v2::PinnedStage pk_stage;              // pinned staging of the tables (outlives the workspace)
     // bf16 shadows (precision mode 1, inference forward; forward.hip::w2v2_ensure_shadows).  Weight shadows are the
     // GEMM kernels transposed to (N, K); activation shadows are written by the producing kernels.

@@ -214,6 +214,8 @@ static void free_workspace(w2v2_model* m) {
     m->pk_L = 0;                   // the packed stream buffers live in `allocs`
     m->pk_wave = m->pk_scale = m->pk_out = nullptr;
     m->pk_tab = nullptr;
+    m->pk_stats = nullptr;
+    m->pk_gram = nullptr;
     m->pk_seg_cap = m->pk_tile_cap = 0;
 }
 
@@ -539,6 +541,13 @@ int w2v2_ctc_beam_search_words(const float* logits, int32_t V, int32_t n, const 
                                double* score, double* total, void* stream) {
     return launch_ctc_beam_search_words(logits, V, n, row0, frames, blank, beam_width, nbest, lm, delim, lm_alpha, lm_beta, unk_penalty,
                                         score_eos, max_len, labels_out, length, score, total, reinterpret_cast<hipStream_t>(stream));
+}
+
+int w2v2_ctc_pause_cuts(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t blank,
+                        int32_t delim, float margin, int32_t min_pause, int32_t max_cuts, int32_t* cut, int32_t* pause, int32_t* count,
+                        void* stream) {
+    return launch_ctc_pause_cuts(logits, V, n, row0, frames, blank, delim, margin, min_pause, max_cuts, cut, pause, count,
+                                 reinterpret_cast<hipStream_t>(stream));
 }
 
 int w2v2_activation_info(const w2v2_model* m, const char* name, int64_t shape[3]) {

@@ -17,6 +17,8 @@ MAX_CONV_LAYERS = 16
 ALIGN_MAX_LABELS = 8191          # W2V2_ALIGN_MAX_LABELS: labels per utterance of w2v2_ctc_align
 BEAM_MAX_WIDTH = 64              # W2V2_BEAM_MAX_WIDTH, W2V2_BEAM_MAX_VOCAB: limits of w2v2_ctc_beam_search
 BEAM_MAX_VOCAB = 64
+CUTS_CHUNK = 1024                # W2V2_CUTS_CHUNK: frames per block of w2v2_ctc_pause_cuts
+CUTS_MAX_FRAMES = 1 << 24        # W2V2_CUTS_MAX_FRAMES
 WORDLM_MAX_ORDER = 5             # W2V2_WORDLM_MAX_ORDER: order of the word n-gram model of w2v2_ctc_beam_search_words
 
 
@@ -70,12 +72,14 @@ PROTOTYPES = {
     "w2v2_get_precision": (C.c_int, [_P]),
     "w2v2_forward": (C.c_int, [_P, _P, _I32, _I64, _P, _P, _P]),
     "w2v2_forward_packed": (C.c_int, [_P, _P, _I32, _P, _P, _P]),
+    "w2v2_forward_windows": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _I32, _P, _P]),
     "w2v2_ctc_loss": (C.c_int, [_P, _I32, _I32, _I32, _P, _I32, _P, _P, _I32, _P, _P, _P]),
     "w2v2_ctc_loss_fused": (C.c_int, [_P, _I32, _I32, _I32, _P, _I32, _I32, _I32, C.c_float, _P, _P, _P, _P]),
     "w2v2_ctc_align": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "w2v2_ctc_beam_search": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_float, C.c_float, _I32, _P, _P, _P, _P, _P]),
     "w2v2_ctc_beam_search_words": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, C.POINTER(W2V2WordLM), _I32, C.c_float, C.c_float,
                                              C.c_float, _I32, _I32, _P, _P, _P, _P, _P]),
+    "w2v2_ctc_pause_cuts": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, C.c_float, _I32, _I32, _P, _P, _P, _P]),
     "w2v2_set_trainable": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "w2v2_set_trainable_flags": (C.c_int, [_P, _P, _I32]),
     "w2v2_set_option": (C.c_int, [_P, _I32, _I32]),
@@ -140,6 +144,7 @@ PROTOTYPES = {
     "w2v2_op_attention": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "w2v2_op_attention_packed": (C.c_int, [_P, _I32, _P, _P, _P, _I64, _P, _I32, _I32, _P]),
     "w2v2_op_frame_lengths": (C.c_int, [_P, _P, _I32, _I64, C.POINTER(_I32), C.POINTER(_I32), _I32, _P]),
+    "w2v2_op_normalize_windows": (C.c_int, [_P, _I32, _P, _P, _P, _P]),
 }
 
 _lib = None

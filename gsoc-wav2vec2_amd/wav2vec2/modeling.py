@@ -572,6 +572,20 @@ class TFKerasModel(Layer):
         out = DeviceTensor.wrap(out)
         return list(torch.split(out, frames, dim=0))
 
+    def predict_long(self, waveform, window_s=20.0, margin_s=2.0, normalize=True, max_stream_s=1200.0):
+        """Inference on recordings of any length (minutes, hours): overlapping windows of `window_s` seconds, each computed
+        exactly as `self(window[None])` computes it alone (identical bits in fp32), and every frame of the recording taken from the window that holds at least `margin_s` seconds of context on each side of it
+        (wav2vec2.longform.window_plan; w2v2_forward_windows).  The
+        seconds are rounded to whole frames.  `waveform`: one 1-D waveform or a list of them; the windows of all recordings
+        are pooled.  `normalize=True` normalises every window over its own samples on the device, as
+        `Wav2Vec2Processor._normalize` would: pass the raw recording.  The windows go, in order, through packed calls whose
+        stream stays under `max_stream_s` seconds of audio (the workspace grows with the stream); the grouping changes no bit
+        of the result.  Returns one (num_frames(len), vocab | hidden) tensor per recording -- for a list, views of one
+        buffer, as `predict_packed` returns.  A recording no longer than the window is bit-equal to `self(wave[None])` (of
+        the normalised wave).  Precision modes as `predict_packed`."""
+        from .longform import predict_long
+        return predict_long(self, waveform, window_s, margin_s, normalize, max_stream_s)
+
     # ---- introspection used by the parity tests / bench -----------------------
     def activation(self, name):
         shape = (C.c_int64 * 3)()
@@ -737,3 +751,17 @@ class Wav2Vec2ForCTC(TFKerasModel):
             texts = [x.text(tokenizer) for x in h]
             out.append(Transcript(texts[0] if texts else "", h, texts, w))
         return out
+
+    def transcribe_long(self, waveform, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False, window_s=20.0, margin_s=2.0,
+                        normalize=True, max_stream_s=1200.0, **cut_options):
+        """Text of recordings of any length: `predict_long(waveform, ...)`, then `wav2vec2.longform.decode_long` on the stitched
+        logits with blank = config.pad_id, the tokenizer's word delimiter and the frame period of the conv strides: the logits
+        are cut at pauses between words, all segments go through one beam search (and one forced alignment with
+        `timestamps=True`), and the pieces are concatenated.  `cut_options`: decode_long's pause_margin, min_pause, min_frames,
+        max_frames.  A language model sees each segment as an utterance (a WordNgramLM restarts at every segment).  Returns one
+        wav2vec2.longform.LongTranscript(text, ids, score, total, words, segments) per recording."""
+        from .longform import decode_long
+        logits = self.predict_long(waveform, window_s, margin_s, normalize, max_stream_s)
+        seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
+        return decode_long(logits, tokenizer, beam_width=beam_width, nbest=nbest, lm=lm, blank=self.config.pad_id, timestamps=timestamps,
+                           seconds_per_frame=seconds_per_frame, **cut_options)

@@ -202,6 +202,26 @@ int w2v2_forward(w2v2_model* m, const float* wave_dev, int32_t B, int64_t L,
 int w2v2_forward_packed(w2v2_model* m, const float* wave_dev, int32_t n, const int64_t* cu_samples_host,
                         float* out_dev, void* stream);
 
+/* Windowed inference forward for long recordings: n windows of ONE device buffer in one call, each computed as
+ * w2v2_forward computes it alone (B = 1, no mask), and a range of each window's frames kept.  w2v2_forward_packed is the special
+ * case sample0 = cu_samples, every frame kept, normalize = 0, and shares the body: layout, workspace, precision modes, the range
+ * contract of f16x2 and the synchronisation are as described there.  One difference: conv0's GroupNorm statistics are taken per
+ * window in the form w2v2_forward takes them, so that in fp32 a window's rows carry the bits w2v2_forward gives that window alone;
+ * w2v2_forward_packed keeps its own summation (and its bits), which agrees with w2v2_forward to the fp32 bar.
+ *   wave_dev       (wave_samples) fp32
+ *   window i       wave_dev[sample0_host[i] .. sample0_host[i] + samples_host[i]); windows may overlap and need not be ordered
+ *   keep0_host, keepn_host   rows [keep0_i, keep0_i + keepn_i) of window i's w2v2_num_frames(samples_i) output rows are kept
+ *   normalize      1: every window is normalised over its own samples as Wav2Vec2Processor._normalize does it,
+ *                  (x - mean) / sqrt(var + 1e-5) with the population variance; mean and variance accumulate in fp64 (two passes, a
+ *                  fixed reduction order, no atomics: deterministic) and the quotient is formed in fp64 and rounded once to fp32.
+ *                  0: the samples are used as they are
+ *   out_dev        (sum keepn_i, vocab | hidden); window i's kept rows at row sum_{j<i} keepn_j
+ * W2V2_EINVAL with a message naming the window: a window outside [0, wave_samples), shorter than the receptive field, keepn_i == 0,
+ * a kept range outside the window's frames; also precision W2V2_PRECISION_BF16 (naming the mode) and normalize outside {0, 1}. */
+int w2v2_forward_windows(w2v2_model* m, const float* wave_dev, int64_t wave_samples, int32_t n, const int64_t* sample0_host,
+                         const int64_t* samples_host, const int32_t* keep0_host, const int32_t* keepn_host, int32_t normalize,
+                         float* out_dev, void* stream);
+
 /* Replaces CTCLoss.call (losses.py:14-45) = tf.nn.ctc_loss(
  * logits_time_major=False, blank_index=pad_id) with the reference's length
  * convention supplied by the caller:
@@ -300,6 +320,28 @@ int w2v2_ctc_beam_search_words(const float* logits_dev, int32_t V, int32_t n, co
                                int32_t blank, int32_t beam_width, int32_t nbest, const w2v2_word_lm* lm, int32_t delim,
                                float lm_alpha, float lm_beta, float unk_penalty, int32_t score_eos, int32_t max_len,
                                int32_t* labels_out_dev, int32_t* length_dev, double* score_dev, double* total_dev, void* stream);
+
+/* Pause cuts (exact definition in csrc/segment.hip and, in numpy, tests/longform_reference.py): where the logits
+ * of a long recording can be cut into utterance-sized pieces for w2v2_ctc_beam_search and w2v2_ctc_align.  Model-free, with their
+ * addressing:  utterance i: logits_dev rows [row0_host[i], row0_host[i] + frames_host[i]) of V fp32.
+ * With a_t the argmax of row t (lowest index on ties; -1 for a row that holds a NaN), frame t is QUIET when a_t == blank and
+ * x_t[blank] - max_{v != blank} x_t[v] >= margin (one fp32 subtraction; V == 1: quiet).  A pause is a maximal run [a, b) of quiet
+ * frames with b - a >= min_pause, a > 0 and b < frames_i; with delim >= 0 it counts only if the last frame before a whose a_t is not
+ * the blank exists and has a_t == delim (the cut then falls between words of the greedy path); delim = -1 drops that condition.
+ * The cut of a pause is a + (b - a) / 2.
+ *   cut_dev, pause_dev  (n, max_cuts) int32: the cuts in ascending order and their pauses' lengths b - a; -1 behind the last
+ *   count_dev           (n) int32: the TRUE count, which may exceed max_cuts; only the first max_cuts are stored
+ * n >= 1, V >= 1, blank in [0, V), delim -1 or a label in [0, V) other than the blank, margin not NaN, min_pause >= 1,
+ * max_cuts >= 1, 1 <= frames_i <= W2V2_CUTS_MAX_FRAMES, row0_i >= 0: otherwise W2V2_EINVAL.  One utterance is spread over blocks of
+ * W2V2_CUTS_CHUNK frames; what crosses a block's edge (the running count of quiet frames, the last label that is not the blank) is
+ * carried by a scan, and the cuts are compacted in order by a prefix sum: no atomics, the same bits on every call, and results do
+ * not depend on the other utterances of the call.  Launches are attributed to the `ctc` profiling family.  Synchronises with the
+ * previous call's table upload (host-side), otherwise enqueued on `stream`. */
+#define W2V2_CUTS_CHUNK 1024
+#define W2V2_CUTS_MAX_FRAMES (1 << 24)
+int w2v2_ctc_pause_cuts(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host,
+                        int32_t blank, int32_t delim, float margin, int32_t min_pause, int32_t max_cuts, int32_t* cut_dev,
+                        int32_t* pause_dev, int32_t* count_dev, void* stream);
 
 /* ---- the training step (reference src/main.py:136-259) --------
  * Replaces what Keras' train_step does around the forward: training-mode forward, backward of every
@@ -602,6 +644,11 @@ int w2v2_op_attention_packed(const float* qkv_dev, int32_t n, const int32_t* cu_
 int w2v2_op_frame_lengths(const int32_t* mask_dev, int32_t* frame_len_dev, int32_t B,
                           int64_t L, const int32_t* kernal_sizes, const int32_t* strides,
                           int32_t num_layers, void* stream);
+
+/* The normalisation of w2v2_forward_windows on its own: window i = wave_dev[sample0_host[i] .. + samples_host[i]) (samples_i >= 1),
+ * normalised over its own samples, written to out_dev (sum samples_i) back to back. */
+int w2v2_op_normalize_windows(const float* wave_dev, int32_t n, const int64_t* sample0_host, const int64_t* samples_host,
+                              float* out_dev, void* stream);
 
 /* ---- training operators (parity-tested on their own) ----------------------------------------- */
 
