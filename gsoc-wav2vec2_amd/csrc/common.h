@@ -174,7 +174,7 @@ int launch_gemm(Profiler* prof, const float* A, int64_t lda, int64_t strideA, co
                 int64_t ldb, float* C, int64_t ldc, int64_t strideC, const float* bias,
                 const float* residual, int M, int N, int K, int nbatch, int act, hipStream_t s);
 
-// fp32 GEMM on the LDS-ring kernels (gemm_f32_sw.hip): tile 0 = 256 x 128, 1 = 128 x 128; persist: at most two blocks per CU,
+// fp32 GEMM on the LDS-ring kernels (gemm_f32_sw.hip): tile 0 = 256 x 128, 1 = 128 x 128, 2 = 64 x 64; persist: at most two blocks per CU,
 // each looping over its tiles.  launch_gemm routes to them; gemm_f32_ring_ok says whether a shape fits.
 void gemm_f32_force_ring(int route);      // this thread's next launch_gemm calls: 0 | 1 | 2 as gemm_f32.hip's RING_DEFAULT, -1 = by shape
 bool gemm_f32_ring_ok(int tile, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb, int64_t strideB,
@@ -182,6 +182,9 @@ bool gemm_f32_ring_ok(int tile, const float* A, int64_t lda, int64_t strideA, co
 int launch_gemm_f32_ring(int tile, bool persist, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb,
                          int64_t strideB, float* C, int64_t ldc, int64_t strideC, const float* bias, const float* residual, int M,
                          int N, int K, int nbatch, int act, hipStream_t s);
+// ... split at main_tiles of the 128 x 128 tile order: those at 128 x 128, the rest as 64 x 64 quarters (M % 128 == 0, N % 128 == 0)
+int launch_gemm_f32_ring_split(bool persist, int64_t main_tiles, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+                               int64_t ldc, const float* bias, const float* residual, int M, int N, int K, int act, hipStream_t s);
 
 // precision mode 1: operands rounded to bf16 on the way into LDS, fp32 accumulate (gemm_bf16.hip)
 int launch_gemm_bf16(Profiler* prof, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb,

@@ -418,8 +418,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 thread_local int tl_precision = 0;
 thread_local int tl_ring = -1;      // w2v2_op_gemm_variant: forces the ring route below for one call (-1: by shape)
 
-// The LDS-ring kernels (gemm_f32_sw.hip) for the shapes that took gemm_f32_dma_kernel's 256 x 128 x 16 and 128 x 128 x 32
-// instances: 0 = those instances, 1 = the ring kernels with one tile per block, 2 = the ring kernels with a persistent grid.
+// The LDS-ring kernels (gemm_f32_sw.hip) for the shapes that took gemm_f32_dma_kernel's 256 x 128 x 16, 128 x 128 x 32 and
+// 64 x 64 x 32 instances (the split-K slabs keep the last): 0 = those instances, 1 = the ring kernels with one tile per block, 2 = the ring kernels with a persistent grid.
 constexpr int RING_DEFAULT = 2;
 int ring_route() { return tl_ring >= 0 ? tl_ring : tune_int("W2V2_GEMM_RING", RING_DEFAULT); }
 
@@ -499,12 +499,22 @@ int launch_gemm_ex(Profiler* prof, const float* A, int64_t lda, int64_t strideA,
         // (A half-full last round is better left alone: large-robust at B = 16 has 768 = 512 + 256 tiles for N = 1024,
         // a third of the work would move to the slower 64x64 kernel, 82.3 vs 80.5 ms per forward.)
         // The rows of that partial round are computed with 64x64 tiles instead (4x the blocks, a quarter of the time each).
+        // Whole tile rows leave the small tiles a partial round of their own (N = 768 at B = 32: 22 tile rows = 528 tiles of 64x64 for
+        // 512 places at two 4-wave blocks per CU; sixteen CUs run three and set the time: 142 us where 512 tiles take 102), so the
+        // ring kernels split the tile order instead of the rows where they can (below).
         // Every output element still sums its K products in the same order, so results do not depend on the tiling
         // (a row's value is independent of its position in the batch: test_linearity_of_lm_head_at_full_size).
         const int tail_knob = tune_int("W2V2_GEMM_TAIL", 1);
         const int64_t tn = (N + 127) / 128, S = 512, r = tiles128 % S;
-        if (tail_knob && fast && cfg == 7 && nbatch == 1 && tiles128 > S && r != 0 && 4 * r <= S) {
+        if (tail_knob && fast && cfg == 7 && nbatch == 1 && tiles128 > S && r != 0 && tune_int("W2V2_GEMM_TAIL_DIV", 4) * r <= S) {
             const int64_t main_rows = ((tiles128 - r) / tn) * 128;
+            // No partial tile (M, N multiples of 128): the ring kernels split the tile order itself, its first tiles128 - r tiles at
+            // 128 x 128 (whole rounds) and the r others as 4 r <= 512 tiles of 64 x 64 (launch_gemm_f32_ring_split, gemm_f32_sw.hip).
+            // Other shapes, and the double buffer, split at a tile row:
+            const int ring_flat = by_shape && tune_int("W2V2_GEMM_TAIL_FLAT", 1) ? ring_route() : 0;
+            if (ring_flat && strideB == 0 && M % 128 == 0 && N % 128 == 0 && gemm_f32_ring_ok(1, A, lda, 0, B, ldb, 0, M, N, K) &&
+                gemm_f32_ring_ok(2, A, lda, 0, B, ldb, 0, M, N, K))
+                return launch_gemm_f32_ring_split(ring_flat == 2, tiles128 - r, A, lda, B, ldb, C, ldc, bias, residual, M, N, K, act, s);
             if (main_rows > 0 && main_rows < M) {
                 GemmArgs h = g;
                 h.M = (int)main_rows;
@@ -527,9 +537,18 @@ int launch_gemm_ex(Profiler* prof, const float* A, int64_t lda, int64_t strideA,
                 //  62.8-62.9 (profiles/r04_ab_gemm_tail_splitk.txt): a quarter-length K loop pays prologue + epilogue + the fold of 25 MB
                 //  of slabs, which is what the small tiles lose to their single accumulator per wave.  Not kept: it also gave up the
                 //  bit-for-bit independence of a row from its position in the batch.)
+                if (ring && strideB == 0 && gemm_f32_ring_ok(2, t.A, lda, strideA, B, ldb, strideB, t.M, N, K))
+                    return launch_gemm_f32_ring(2, ring == 2, t.A, lda, strideA, B, ldb, strideB, t.C, ldc, strideC, bias,
+                                                t.residual, t.M, N, K, 1, act, s);
                 return launch_dma<2, 2, 2, 32, 64, 64>(t, 1, s);
             }
         }
+    }
+    if (cfg == 16 && fast && by_shape) {      // the small problems, batched ones included (conv rows of a short input)
+        const int ring = ring_route();
+        if (ring && strideB == 0 && gemm_f32_ring_ok(2, A, lda, strideA, B, ldb, strideB, M, N, K))
+            return launch_gemm_f32_ring(2, ring == 2, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, bias, residual, M, N, K,
+                                        nbatch, act, s);
     }
     // Wide tiles for the well-filled shapes (round 4, profiles/r04_gemm_f32_tile_study.txt): 256 x 128 x 16, 8 waves of 64 x 64 (4 x 2), still
     // two blocks per CU (48 KiB of LDS each, 118 VGPRs) -- 25 % less LDS-DMA per flop and a third fewer fragment reads per MFMA than

@@ -1,4 +1,4 @@
-// fp32 GEMM with an NS-stage LDS ring and an optional persistent tile loop (the forward's wide and 128 x 128 shapes).
+// fp32 GEMM with an NS-stage LDS ring and an optional persistent tile loop (the forward's wide, 128 x 128 and 64 x 64 shapes).
 //
 // Same tiles, wave grid, swizzled LDS images and MFMA loop as gemm_f32_dma_kernel (gemm_f32.hip); what differs is the
 // pipeline around them:
@@ -30,6 +30,8 @@ struct GemmRingArgs {
     int M, N, K, act;
     int tiles_m, tiles_n, nbatch;
     int gm;          // grouped tile order (common.h::grouped_tile); 0 = linear order
+    int total;       // tiles of this launch: tiles_m x tiles_n x nbatch, or a prefix of that order (the split launch below)
+    int first;       // QUAD: first tile of the (2 BM) x (2 BN) grid's order that this launch takes, as four BM x BN tiles each
 };
 
 template <int WM, int WN, int BKT, int BM, int BN, int NS>
@@ -45,7 +47,9 @@ struct RingCfg {
 };
 
 // (waves_per_eu(4): two 8-wave blocks per CU need <= 128 VGPRs; the 256 x 128 instance otherwise takes 132 and one block per CU)
-template <int WM, int WN, int BKT, int BM, int BN, int NS>
+// QUAD: tiles_m x tiles_n is the grid of (2 BM) x (2 BN) tiles; this launch runs tiles first, first + 1, ... of ITS order, four
+// BM x BN quarters each (the rest of an order whose first `first` tiles ran at the large tile; M and N are multiples of the large tile).
+template <int WM, int WN, int BKT, int BM, int BN, int NS, bool QUAD = false>
 __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(4))) void gemm_f32_ring_kernel(GemmRingArgs g) {
     using R_ = RingCfg<WM, WN, BKT, BM, BN, NS>;
     constexpr int NW = R_::NW, PPA = R_::PPA, PPB = R_::PPB, P = R_::P, STAGE = R_::STAGE;
@@ -58,7 +62,7 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(4))
     const int wm = wave / WN, wn = wave % WN, li = lane & 31, lh = lane >> 5;
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)smem;
 
-    const int nwg = g.tiles_m * g.tiles_n, total = nwg * g.nbatch, G = gridDim.x;
+    const int nwg = g.tiles_m * g.tiles_n, total = g.total, G = gridDim.x;
     const int ntl = (total - (int)blockIdx.x + G - 1) / G;      // tiles of this block (the grid never exceeds the tile count)
     const int nk = g.K / BKT, nsteps = ntl * nk;
     // i-th tile of this block -> (batch, first row, first column).  XCD-aware order over the flat tile range: G is a multiple
@@ -67,12 +71,21 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(4))
         const int v = (int)blockIdx.x + i * G;
         const int q = total >> 3, r = total & 7, xcd = v & 7, idx = v >> 3;
         int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+        int sub = 0;
+        if constexpr (QUAD) {
+            sub = t & 3;
+            t = g.first + (t >> 2);
+        }
         z = t / nwg;
         t -= z * nwg;
         int tm = t / g.tiles_n, tn = t % g.tiles_n;
         if (g.gm > 0) grouped_tile(t, g.tiles_m, g.tiles_n, g.gm, tm, tn);
         m0 = tm * BM;
         n0 = tn * BN;
+        if constexpr (QUAD) {
+            m0 = 2 * m0 + (sub >> 1) * BM;
+            n0 = 2 * n0 + (sub & 1) * BN;
+        }
     };
 
     // ---- issue side: cursor (tile ii, K tile ikt, ring stage ist), wave-uniform bases, per-lane 32-bit byte offsets
@@ -206,31 +219,41 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(4))
     __builtin_amdgcn_s_setprio(0);
 }
 
-template <int WM, int WN, int BKT, int BM, int BN, int NS>
-int launch_ring(GemmRingArgs& g, bool persist, hipStream_t s) {
+// split launch (nbatch == 1, M and N multiples of the large tile): `first` tiles of the order, group height gm, run at the large tile
+// (!QUAD: limit = first), the other tiles as quarters (QUAD).  first < 0: the whole problem.
+template <int WM, int WN, int BKT, int BM, int BN, int NS, bool QUAD = false>
+int launch_ring(GemmRingArgs& g, bool persist, hipStream_t s, int64_t first = -1, int gm = 0) {
     using R_ = RingCfg<WM, WN, BKT, BM, BN, NS>;
     static_assert(2 * R_::LDS <= 160 * 1024, "two blocks per CU");
-    g.tiles_m = (g.M + BM - 1) / BM;
-    g.tiles_n = (g.N + BN - 1) / BN;
-    const int64_t total = (int64_t)g.tiles_m * g.tiles_n * g.nbatch;
+    constexpr int TM = QUAD ? 2 * BM : BM, TN = QUAD ? 2 * BN : BN;
+    g.tiles_m = (g.M + TM - 1) / TM;
+    g.tiles_n = (g.N + TN - 1) / TN;
+    int64_t total = (int64_t)g.tiles_m * g.tiles_n * g.nbatch;
+    W2V2_REQUIRE(first < 0 || (first > 0 && first < total && g.nbatch == 1 && g.M % TM == 0 && g.N % TN == 0), "gemm ring: bad split");
+    W2V2_REQUIRE(!QUAD || first > 0, "gemm ring: quarter tiles need a split");
+    g.first = QUAD ? (int)first : 0;
+    if (first > 0) total = QUAD ? 4 * (total - first) : first;
     W2V2_REQUIRE(total < (1ll << 31), "gemm ring: %lld tiles", (long long)total);
+    g.total = (int)total;
+    // blocks a CU holds: two of the 8-wave instances; the 4-wave 64 x 64 instance as many as its ring leaves LDS for (at most 4)
+    constexpr int PER_CU = WM * WN == 8 ? 2 : 160 * 1024 / R_::LDS > 4 ? 4 : 160 * 1024 / R_::LDS;
     int grid = (int)total;
     if (persist) {
         int dev = 0, cus = 0;
         W2V2_HIP_CHECK(hipGetDevice(&dev));
         W2V2_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        const int resident = (2 * cus) & ~7;            // two blocks per CU, a multiple of the 8 XCDs
+        const int resident = (PER_CU * cus) & ~7;       // a multiple of the 8 XCDs
         if (resident >= 8 && total > resident) grid = resident;
     }
     // (tiles an XCD has in flight, as counted for the gemm_f32_dma_kernel instance of the same tile: same tile order)
-    g.gm = g.nbatch == 1 ? tile_group_rows(g.tiles_m, g.tiles_n, (int64_t)BM * g.K * 4, BM == 256 ? 96 : 64) : 0;
+    g.gm = first > 0 ? gm : g.nbatch == 1 ? tile_group_rows(g.tiles_m, g.tiles_n, (int64_t)BM * g.K * 4, BM == 256 ? 96 : 32 * PER_CU) : 0;
     static std::atomic<bool> attr_set{false};
     if (!attr_set) {
-        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_ring_kernel<WM, WN, BKT, BM, BN, NS>),
+        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_ring_kernel<WM, WN, BKT, BM, BN, NS, QUAD>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, R_::LDS));
         attr_set = true;
     }
-    W2V2_LAUNCH((gemm_f32_ring_kernel<WM, WN, BKT, BM, BN, NS>), dim3(grid), dim3(WM * WN * 64), R_::LDS, s, g);
+    W2V2_LAUNCH((gemm_f32_ring_kernel<WM, WN, BKT, BM, BN, NS, QUAD>), dim3(grid), dim3(WM * WN * 64), R_::LDS, s, g);
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }
@@ -239,7 +262,7 @@ int launch_ring(GemmRingArgs& g, bool persist, hipStream_t s) {
 
 bool gemm_f32_ring_ok(int tile, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb, int64_t strideB,
                       int M, int N, int K) {
-    const int BM = tile == 0 ? 256 : 128, BKT = 16;
+    const int BM = tile == 0 ? 256 : tile == 1 ? 128 : 64, BKT = tile == 2 ? 32 : 16;
     const bool align = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 && lda % 4 == 0 &&
                        ldb % 4 == 0 && strideA % 4 == 0 && strideB % 4 == 0;
     // per-lane DMA offsets are 32-bit byte offsets from the tile's row / column base
@@ -250,14 +273,36 @@ bool gemm_f32_ring_ok(int tile, const float* A, int64_t lda, int64_t strideA, co
 int launch_gemm_f32_ring(int tile, bool persist, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb,
                          int64_t strideB, float* C, int64_t ldc, int64_t strideC, const float* bias, const float* residual, int M,
                          int N, int K, int nbatch, int act, hipStream_t s) {
-    W2V2_REQUIRE(tile == 0 || tile == 1, "gemm ring: tile %d", tile);
+    W2V2_REQUIRE(tile >= 0 && tile <= 2, "gemm ring: tile %d", tile);
     W2V2_REQUIRE(gemm_f32_ring_ok(tile, A, lda, strideA, B, ldb, strideB, M, N, K), "gemm ring: unsupported shape M=%d N=%d K=%d", M, N, K);
     GemmRingArgs g;
     g.A = A; g.B = B; g.C = C; g.bias = bias; g.residual = residual;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.strideA = strideA; g.strideB = strideB; g.strideC = strideC;
     g.M = M; g.N = N; g.K = K; g.act = act; g.nbatch = nbatch;
     if (tile == 0) return launch_ring<4, 2, 16, 256, 128, 3>(g, persist, s);      // 72 KiB: two blocks per CU
-    return launch_ring<2, 4, 16, 128, 128, 4>(g, persist, s);                     // 64 KiB
+    if (tile == 1) return launch_ring<2, 4, 16, 128, 128, 4>(g, persist, s);      // 64 KiB
+    // 64 x 64, four waves of 32 x 32 (the tail rows and the small problems).  48 KiB: three blocks per CU, so the 528 tail tiles of
+    // N = 768 at B = 32 are all resident at once, as with the double buffer; the 64-KiB 32 x 4 ring runs them in two rounds and loses
+    // (instances 16 x 4 / 5 / 6 and 32 x 4 measured and dropped: profiles/ring_tail_ab.md).
+    return launch_ring<2, 2, 32, 64, 64, 3>(g, persist, s);
+}
+
+// One GEMM as two launches that split the 128 x 128 tile order (XCD runs, grouped rows) at `main_tiles`: the first main_tiles tiles on
+// the 128 x 128 ring kernel, every later tile as four 64 x 64 quarters on the 64 x 64 one.  With main_tiles a multiple of the resident
+// 128 x 128 slots and at most a quarter of them left over, both launches fill the CUs evenly: two 8-wave blocks per CU in whole rounds,
+// then at most two 4-wave blocks per CU (whole tile ROWS for the second launch leave 528 tiles for 512 such places at N = 768, B = 32:
+// sixteen CUs run three blocks and everything waits for them).  Needs M % 128 == 0 and N % 128 == 0: no quarter lies outside C.
+int launch_gemm_f32_ring_split(bool persist, int64_t main_tiles, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+                               int64_t ldc, const float* bias, const float* residual, int M, int N, int K, int act, hipStream_t s) {
+    W2V2_REQUIRE(M % 128 == 0 && N % 128 == 0 && gemm_f32_ring_ok(1, A, lda, 0, B, ldb, 0, M, N, K) && gemm_f32_ring_ok(2, A, lda, 0, B, ldb, 0, M, N, K),
+                 "gemm ring split: unsupported shape M=%d N=%d K=%d", M, N, K);
+    GemmRingArgs g;
+    g.A = A; g.B = B; g.C = C; g.bias = bias; g.residual = residual;
+    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.strideA = 0; g.strideB = 0; g.strideC = 0;
+    g.M = M; g.N = N; g.K = K; g.act = act; g.nbatch = 1;
+    const int gm = tile_group_rows(M / 128, N / 128, (int64_t)128 * K * 4, 64);
+    if (int e = launch_ring<2, 4, 16, 128, 128, 4>(g, persist, s, main_tiles, gm)) return e;
+    return launch_ring<2, 2, 32, 64, 64, 3, true>(g, false, s, main_tiles, gm);
 }
 
 }  // namespace w2v2
