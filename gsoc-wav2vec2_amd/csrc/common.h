@@ -363,6 +363,8 @@ int launch_pos_conv_bf16(Profiler* prof, const float* x, const uint16_t* w16, co
 
 // kernel gradient of the positional conv as a batched transposed-A GEMM (precision mode 1, T % 64 == 0):
 //   dwg (groups, K, cg, og) = sum over samples and frames; pack32: (B, G, 64 ceil(T/64)+K-1, cg) fp32 scratch, slabs: B * K*cg*H fp32 scratch
+int pos_conv_dw_bf16_slabs(int B, int H, int K, int groups);      // the slab count S (1, 2 or 4) launch_pos_conv_dw_bf16 picks
+void pos_conv_dw_bf16_ws_floats(int B, int T, int H, int K, int groups, int64_t sizes[4], int* S_out);   // pack32, slabs, red_ws, dc_pad
 int launch_pos_conv_dw_bf16(Profiler* prof, const float* xz, const float* dc, float* dwg, float* pack32, float* slabs, float* red_ws,
                             int B, int T, int H, int K, int groups, hipStream_t s, float* dc_pad = nullptr /* (B, 64 ceil(T/64), H): T % 64 != 0 */);
 

@@ -617,6 +617,35 @@ int launch_pos_conv_bf16(Profiler* prof, const float* x, const uint16_t* w16, co
                               gx, s);
 }
 
+// The slab count S of launch_pos_conv_dw_bf16 (see there): 1, 2 or 4, a divisor of B, the one whose tiles x groups x S blocks waste the
+// least of whole rounds of the 512 block slots (the smallest on a tie).
+int pos_conv_dw_bf16_slabs(int B, int H, int K, int groups) {
+    const int cg = H / groups, M = K * cg;
+    const int64_t tiles = (int64_t)((M + 127) / 128) * groups;
+    int S = 1;
+    double best = 1e30;
+    for (int cand : {1, 2, 4}) {
+        if (B % cand) continue;
+        const int64_t blocks = tiles * cand;
+        const double waste = (double)((blocks + 511) / 512 * 512) / (double)blocks;
+        if (waste < best - 1e-9) { best = waste; S = cand; }
+    }
+    return S;
+}
+
+// Scratch of launch_pos_conv_dw_bf16 in floats: sizes[0] pack32, [1] slabs (S slabs; one per sample in the tools-only form without the
+// concatenated K), [2] red_ws (the colsum's), [3] dc_pad (0 when T % 64 == 0).  *S_out: the slab count the launcher will use.
+void pos_conv_dw_bf16_ws_floats(int B, int T, int H, int K, int groups, int64_t sizes[4], int* S_out) {
+    const int Tk = (T + 63) / 64 * 64, cg = H / groups;
+    const int S = tune_int("W2V2_POS_DW_KCAT", 1) != 0 ? pos_conv_dw_bf16_slabs(B, H, K, groups) : B;
+    const int64_t slab = (int64_t)groups * K * cg * cg;
+    sizes[0] = (int64_t)B * (Tk + K - 1) * H;
+    sizes[1] = (int64_t)S * slab;
+    sizes[2] = colsum_ws_floats(S, (int)slab);
+    sizes[3] = Tk != T ? (int64_t)B * Tk * H : 0;
+    if (S_out) *S_out = S;
+}
+
 // dwg[g][f = j cg + c][n] = sum_{b, t} xz[b][t + j - pad][g cg + c] dc[b][t][g og + n]: per (sample, group) a GEMM with the
 // packed input as a TRANSPOSED, overlapping-row A (element (f, t) at P[t cg + f]) and dc as B; one slab per sample, summed after.
 // T % 64 != 0: the contraction runs over Tk = 64 ceil(T / 64) frames, the extra ones contributing exact zeros: dc is copied into
@@ -654,15 +683,7 @@ int launch_pos_conv_dw_bf16(Profiler* prof, const float* xz, const float* dc, fl
     // base 48 tiles x 16 groups x S = 2 -> 1536 blocks, large 64 x 16 x 1 -> 1024.  The sum over a slab's samples is taken in the MFMA
     // accumulators in sample order (deterministic); S = 1 writes the gradient itself.
     if (tune_int("W2V2_POS_DW_KCAT", 1) != 0) {
-        const int64_t tiles = (int64_t)((M + 127) / 128) * groups;
-        int S = 1;
-        double best = 1e30;
-        for (int cand : {1, 2, 4}) {
-            if (B % cand) continue;
-            const int64_t blocks = tiles * cand;
-            const double waste = (double)((blocks + 511) / 512 * 512) / (double)blocks;
-            if (waste < best - 1e-9) { best = waste; S = cand; }
-        }
+        const int S = pos_conv_dw_bf16_slabs(B, H, K, groups);
         gx.kseg = Tk;
         gx.segA = (int64_t)S * groups * Tp * cg;
         gx.segB = (int64_t)S * Tk * H;

@@ -1569,6 +1569,44 @@ int w2v2_op_dropout(const float* x, const float* residual, float* y, int64_t n, 
                     uint64_t seed, uint32_t stream_id, void* stream) {
     return launch_dropout_fwd(x, residual, y, n, act, p, seed, stream_id, reinterpret_cast<hipStream_t>(stream));
 }
+int w2v2_op_pos_conv_ex(const float* x, const float* wg, const float* bias, const int32_t* frame_len, float* y, float* pre_act,
+                        int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, int32_t act, int32_t pad_left, int32_t add_residual,
+                        void* stream) {
+    return launch_pos_conv_ex(nullptr, x, wg, bias, frame_len, y, pre_act, B, T, H, K, groups, act, pad_left, add_residual,
+                              reinterpret_cast<hipStream_t>(stream));
+}
+int64_t w2v2_op_pos_conv_bf16_pack_elems(int32_t B, int32_t T, int32_t H, int32_t K) { return pos_conv_bf16_pack_elems(B, T, H, K); }
+int w2v2_op_pos_conv_weight_shadow(const float* wg, uint16_t* w16, int32_t K, int32_t cg, int32_t groups, void* stream) {
+    return launch_pos_conv_weight_shadow(wg, w16, K, cg, groups, reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_pos_conv_bf16(const float* x, const uint16_t* w16, const float* bias, const int32_t* frame_len, float* y, float* pre_act,
+                          uint16_t* pack16, float* xz_ws, int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, int32_t act,
+                          int32_t pad_left, int32_t add_residual, void* stream) {
+    return launch_pos_conv_bf16(nullptr, x, w16, bias, frame_len, y, pre_act, pack16, xz_ws, B, T, H, K, groups, act, pad_left, add_residual,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_pos_conv_flip_regroup(const float* wg, float* wg_t, int32_t K, int32_t cg, int32_t groups, void* stream) {
+    return launch_pos_conv_flip_regroup(wg, wg_t, K, cg, groups, reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_pos_conv_dw(const float* xz, const float* dc, float* dwg, int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups,
+                        void* stream) {
+    return launch_pos_conv_dw(nullptr, xz, dc, dwg, nullptr, B, T, H, K, groups, reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_pos_conv_dw_bf16_ws_floats(int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, int64_t* sizes4, int32_t* slabs_S) {
+    W2V2_REQUIRE(sizes4 && B > 0 && T > 0 && K > 0 && groups > 0 && H > 0 && H % groups == 0, "pos_conv_dw_bf16_ws_floats: bad argument");
+    int S = 0;
+    pos_conv_dw_bf16_ws_floats(B, T, H, K, groups, sizes4, &S);
+    if (slabs_S) *slabs_S = S;
+    return W2V2_OK;
+}
+int w2v2_op_pos_conv_dw_bf16(const float* xz, const float* dc, float* dwg, float* pack32, float* slabs, float* red_ws, float* dc_pad,
+                             int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, void* stream) {
+    return launch_pos_conv_dw_bf16(nullptr, xz, dc, dwg, pack32, slabs, red_ws, B, T, H, K, groups, reinterpret_cast<hipStream_t>(stream), dc_pad);
+}
+int w2v2_op_weight_norm_bwd(const float* weight_v, const float* weight_g, const float* dwg, float* dweight_v, float* dweight_g, int32_t K,
+                            int32_t cg, int32_t H, int32_t groups, void* stream) {
+    return launch_weight_norm_bwd(weight_v, weight_g, dwg, dweight_v, dweight_g, K, cg, H, groups, reinterpret_cast<hipStream_t>(stream));
+}
 
 }  // extern "C"
 

@@ -111,6 +111,15 @@ PROTOTYPES = {
     "w2v2_op_attention_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, C.c_float, C.c_uint64, C.c_uint32, _P]),
     "w2v2_op_dropout": (C.c_int, [_P, _P, _P, _I64, _I32, C.c_float, C.c_uint64, C.c_uint32, _P]),
     "w2v2_op_layer_norm_dropout": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, C.c_float, C.c_float, C.c_uint64, C.c_uint32, _P]),
+    "w2v2_op_pos_conv_ex": (C.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "w2v2_op_pos_conv_bf16_pack_elems": (_I64, [_I32, _I32, _I32, _I32]),
+    "w2v2_op_pos_conv_weight_shadow": (C.c_int, [_P, _P, _I32, _I32, _I32, _P]),
+    "w2v2_op_pos_conv_bf16": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "w2v2_op_pos_conv_flip_regroup": (C.c_int, [_P, _P, _I32, _I32, _I32, _P]),
+    "w2v2_op_pos_conv_dw": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    "w2v2_pos_conv_dw_bf16_ws_floats": (C.c_int, [_I32, _I32, _I32, _I32, _I32, C.POINTER(_I64), C.POINTER(_I32)]),
+    "w2v2_op_pos_conv_dw_bf16": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    "w2v2_op_weight_norm_bwd": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "w2v2_activation_info": (C.c_int, [_P, C.c_char_p, C.POINTER(_I64)]),
     "w2v2_copy_activation": (C.c_int, [_P, C.c_char_p, _P, _I64, _P]),
     "w2v2_profile_enable": (C.c_int, [_P, C.c_int]),

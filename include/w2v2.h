@@ -684,6 +684,46 @@ int w2v2_op_layer_norm_dropout(const float* x_dev, const float* residual_dev, fl
                                const float* gamma_dev, const float* beta_dev, int64_t rows, int32_t C, float eps, float p, uint64_t seed,
                                uint32_t stream_id, void* stream);
 
+/* ---- the positional convolution's training launch paths, one entry each (PositionalConvEmbedding, encoder.py:153-181) ----
+ * Layouts: x, y, pre_act, xz, dc (B, T, H); wg, wg_t, dwg (groups, K, cg, cg) with cg = H / groups, as w2v2_op_weight_norm_regroup
+ * writes it; frame_len (B) or NULL.  cg is 16, 32, 48 or 64 on the fp32 entries; the bf16 entries need (K cg) % 64 == 0. */
+
+/* y = [xz +] act(conv(xz, wg, pad_left) + bias), xz = x with frames >= frame_len[b] zeroed; output frame t reads input frames
+ * t - pad_left .. t - pad_left + K - 1.  bias_dev may be NULL; pre_act_dev (optional) receives conv + bias.  pad_left = K / 2 is the
+ * forward; the data gradient is the same conv of dc with the flipped kernel at pad_left = K - 1 - K / 2, no bias, no residual. */
+int w2v2_op_pos_conv_ex(const float* x_dev, const float* wg_dev, const float* bias_dev, const int32_t* frame_len_dev, float* y_dev,
+                        float* pre_act_dev, int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, int32_t act, int32_t pad_left,
+                        int32_t add_residual, void* stream);
+
+/* The same contract on the bf16 matrix pipe (precision mode 1: x and the kernel rounded to bf16, fp32 accumulation), as one batched
+ * GEMM over overlapping rows.  w16: (groups, cg, K cg) bf16 from w2v2_op_pos_conv_weight_shadow; pack16_dev: scratch of
+ * w2v2_op_pos_conv_bf16_pack_elems(B, T, H, K) bf16 elements; xz_ws_dev: (B, T, H) floats, needed when frame_len and add_residual. */
+int64_t w2v2_op_pos_conv_bf16_pack_elems(int32_t B, int32_t T, int32_t H, int32_t K);
+int w2v2_op_pos_conv_weight_shadow(const float* wg_dev, uint16_t* w16_dev, int32_t K, int32_t cg, int32_t groups, void* stream);
+int w2v2_op_pos_conv_bf16(const float* x_dev, const uint16_t* w16_dev, const float* bias_dev, const int32_t* frame_len_dev, float* y_dev,
+                          float* pre_act_dev, uint16_t* pack16_dev, float* xz_ws_dev, int32_t B, int32_t T, int32_t H, int32_t K,
+                          int32_t groups, int32_t act, int32_t pad_left, int32_t add_residual, void* stream);
+
+/* wg_t[g][K-1-k][co][ci] = wg[g][k][ci][co]: the kernel of the data-gradient pass. */
+int w2v2_op_pos_conv_flip_regroup(const float* wg_dev, float* wg_t_dev, int32_t K, int32_t cg, int32_t groups, void* stream);
+
+/* Kernel gradient dwg[g][k][ci][co] = sum over b, t of xz[b][t + k - K/2][g cg + ci] dc[b][t][g cg + co] (xz already masked), fp32. */
+int w2v2_op_pos_conv_dw(const float* xz_dev, const float* dc_dev, float* dwg_dev, int32_t B, int32_t T, int32_t H, int32_t K,
+                        int32_t groups, void* stream);
+
+/* The same gradient on the bf16 pipe (xz and dc rounded to bf16): samples concatenated along the contraction in S = 1, 2 or 4
+ * slabs that are summed afterwards, B <= 64.  The query fills sizes4 with the floats of pack32, slabs, red_ws and dc_pad (0: T is a
+ * multiple of 64 and dc_pad may be NULL) and *slabs_S with the S the launcher will pick. */
+int w2v2_pos_conv_dw_bf16_ws_floats(int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, int64_t* sizes4, int32_t* slabs_S);
+int w2v2_op_pos_conv_dw_bf16(const float* xz_dev, const float* dc_dev, float* dwg_dev, float* pack32_dev, float* slabs_dev,
+                             float* red_ws_dev, float* dc_pad_dev, int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups,
+                             void* stream);
+
+/* Weight-norm backward, W_eff[k] = g[k] v[k] / n[k], n^2 = max(sum v[k]^2, 1e-12): dweight_g = <dW, v> / n,
+ * dweight_v = (g / n)(dW - <dW, v> v / n^2).  weight_v, dweight_v (K, cg, H); weight_g, dweight_g (K); dwg as above. */
+int w2v2_op_weight_norm_bwd(const float* weight_v_dev, const float* weight_g_dev, const float* dwg_dev, float* dweight_v_dev,
+                            float* dweight_g_dev, int32_t K, int32_t cg, int32_t H, int32_t groups, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
