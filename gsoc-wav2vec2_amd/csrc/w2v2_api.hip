@@ -550,6 +550,18 @@ int w2v2_ctc_pause_cuts(const float* logits, int32_t V, int32_t n, const int64_t
                                  reinterpret_cast<hipStream_t>(stream));
 }
 
+int w2v2_resample_design(int32_t rate_in, int32_t rate_out, int32_t zeros, double rolloff, double beta, int32_t* L, int32_t* M,
+                         int32_t* K, int32_t* lead, float* table, int64_t table_capacity) {
+    return resample_design(rate_in, rate_out, zeros, rolloff, beta, L, M, K, lead, table, table_capacity);
+}
+
+int64_t w2v2_resample_length(int64_t len, int32_t L, int32_t M) { return resample_length(len, L, M); }
+
+int w2v2_resample(const float* in, int32_t n, const int64_t* in0, const int64_t* in_len, const int32_t* filter_of,
+                  const w2v2_resample_filter* filters, int32_t n_filters, float* out, const int64_t* out0, void* stream) {
+    return launch_resample(in, n, in0, in_len, filter_of, filters, n_filters, out, out0, reinterpret_cast<hipStream_t>(stream));
+}
+
 int w2v2_activation_info(const w2v2_model* m, const char* name, int64_t shape[3]) {
     W2V2_REQUIRE(m && name && shape, "activation_info: null argument");
     auto it = m->acts.find(name);

@@ -19,6 +19,9 @@ BEAM_MAX_WIDTH = 64              # W2V2_BEAM_MAX_WIDTH, W2V2_BEAM_MAX_VOCAB: lim
 BEAM_MAX_VOCAB = 64
 CUTS_CHUNK = 1024                # W2V2_CUTS_CHUNK: frames per block of w2v2_ctc_pause_cuts
 CUTS_MAX_FRAMES = 1 << 24        # W2V2_CUTS_MAX_FRAMES
+RESAMPLE_TILE = 2048             # W2V2_RESAMPLE_TILE: outputs per block of w2v2_resample
+RESAMPLE_MAX_L = 4096            # W2V2_RESAMPLE_MAX_L, W2V2_RESAMPLE_MAX_TABLE: limits of a filter of w2v2_resample
+RESAMPLE_MAX_TABLE = 1 << 22
 WORDLM_MAX_ORDER = 5             # W2V2_WORDLM_MAX_ORDER: order of the word n-gram model of w2v2_ctc_beam_search_words
 
 
@@ -52,6 +55,11 @@ class W2V2WordLM(C.Structure):
                [(k, C.c_int32) for k in ("n_nodes", "n_states", "n_arcs", "n_words", "order", "start_state", "unk", "eos")]
 
 
+class W2V2ResampleFilter(C.Structure):
+    """struct w2v2_resample_filter (include/w2v2.h): the (L, K) fp32 table on the device and the filter's integers."""
+    _fields_ = [("table", C.c_void_p), ("L", C.c_int32), ("M", C.c_int32), ("K", C.c_int32), ("lead", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/w2v2.h
 _P = C.c_void_p
 _I32 = C.c_int32
@@ -80,6 +88,10 @@ PROTOTYPES = {
     "w2v2_ctc_beam_search_words": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, C.POINTER(W2V2WordLM), _I32, C.c_float, C.c_float,
                                              C.c_float, _I32, _I32, _P, _P, _P, _P, _P]),
     "w2v2_ctc_pause_cuts": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, C.c_float, _I32, _I32, _P, _P, _P, _P]),
+    "w2v2_resample_design": (C.c_int, [_I32, _I32, _I32, C.c_double, C.c_double, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32),
+                                       C.POINTER(_I32), _P, _I64]),
+    "w2v2_resample_length": (_I64, [_I64, _I32, _I32]),
+    "w2v2_resample": (C.c_int, [_P, _I32, _P, _P, _P, C.POINTER(W2V2ResampleFilter), _I32, _P, _P, _P]),
     "w2v2_set_trainable": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "w2v2_set_trainable_flags": (C.c_int, [_P, _P, _I32]),
     "w2v2_set_option": (C.c_int, [_P, _I32, _I32]),

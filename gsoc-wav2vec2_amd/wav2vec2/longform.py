@@ -101,8 +101,9 @@ def group_windows(windows, max_stream_samples, config):
     return groups
 
 
-def predict_long(model, waveform, window_s=20.0, margin_s=2.0, normalize=True, max_stream_s=1200.0, window=None, margin=None):
-    """See ``TFKerasModel.predict_long``.  ``window`` / ``margin`` (samples) override the seconds."""
+def predict_long(model, waveform, window_s=20.0, margin_s=2.0, normalize=True, max_stream_s=1200.0, window=None, margin=None,
+                 sampling_rate=None):
+    """See ``TFKerasModel.predict_long``.  ``window`` / ``margin`` (samples of the 16 kHz audio) override the seconds."""
     import torch
     from .modeling import DeviceTensor, _require_gpu
     _require_gpu()
@@ -110,6 +111,9 @@ def predict_long(model, waveform, window_s=20.0, margin_s=2.0, normalize=True, m
     recordings = [waveform] if single else list(waveform)
     if not recordings:
         raise ValueError("`waveform` must be a 1-D waveform or a non-empty list of them")
+    if sampling_rate is not None and sampling_rate != 16000:
+        from .audio import resample
+        recordings = resample(recordings, sampling_rate)
     cfg = model.config
     w_s, m_s = seconds_to_samples(window_s, margin_s, cfg)
     window = w_s if window is None else int(window)

@@ -539,16 +539,23 @@ class TFKerasModel(Layer):
     def predict(self, batch, attention_mask=None):
         return self(batch, attention_mask=attention_mask, training=False)
 
-    def predict_packed(self, waveforms):
+    def predict_packed(self, waveforms, sampling_rate=None, normalize=False):
         """Inference on utterances of different lengths in one call, each computed exactly as `self(wave[None])` computes it
         alone: no padding enters any statistic and no frame attends across utterances (w2v2_forward_packed).  Precision modes
         "fp32", "bf16x3" and "f16x2" (set_precision); "bf16" raises.  In "f16x2" the contract of set_precision holds: poll
         `range_overflow()` after the calls whose activations are not known to stay in range.
         `waveforms`: a list of 1-D numpy arrays or torch tensors, each already normalised.  Returns a list of
-        (T_i, vocab | hidden) tensors, T_i = num_frames(len_i): views of one packed output."""
+        (T_i, vocab | hidden) tensors, T_i = num_frames(len_i): views of one packed output.
+        `sampling_rate`: the waveforms' samples per second; None or 16000 is the model's own rate, any other positive integer
+        resamples all of them first in one call (wav2vec2.audio.resample), and T_i counts frames of the resampled utterance.
+        `normalize=True` normalises each utterance over its own (resampled) samples on the device, as
+        `Wav2Vec2Processor._normalize` would: pass raw audio."""
         torch = _require_gpu()
         if isinstance(waveforms, (np.ndarray, torch.Tensor)) or not len(waveforms):
             raise ValueError("`waveforms` must be a non-empty list of 1-D waveforms")
+        if sampling_rate is not None and sampling_rate != 16000:
+            from .audio import resample
+            waveforms = resample(list(waveforms), sampling_rate)
         dev = torch.device("cuda", torch.cuda.current_device())
         parts, frames = [], []
         for i, w in enumerate(waveforms):
@@ -565,6 +572,9 @@ class TFKerasModel(Layer):
         wave = torch.cat(parts).contiguous()
         cu = np.zeros(len(parts) + 1, dtype=np.int64)
         cu[1:] = np.cumsum([p.shape[0] for p in parts])
+        if normalize:
+            from .longform import normalize_windows
+            wave = normalize_windows(wave, cu[:-1], np.diff(cu))
         width = self.config.vocab_size if self._with_lm_head else self.config.hidden_size
         out = torch.empty((sum(frames), width), device=dev, dtype=torch.float32)
         N.check(self._lib.w2v2_forward_packed(self._handle, N.ptr(wave), len(parts), N.ptr(cu), N.ptr(out),
@@ -572,7 +582,7 @@ class TFKerasModel(Layer):
         out = DeviceTensor.wrap(out)
         return list(torch.split(out, frames, dim=0))
 
-    def predict_long(self, waveform, window_s=20.0, margin_s=2.0, normalize=True, max_stream_s=1200.0):
+    def predict_long(self, waveform, window_s=20.0, margin_s=2.0, normalize=True, max_stream_s=1200.0, sampling_rate=None):
         """Inference on recordings of any length (minutes, hours): overlapping windows of `window_s` seconds, each computed
         exactly as `self(window[None])` computes it alone (identical bits in fp32), and every frame of the recording taken from the window that holds at least `margin_s` seconds of context on each side of it
         (wav2vec2.longform.window_plan; w2v2_forward_windows).  The
@@ -582,9 +592,10 @@ class TFKerasModel(Layer):
         stream stays under `max_stream_s` seconds of audio (the workspace grows with the stream); the grouping changes no bit
         of the result.  Returns one (num_frames(len), vocab | hidden) tensor per recording -- for a list, views of one
         buffer, as `predict_packed` returns.  A recording no longer than the window is bit-equal to `self(wave[None])` (of
-        the normalised wave).  Precision modes as `predict_packed`."""
+        the normalised wave).  Precision modes as `predict_packed`.  `sampling_rate`: as `predict_packed`; the recordings are
+        resampled to 16 kHz first, in one call, and the windows are then cut and normalised as above."""
         from .longform import predict_long
-        return predict_long(self, waveform, window_s, margin_s, normalize, max_stream_s)
+        return predict_long(self, waveform, window_s, margin_s, normalize, max_stream_s, sampling_rate=sampling_rate)
 
     # ---- introspection used by the parity tests / bench -----------------------
     def activation(self, name):
@@ -681,12 +692,14 @@ class Wav2Vec2ForCTC(TFKerasModel):
 
     call = __call__
 
-    def align(self, waveforms, transcripts, tokenizer=None, delimiter_id=None):
+    def align(self, waveforms, transcripts, tokenizer=None, delimiter_id=None, sampling_rate=None, normalize=False):
         """Word timestamps: `predict_packed(waveforms)`, then the CTC forced alignment of each transcript on the packed logits
         in place (wav2vec2.alignment: forced_align, token_spans, word_spans; blank = config.pad_id).  A transcript is text,
         encoded with `tokenizer` (a Wav2Vec2Processor(is_tokenizer=True)), or a sequence of ids, used as it is.  Frame f lies at
         f * prod(strides) / 16000 s.  The word delimiter is the tokenizer's "|" unless `delimiter_id` is given.  Returns one list
-        of WordSpan(text, start_s, end_s, score) per utterance.  Runs in the precision modes predict_packed accepts."""
+        of WordSpan(text, start_s, end_s, score) per utterance.  Runs in the precision modes predict_packed accepts.
+        `sampling_rate`, `normalize`: as `predict_packed`.  A frame is prod(strides) samples of the 16 kHz audio whatever the
+        rate of the input, so the times stay seconds of the recording."""
         from .alignment import forced_align, token_spans, word_spans
         from .processor import WORD_DELIMITER
         if isinstance(transcripts, str) or len(transcripts) != len(waveforms):
@@ -708,10 +721,10 @@ class Wav2Vec2ForCTC(TFKerasModel):
         if delimiter_id is None:
             raise ValueError("ids without a tokenizer: pass delimiter_id")
         seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
-        alignments = forced_align(self.predict_packed(waveforms), ids, blank=self.config.pad_id)
+        alignments = forced_align(self.predict_packed(waveforms, sampling_rate, normalize), ids, blank=self.config.pad_id)
         return [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab) for a in alignments]
 
-    def transcribe(self, waveforms, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False):
+    def transcribe(self, waveforms, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False, sampling_rate=None, normalize=False):
         """Text: `predict_packed(waveforms)`, then the CTC prefix beam search on the packed logits in place
         (wav2vec2.decoding.beam_search; blank = config.pad_id), ids -> text with `tokenizer` (a Wav2Vec2Processor(is_tokenizer=True);
         "|" -> space, as its `decode`).  `lm`: a wav2vec2.decoding.CharNgramLM, a wav2vec2.decoding.WordNgramLM (a word n-gram model
@@ -719,12 +732,13 @@ class Wav2Vec2ForCTC(TFKerasModel):
         `beam_width=None` is the greedy path for comparison: the argmax of every frame on the device, then `tokenizer.decode`.  With `timestamps=True` the best hypothesis
         of each utterance goes through the forced alignment (wav2vec2.alignment) and the result carries its WordSpans (none for
         an empty transcript).  Returns one wav2vec2.decoding.Transcript(text, hypotheses, texts, words) per utterance; see
-        `beam_search` for what a hypothesis' score means.  Runs in the precision modes predict_packed accepts."""
+        `beam_search` for what a hypothesis' score means.  Runs in the precision modes predict_packed accepts.
+        `sampling_rate`, `normalize`: as `predict_packed`; times stay seconds of the recording."""
         from .alignment import forced_align, token_spans, word_spans
         from .decoding import Hypothesis, Transcript, beam_search
         from .processor import WORD_DELIMITER
         blank = self.config.pad_id
-        logits = self.predict_packed(waveforms)
+        logits = self.predict_packed(waveforms, sampling_rate, normalize)
         if beam_width is None:
             if lm is not None:
                 raise ValueError("the greedy path takes no language model")
@@ -753,15 +767,16 @@ class Wav2Vec2ForCTC(TFKerasModel):
         return out
 
     def transcribe_long(self, waveform, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False, window_s=20.0, margin_s=2.0,
-                        normalize=True, max_stream_s=1200.0, **cut_options):
+                        normalize=True, max_stream_s=1200.0, sampling_rate=None, **cut_options):
         """Text of recordings of any length: `predict_long(waveform, ...)`, then `wav2vec2.longform.decode_long` on the stitched
         logits with blank = config.pad_id, the tokenizer's word delimiter and the frame period of the conv strides: the logits
         are cut at pauses between words, all segments go through one beam search (and one forced alignment with
         `timestamps=True`), and the pieces are concatenated.  `cut_options`: decode_long's pause_margin, min_pause, min_frames,
         max_frames.  A language model sees each segment as an utterance (a WordNgramLM restarts at every segment).  Returns one
-        wav2vec2.longform.LongTranscript(text, ids, score, total, words, segments) per recording."""
+        wav2vec2.longform.LongTranscript(text, ids, score, total, words, segments) per recording.  `sampling_rate`: as
+        `predict_long`; the times stay seconds of the recording."""
         from .longform import decode_long
-        logits = self.predict_long(waveform, window_s, margin_s, normalize, max_stream_s)
+        logits = self.predict_long(waveform, window_s, margin_s, normalize, max_stream_s, sampling_rate)
         seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
         return decode_long(logits, tokenizer, beam_width=beam_width, nbest=nbest, lm=lm, blank=self.config.pad_id, timestamps=timestamps,
                            seconds_per_frame=seconds_per_frame, **cut_options)

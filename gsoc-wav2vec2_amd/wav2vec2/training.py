@@ -53,7 +53,10 @@ class Trainer:
     Randomness is per data-parallel rank, as under MirroredStrategy where every replica draws its own dropout and
     spec-augment masks: the effective seed is `seed * world_size + rank` (kept in `state_dict`, so resume stays exact).
 
-    `allreduce_dtype`: "fp32" (default) or "bf16" -- the gradient payload of the data-parallel all-reduce."""
+    `allreduce_dtype`: "fp32" (default) or "bf16" -- the gradient payload of the data-parallel all-reduce.
+
+    Speed perturbation (utterances played 0.9x / 1.1x) is not part of the step: apply `wav2vec2.audio.speed_perturb` to the
+    raw utterances before `batchify`."""
 
     def __init__(self, model, loss, learning_rate=1e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-7, seed=0,
                  dropout=None, apply_spec_augment=None, overlap_all_reduce=True, reset_optimizer=True, allreduce_dtype="fp32",

@@ -343,6 +343,43 @@ int w2v2_ctc_pause_cuts(const float* logits_dev, int32_t V, int32_t n, const int
                         int32_t blank, int32_t delim, float margin, int32_t min_pause, int32_t max_cuts, int32_t* cut_dev,
                         int32_t* pause_dev, int32_t* count_dev, void* stream);
 
+/* Resampling (the same definition in fp64 numpy: tests/resample_reference.py): a polyphase Kaiser-windowed-sinc
+ * filter with a rational ratio.  Model-free: many segments per call, addressed by host tables, each computed as if it were alone.
+ *
+ * Design (host only, no device needed).  g = gcd(rate_in, rate_out), M = rate_in / g, L = rate_out / g; fc = min(L, M) rolloff / M,
+ * width = ceil(zeros / fc), K = 2 width, lead = width - 1.  For phase r in [0, L) and tap t in [0, K): u = (t - lead) - r / L,
+ * s = u fc, table[r][t] = fc sinc(s) I0(beta sqrt(1 - (s / zeros)^2)) / I0(beta) where |s| < zeros and 0 elsewhere, formed in fp64
+ * and rounded once to fp32.  L == M: K = 1, lead = 0, table = [[1.0]].  The sizes are always written; the (L, K) row-major table
+ * when table != NULL, and then table_capacity (in floats) below L K is W2V2_EINVAL.  W2V2_EINVAL also for a rate or zeros < 1,
+ * rolloff outside (0, 1], beta negative or not finite, or a K beyond 2^31.
+ *
+ * Application.  Segment i is in_dev[in0_host[i] .. + in_len_host[i]), zero outside, with filter f = filter_of_host[i] (NULL: filter
+ * 0 for all); it writes out_dev[out0_host[i] .. + w2v2_resample_length(in_len_host[i], L_f, M_f)).  For output n, with 64-bit
+ * integers q = floor(n M / L), r = (n M) mod L:
+ *     out[n] = sum_{t < K} table[r][t] x[q - lead + t]
+ * as ONE fp32 chain in ascending t over all K taps, zero pads included: the product of tap 0, then one fmaf per tap.  The bits of
+ * out[n] therefore depend on the segment's own samples, the table and n alone -- not on the other segments, on where the segment
+ * lies in the buffers, or on the tiling -- and the copy filter returns the input's bits.  table_dev is (L, K) fp32, row-major, and
+ * is not interpreted.  A block computes W2V2_RESAMPLE_TILE consecutive outputs of one segment (fewer where their input span would
+ * not fit the LDS).
+ * W2V2_EINVAL with a message: a null pointer, n < 1, n_filters < 1, in_len outside [1, 2^31), a negative in0 / out0, filter_of out of
+ * range, a filter with L < 1, M < 1, K < 1, lead outside [0, K), L > W2V2_RESAMPLE_MAX_L or L K > W2V2_RESAMPLE_MAX_TABLE, more
+ * than 2^31 - 1 tiles in all.  Output ranges that overlap each other or the input are the caller's error and are not detected.
+ * Launches are attributed to the `misc` profiling family.  Synchronises with the previous call's table upload (host-side),
+ * otherwise enqueued on `stream`. */
+#define W2V2_RESAMPLE_TILE 2048
+#define W2V2_RESAMPLE_MAX_L 4096
+#define W2V2_RESAMPLE_MAX_TABLE (1 << 22)
+int w2v2_resample_design(int32_t rate_in, int32_t rate_out, int32_t zeros, double rolloff, double beta, int32_t* L, int32_t* M,
+                         int32_t* K, int32_t* lead, float* table, int64_t table_capacity);
+int64_t w2v2_resample_length(int64_t len, int32_t L, int32_t M);      /* ceil(len L / M); -1 for len < 0, L < 1 or M < 1 */
+typedef struct w2v2_resample_filter {
+    const float* table_dev;
+    int32_t L, M, K, lead;
+} w2v2_resample_filter;
+int w2v2_resample(const float* in_dev, int32_t n, const int64_t* in0_host, const int64_t* in_len_host, const int32_t* filter_of_host,
+                  const w2v2_resample_filter* filters, int32_t n_filters, float* out_dev, const int64_t* out0_host, void* stream);
+
 /* ---- the training step (reference src/main.py:136-259) --------
  * Replaces what Keras' train_step does around the forward: training-mode forward, backward of every
  * trainable variable, Adam.  Postnorm (base) and prenorm (robust / xlsr) transformers; the conv feature
