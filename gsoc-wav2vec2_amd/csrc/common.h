@@ -393,7 +393,7 @@ int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int widt
 
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
 enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4, SCRATCH_BEAM = 5, SCRATCH_WINDOWS = 6,
-                   SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8 };
+                   SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8, SCRATCH_EDIT = 9 };
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out);
 int stream_scratch_release();       // frees the calling device's scratch buffers
 // pinned staging of a small host table on its way to the device (shadow.hip): grow-only, and the previous upload out of it has
@@ -458,6 +458,10 @@ int launch_resample(const float* in, int n, const int64_t* in0, const int64_t* i
 int resample_design(int rate_in, int rate_out, int zeros, double rolloff, double beta, int32_t* L, int32_t* M, int32_t* K, int32_t* lead,
                     float* table, int64_t table_capacity);
 int64_t resample_length(int64_t len, int L, int M);
+// edit distance and its breakdown (edit.hip; w2v2_edit_distance): pair p = tokens[hyp0_p, + hyp_len_p) against tokens[ref0_p, + ref_len_p);
+// out (n_pairs, 4) = distance, substitutions, deletions, insertions
+int launch_edit_distance(const int32_t* tokens, int64_t n_tokens, int n_pairs, const int64_t* hyp0, const int32_t* hyp_len,
+                         const int64_t* ref0, const int32_t* ref_len, int32_t* out, hipStream_t s);
 // the same search with a word n-gram model and a lexicon in place of the table (w2v2_ctc_beam_search_words)
 int launch_ctc_beam_search_words(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank,
                                  int beam_width, int nbest, const w2v2_word_lm* lm, int delim, float lm_alpha, float lm_beta,

@@ -550,6 +550,11 @@ int w2v2_ctc_pause_cuts(const float* logits, int32_t V, int32_t n, const int64_t
                                  reinterpret_cast<hipStream_t>(stream));
 }
 
+int w2v2_edit_distance(const int32_t* tokens, int64_t n_tokens, int32_t n_pairs, const int64_t* hyp0, const int32_t* hyp_len,
+                       const int64_t* ref0, const int32_t* ref_len, int32_t* out, void* stream) {
+    return launch_edit_distance(tokens, n_tokens, n_pairs, hyp0, hyp_len, ref0, ref_len, out, reinterpret_cast<hipStream_t>(stream));
+}
+
 int w2v2_resample_design(int32_t rate_in, int32_t rate_out, int32_t zeros, double rolloff, double beta, int32_t* L, int32_t* M,
                          int32_t* K, int32_t* lead, float* table, int64_t table_capacity) {
     return resample_design(rate_in, rate_out, zeros, rolloff, beta, L, M, K, lead, table, table_capacity);

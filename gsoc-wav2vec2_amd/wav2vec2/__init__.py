@@ -1,16 +1,19 @@
 """MI355X-native drop-in for the reference's ``wav2vec2`` package surface
 (src/wav2vec2/__init__.py:1-4): the same six names, and the long-recording layer on top
 (wav2vec2.longform: window_plan, decode_long, LongTranscript) and the sampling rates (wav2vec2.audio: Resampler, resample,
-resampled_length, speed_perturb)."""
+resampled_length, speed_perturb) and the error rates (wav2vec2.metrics: wer, cer, oracle_wer, mbr_select, edit_distance)."""
 
 from .audio import Resampler, resample, resampled_length, speed_perturb
 from .config import RobustWav2Vec2Config, Wav2Vec2Config
 from .longform import LongTranscript, decode_long, window_plan
 from .losses import CTCLoss
+from .metrics import (EditCounts, ErrorRate, Evaluation, cer, edit_distance, edit_distance_pairs, mbr_select, oracle_wer,
+                      wer)
 from .modeling import Wav2Vec2ForCTC, Wav2Vec2Model
 from .processor import Wav2Vec2Processor
 from .training import Trainer
 
 __all__ = ["Wav2Vec2Config", "RobustWav2Vec2Config", "CTCLoss", "Wav2Vec2ForCTC", "Wav2Vec2Model",
            "Wav2Vec2Processor", "Trainer", "window_plan", "decode_long", "LongTranscript", "Resampler", "resample",
-           "resampled_length", "speed_perturb"]
+           "resampled_length", "speed_perturb", "EditCounts", "ErrorRate", "Evaluation", "wer", "cer", "oracle_wer", "mbr_select",
+           "edit_distance", "edit_distance_pairs"]

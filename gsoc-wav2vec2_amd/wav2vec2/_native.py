@@ -22,6 +22,7 @@ CUTS_MAX_FRAMES = 1 << 24        # W2V2_CUTS_MAX_FRAMES
 RESAMPLE_TILE = 2048             # W2V2_RESAMPLE_TILE: outputs per block of w2v2_resample
 RESAMPLE_MAX_L = 4096            # W2V2_RESAMPLE_MAX_L, W2V2_RESAMPLE_MAX_TABLE: limits of a filter of w2v2_resample
 RESAMPLE_MAX_TABLE = 1 << 22
+EDIT_MAX_LEN = 65535             # W2V2_EDIT_MAX_LEN: tokens per sequence of w2v2_edit_distance
 WORDLM_MAX_ORDER = 5             # W2V2_WORDLM_MAX_ORDER: order of the word n-gram model of w2v2_ctc_beam_search_words
 
 
@@ -88,6 +89,7 @@ PROTOTYPES = {
     "w2v2_ctc_beam_search_words": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, C.POINTER(W2V2WordLM), _I32, C.c_float, C.c_float,
                                              C.c_float, _I32, _I32, _P, _P, _P, _P, _P]),
     "w2v2_ctc_pause_cuts": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, C.c_float, _I32, _I32, _P, _P, _P, _P]),
+    "w2v2_edit_distance": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     "w2v2_resample_design": (C.c_int, [_I32, _I32, _I32, C.c_double, C.c_double, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32),
                                        C.POINTER(_I32), _P, _I64]),
     "w2v2_resample_length": (_I64, [_I64, _I32, _I32]),

@@ -766,6 +766,36 @@ class Wav2Vec2ForCTC(TFKerasModel):
             out.append(Transcript(texts[0] if texts else "", h, texts, w))
         return out
 
+    def evaluate(self, waveforms, references, tokenizer, beam_width=16, nbest=1, lm=None, sampling_rate=None, normalize=False):
+        """Error rates: `transcribe(waveforms, tokenizer, ...)`, then the word and character error rates of the best hypotheses
+        against `references` (one text per waveform) and, with `nbest > 1`, the oracle word error rate of the n-best lists
+        (wav2vec2.metrics: wer, cer, oracle_wer; the edit distances run on the device).  The texts are compared as they are: no
+        case or punctuation normalisation.  Returns wav2vec2.metrics.Evaluation(wer, cer, oracle_wer, transcripts), the first
+        three ErrorRate (oracle_wer None when nbest == 1), `transcripts` what `transcribe` returned."""
+        from .metrics import evaluate_transcripts
+        if isinstance(references, str) or len(references) != len(waveforms):
+            raise ValueError("one reference per waveform")
+        transcripts = self.transcribe(waveforms, tokenizer, beam_width=beam_width, nbest=nbest, lm=lm, sampling_rate=sampling_rate,
+                                      normalize=normalize)
+        return evaluate_transcripts(transcripts, references, nbest)
+
+    def evaluate_long(self, waveform, references, tokenizer, beam_width=16, nbest=1, lm=None, window_s=20.0, margin_s=2.0,
+                      normalize=True, max_stream_s=1200.0, sampling_rate=None, **cut_options):
+        """`evaluate` over `transcribe_long`: the word and character error rates of each recording's concatenated text against
+        its reference.  `waveform` is one recording or a list of them, `references` one text or a list to match.  A recording's
+        n-best lists belong to its segments, which have no references of their own, so `oracle_wer` is None here."""
+        from .metrics import evaluate_transcripts
+        if isinstance(references, str):
+            references = [references]
+        transcripts = self.transcribe_long(waveform, tokenizer, beam_width=beam_width, nbest=nbest, lm=lm, window_s=window_s,
+                                           margin_s=margin_s, normalize=normalize, max_stream_s=max_stream_s,
+                                           sampling_rate=sampling_rate, **cut_options)
+        if not isinstance(transcripts, list):
+            transcripts = [transcripts]
+        if len(references) != len(transcripts):
+            raise ValueError("one reference per recording")
+        return evaluate_transcripts(transcripts, references, 1)
+
     def transcribe_long(self, waveform, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False, window_s=20.0, margin_s=2.0,
                         normalize=True, max_stream_s=1200.0, sampling_rate=None, **cut_options):
         """Text of recordings of any length: `predict_long(waveform, ...)`, then `wav2vec2.longform.decode_long` on the stitched

@@ -343,6 +343,31 @@ int w2v2_ctc_pause_cuts(const float* logits_dev, int32_t V, int32_t n, const int
                         int32_t blank, int32_t delim, float margin, int32_t min_pause, int32_t max_cuts, int32_t* cut_dev,
                         int32_t* pause_dev, int32_t* count_dev, void* stream);
 
+/* Edit distance with its breakdown (exact definition in csrc/edit.hip and, in plain Python,
+ * tests/edit_reference.py): what a word or character error rate is made of.  Model-free: many pairs per call, addressed by host
+ * tables into ONE token buffer, each pair computed as if it were alone.
+ *   pair p: the hypothesis tokens_dev[hyp0_host[p] .. + hyp_len_host[p]) (length m) against the reference
+ *           tokens_dev[ref0_host[p] .. + ref_len_host[p]) (length n), int32 tokens compared for equality only.  Ranges may
+ *           overlap and may be shared by any number of pairs.
+ *   out_dev (n_pairs, 4) int32: distance, substitutions, deletions, insertions.
+ * distance is the least number of substitutions, deletions (a reference token without a counterpart) and insertions (a
+ * hypothesis token without one) that turn the reference into the hypothesis.  The counts are those of the alignment of that
+ * distance with the FEWEST substitutions -- which is also the one with the most hits (hits = n - substitutions - deletions) --
+ * and are unique: with (C, S) the lexicographic minimum of (cost, substitutions) over all alignments, deletions =
+ * (C - S - (m - n)) / 2 and insertions = deletions + m - n.  No tie-break rule enters the result, so the split can differ from a
+ * tool that backtraces with a fixed priority (`ab` against `ba`: one deletion, one insertion and a hit here, two substitutions
+ * there); the distance, and with it any error rate, cannot.  Lengths of 0 are legal: an empty hypothesis gives n deletions, an
+ * empty reference m insertions.
+ * W2V2_EINVAL with a message: a null pointer, n_pairs < 1, a negative offset or length, a range past n_tokens, a length above
+ * W2V2_EDIT_MAX_LEN (a cell packs cost and substitutions into 16 bits each).  Device memory is O(n) per pair in flight, never
+ * O(m n); no atomics, the same bits on every call, and a pair's result does not depend on the other pairs of the call, their
+ * order, or repetition.  At most two launches per call, attributed to the `ctc` profiling family.  Synchronises with the previous
+ * call's table upload (host-side), otherwise enqueued on `stream`. */
+#define W2V2_EDIT_MAX_LEN 65535
+int w2v2_edit_distance(const int32_t* tokens_dev, int64_t n_tokens, int32_t n_pairs, const int64_t* hyp0_host,
+                       const int32_t* hyp_len_host, const int64_t* ref0_host, const int32_t* ref_len_host, int32_t* out_dev,
+                       void* stream);
+
 /* Resampling (the same definition in fp64 numpy: tests/resample_reference.py): a polyphase Kaiser-windowed-sinc
  * filter with a rational ratio.  Model-free: many segments per call, addressed by host tables, each computed as if it were alone.
  *
