@@ -393,7 +393,7 @@ int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int widt
 
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
 enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4, SCRATCH_BEAM = 5, SCRATCH_WINDOWS = 6,
-                   SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8, SCRATCH_EDIT = 9 };
+                   SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8, SCRATCH_EDIT = 9, SCRATCH_ALIGN_LONG = 10 };
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out);
 int stream_scratch_release();       // frees the calling device's scratch buffers
 // pinned staging of a small host table on its way to the device (shadow.hip): grow-only, and the previous upload out of it has
@@ -442,6 +442,14 @@ int launch_ctc_x(Profiler* prof, const float* logits, int B, int T, int V, const
 int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
                      const int64_t* label0, const int32_t* nlabels, int blank, int32_t* token, int32_t* label_index,
                      float* frame_logp, double* score, hipStream_t s);
+// ... of whole recordings (align_long.hip; w2v2_ctc_align_long): the same addressing and outputs, any label count; the plane of
+// frames x states runs as tiles of panel_frames steps x strip_pairs state pairs (0 = the defaults), one launch per anti-diagonal.
+// ctc_align_long_workspace: the bytes of scratch such a call needs (host only; a negative W2V2_E* for bad shapes)
+int launch_ctc_align_long(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
+                          const int64_t* label0, const int32_t* nlabels, int blank, int32_t* token, int32_t* label_index,
+                          float* frame_logp, double* score, int strip_pairs, int panel_frames, int64_t max_workspace_bytes,
+                          hipStream_t s);
+int64_t ctc_align_long_workspace(int n, const int32_t* frames, const int32_t* nlabels, int strip_pairs, int panel_frames);
 // CTC prefix beam search (beam.hip; w2v2_ctc_beam_search): the same addressing of the logits; per utterance nbest rows of max_len
 // labels, their lengths (-1: no such hypothesis), score (CTC log-probability over the kept paths) and total (score + LM)
 int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int beam_width,

@@ -1,8 +1,11 @@
-"""CTC forced alignment on the GPU (w2v2_ctc_align, csrc/align.hip).
+"""CTC forced alignment on the GPU (w2v2_ctc_align, csrc/align.hip; whole recordings: w2v2_ctc_align_long,
+csrc/align_long.hip).
 
 ``forced_align`` finds, per utterance, the single best frame-level CTC path (Viterbi) that spells a given label sequence;
-``token_spans`` and ``word_spans`` turn a path into per-token frame spans and per-word time spans.  The path and its
-per-frame log-probabilities are computed by HIP kernels; the span helpers are host code over the (short) per-frame arrays.
+``forced_align_long`` is the same path without the limit of 8191 labels, for whole recordings and their texts;
+``token_spans`` and ``word_spans`` turn a path into per-token frame spans and per-word time spans; ``split_at_pauses`` cuts an
+aligned recording into utterance-sized pieces.  The path and its per-frame log-probabilities are computed by HIP kernels; the
+span helpers are host code over the per-frame arrays.
 """
 
 from dataclasses import dataclass
@@ -37,6 +40,17 @@ class WordSpan(NamedTuple):
     start_s: float
     end_s: float
     score: float    # mean of exp(frame_logp) over the frames of the word's tokens
+
+
+class AlignedSegment(NamedTuple):
+    text: object    # the words' texts joined by spaces (or the tuple of the words' id tuples when they carry ids)
+    start_s: float  # the first word's start
+    end_s: float    # the last word's end
+    score: float    # mean of the words' scores
+    words: list     # the piece's WordSpans
+
+
+DEFAULT_LONG_WORKSPACE = 32 << 30      # w2v2_ctc_align_long's cap when max_workspace_bytes is 0
 
 
 def _host(x):
@@ -90,7 +104,7 @@ def _logits_base(logits, frame_lengths):
     return base, list(np.cumsum([0] + lens[:-1]).tolist()), lens
 
 
-def _check_labels(labels, lens, V, blank):
+def _check_labels(labels, lens, V, blank, max_labels=N.ALIGN_MAX_LABELS):
     out = []
     for i, lab in enumerate(labels):
         a = np.asarray(_host(lab) if hasattr(lab, "cpu") else list(lab), dtype=np.int64).reshape(-1)
@@ -98,8 +112,8 @@ def _check_labels(labels, lens, V, blank):
             raise ValueError(f"utterance {i}: labels must lie in [0, {V}), got [{a.min()}, {a.max()}]")
         if a.size and (a == blank).any():
             raise ValueError(f"utterance {i}: label {blank} is the blank")
-        if a.size > N.ALIGN_MAX_LABELS:
-            raise ValueError(f"utterance {i}: {a.size} labels; at most {N.ALIGN_MAX_LABELS} per utterance")
+        if max_labels is not None and a.size > max_labels:
+            raise ValueError(f"utterance {i}: {a.size} labels; at most {max_labels} per utterance")
         repeats = int((a[1:] == a[:-1]).sum()) if a.size > 1 else 0
         if lens[i] < a.size + repeats:
             raise ValueError(f"utterance {i}: {lens[i]} frames cannot hold {a.size} labels with {repeats} repeats "
@@ -144,6 +158,64 @@ def forced_align(logits, labels, blank=0, frame_lengths=None):
             zip(torch.split(token, lens), torch.split(label_index, lens), torch.split(frame_logp, lens), scores)]
 
 
+def forced_align_long(logits, labels, blank=0, frame_lengths=None, strip_pairs=None, panel_frames=None, max_workspace_bytes=None):
+    """``forced_align`` for whole recordings: the same path, bit for bit, with any number of labels (w2v2_ctc_align_long).
+
+    ``logits``: what ``forced_align`` accepts, read in place where it reads in place (``predict_long``'s list included), or one
+    (T, V) tensor with ``labels`` one id sequence: then the result is that recording's ``Alignment`` and not a list.  The same
+    ValueErrors as ``forced_align``, without the limit of 8191 labels.  ``strip_pairs`` (a multiple of 64 in [64, 8192]) and
+    ``panel_frames`` (a multiple of 8) set the tile of the frames x states plane that one block sweeps; they change speed, never a
+    bit of the result; None is the measured default.  The workspace holds 2 bits per frame and state, about T (U + 1) / 2 bytes
+    per recording (5 GB for an hour of speech); a call that needs more than ``max_workspace_bytes`` (None: 32 GiB) raises
+    MemoryError, with the shapes and the bytes, before anything is allocated."""
+    import torch
+    single = isinstance(logits, torch.Tensor) and logits.dim() == 2
+    if single:
+        logits, labels = [logits], [labels]
+    base, row0, lens = _logits_base(logits, frame_lengths)
+    n, V = len(lens), int(base.shape[1])
+    if len(labels) != n:
+        raise ValueError(f"{len(labels)} label sequences for {n} recordings")
+    if not 0 <= blank < V:
+        raise ValueError(f"blank {blank} outside the vocabulary [0, {V})")
+    labs = _check_labels(labels, lens, V, blank, max_labels=None)
+    sp = 0 if strip_pairs is None else int(strip_pairs)
+    pf = 0 if panel_frames is None else int(panel_frames)
+    if sp and (sp % 64 or not 64 <= sp <= 8192):
+        raise ValueError(f"strip_pairs {sp}: a multiple of 64 in [64, 8192]")
+    if pf and (pf % 8 or pf < 8):
+        raise ValueError(f"panel_frames {pf}: a multiple of 8, at least 8")
+    cap = DEFAULT_LONG_WORKSPACE if max_workspace_bytes is None else int(max_workspace_bytes)
+    if cap < 1:
+        raise ValueError(f"max_workspace_bytes {cap} must be positive")
+    frames_h = np.asarray(lens, np.int32)
+    nlab_h = np.asarray([a.size for a in labs], np.int32)
+    lib = N.load()
+    need = int(lib.w2v2_ctc_align_long_workspace(n, N.ptr(frames_h), N.ptr(nlab_h), sp, pf))
+    if need < 0:
+        N.check(need, "w2v2_ctc_align_long_workspace")
+    if need > cap:
+        shapes = ", ".join(f"{t} frames x {u} labels" for t, u in zip(lens, nlab_h.tolist()))
+        raise MemoryError(f"forced_align_long: {shapes} need {need} bytes of workspace; max_workspace_bytes is {cap}")
+    dev = base.device
+    flat = np.concatenate(labs + [np.zeros(1, np.int32)])      # (one spare entry: never an empty buffer)
+    label0 = np.cumsum([0] + [a.size for a in labs[:-1]]).astype(np.int64)
+    labels_dev = torch.from_numpy(flat).to(dev)
+    total = sum(lens)
+    token = torch.empty(total, dtype=torch.int32, device=dev)
+    label_index = torch.empty(total, dtype=torch.int32, device=dev)
+    frame_logp = torch.empty(total, dtype=torch.float32, device=dev)
+    score = torch.empty(n, dtype=torch.float64, device=dev)
+    row0_h = np.asarray(row0, np.int64)
+    N.check(lib.w2v2_ctc_align_long(N.ptr(base), V, n, N.ptr(row0_h), N.ptr(frames_h), N.ptr(labels_dev), N.ptr(label0),
+                                    N.ptr(nlab_h), int(blank), N.ptr(token), N.ptr(label_index), N.ptr(frame_logp), N.ptr(score),
+                                    sp, pf, cap, N.current_stream()), "w2v2_ctc_align_long")
+    scores = score.cpu().numpy()
+    out = [Alignment(tk, li, fl, float(sc)) for tk, li, fl, sc in
+           zip(torch.split(token, lens), torch.split(label_index, lens), torch.split(frame_logp, lens), scores)]
+    return out[0] if single else out
+
+
 def token_spans(alignment):
     """The U labels of an alignment as ``TokenSpan(token, start, end, score)`` in frames, ``end`` exclusive, in label
     order; ``score`` is the mean of exp(frame_logp) over the span.  An alignment without a path (-1 rows) has none."""
@@ -181,3 +253,34 @@ def word_spans(spans, delimiter_id, seconds_per_frame, vocab=None):
             cur.append(s)
     close()
     return words
+
+
+def split_at_pauses(words, min_pause_s=0.3, max_len_s=20.0):
+    """Utterance-sized pieces of an aligned recording (host code): ``words`` is a recording's WordSpan list in time order.
+    A cut falls between words i and i + 1 wherever ``start_s[i + 1] - end_s[i] >= min_pause_s``.  A piece longer than
+    ``max_len_s`` (last end minus first start) is cut again at its largest internal gap, the earliest among equal gaps, until
+    every piece fits or is a single word.  Returns ``AlignedSegment(text, start_s, end_s, score, words)`` in time order: ``text``
+    the words joined by spaces (the tuple of the words' id tuples when they carry ids), ``score`` the mean of the words' scores."""
+    words = list(words)
+    if not words:
+        return []
+    pieces, first = [], 0
+    for i in range(len(words) - 1):
+        if words[i + 1].start_s - words[i].end_s >= min_pause_s:
+            pieces.append((first, i + 1))
+            first = i + 1
+    pieces.append((first, len(words)))
+    out, todo = [], pieces[::-1]
+    while todo:
+        a, b = todo.pop()
+        if b - a > 1 and words[b - 1].end_s - words[a].start_s > max_len_s:
+            gaps = [words[i + 1].start_s - words[i].end_s for i in range(a, b - 1)]
+            cut = a + 1 + max(range(len(gaps)), key=lambda i: (gaps[i], -i))
+            todo.append((cut, b))
+            todo.append((a, cut))
+            continue
+        ws = words[a:b]
+        texts = [w.text for w in ws]
+        text = " ".join(texts) if all(isinstance(t, str) for t in texts) else tuple(texts)
+        out.append(AlignedSegment(text, ws[0].start_s, ws[-1].end_s, sum(w.score for w in ws) / len(ws), ws))
+    return out

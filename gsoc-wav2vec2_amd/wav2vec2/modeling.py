@@ -724,6 +724,48 @@ class Wav2Vec2ForCTC(TFKerasModel):
         alignments = forced_align(self.predict_packed(waveforms, sampling_rate, normalize), ids, blank=self.config.pad_id)
         return [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab) for a in alignments]
 
+    def align_long(self, waveform, transcript, tokenizer=None, delimiter_id=None, window_s=20.0, margin_s=2.0, normalize=True,
+                   max_stream_s=1200.0, sampling_rate=None):
+        """Word timestamps of whole recordings and their texts: `predict_long(waveform, ...)`, then the forced alignment of each
+        transcript on the stitched logits without a limit on its length (wav2vec2.alignment.forced_align_long; blank =
+        config.pad_id), then token_spans / word_spans.  `waveform`: one recording or a list of them; `transcript`: one transcript
+        or a list to match, each text (encoded with `tokenizer`) or a sequence of ids, as `align` takes them; `delimiter_id` as
+        `align`.  Returns the list of WordSpan(text, start_s, end_s, score) of the recording (a list of such lists for a list),
+        the times in seconds of the recording exactly as `align` states them.  `window_s` ... `sampling_rate`: as `predict_long`.
+        The alignment's workspace grows with frames x labels (about 5 GB for an hour of speech); wav2vec2.alignment's
+        `split_at_pauses` cuts the result into utterance-sized pieces."""
+        import torch
+        from .alignment import forced_align_long, token_spans, word_spans
+        from .processor import WORD_DELIMITER
+        single = isinstance(waveform, (np.ndarray, torch.Tensor)) and getattr(waveform, "ndim", 0) == 1
+        if single:
+            waveform, transcripts = [waveform], [transcript]
+        else:
+            waveform, transcripts = list(waveform), transcript
+        if isinstance(transcripts, str) or len(transcripts) != len(waveform):
+            raise ValueError("one transcript per recording")
+        ids = []
+        for i, tr in enumerate(transcripts):
+            if isinstance(tr, str):
+                if tokenizer is None:
+                    raise ValueError(f"transcript {i} is text: pass the tokenizer that encodes it")
+                ids.append(list(tokenizer(tr)))
+            else:
+                ids.append([int(x) for x in tr])
+        vocab = None
+        if tokenizer is not None:
+            tokens = tokenizer.get_vocab()
+            vocab = {i: (" " if t == WORD_DELIMITER else t) for t, i in tokens.items()}
+            if delimiter_id is None:
+                delimiter_id = tokens[WORD_DELIMITER]
+        if delimiter_id is None:
+            raise ValueError("ids without a tokenizer: pass delimiter_id")
+        seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
+        logits = self.predict_long(waveform, window_s, margin_s, normalize, max_stream_s, sampling_rate)
+        alignments = forced_align_long(logits, ids, blank=self.config.pad_id)
+        words = [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab) for a in alignments]
+        return words[0] if single else words
+
     def transcribe(self, waveforms, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False, sampling_rate=None, normalize=False):
         """Text: `predict_packed(waveforms)`, then the CTC prefix beam search on the packed logits in place
         (wav2vec2.decoding.beam_search; blank = config.pad_id), ids -> text with `tokenizer` (a Wav2Vec2Processor(is_tokenizer=True);

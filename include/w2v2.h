@@ -70,7 +70,7 @@ typedef struct w2v2_model w2v2_model;
 
 const char* w2v2_last_error(void);
 const char* w2v2_version(void);
-/* Free the library-owned per-(device, stream) scratch buffers (split-K slabs, CTC alpha / beta) of the calling thread's
+/* Free the library-owned per-(device, stream) scratch buffers (split-K slabs, CTC alpha / beta, the aligners' workspaces) of the calling thread's
  * current device; they are otherwise kept, grow-only, for the life of the process.  The device must be idle. */
 int w2v2_release_scratch(void);
 
@@ -261,6 +261,34 @@ int w2v2_ctc_loss_fused(const float* logits_dev, int32_t B, int32_t T, int32_t V
 int w2v2_ctc_align(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host,
                    const int32_t* labels_dev, const int64_t* label0_host, const int32_t* nlabels_host, int32_t blank,
                    int32_t* token_dev, int32_t* label_index_dev, float* frame_logp_dev, double* score_dev, void* stream);
+
+/* CTC forced alignment of whole recordings (csrc/align_long.hip): w2v2_ctc_align without the label limit.  The same
+ * definition, addressing and outputs, and the same bits: every output, the score included, is identical to w2v2_ctc_align's wherever
+ * that one accepts the input, and to the fp64 reference on every input (ties, -inf and NaN logits included).  nlabels_i is any
+ * non-negative int32.  The plane of frames x states runs as tiles: a strip of `strip_pairs` state pairs (blank 2k, label 2k + 1) by a
+ * panel of `panel_frames` steps, one kernel launch per anti-diagonal of tiles over all recordings of the call; stream order is the
+ * only synchronisation between tiles (no block waits for another, no atomics), so results do not depend on the other recordings of
+ * the call, their order, the geometry, or repetition.
+ *   strip_pairs   0 (the measured default) or a multiple of 64 in [64, 8192]; a strip is never wider than the longest recording needs
+ *   panel_frames  0 (the measured default) or a multiple of 8 that is >= 8
+ *   max_workspace_bytes  cap of the library-owned scratch of the call; 0 = 32 GiB.  The scratch holds the tile table, lse, one carry
+ *                 row (8 S_i bytes) and the strips' boundary columns (8 T_i strips_i bytes) per recording, and 2 bits of backpointer
+ *                 per frame and state, about T_i (U_i + 1) / 2 bytes: 5 GB for one hour of speech (180 000 frames, 54 000
+ *                 labels), growing with the product.  A call that needs more returns W2V2_EINVAL, its message naming the bytes,
+ *                 BEFORE anything is allocated.
+ * Anything else outside the ranges above is W2V2_EINVAL, with w2v2_ctc_align's other argument checks (frames_i >= 1, non-negative
+ * offsets, blank in [0, V), no null pointer, n >= 1).  Infeasible recordings and bad device labels as w2v2_ctc_align, neighbours
+ * unaffected.  The scratch is grow-only per (device, stream) like the library's other scratch: w2v2_release_scratch gives it back.
+ * Synchronises with the previous call's table upload (host-side), otherwise enqueued on `stream`.
+ *
+ * w2v2_ctc_align_long_workspace: host only; the bytes of scratch a call of these shapes and this geometry needs (INT64_MAX when the
+ * figure does not fit), or a negative W2V2_E* for arguments the call itself would refuse. */
+int w2v2_ctc_align_long(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host,
+                        const int32_t* labels_dev, const int64_t* label0_host, const int32_t* nlabels_host, int32_t blank,
+                        int32_t* token_dev, int32_t* label_index_dev, float* frame_logp_dev, double* score_dev,
+                        int32_t strip_pairs, int32_t panel_frames, int64_t max_workspace_bytes, void* stream);
+int64_t w2v2_ctc_align_long_workspace(int32_t n, const int32_t* frames_host, const int32_t* nlabels_host, int32_t strip_pairs,
+                                      int32_t panel_frames);
 
 /* CTC prefix beam search (exact definition in csrc/beam.hip): the nbest most probable transcripts of each utterance,
  * optionally fused with a character n-gram language model.  Model-free, like w2v2_ctc_align, and with the same addressing:
