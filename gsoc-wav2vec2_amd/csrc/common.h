@@ -393,7 +393,7 @@ int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int widt
 
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
 enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4, SCRATCH_BEAM = 5, SCRATCH_WINDOWS = 6,
-                   SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8, SCRATCH_EDIT = 9, SCRATCH_ALIGN_LONG = 10 };
+                   SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8, SCRATCH_EDIT = 9, SCRATCH_ALIGN_LONG = 10, SCRATCH_SCORE = 11 };
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out);
 int stream_scratch_release();       // frees the calling device's scratch buffers
 // pinned staging of a small host table on its way to the device (shadow.hip): grow-only, and the previous upload out of it has
@@ -450,6 +450,10 @@ int launch_ctc_align_long(const float* logits, int V, int n, const int64_t* row0
                           float* frame_logp, double* score, int strip_pairs, int panel_frames, int64_t max_workspace_bytes,
                           hipStream_t s);
 int64_t ctc_align_long_workspace(int n, const int32_t* frames, const int32_t* nlabels, int strip_pairs, int panel_frames);
+// exact CTC scoring (score.hip; w2v2_ctc_score): the same addressing of the logits; pair j = utterance utt_of[j] against labels
+// [label0_j, label0_j + nlabels_j); one fp64 log-probability per pair, in the caller's order
+int launch_ctc_score(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int m, const int32_t* utt_of,
+                     const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank, double* logp, hipStream_t s);
 // CTC prefix beam search (beam.hip; w2v2_ctc_beam_search): the same addressing of the logits; per utterance nbest rows of max_len
 // labels, their lengths (-1: no such hypothesis), score (CTC log-probability over the kept paths) and total (score + LM)
 int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int beam_width,

@@ -541,6 +541,12 @@ int64_t w2v2_ctc_align_long_workspace(int32_t n, const int32_t* frames, const in
     return ctc_align_long_workspace(n, frames, nlabels, strip_pairs, panel_frames);
 }
 
+int w2v2_ctc_score(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t m, const int32_t* utt_of,
+                   const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int32_t blank, double* logp, void* stream) {
+    return launch_ctc_score(logits, V, n, row0, frames, m, utt_of, labels, label0, nlabels, blank, logp,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
 int w2v2_ctc_beam_search(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t blank,
                          int32_t beam_width, int32_t nbest, const float* lm_table, int32_t lm_order, float lm_alpha, float lm_beta,
                          int32_t max_len, int32_t* labels_out, int32_t* length, double* score, double* total, void* stream) {

@@ -5,7 +5,7 @@ resampled_length, speed_perturb) and the error rates (wav2vec2.metrics: wer, cer
 
 from .audio import Resampler, resample, resampled_length, speed_perturb
 from .config import RobustWav2Vec2Config, Wav2Vec2Config
-from .longform import LongTranscript, decode_long, window_plan
+from .longform import LongTranscript, ScoredLongTranscript, decode_long, window_plan
 from .losses import CTCLoss
 from .metrics import (EditCounts, ErrorRate, Evaluation, cer, edit_distance, edit_distance_pairs, mbr_select, oracle_wer,
                       wer)
@@ -14,6 +14,6 @@ from .processor import Wav2Vec2Processor
 from .training import Trainer
 
 __all__ = ["Wav2Vec2Config", "RobustWav2Vec2Config", "CTCLoss", "Wav2Vec2ForCTC", "Wav2Vec2Model",
-           "Wav2Vec2Processor", "Trainer", "window_plan", "decode_long", "LongTranscript", "Resampler", "resample",
+           "Wav2Vec2Processor", "Trainer", "window_plan", "decode_long", "LongTranscript", "ScoredLongTranscript", "Resampler", "resample",
            "resampled_length", "speed_perturb", "EditCounts", "ErrorRate", "Evaluation", "wer", "cer", "oracle_wer", "mbr_select",
            "edit_distance", "edit_distance_pairs"]

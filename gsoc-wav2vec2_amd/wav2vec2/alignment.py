@@ -4,7 +4,7 @@ csrc/align_long.hip).
 ``forced_align`` finds, per utterance, the single best frame-level CTC path (Viterbi) that spells a given label sequence;
 ``forced_align_long`` is the same path without the limit of 8191 labels, for whole recordings and their texts;
 ``token_spans`` and ``word_spans`` turn a path into per-token frame spans and per-word time spans; ``split_at_pauses`` cuts an
-aligned recording into utterance-sized pieces.  The path and its per-frame log-probabilities are computed by HIP kernels; the
+aligned recording into utterance-sized pieces; ``score_segments`` gives each piece the exact likelihood of its text.  The path and its per-frame log-probabilities are computed by HIP kernels; the
 span helpers are host code over the per-frame arrays.
 """
 
@@ -284,3 +284,35 @@ def split_at_pauses(words, min_pause_s=0.3, max_len_s=20.0):
         text = " ".join(texts) if all(isinstance(t, str) for t in texts) else tuple(texts)
         out.append(AlignedSegment(text, ws[0].start_s, ws[-1].end_s, sum(w.score for w in ws) / len(ws), ws))
     return out
+
+
+def score_segments(logits, segments, tokenizer, seconds_per_frame, blank=0):
+    """The likelihood filter for ``align_long`` followed by ``split_at_pauses``: the exact CTC log-probability PER FRAME of each
+    ``AlignedSegment``'s text over its own frame range of the recording's (T, V) ``logits``, in ONE ``wav2vec2.decoding.ctc_score``
+    call on views of the logits (nothing is copied).  A segment's frames are ``[round(start_s / seconds_per_frame),
+    round(end_s / seconds_per_frame))``, clipped to the recording and never empty; its text is encoded with ``tokenizer`` (words
+    that carry ids are joined with the tokenizer's word delimiter).  Returns one float per segment; a piece whose text does not
+    belong to its audio stands out by a value far below its neighbours' (``-inf`` where the frames cannot hold the text)."""
+    from .decoding import ctc_score
+    from .processor import WORD_DELIMITER
+    segments = list(segments)
+    if not segments:
+        return []
+    if getattr(logits, "dim", lambda: 0)() != 2:
+        raise ValueError("`logits` must be one recording's (T, V) tensor")
+    T = int(logits.shape[0])
+    views, ids = [], []
+    for i, sg in enumerate(segments):
+        f0 = min(max(int(round(sg.start_s / seconds_per_frame)), 0), T - 1)
+        f1 = min(max(int(round(sg.end_s / seconds_per_frame)), f0 + 1), T)
+        views.append(logits[f0:f1])
+        if isinstance(sg.text, str):
+            ids.append(list(tokenizer(sg.text)))
+        else:
+            delim = tokenizer.get_vocab()[WORD_DELIMITER]
+            seq = []
+            for k, w in enumerate(sg.text):
+                seq.extend(([delim] if k else []) + [int(c) for c in w])
+            ids.append(seq)
+    logp = ctc_score(views, ids, blank=blank)
+    return [float(v) / int(p.shape[0]) for v, p in zip(logp, views)]

@@ -1,4 +1,5 @@
-"""CTC prefix beam search on the GPU (w2v2_ctc_beam_search, csrc/beam.hip).
+"""CTC prefix beam search and exact CTC scoring on the GPU (w2v2_ctc_beam_search, csrc/beam.hip, DESIGN.md §12;
+w2v2_ctc_score, csrc/score.hip).
 
 ``beam_search`` returns, per utterance, the n most probable transcripts with their log-probabilities; ``CharNgramLM`` is an
 optional character n-gram language model, a dense table of log-probabilities that the kernel reads on the device.  The search
@@ -6,6 +7,10 @@ is a HIP kernel; the table is counted and smoothed on the host (it is built once
 
 ``WordNgramLM`` is the other kind of language model: a word-level backoff n-gram (read from an ARPA file or counted from text)
 with a lexicon that spells its words in the model's labels (w2v2_ctc_beam_search_words).
+
+``ctc_score`` is the exact CTC log-probability of label sequences given logits (the sum over all frame paths, a HIP kernel);
+``rescore`` replaces the beam's lower bounds in n-best lists by it; ``hypothesis_posteriors`` and ``word_confidence`` turn the
+rescored lists into probabilities of the hypotheses and of the best hypothesis' words (host code over a few numbers).
 """
 
 import math
@@ -542,8 +547,8 @@ def beam_search(logits, beam_width=16, nbest=1, blank=0, frame_lengths=None, lm=
     ``score`` is the log of the summed probability of the frame paths that spell the transcript AND whose prefixes stayed in
     the beam at every frame: a LOWER bound of the transcript's exact CTC log-probability (``-ctc_loss``), equal to it only
     when nothing was pruned.  So the best beam score may lie below the exact log-probability of the greedy transcript even
-    where the beam's transcript is the better one; compare hypotheses by ``total`` (= ``score`` + LM score), and re-score with
-    the CTC loss where exact values are needed.  An utterance with a NaN or +inf logit returns an empty list.  Raises
+    where the beam's transcript is the better one; compare hypotheses by ``total`` (= ``score`` + LM score), and pass the lists
+    through ``rescore`` where exact values are needed.  An utterance with a NaN or +inf logit returns an empty list.  Raises
     ValueError before anything is launched for a width, nbest, blank, vocabulary or language model that does not fit."""
     import torch
     from .alignment import _logits_base
@@ -589,3 +594,147 @@ class Transcript(NamedTuple):
     hypotheses: list    # the n best Hypothesis, best first (greedy: one, with score = total = NaN: the argmax path has no beam score)
     texts: list         # their texts
     words: object       # WordSpan list of the best hypothesis (timestamps=True), else None
+
+
+class ScoredTranscript(NamedTuple):
+    text: str               # the best hypothesis as text
+    hypotheses: list        # the n best Hypothesis with exact scores, best first
+    texts: list             # their texts
+    words: list             # WordSpan list of the best hypothesis
+    confidence: float       # posterior of the best hypothesis among the list (NaN for an utterance without hypotheses)
+    posteriors: list        # posterior of every hypothesis, parallel to ``hypotheses``
+    word_confidence: list   # per word of ``words``: the summed posterior of the hypotheses that hold the word at its place
+
+
+def ctc_score(logits, labels, blank=0, frame_lengths=None, utterance=None):
+    """Exact CTC log-probability of each label sequence given its utterance's logits (``-ctc_loss`` in fp64; w2v2_ctc_score):
+    a float64 numpy array with one entry per pair.
+
+    ``logits``: what ``forced_align`` accepts, read in place.  ``labels``: one id sequence per pair, none of them the blank, at
+    most 8191 ids.  ``utterance[j]`` is the utterance pair j scores (default: j, which needs one label sequence per utterance);
+    several pairs may score the same utterance, whose logits are read where they lie.  Too few frames for the labels
+    (T < U + repeated neighbours) is no error: that pair's result is ``-inf``.  An utterance with a NaN or +inf logit gives NaN.
+    Raises ValueError, naming the pair, for a label outside the vocabulary, a blank label or more than 8191 labels."""
+    import torch
+    from .alignment import _host, _logits_base
+    base, row0, lens = _logits_base(logits, frame_lengths)
+    n, V = len(lens), int(base.shape[1])
+    labels = list(labels)
+    m = len(labels)
+    if utterance is None:
+        if m != n:
+            raise ValueError(f"{m} label sequences for {n} utterances (pass `utterance` to score several per utterance)")
+        utt = np.arange(n, dtype=np.int32)
+    else:
+        utt = np.asarray(list(utterance), dtype=np.int64).reshape(-1)
+        if utt.size != m:
+            raise ValueError(f"{m} label sequences with {utt.size} entries of `utterance`")
+        if m and (utt.min() < 0 or utt.max() >= n):
+            raise ValueError(f"`utterance` must lie in [0, {n}), got [{utt.min()}, {utt.max()}]")
+        utt = utt.astype(np.int32)
+    if m < 1:
+        raise ValueError("no label sequence to score")
+    blank = int(blank)
+    if V < 2:
+        raise ValueError(f"vocabulary {V}; the blank and at least one label")
+    if not 0 <= blank < V:
+        raise ValueError(f"blank {blank} outside the vocabulary [0, {V})")
+    labs = []
+    for j, lab in enumerate(labels):
+        a = np.asarray(_host(lab) if hasattr(lab, "cpu") else list(lab), dtype=np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() >= V):
+            raise ValueError(f"pair {j}: labels must lie in [0, {V}), got [{a.min()}, {a.max()}]")
+        if a.size and (a == blank).any():
+            raise ValueError(f"pair {j}: label {blank} is the blank")
+        if a.size > N.SCORE_MAX_LABELS:
+            raise ValueError(f"pair {j}: {a.size} labels; at most {N.SCORE_MAX_LABELS} per pair")
+        labs.append(a.astype(np.int32))
+    dev = base.device
+    flat = np.concatenate(labs + [np.zeros(1, np.int32)])      # (one spare entry: never an empty buffer)
+    label0 = np.cumsum([0] + [a.size for a in labs[:-1]]).astype(np.int64)
+    nlab_h = np.asarray([a.size for a in labs], np.int32)
+    labels_dev = torch.from_numpy(flat).to(dev)
+    logp = torch.empty(m, dtype=torch.float64, device=dev)
+    row0_h = np.asarray(row0, np.int64)
+    frames_h = np.asarray(lens, np.int32)
+    N.check(N.load().w2v2_ctc_score(N.ptr(base), V, n, N.ptr(row0_h), N.ptr(frames_h), m, N.ptr(utt), N.ptr(labels_dev), N.ptr(label0),
+                                    N.ptr(nlab_h), blank, N.ptr(logp), N.current_stream()), "w2v2_ctc_score")
+    return logp.cpu().numpy()
+
+
+def rescore(logits, hypotheses, blank=0, frame_lengths=None):
+    """The n-best lists of ``beam_search`` (one list of ``Hypothesis`` per utterance of ``logits``) with exact scores: ONE
+    ``ctc_score`` call over every hypothesis of every utterance.  ``score`` becomes the exact CTC log-probability; ``total``
+    keeps its language-model part, ``exact + (old total - old score)``; a hypothesis without a beam score (NaN: the greedy
+    path) gets ``score = total = exact``.  Each list is sorted again by ``total``, best first, equal totals in their old order.
+    Exact scores are comparable across a list and across utterances; the beam's were lower bounds, each pruned differently."""
+    lists = [list(h) for h in hypotheses]
+    flat = [(i, x) for i, h in enumerate(lists) for x in h]
+    if not flat:
+        return lists
+    exact = ctc_score(logits, [list(x.ids) for _, x in flat], blank=blank, frame_lengths=frame_lengths, utterance=[i for i, _ in flat])
+    out = [[] for _ in lists]
+    for (i, x), e in zip(flat, exact):
+        e = float(e)
+        lm = 0.0 if math.isnan(x.score) else x.total - x.score
+        out[i].append(Hypothesis(x.ids, e, e + lm))
+    return [sorted(h, key=lambda x: -x.total) if not any(math.isnan(x.total) for x in h) else h for h in out]
+
+
+def hypothesis_posteriors(totals, scale=1.0):
+    """Posterior of each hypothesis of ONE list: the fp64 softmax of ``scale * total`` (max-subtracted), a float64 numpy array.
+    Meaningful on rescored lists, whose totals are exact; ``scale`` below 1 flattens the distribution (the usual acoustic scale
+    of confidence estimation), 0 gives the uniform one.  An empty list gives an empty array."""
+    t = np.asarray(list(totals), dtype=np.float64).reshape(-1) * np.float64(scale)
+    if not t.size:
+        return t
+    e = np.exp(t - t.max())
+    return e / e.sum()
+
+
+def word_confidence(word_frames_per_hypothesis, posteriors):
+    """Confidence of each word of the best hypothesis: the summed posterior of the hypotheses that hold the same word at the same
+    place.  ``word_frames_per_hypothesis[k]``: the words of hypothesis k as ``(text, start, end)`` in whole frames, ``end``
+    exclusive (hypothesis 0 is the best).  Hypothesis k supports the word ``(text, s, e)`` of hypothesis 0 iff it has a word of
+    the same text whose frames ``[s', e')`` overlap at least half of it: ``2 (min(e, e') - max(s, s')) >= e - s``, in integers.
+    Hypothesis 0 supports its own words, so every value lies in ``[posteriors[0], 1]``."""
+    lists = [list(w) for w in word_frames_per_hypothesis]
+    post = [float(p) for p in posteriors]
+    if len(post) != len(lists):
+        raise ValueError(f"{len(lists)} hypotheses with {len(post)} posteriors")
+    if not lists:
+        return []
+    out = []
+    for text, s, e in lists[0]:
+        s, e = int(s), int(e)
+        conf = 0.0
+        for k, words in enumerate(lists):
+            if k == 0 or any(t2 == text and 2 * (min(e, int(e2)) - max(s, int(s2))) >= e - s for t2, s2, e2 in words):
+                conf += post[k]
+        out.append(conf)
+    return out
+
+
+def score_transcripts(logits, hypotheses, tokenizer, blank, delimiter_id, seconds_per_frame, posterior_scale=1.0, vocab=None):
+    """``ScoredTranscript`` of each utterance from its (rescored) n-best list: ONE ``forced_align`` call over every non-empty
+    hypothesis of every utterance (the pairs of an utterance share its rows), then ``hypothesis_posteriors`` over each list and
+    ``word_confidence`` over its word spans.  An utterance without hypotheses gets NaN and empty lists."""
+    from .alignment import forced_align, token_spans, word_spans
+    lists = [list(h) for h in hypotheses]
+    flat = [(i, k) for i, h in enumerate(lists) for k, x in enumerate(h) if x.ids]
+    spans = {}
+    if flat:
+        alignments = forced_align([logits[i] for i, _ in flat], [list(lists[i][k].ids) for i, k in flat], blank=blank)
+        for key, a in zip(flat, alignments):
+            spans[key] = token_spans(a)
+    out = []
+    for i, h in enumerate(lists):
+        texts = [x.text(tokenizer) if tokenizer is not None else None for x in h]
+        if not h:
+            out.append(ScoredTranscript("", [], [], [], float("nan"), [], []))
+            continue
+        post = hypothesis_posteriors([x.total for x in h], posterior_scale)
+        frames = [[(w.text, w.start_s, w.end_s) for w in word_spans(spans.get((i, k), []), delimiter_id, 1, vocab)] for k in range(len(h))]
+        words = word_spans(spans.get((i, 0), []), delimiter_id, seconds_per_frame, vocab)
+        out.append(ScoredTranscript(texts[0], h, texts, words, float(post[0]), [float(p) for p in post], word_confidence(frames, post)))
+    return out

@@ -252,13 +252,25 @@ class LongTranscript(NamedTuple):
     segments: list        # Segment(start_s, end_s, transcript)
 
 
+class ScoredLongTranscript(NamedTuple):
+    text: object          # as LongTranscript
+    ids: tuple
+    score: float          # sum of the best hypotheses' exact scores
+    total: float
+    words: list           # WordSpans in the recording's time
+    segments: list        # Segment(start_s, end_s, transcript), the transcript a wav2vec2.decoding.ScoredTranscript
+    confidence: float     # geometric mean of the segments' confidences, weighted by their word counts (NaN without a word)
+    word_confidence: list # parallel to ``words``: each word's confidence within its segment
+
+
 def _collapse(path, blank):
     keep = np.flatnonzero((path != blank) & (np.concatenate(([True], path[1:] != path[:-1]))))
     return tuple(int(v) for v in path[keep])
 
 
 def decode_long(logits, tokenizer=None, beam_width=16, nbest=1, lm=None, blank=0, delimiter_id=None, timestamps=False,
-                pause_margin=2.0, min_pause=10, min_frames=250, max_frames=1500, seconds_per_frame=0.02):
+                pause_margin=2.0, min_pause=10, min_frames=250, max_frames=1500, seconds_per_frame=0.02, rescore=False,
+                confidence=False, posterior_scale=1.0):
     """Transcripts of long recordings from their logits: one ``LongTranscript`` per recording (a single (T, V) tensor gives one
     result, a list gives a list).  Model-free, like ``beam_search``.
 
@@ -272,10 +284,19 @@ def decode_long(logits, tokenizer=None, beam_width=16, nbest=1, lm=None, blank=0
     decode the collapse of the whole equals the concatenation of the collapses of the pieces, and ``ids`` is the
     concatenation of the segments' best hypotheses; ``text`` decodes ``ids`` without grouping.  A language model sees every
     segment as an utterance: a ``WordNgramLM`` restarts from its start state at each segment and scores ``</s>`` at each
-    segment's end when its ``score_eos`` is set; no LM state or beam entry is carried across a cut."""
+    segment's end when its ``score_eos`` is set; no LM state or beam entry is carried across a cut.
+
+    ``rescore=True``: the segments' n-best lists go through ONE ``wav2vec2.decoding.rescore`` call (exact scores, lists ordered
+    by the exact totals) before anything is made of them.  ``confidence=True`` (implies ``rescore``; needs a beam with
+    ``nbest >= 2``, else ValueError) aligns ALL hypotheses of all segments in one ``forced_align`` call and returns
+    ``ScoredLongTranscript``: posteriors are per segment (each ``Segment.transcript`` a ``ScoredTranscript``), a word's confidence
+    comes from its segment, and the recording's ``confidence`` is the geometric mean of its segments' confidences weighted by
+    their word counts."""
+    import math
     import torch
     from .alignment import forced_align, token_spans, word_spans
     from .decoding import Hypothesis, Transcript, beam_search
+    from .decoding import rescore as rescore_lists, score_transcripts
     from .processor import WORD_DELIMITER
     single = isinstance(logits, torch.Tensor)
     recs = [logits] if single else list(logits)
@@ -291,6 +312,10 @@ def decode_long(logits, tokenizer=None, beam_width=16, nbest=1, lm=None, blank=0
         raise ValueError("timestamps without a tokenizer: pass delimiter_id")
     if beam_width is None and lm is not None:
         raise ValueError("the greedy path takes no language model")
+    if confidence and (beam_width is None or nbest < 2):
+        raise ValueError("confidence=True needs a beam search with nbest >= 2: a posterior is taken over a list")
+    if confidence and delimiter_id is None:
+        raise ValueError("confidence without a tokenizer: pass delimiter_id")
     found = pause_cuts(recs, blank=blank, delimiter_id=delimiter_id, margin=pause_margin, min_pause=min_pause)
     bounds, pieces = [], []
     for l, f in zip(recs, found):
@@ -302,6 +327,31 @@ def decode_long(logits, tokenizer=None, beam_width=16, nbest=1, lm=None, blank=0
         hyps = [[Hypothesis(_collapse(p.argmax(dim=1).cpu().numpy(), blank), float("nan"), float("nan"))] for p in pieces]
     else:
         hyps = beam_search(pieces, beam_width=beam_width, nbest=nbest, blank=blank, lm=lm)
+    if rescore or confidence:
+        hyps = rescore_lists(pieces, hyps, blank=blank)
+    if confidence:
+        scored = score_transcripts(pieces, hyps, tokenizer, blank, delimiter_id, seconds_per_frame, posterior_scale, vocab)
+        out, k = [], 0
+        for b in bounds:
+            segments, ids, all_words, all_conf, score, total, logc, nw = [], [], [], [], 0.0, 0.0, 0.0, 0
+            for x, y in zip(b, b[1:]):
+                st = scored[k]
+                k += 1
+                start = x * seconds_per_frame
+                segments.append(Segment(start, y * seconds_per_frame, st))
+                if st.hypotheses:
+                    ids.extend(st.hypotheses[0].ids)
+                    score += st.hypotheses[0].score
+                    total += st.hypotheses[0].total
+                all_words.extend(s._replace(start_s=s.start_s + start, end_s=s.end_s + start) for s in st.words)
+                all_conf.extend(st.word_confidence)
+                if st.words:
+                    logc += len(st.words) * math.log(st.confidence)
+                    nw += len(st.words)
+            text = tokenizer.decode(ids, skip_special_tokens=True, group_tokens=False) if tokenizer is not None else None
+            out.append(ScoredLongTranscript(text, tuple(ids), score, total, all_words, segments,
+                                            math.exp(logc / nw) if nw else float("nan"), all_conf))
+        return out[0] if single else out
     words = [None] * len(pieces)
     if timestamps:
         words = [[] for _ in pieces]

@@ -766,7 +766,29 @@ class Wav2Vec2ForCTC(TFKerasModel):
         words = [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab) for a in alignments]
         return words[0] if single else words
 
-    def transcribe(self, waveforms, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False, sampling_rate=None, normalize=False):
+    def score(self, waveforms, transcripts, tokenizer=None, sampling_rate=None, normalize=False):
+        """Exact CTC log-probability of each transcript given its waveform, the sibling of `align`: `predict_packed(waveforms)`,
+        then wav2vec2.decoding.ctc_score on the packed logits in place (blank = config.pad_id; the sum over ALL frame paths,
+        -ctc_loss in fp64).  A transcript is text, encoded with `tokenizer`, or a sequence of ids.  Returns one
+        (logp, logp / frames) per utterance; a transcript its frames cannot hold gives -inf.  `sampling_rate`, `normalize`: as
+        `predict_packed`."""
+        from .decoding import ctc_score
+        if isinstance(transcripts, str) or len(transcripts) != len(waveforms):
+            raise ValueError("one transcript per waveform")
+        ids = []
+        for i, tr in enumerate(transcripts):
+            if isinstance(tr, str):
+                if tokenizer is None:
+                    raise ValueError(f"transcript {i} is text: pass the tokenizer that encodes it")
+                ids.append(list(tokenizer(tr)))
+            else:
+                ids.append([int(x) for x in tr])
+        logits = self.predict_packed(waveforms, sampling_rate, normalize)
+        logp = ctc_score(logits, ids, blank=self.config.pad_id)
+        return [(float(v), float(v) / int(l.shape[0])) for v, l in zip(logp, logits)]
+
+    def transcribe(self, waveforms, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False, sampling_rate=None, normalize=False,
+                   rescore=False, confidence=False, posterior_scale=1.0):
         """Text: `predict_packed(waveforms)`, then the CTC prefix beam search on the packed logits in place
         (wav2vec2.decoding.beam_search; blank = config.pad_id), ids -> text with `tokenizer` (a Wav2Vec2Processor(is_tokenizer=True);
         "|" -> space, as its `decode`).  `lm`: a wav2vec2.decoding.CharNgramLM, a wav2vec2.decoding.WordNgramLM (a word n-gram model
@@ -775,9 +797,18 @@ class Wav2Vec2ForCTC(TFKerasModel):
         of each utterance goes through the forced alignment (wav2vec2.alignment) and the result carries its WordSpans (none for
         an empty transcript).  Returns one wav2vec2.decoding.Transcript(text, hypotheses, texts, words) per utterance; see
         `beam_search` for what a hypothesis' score means.  Runs in the precision modes predict_packed accepts.
-        `sampling_rate`, `normalize`: as `predict_packed`; times stay seconds of the recording."""
+        `sampling_rate`, `normalize`: as `predict_packed`; times stay seconds of the recording.
+        `rescore=True` passes the n-best lists through wav2vec2.decoding.rescore before texts and timestamps are made: every
+        score is then the exact CTC log-probability and the lists are ordered by the exact totals.  `confidence=True` (implies
+        `rescore`; needs a beam with `nbest >= 2`) aligns ALL hypotheses in one forced alignment and returns
+        wav2vec2.decoding.ScoredTranscript(text, hypotheses, texts, words, confidence, posteriors, word_confidence) instead:
+        `posteriors` the softmax of `posterior_scale * total` over the list, `confidence` the best hypothesis' posterior,
+        `word_confidence` per word of `words` the summed posterior of the hypotheses that hold the word at its place."""
         from .alignment import forced_align, token_spans, word_spans
         from .decoding import Hypothesis, Transcript, beam_search
+        from .decoding import rescore as rescore_lists, score_transcripts
+        if confidence and (beam_width is None or nbest < 2):
+            raise ValueError("confidence=True needs a beam search with nbest >= 2: a posterior is taken over a list")
         from .processor import WORD_DELIMITER
         blank = self.config.pad_id
         logits = self.predict_packed(waveforms, sampling_rate, normalize)
@@ -791,6 +822,13 @@ class Wav2Vec2ForCTC(TFKerasModel):
                 hyps.append([Hypothesis(tuple(int(v) for v in path[keep]), float("nan"), float("nan"))])
         else:
             hyps = beam_search(logits, beam_width=beam_width, nbest=nbest, blank=blank, lm=lm)
+        if rescore or confidence:
+            hyps = rescore_lists(logits, hyps, blank=blank)
+        if confidence:
+            tokens = tokenizer.get_vocab()
+            vocab = {i: (" " if t == WORD_DELIMITER else t) for t, i in tokens.items()}
+            return score_transcripts(logits, hyps, tokenizer, blank, tokens[WORD_DELIMITER], float(np.prod(self.config.strides)) / 16000.0,
+                                     posterior_scale, vocab)
         words = [None] * len(hyps)
         if timestamps:
             tokens = tokenizer.get_vocab()
@@ -839,16 +877,19 @@ class Wav2Vec2ForCTC(TFKerasModel):
         return evaluate_transcripts(transcripts, references, 1)
 
     def transcribe_long(self, waveform, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False, window_s=20.0, margin_s=2.0,
-                        normalize=True, max_stream_s=1200.0, sampling_rate=None, **cut_options):
+                        normalize=True, max_stream_s=1200.0, sampling_rate=None, rescore=False, confidence=False, posterior_scale=1.0,
+                        **cut_options):
         """Text of recordings of any length: `predict_long(waveform, ...)`, then `wav2vec2.longform.decode_long` on the stitched
         logits with blank = config.pad_id, the tokenizer's word delimiter and the frame period of the conv strides: the logits
         are cut at pauses between words, all segments go through one beam search (and one forced alignment with
         `timestamps=True`), and the pieces are concatenated.  `cut_options`: decode_long's pause_margin, min_pause, min_frames,
         max_frames.  A language model sees each segment as an utterance (a WordNgramLM restarts at every segment).  Returns one
         wav2vec2.longform.LongTranscript(text, ids, score, total, words, segments) per recording.  `sampling_rate`: as
-        `predict_long`; the times stay seconds of the recording."""
+        `predict_long`; the times stay seconds of the recording.  `rescore`, `confidence`, `posterior_scale`: as `transcribe`,
+        per segment; with `confidence=True` the result is decode_long's ScoredLongTranscript."""
         from .longform import decode_long
         logits = self.predict_long(waveform, window_s, margin_s, normalize, max_stream_s, sampling_rate)
         seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
         return decode_long(logits, tokenizer, beam_width=beam_width, nbest=nbest, lm=lm, blank=self.config.pad_id, timestamps=timestamps,
-                           seconds_per_frame=seconds_per_frame, **cut_options)
+                           seconds_per_frame=seconds_per_frame, rescore=rescore, confidence=confidence, posterior_scale=posterior_scale,
+                           **cut_options)

@@ -290,6 +290,23 @@ int w2v2_ctc_align_long(const float* logits_dev, int32_t V, int32_t n, const int
 int64_t w2v2_ctc_align_long_workspace(int32_t n, const int32_t* frames_host, const int32_t* nlabels_host, int32_t strip_pairs,
                                       int32_t panel_frames);
 
+/* Exact CTC scoring (exact definition in csrc/score.hip): the log-probability of a label string given an utterance's
+ * logits, summed over every frame path that spells it (-ctc_loss in fp64), for m (utterance, label string) pairs in one call.
+ * Model-free, like w2v2_ctc_align, and with its addressing of the utterances; asynchronous on `stream`.
+ *   utterance i: logits_dev rows [row0_host[i], row0_host[i] + frames_host[i]) of V fp32 (read in place; pairs share rows)
+ *   pair j:      scores utterance utt_of_host[j] against labels_dev[label0_host[j] .. label0_host[j] + nlabels_host[j]) (int32, device)
+ *   logp_dev     (m) fp64, in the caller's order
+ * n >= 1, m >= 1, V >= 2, frames_i >= 1, utt_of_j in [0, n), 0 <= nlabels_j <= W2V2_SCORE_MAX_LABELS, non-negative offsets, blank in
+ * [0, V), no null pointer: otherwise W2V2_EINVAL, before anything is launched.  Per pair, the others unaffected: frames < nlabels +
+ * (count of labels equal to the one before) gives -inf (a result, not an error); a label outside [0, V) or equal to the blank gives
+ * NaN; an utterance with a NaN or +inf logit gives NaN for each of its pairs; -inf logits are legal.  fp64 log space: nothing
+ * underflows.  No atomics; a pair's bits do not depend on the other pairs, their order or repetition.  Synchronises with the previous
+ * call's table upload (host-side), otherwise enqueued on `stream`. */
+#define W2V2_SCORE_MAX_LABELS 8191
+int w2v2_ctc_score(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host, int32_t m,
+                   const int32_t* utt_of_host, const int32_t* labels_dev, const int64_t* label0_host, const int32_t* nlabels_host,
+                   int32_t blank, double* logp_dev, void* stream);
+
 /* CTC prefix beam search (exact definition in csrc/beam.hip): the nbest most probable transcripts of each utterance,
  * optionally fused with a character n-gram language model.  Model-free, like w2v2_ctc_align, and with the same addressing:
  *   utterance i: logits_dev rows [row0_host[i], row0_host[i] + frames_host[i]) of V fp32
