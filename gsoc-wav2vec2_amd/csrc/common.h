@@ -393,7 +393,7 @@ int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int widt
 
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
 enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4, SCRATCH_BEAM = 5, SCRATCH_WINDOWS = 6,
-                   SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8, SCRATCH_EDIT = 9, SCRATCH_ALIGN_LONG = 10, SCRATCH_SCORE = 11 };
+                   SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8, SCRATCH_EDIT = 9, SCRATCH_ALIGN_LONG = 10, SCRATCH_SCORE = 11, SCRATCH_SPOT = 12 };
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out);
 int stream_scratch_release();       // frees the calling device's scratch buffers
 // pinned staging of a small host table on its way to the device (shadow.hip): grow-only, and the previous upload out of it has
@@ -454,6 +454,12 @@ int64_t ctc_align_long_workspace(int n, const int32_t* frames, const int32_t* nl
 // [label0_j, label0_j + nlabels_j); one fp64 log-probability per pair, in the caller's order
 int launch_ctc_score(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int m, const int32_t* utt_of,
                      const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank, double* logp, hipStream_t s);
+// CTC phrase search (spot.hip; w2v2_ctc_spot): the same addressing and pairs; per pair max_hits slots of (score, begin, end), the
+// true count, and optionally z_t and c_t of every frame from trace0_j on (-1: none)
+int launch_ctc_spot(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int m, const int32_t* utt_of,
+                    const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank, int delim,
+                    const double* min_score, int max_hits, double* hit_score, int32_t* hit_begin, int32_t* hit_end, int32_t* count,
+                    double* trace_score, int32_t* trace_begin, const int64_t* trace0, hipStream_t s);
 // CTC prefix beam search (beam.hip; w2v2_ctc_beam_search): the same addressing of the logits; per utterance nbest rows of max_len
 // labels, their lengths (-1: no such hypothesis), score (CTC log-probability over the kept paths) and total (score + LM)
 int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int beam_width,

@@ -547,6 +547,14 @@ int w2v2_ctc_score(const float* logits, int32_t V, int32_t n, const int64_t* row
                             reinterpret_cast<hipStream_t>(stream));
 }
 
+int w2v2_ctc_spot(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t m, const int32_t* utt_of,
+                  const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int32_t blank, int32_t delim,
+                  const double* min_score, int32_t max_hits, double* hit_score, int32_t* hit_begin, int32_t* hit_end, int32_t* count,
+                  double* trace_score, int32_t* trace_begin, const int64_t* trace0, void* stream) {
+    return launch_ctc_spot(logits, V, n, row0, frames, m, utt_of, labels, label0, nlabels, blank, delim, min_score, max_hits, hit_score,
+                           hit_begin, hit_end, count, trace_score, trace_begin, trace0, reinterpret_cast<hipStream_t>(stream));
+}
+
 int w2v2_ctc_beam_search(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t blank,
                          int32_t beam_width, int32_t nbest, const float* lm_table, int32_t lm_order, float lm_alpha, float lm_beta,
                          int32_t max_len, int32_t* labels_out, int32_t* length, double* score, double* total, void* stream) {

@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_PKG_ROOT, "lib", "libw2v2.so")
 MAX_CONV_LAYERS = 16
 ALIGN_MAX_LABELS = 8191          # W2V2_ALIGN_MAX_LABELS: labels per utterance of w2v2_ctc_align
 SCORE_MAX_LABELS = 8191          # W2V2_SCORE_MAX_LABELS: labels per pair of w2v2_ctc_score
+SPOT_MAX_LABELS = 256            # W2V2_SPOT_MAX_LABELS: labels per phrase of w2v2_ctc_spot
 BEAM_MAX_WIDTH = 64              # W2V2_BEAM_MAX_WIDTH, W2V2_BEAM_MAX_VOCAB: limits of w2v2_ctc_beam_search
 BEAM_MAX_VOCAB = 64
 CUTS_CHUNK = 1024                # W2V2_CUTS_CHUNK: frames per block of w2v2_ctc_pause_cuts
@@ -89,6 +90,7 @@ PROTOTYPES = {
     "w2v2_ctc_align_long": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I64, _P]),
     "w2v2_ctc_align_long_workspace": (_I64, [_I32, _P, _P, _I32, _I32]),
     "w2v2_ctc_score": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _P, _P]),
+    "w2v2_ctc_spot": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "w2v2_ctc_beam_search": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_float, C.c_float, _I32, _P, _P, _P, _P, _P]),
     "w2v2_ctc_beam_search_words": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, C.POINTER(W2V2WordLM), _I32, C.c_float, C.c_float,
                                              C.c_float, _I32, _I32, _P, _P, _P, _P, _P]),

@@ -787,6 +787,33 @@ class Wav2Vec2ForCTC(TFKerasModel):
         logp = ctc_score(logits, ids, blank=self.config.pad_id)
         return [(float(v), float(v) / int(l.shape[0])) for v, l in zip(logp, logits)]
 
+    def search(self, waveforms, phrases, tokenizer=None, sampling_rate=None, normalize=False, whole_words=True, **options):
+        """Where phrases are spoken: `predict_packed(waveforms)`, then wav2vec2.spotting.find_phrases on the packed logits in place,
+        every phrase in every recording (blank = config.pad_id, the word delimiter the tokenizer's "|").  A phrase is text, encoded
+        with `tokenizer` through wav2vec2.spotting.phrase_labels (`whole_words=True` puts the word delimiter on both ends), or a
+        sequence of ids, used as it is.  `options`: find_phrases' margin_per_label, min_score, max_hits, exact, chunk_frames,
+        overlap_frames, delimiter_id.  Returns, per recording, the hits of all phrases sorted by start, each a
+        wav2vec2.spotting.PhraseSpan(text, start_s, end_s, score, logp) with start_s = begin * prod(strides) / 16000 and end_s =
+        (end + 1) * prod(strides) / 16000, the clock of `align`.  `sampling_rate`, `normalize`: as `predict_packed`."""
+        from .spotting import search_logits
+        seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
+        logits = self.predict_packed(waveforms, sampling_rate, normalize)
+        return search_logits(logits, phrases, tokenizer, self.config.pad_id, seconds_per_frame, whole_words, **options)
+
+    def search_long(self, waveform, phrases, tokenizer=None, window_s=20.0, margin_s=2.0, normalize=True, max_stream_s=1200.0,
+                    sampling_rate=None, whole_words=True, **options):
+        """`search` over recordings of any length: `predict_long(waveform, ...)`, then the same search on the stitched logits.
+        `waveform`: one recording or a list of them; returns the PhraseSpan list of the recording (a list of such lists for a
+        list).  `chunk_frames` / `overlap_frames` (find_phrases) spread one long recording over the device."""
+        import torch
+        from .spotting import search_logits
+        single = isinstance(waveform, (np.ndarray, torch.Tensor)) and getattr(waveform, "ndim", 0) == 1
+        seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
+        logits = self.predict_long(waveform, window_s, margin_s, normalize, max_stream_s, sampling_rate)
+        spans = search_logits([logits] if single else logits, phrases, tokenizer, self.config.pad_id, seconds_per_frame, whole_words,
+                              **options)
+        return spans[0] if single else spans
+
     def transcribe(self, waveforms, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False, sampling_rate=None, normalize=False,
                    rescore=False, confidence=False, posterior_scale=1.0):
         """Text: `predict_packed(waveforms)`, then the CTC prefix beam search on the packed logits in place

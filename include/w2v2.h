@@ -307,6 +307,41 @@ int w2v2_ctc_score(const float* logits_dev, int32_t V, int32_t n, const int64_t*
                    const int32_t* utt_of_host, const int32_t* labels_dev, const int64_t* label0_host, const int32_t* nlabels_host,
                    int32_t blank, double* logp_dev, void* stream);
 
+/* CTC phrase search (csrc/spot.hip): where in a recording a label string is spoken, for m (recording, phrase) pairs
+ * in one call.  Model-free, with w2v2_ctc_score's addressing of recordings and pairs; asynchronous on `stream`.
+ *   recording i: logits_dev rows [row0_host[i], row0_host[i] + frames_host[i]) of V fp32 (read in place; pairs share rows)
+ *   pair j:      searches recording utt_of_host[j] for labels_dev[label0_host[j] .. + nlabels_host[j]) (int32, device), l_0 .. l_{U-1}
+ * Definition.  S = 2U - 1 states, ext[2k] = l_k, ext[2k + 1] = blank: no leading or trailing blank state, a hit begins on a frame of
+ * its first label and ends on a frame of its last.  m_t = max_v x_t(v) (fp32); e_t(v) = (double)x_t(v) - (double)m_t, <= 0 and 0 for
+ * the argmax: a path's score is ln P(path) - ln P(greedy path) over the same frames.  A state carries a score d (fp64) and the begin
+ * frame b (int32) of the path that produced it; before frame 0 d = -inf, b = -1.  At frame t the candidates of state s are taken
+ * in this order, each compared with a strict > against the best so far: (1) stay, (d_{t-1}(s), b_{t-1}(s)); (2) s >= 1: from s - 1;
+ * (3) s >= 2, s even and ext[s] != ext[s-2]: from s - 2; (4) s == 0: the fresh start (0.0, t).  d_t(s) = chosen + e_t(ext[s]), b_t(s)
+ * the chosen begin, so ties keep the earlier begin.  The phrase ends at t with z_t = d_t(S-1), c_t = b_t(S-1).
+ * Recording edges, delim >= 0 and U >= 3 only (delim = -1: off): l_0 == delim: state 2 also gets the fresh start (0.0, 0) at t = 0,
+ * compared last; l_{U-1} == delim: at t = T - 1, d_t(S-2) and then d_t(S-3) also compete for (z, c), each with strict >.
+ * Hits, one pass over t with thr = min_score_host[j]: frame t is a candidate (z_t, c_t, t) when z_t >= thr and z_t > -inf.  One
+ * current hit is kept; a candidate with c_t <= cur.end overlaps it and replaces it only if z_t > cur.score; a candidate that does
+ * not overlap flushes the current hit to the output and becomes the current hit; the last one is flushed behind the last frame.
+ *   hit_score_dev (m, max_hits) fp64, hit_begin_dev / hit_end_dev (m, max_hits) int32: the hits in time order, end inclusive; NaN and
+ *                 -1 behind the stored ones.  count_dev (m): the TRUE number of hits, which may exceed max_hits.
+ *   trace_score_dev fp64 / trace_begin_dev int32: both NULL, or both given with trace0_host (m): z_t and c_t of every frame of pair j
+ *                 at entries [trace0_host[j], + frames), -1: no trace for this pair.
+ * Per pair, the others unaffected: a recording with a NaN logit, a +inf logit or a frame whose max is -inf, or a label outside
+ * [0, V) or equal to the blank, gives count -1, empty slots and an empty trace (NaN, -1).  -inf logits are otherwise legal; fewer
+ * frames than labels simply yields no hit.  Every step is one fp64 compare-select or add in a fixed order and there is no multiply:
+ * the results do not depend on the other pairs, their order or repetition.  No atomics.
+ * W2V2_EINVAL before anything is launched: a null pointer, n, m or max_hits < 1, V < 2, frames_i < 1, a negative offset, utt_of_j
+ * outside [0, n), nlabels_j outside [1, W2V2_SPOT_MAX_LABELS], blank outside [0, V), delim neither -1 nor a label other than the
+ * blank, a NaN min_score, only one trace pointer (or trace pointers without trace0_host).  Scratch is the library's grow-only
+ * scratch; synchronises with the previous call's table upload (host-side), otherwise enqueued on `stream`. */
+#define W2V2_SPOT_MAX_LABELS 256
+int w2v2_ctc_spot(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host, int32_t m,
+                  const int32_t* utt_of_host, const int32_t* labels_dev, const int64_t* label0_host, const int32_t* nlabels_host,
+                  int32_t blank, int32_t delim, const double* min_score_host, int32_t max_hits, double* hit_score_dev,
+                  int32_t* hit_begin_dev, int32_t* hit_end_dev, int32_t* count_dev, double* trace_score_dev, int32_t* trace_begin_dev,
+                  const int64_t* trace0_host, void* stream);
+
 /* CTC prefix beam search (exact definition in csrc/beam.hip): the nbest most probable transcripts of each utterance,
  * optionally fused with a character n-gram language model.  Model-free, like w2v2_ctc_align, and with the same addressing:
  *   utterance i: logits_dev rows [row0_host[i], row0_host[i] + frames_host[i]) of V fp32
