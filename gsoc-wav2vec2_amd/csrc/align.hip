@@ -13,36 +13,30 @@
 // The recursion runs on raw logits (sum_t lse_t is common to every path); every step is one IEEE fp64 compare-select and add in a
 // fixed order, so the decisions are bit-identical to an fp64 numpy loop on every input, ties and NaN included.
 // Outputs per frame (sum T_i, back to back): token[t] = ext[s_t]; label_index[t] = k for state 2k+1, -1 for a blank;
-// frame_logp[t] = x_t(token[t]) - lse_t as fp32, lse_t the fp64 log-sum-exp of the frame (fp32 max, then lane-strided fp64 sums
-// and a fixed butterfly, as ctc_softmax_kernel).  Per utterance: score = delta_{T-1}(s_end) - sum_t lse_t (fp64).
+// frame_logp[t] = x_t(token[t]) - lse_t as fp32, lse_t the fp64 log-sum-exp of the frame (ctc_lattice.h: frame_lse).  Per
+// utterance: score = delta_{T-1}(s_end) - sum_t lse_t (fp64).
 // An utterance is feasible only if T >= U + R, R = #{k >= 1: l_k = l_{k-1}}: otherwise score = -inf, token = label_index = -1 and
 // frame_logp = NaN.  A label outside [0, V) or equal to the blank (labels are on the device): score = NaN, the same -1 / NaN rows.
 //
-// Structure.  align_lse_kernel: one wave per frame, lse_t into the workspace (fully parallel).  align_viterbi_kernel: one block per
-// utterance.  A thread owns P consecutive state pairs (2k blank, 2k+1 label k) in registers as fp64; per step the only value that
-// crosses threads is the odd state of a thread's last pair, through a double-buffered LDS array behind ONE LDS-only barrier
-// (s_waitcnt lgkmcnt(0); s_barrier -- as ctc.hip: the step's fire-and-forget backpointer stores are not drained).  The P + 1
-// emissions a step needs are loaded PF steps ahead.  Backpointers: 2 bits per state, 4 per pair; a thread collects its 4P bits of
+// Structure.  lds_barrier, frame_lse and block_count are ctc_lattice.h's; the step and the backtrace below have a copy in
+// align_long.hip, which must stay the same operations in the same order.  align_lse_kernel: one wave per frame, lse_t into the
+// workspace.  align_viterbi_kernel: one block per utterance.
+// A thread owns P consecutive state pairs in registers as fp64; per step the only value that crosses threads is the odd state of
+// a thread's last pair, through a double-buffered LDS array behind ONE lds_barrier (the step's fire-and-forget backpointer stores
+// are not drained).  The P + 1 emissions a step needs are loaded PF steps ahead.  Backpointers: a thread collects its 4P bits of
 // G = 8 / P steps in one 32-bit word and stores it (a plain vector store) to the workspace: word (g, tid) of an utterance holds
 // steps 1 + gG .. gG + G, i.e. T S / 4 bytes per utterance, rounded up to the block's thread count.  P comes from the largest U
-// at launch (1, 2, 4 while at most 256 threads suffice, i.e. up to 1023 labels; 8 beyond, up to 1024 threads: 8191 labels).  After
-// the sweep the same block backtracks: the state moves down by at most 2 per step, so the backpointer words of the next C frames lie
+// at launch (pairs_per_thread: 1, 2, 4 up to 1023 labels on 256 threads; 8 beyond, up to 1024 threads: 8191 labels).  After the
+// sweep the same block backtracks: the state moves down by at most 2 per step, so the backpointer words of the next C frames lie
 // in a window of C frames x C pairs; the block loads that window into LDS, one lane walks it, and the block writes the C frames'
 // outputs (token, label index, frame_logp) in parallel.  No atomics: two identical calls give identical bits.
-#include "common.h"
+#include "ctc_lattice.h"
 
 #include <algorithm>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <vector>
 
 namespace w2v2 {
 namespace {
-
-constexpr int ALIGN_MAX_THREADS = 1024;
-constexpr int ALIGN_CHUNK = 128;             // frames per backtrace window
-constexpr int ALIGN_WIN_WORDS = 2304;        // >= ((C - 1) / G + 2) ((C - 1) / P + 2) <= 2193 for C = 128, any P
 
 struct AlignSeg {
     int64_t row0;      // first logits row
@@ -65,46 +59,21 @@ struct AlignArgs {
     int V, blank, nt;       // nt: threads per block (= backpointer words per step group)
 };
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // lse_t of frame t of utterance blockIdx.y: one wave per frame, grid.x covers the longest utterance
 __global__ __launch_bounds__(256) void align_lse_kernel(AlignArgs a) {
     const AlignSeg sg = a.segs[blockIdx.y];
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= sg.T) return;
-    const int lane = threadIdx.x & 63;
-    const float* __restrict__ r = a.logits + (sg.row0 + t) * a.V;
-    float m = -INFINITY;
-    for (int v = lane; v < a.V; v += 64) m = fmaxf(m, r[v]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    double acc = 0.0;
-    for (int v = lane; v < a.V; v += 64) acc += exp((double)r[v] - (double)m);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (lane == 0) a.lse[sg.out0 + t] = (double)m + log(acc);
-}
-
-// number of threads of the block for which pred holds (wave ballots, then the waves in order)
-__device__ __forceinline__ int block_count(bool pred, int* red) {
-    const unsigned long long b = __ballot(pred);
-    __syncthreads();                                    // (red may still be read by the previous call)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
-    int c = 0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) c += red[i];
-    return c;
+    frame_lse(a.logits, a.V, sg.row0, sg.T, a.lse + sg.out0);
 }
 
 template <int P>
-__global__ __launch_bounds__(P == 8 ? ALIGN_MAX_THREADS : 256) void align_viterbi_kernel(AlignArgs a) {
+__global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_viterbi_kernel(AlignArgs a) {
     constexpr int G = 8 / P;                 // steps per backpointer word
     constexpr int PF = P == 8 ? 2 : 8;       // steps the emissions are loaded ahead (a multiple of G; P = 8: registers)
     constexpr double NEG = -__builtin_inf();
-    __shared__ double xv[2][ALIGN_MAX_THREADS + 1];      // exchange: entry i + 1 = thread i's last odd state; entry 0 = "state -1"
-    __shared__ uint32_t win[ALIGN_WIN_WORDS];            // backtrace window of backpointer words
-    __shared__ int path[ALIGN_CHUNK + 1];
-    __shared__ int red[ALIGN_MAX_THREADS / 64];
+    __shared__ double xv[2][LATTICE_MAX_THREADS + 1];    // exchange: entry i + 1 = thread i's last odd state; entry 0 = "state -1"
+    __shared__ uint32_t win[LATTICE_WIN_WORDS];          // backtrace window of backpointer words
+    __shared__ int path[LATTICE_CHUNK + 1];
+    __shared__ int red[LATTICE_MAX_THREADS / 64];
     __shared__ double fin[2];
     __shared__ int s_cur;
 
@@ -155,7 +124,7 @@ __global__ __launch_bounds__(P == 8 ? ALIGN_MAX_THREADS : 256) void align_viterb
         ev[0] = (double)lg[blank];
         if (U >= 1) od[0] = (double)lg[lj[0]];
     }
-    for (int i = tid; i < 2 * (ALIGN_MAX_THREADS + 1); i += NT) (&xv[0][0])[i] = NEG;
+    for (int i = tid; i < 2 * (LATTICE_MAX_THREADS + 1); i += NT) (&xv[0][0])[i] = NEG;
     __syncthreads();
     xv[0][tid + 1] = od[P - 1];
     uint32_t* __restrict__ bpw = a.bp + sg.bp0 + tid;
@@ -239,15 +208,15 @@ __global__ __launch_bounds__(P == 8 ? ALIGN_MAX_THREADS : 256) void align_viterb
         if (tid == 0) a.score[blockIdx.x] = dend - acc;
     }
 
-    // ---- backtrace, ALIGN_CHUNK frames per window ----
+    // ---- backtrace, LATTICE_CHUNK frames per window ----
     const uint32_t* __restrict__ bpg = a.bp + sg.bp0;
     int t_hi = T - 1;
     __syncthreads();
     while (true) {
-        const int t_lo = max(0, t_hi - ALIGN_CHUNK);
+        const int t_lo = max(0, t_hi - LATTICE_CHUNK);
         const int s_hi = s_cur;
         // frames (t_lo, t_hi] read the words of step groups (t - 1) / G and of pairs (s_hi >> 1) - C + 1 .. s_hi >> 1
-        const int ph = s_hi >> 1, pl = max(0, ph - ALIGN_CHUNK + 1);
+        const int ph = s_hi >> 1, pl = max(0, ph - LATTICE_CHUNK + 1);
         const int w_lo = pl / P, ncol = ph / P - w_lo + 1;
         const int g_lo = t_lo / G, nrow = t_hi > t_lo ? (t_hi - 1) / G - g_lo + 1 : 0;
         for (int i = tid; i < nrow * ncol; i += NT) {
@@ -280,15 +249,6 @@ __global__ __launch_bounds__(P == 8 ? ALIGN_MAX_THREADS : 256) void align_viterb
     }
 }
 
-// pinned staging of the per-utterance table, per device; the previous call's copy out of it completes before it is rewritten
-std::mutex g_stage_mu;
-std::map<int, PinnedStage> g_stage;
-
-template <int P>
-void launch_viterbi(const AlignArgs& a, int n, hipStream_t s) {
-    W2V2_LAUNCH(align_viterbi_kernel<P>, dim3((unsigned)n), dim3((unsigned)a.nt), 0, s, a);
-}
-
 }  // namespace
 
 int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
@@ -309,9 +269,9 @@ int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, con
         Umax = std::max(Umax, (int)nlabels[i]);
         Tmax = std::max(Tmax, (int)frames[i]);
     }
-    // pairs per thread from the largest label count: the fewest that need at most 256 threads, else 8 (up to 1024 threads)
+    // pairs per thread from the largest label count
     const int pairs = Umax + 1;
-    const int P = pairs <= 256 ? 1 : pairs <= 512 ? 2 : pairs <= 1024 ? 4 : 8, G = 8 / P;
+    const int P = pairs_per_thread(pairs), G = 8 / P;
     const int nt = (((pairs + P - 1) / P + 63) / 64) * 64;
     std::vector<AlignSeg> segs((size_t)n);
     int64_t out = 0, words = 0;
@@ -321,8 +281,7 @@ int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, con
         words += (int64_t)((frames[i] - 1 + G - 1) / G) * nt;
     }
     // workspace: the table | lse (fp64, sum T_i) | backpointer words
-    const size_t tab_bytes = ((size_t)n * sizeof(AlignSeg) + 255) & ~(size_t)255;
-    const size_t lse_bytes = ((size_t)out * sizeof(double) + 255) & ~(size_t)255;
+    const size_t tab_bytes = up256((size_t)n * sizeof(AlignSeg)), lse_bytes = up256((size_t)out * sizeof(double));
     void* raw = nullptr;
     if (int e = stream_scratch(SCRATCH_ALIGN, s, tab_bytes + lse_bytes + (size_t)std::max<int64_t>(words, 1) * sizeof(uint32_t), &raw))
         return e;
@@ -339,23 +298,13 @@ int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, con
     a.V = V;
     a.blank = blank;
     a.nt = nt;
-    {
-        int dev = 0;
-        W2V2_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(g_stage_mu);
-        PinnedStage& st = g_stage[dev];
-        const size_t bytes = (size_t)n * sizeof(AlignSeg);
-        if (int e = pinned_stage_begin(st, bytes, (size_t)16 << 10)) return e;
-        memcpy(st.p, segs.data(), bytes);
-        if (int e = pinned_stage_upload(st, raw, bytes, s)) return e;
-    }
+    if (int e = staged_upload(SCRATCH_ALIGN, s, raw, {{segs.data(), (size_t)n * sizeof(AlignSeg), 0}}, (size_t)16 << 10)) return e;
     // (work for the profile: the sweep's ~12 fp64 operations per state and step; the logits read once by the lse pass)
     ProfScope ps(nullptr, FAM_CTC, 12.0 * (double)out * (2.0 * Umax + 1.0), 4.0 * (double)out * V, s);
     W2V2_LAUNCH(align_lse_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);
-    if (P == 1) launch_viterbi<1>(a, n, s);
-    else if (P == 2) launch_viterbi<2>(a, n, s);
-    else if (P == 4) launch_viterbi<4>(a, n, s);
-    else launch_viterbi<8>(a, n, s);
+    dispatch_pairs(P, [&](auto p) {
+        W2V2_LAUNCH(align_viterbi_kernel<decltype(p)::value>, dim3((unsigned)n), dim3((unsigned)a.nt), 0, s, a);
+    });
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }

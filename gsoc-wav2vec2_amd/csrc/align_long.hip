@@ -7,7 +7,7 @@
 // operation and no order, so every output, the score's bits included, equals w2v2_ctc_align's wherever that one accepts the input.
 //
 // Tiling.  States come in pairs (blank 2k, label 2k + 1); a recording has U + 1 pairs.  A STRIP is `sp` consecutive pairs: one
-// block's share, sp / P threads with P pairs each (P picked from sp as align.hip picks it from U + 1; the block is rounded up to whole
+// block's share, sp / P threads with P pairs each (P = pairs_per_thread(sp); the block is rounded up to whole
 // waves, the spare threads hold no state and store nothing).  A PANEL is `pf` consecutive steps (step t reads frame t - 1 and writes
 // frame t; panel p holds steps 1 + p pf ...).  Tile (p, q) runs align.hip's per-step recursion over panel p for strip q.  It needs
 // from outside only
@@ -23,28 +23,22 @@
 // no grid barrier, no flag and no atomic.  The host builds the tile table sorted by diagonal and uploads it once; a launch gets an
 // offset and a count.  Every tile runs, also those outside the reachable band (their values are -inf by the recursion itself).
 //
-// Pre-pass: align_long_lse_kernel (lse_t, one wave per frame, as align.hip) and align_long_init_kernel (one block per recording:
+// Pre-pass: align_long_lse_kernel (lse_t, one wave per frame) and align_long_init_kernel (one block per recording:
 // any label outside [0, V) or equal to the blank, R = labels equal to their predecessor -> a flag per recording; the carry row at
 // frame 0).  Tiles of a flagged recording return at once.  Finish: one block per recording takes the end state from the carry row,
 // sums the score, and runs align.hip's windowed backtrace (128 frames x 128 pairs of backpointer words in LDS, one lane walking, the
 // block writing the outputs); flagged recordings get their -1 / NaN rows here.  Backpointers: 2 bits per state in align.hip's word
 // layout, word (g, q (sp / P) + tid) = step group g of thread tid of strip q, i.e. column pair / P of a row of strips x (sp / P)
 // words; pf is a multiple of 8, so a step group never straddles a panel.  All backpointer, carry and column indices are 64-bit.
-#include "common.h"
+#include "ctc_lattice.h"
 
 #include <algorithm>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <vector>
 
 namespace w2v2 {
 namespace {
 
-constexpr int LONG_MAX_THREADS = 1024;
-constexpr int LONG_CHUNK = 128;              // frames per backtrace window
 constexpr int LONG_COL_CHUNK = 512;          // steps whose boundary-column values a tile holds in LDS at a time (a multiple of 8)
-constexpr int LONG_WIN_WORDS = 2304;         // >= ((C - 1) / G + 2) ((C - 1) / P + 2) <= 2193 for C = 128, any P
 constexpr int LONG_DEFAULT_STRIP = 1024;     // pairs per strip and frames per panel when the caller passes 0: the fastest of the
 constexpr int LONG_DEFAULT_PANEL = 512;      // measured grid (profiles/align_long.md)
 constexpr int64_t LONG_DEFAULT_CAP = (int64_t)32 << 30;
@@ -81,24 +75,10 @@ struct LongArgs {
     int sp, pf, wps;        // pairs per strip, steps per panel, backpointer words per strip and step group (= sp / P: the threads that hold states)
 };
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// lse_t of frame t of recording blockIdx.y: one wave per frame, the operations of align.hip's align_lse_kernel in its order
+// lse_t of frame t of recording blockIdx.y: one wave per frame, grid.x covers the longest recording
 __global__ __launch_bounds__(256) void align_long_lse_kernel(LongArgs a) {
     const LongSeg sg = a.segs[blockIdx.y];
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= sg.T) return;
-    const int lane = threadIdx.x & 63;
-    const float* __restrict__ r = a.logits + (sg.row0 + t) * a.V;
-    float m = -INFINITY;
-    for (int v = lane; v < a.V; v += 64) m = fmaxf(m, r[v]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    double acc = 0.0;
-    for (int v = lane; v < a.V; v += 64) acc += exp((double)r[v] - (double)m);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (lane == 0) a.lse[sg.out0 + t] = (double)m + log(acc);
+    frame_lse(a.logits, a.V, sg.row0, sg.T, a.lse + sg.out0);
 }
 
 // one block per recording: the two checks that span strips (integer counts: any order gives the same flag), then the carry row at
@@ -138,11 +118,11 @@ __global__ __launch_bounds__(256) void align_long_init_kernel(LongArgs a) {
 
 // tile tile0 + blockIdx.x of the table: align.hip's sweep over one panel for one strip
 template <int P>
-__global__ __launch_bounds__(P == 8 ? LONG_MAX_THREADS : 256) void align_long_tile_kernel(LongArgs a, int64_t tile0) {
+__global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_long_tile_kernel(LongArgs a, int64_t tile0) {
     constexpr int G = 8 / P;                 // steps per backpointer word
     constexpr int PD = P == 8 ? 2 : 8;       // steps the emissions and the column are loaded ahead (a multiple of G)
     constexpr double NEG = -__builtin_inf();
-    __shared__ double xv[2][LONG_MAX_THREADS + 1];       // exchange: entry i + 1 = thread i's last odd state (entry 0 is not used: thread 0 reads cl)
+    __shared__ double xv[2][LATTICE_MAX_THREADS + 1];    // exchange: entry i + 1 = thread i's last odd state (entry 0 is not used: thread 0 reads cl)
     __shared__ double cl[LONG_COL_CHUNK];                // the column of the strip below, frames cb - 1 .. of the current chunk of steps
 
     const LongTile tl = a.tiles[tile0 + blockIdx.x];
@@ -266,8 +246,8 @@ template <int P>
 __global__ __launch_bounds__(256) void align_long_finish_kernel(LongArgs a) {
     constexpr int G = 8 / P;
     constexpr double NEG = -__builtin_inf();
-    __shared__ uint32_t win[LONG_WIN_WORDS];             // backtrace window of backpointer words
-    __shared__ long long path[LONG_CHUNK + 1];
+    __shared__ uint32_t win[LATTICE_WIN_WORDS];          // backtrace window of backpointer words
+    __shared__ long long path[LATTICE_CHUNK + 1];
     __shared__ long long s_cur;
 
     const LongSeg sg = a.segs[blockIdx.x];
@@ -304,16 +284,16 @@ __global__ __launch_bounds__(256) void align_long_finish_kernel(LongArgs a) {
         if (tid == 0) a.score[blockIdx.x] = dend - acc;
     }
 
-    // ---- backtrace, LONG_CHUNK frames per window ----
+    // ---- backtrace, LATTICE_CHUNK frames per window ----
     const uint32_t* __restrict__ bpg = a.bp + sg.bp0;
     const int64_t W = (int64_t)sg.strips * a.wps;
     int t_hi = T - 1;
     __syncthreads();
     while (true) {
-        const int t_lo = max(0, t_hi - LONG_CHUNK);
+        const int t_lo = max(0, t_hi - LATTICE_CHUNK);
         const long long s_hi = s_cur;
         // frames (t_lo, t_hi] read the words of step groups (t - 1) / G and of pairs (s_hi >> 1) - C + 1 .. s_hi >> 1
-        const int ph = (int)(s_hi >> 1), pl = max(0, ph - LONG_CHUNK + 1);
+        const int ph = (int)(s_hi >> 1), pl = max(0, ph - LATTICE_CHUNK + 1);
         const int w_lo = pl / P, ncol = ph / P - w_lo + 1;
         const int g_lo = t_lo / G, nrow = t_hi > t_lo ? (t_hi - 1) / G - g_lo + 1 : 0;
         for (int i = tid; i < nrow * ncol; i += NT) {
@@ -346,19 +326,6 @@ __global__ __launch_bounds__(256) void align_long_finish_kernel(LongArgs a) {
     }
 }
 
-// pinned staging of the two tables, per device; the previous call's copy out of it completes before it is rewritten
-std::mutex g_long_stage_mu;
-std::map<int, PinnedStage> g_long_stage;
-
-template <int P>
-void launch_tiles(const LongArgs& a, int64_t tile0, int64_t count, int nt, hipStream_t s) {
-    W2V2_LAUNCH(align_long_tile_kernel<P>, dim3((unsigned)count), dim3((unsigned)nt), 0, s, a, tile0);
-}
-template <int P>
-void launch_finish(const LongArgs& a, int n, hipStream_t s) {
-    W2V2_LAUNCH(align_long_finish_kernel<P>, dim3((unsigned)n), dim3(256), 0, s, a);
-}
-
 // the geometry of a call and the bytes of its workspace, from the shapes alone
 struct LongPlan {
     int sp, pf, P, G, nt, wps, Tmax, Umax;
@@ -366,8 +333,6 @@ struct LongPlan {
     size_t tile_bytes, seg_bytes, lse_bytes, flag_bytes, carry_bytes, col_bytes, bp_bytes;
     int64_t total;          // INT64_MAX when it does not fit
 };
-
-inline size_t up256(unsigned __int128 b) { return (size_t)((b + 255) & ~(unsigned __int128)255); }
 
 int long_plan(int n, const int32_t* frames, const int32_t* nlabels, int strip_pairs, int panel_frames, LongPlan& pl) {
     W2V2_REQUIRE(frames && nlabels, "ctc_align_long: null argument");
@@ -383,12 +348,11 @@ int long_plan(int n, const int32_t* frames, const int32_t* nlabels, int strip_pa
         pl.Tmax = std::max(pl.Tmax, (int)frames[i]);
         pl.Umax = std::max(pl.Umax, (int)nlabels[i]);
     }
-    // a strip no wider than the longest recording needs (whole waves of pairs); pairs per thread from the strip as align.hip picks
-    // them from U + 1: the fewest that need at most 256 threads, else 8 (up to 1024 threads)
+    // a strip no wider than the longest recording needs (whole waves of pairs); pairs per thread from the strip
     const int64_t need_pairs = (((int64_t)pl.Umax + 1 + 63) / 64) * 64;
     pl.sp = (int)std::min<int64_t>(strip_pairs ? strip_pairs : LONG_DEFAULT_STRIP, need_pairs);
     pl.pf = panel_frames ? panel_frames : LONG_DEFAULT_PANEL;
-    pl.P = pl.sp <= 256 ? 1 : pl.sp <= 512 ? 2 : pl.sp <= 1024 ? 4 : 8;
+    pl.P = pairs_per_thread(pl.sp);
     pl.G = 8 / pl.P;
     pl.wps = pl.sp / pl.P;
     pl.nt = ((pl.wps + 63) / 64) * 64;
@@ -503,17 +467,11 @@ int launch_ctc_align_long(const float* logits, int V, int n, const int64_t* row0
     a.sp = pl.sp;
     a.pf = pl.pf;
     a.wps = pl.wps;
-    {
-        int dev = 0;
-        W2V2_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(g_long_stage_mu);
-        PinnedStage& st = g_long_stage[dev];
-        const size_t tb = (size_t)pl.tiles * sizeof(LongTile), bytes = pl.tile_bytes + (size_t)n * sizeof(LongSeg);
-        if (int e = pinned_stage_begin(st, bytes, (size_t)64 << 10)) return e;
-        if (tb) memcpy(st.p, tiles.data(), tb);
-        memcpy(static_cast<char*>(st.p) + pl.tile_bytes, segs.data(), (size_t)n * sizeof(LongSeg));
-        if (int e = pinned_stage_upload(st, raw, bytes, s)) return e;      // (one upload: the recordings' table lies right behind the tiles)
-    }
+    // (one upload: the recordings' table lies right behind the tiles)
+    if (int e = staged_upload(SCRATCH_ALIGN_LONG, s, raw,
+                              {{tiles.data(), (size_t)pl.tiles * sizeof(LongTile), 0}, {segs.data(), (size_t)n * sizeof(LongSeg), pl.tile_bytes}},
+                              (size_t)64 << 10))
+        return e;
     // (work for the profile: the sweep's ~12 fp64 operations per state and step; the logits read once by the lse pass)
     double work = 0.0;
     for (int i = 0; i < n; ++i) work += 12.0 * (double)frames[i] * (2.0 * nlabels[i] + 1.0);
@@ -523,15 +481,11 @@ int launch_ctc_align_long(const float* logits, int V, int n, const int64_t* row0
     for (int64_t d = 0; d < pl.diagonals; ++d) {
         const int64_t off = first[(size_t)d], count = first[(size_t)d + 1] - off;
         if (!count) continue;
-        if (pl.P == 1) launch_tiles<1>(a, off, count, pl.nt, s);
-        else if (pl.P == 2) launch_tiles<2>(a, off, count, pl.nt, s);
-        else if (pl.P == 4) launch_tiles<4>(a, off, count, pl.nt, s);
-        else launch_tiles<8>(a, off, count, pl.nt, s);
+        dispatch_pairs(pl.P, [&](auto p) {
+            W2V2_LAUNCH(align_long_tile_kernel<decltype(p)::value>, dim3((unsigned)count), dim3((unsigned)pl.nt), 0, s, a, off);
+        });
     }
-    if (pl.P == 1) launch_finish<1>(a, n, s);
-    else if (pl.P == 2) launch_finish<2>(a, n, s);
-    else if (pl.P == 4) launch_finish<4>(a, n, s);
-    else launch_finish<8>(a, n, s);
+    dispatch_pairs(pl.P, [&](auto p) { W2V2_LAUNCH(align_long_finish_kernel<decltype(p)::value>, dim3((unsigned)n), dim3(256), 0, s, a); });
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }

@@ -3,7 +3,7 @@
 // this header).  Model-free, like ctc.hip and align.hip.
 //
 // Definition (tests/beam_reference.py implements exactly this).  x_t(v) is the fp32 logit widened to fp64, lp_t(v) = x_t(v) - lse_t
-// (lse_t reduced as align_lse_kernel reduces it), lse2(a, b) = max + log1p(exp(-|a - b|)) with -inf neutral.  A beam entry is a
+// (lse_t: ctc_lattice.h, frame_lse), lse2(a, b) = max + log1p(exp(-|a - b|)) with -inf neutral.  A beam entry is a
 // prefix p (labels, no blanks) with pb, pnb (log-probability of the frame paths so far that collapse to p and end in a blank / a
 // non-blank) and lm(p).  Start: the empty prefix, pb = 0, pnb = -inf, lm = 0.  Per frame, from every entry, tot = lse2(pb, pnb):
 //   stay    p     : pb'  = tot + lp(blank);  pnb' = pnb + lp(p[-1]) if p is not empty
@@ -16,7 +16,7 @@
 // digits base V, oldest first, blank-filled.  An utterance with a non-finite lse_t (a NaN or +inf logit, a frame of -inf only)
 // has no hypothesis: every length -1, score = total = NaN.
 //
-// Structure.  beam_lse_kernel: one wave per frame (as align_lse_kernel).  beam_search_kernel: one block of 256 threads (one wave
+// Structure.  beam_lse_kernel: one wave per frame.  beam_search_kernel: one block of 256 threads (one wave
 // per SIMD) per utterance, every score fp64.  Why 256: the W V <= 4096 candidate keys of a step live in registers, 16 per thread at
 // the limits (32 VGPRs for the keys); more waves would only add to every barrier of a step that is latency-, not throughput-bound.
 //  * Prefixes are nodes (parent, label) of a per-utterance trie in the workspace, one 8-byte plain store per NEW survivor; node
@@ -65,13 +65,10 @@
 //    step; the c == d rule of an entry is evaluated ONCE, by the lane that writes the entry into the next beam, and kept with it
 //    (dlm, dstate; dstate -1 = dropped), so a step's delimiter candidates and the finalisation only read it; an entry that stays
 //    copies it.  lookup is a binary search per backoff level, state 0 indexed directly.  No barrier is added to a step.
-#include "common.h"
+#include "ctc_lattice.h"
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -128,26 +125,13 @@ struct BeamBufWord : BeamBuf {
     int wnode[BEAM_W], lmstate[BEAM_W], dstate[BEAM_W];
 };
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 __global__ __launch_bounds__(256) void beam_lse_kernel(BeamArgs a) {
     const BeamSeg sg = a.segs[blockIdx.y];
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= sg.T) return;
-    const int lane = threadIdx.x & 63;
-    const float* __restrict__ r = a.logits + (sg.row0 + t) * a.V;
-    float m = -INFINITY;
-    for (int v = lane; v < a.V; v += 64) m = fmaxf(m, r[v]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    double acc = 0.0;
-    for (int v = lane; v < a.V; v += 64) acc += exp((double)r[v] - (double)m);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (lane == 0) a.lse[sg.lse0 + t] = (double)m + log(acc);
+    frame_lse(a.logits, a.V, sg.row0, sg.T, a.lse + sg.lse0);
 }
 
-__device__ __forceinline__ double lse2(double a, double b) {
+// the search's own lse2 (header; tests/beam_reference.py): log1p and early returns, so other bits than ctc_lattice.h's lse2
+__device__ __forceinline__ double beam_lse2(double a, double b) {
     constexpr double NEG = -__builtin_inf();
     if (a == NEG) return b;
     if (b == NEG) return a;
@@ -419,8 +403,8 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t
             const int j = tid, last = B.last[j], i = B.mi[j];
             const double pbn = B.tot[j] + lp[blank];
             double pnbn = last >= 0 ? B.pnb[j] + lp[last] : NEG;
-            if (i >= 0) pnbn = lse2(pnbn, (last == B.last[i] ? B.pb[i] : B.tot[i]) + lp[last]);
-            const double totn = lse2(pbn, pnbn);
+            if (i >= 0) pnbn = beam_lse2(pnbn, (last == B.last[i] ? B.pb[i] : B.tot[i]) + lp[last]);
+            const double totn = beam_lse2(pbn, pnbn);
             spb[j] = pbn;
             spnb[j] = pnbn;
             stot[j] = totn;
@@ -662,10 +646,6 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t
     }
 }
 
-// pinned staging of the per-utterance table, per device; the previous call's copy out of it completes before it is rewritten
-std::mutex g_stage_mu;
-std::map<int, PinnedStage> g_stage;
-
 // the checks, the workspace and the launches both entries share; `a` arrives with its language model fields set
 int beam_run(BeamWordArgs& a, bool word, const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank,
              int beam_width, int nbest, float lm_alpha, float lm_beta, int max_len, int32_t* labels_out, int32_t* length, double* score,
@@ -697,8 +677,7 @@ int beam_run(BeamWordArgs& a, bool word, const float* logits, int V, int n, cons
         nn += (int64_t)frames[i] * beam_width + 1;
     }
     // workspace: the table | lse (fp64, sum T_i) | trie nodes (sum T_i W + 1)
-    const size_t tab_bytes = ((size_t)n * sizeof(BeamSeg) + 255) & ~(size_t)255;
-    const size_t lse_bytes = ((size_t)out * sizeof(double) + 255) & ~(size_t)255;
+    const size_t tab_bytes = up256((size_t)n * sizeof(BeamSeg)), lse_bytes = up256((size_t)out * sizeof(double));
     void* raw = nullptr;
     if (int e = stream_scratch(SCRATCH_BEAM, s, tab_bytes + lse_bytes + (size_t)nn * sizeof(u64), &raw)) return e;
     a.logits = logits;
@@ -716,16 +695,7 @@ int beam_run(BeamWordArgs& a, bool word, const float* logits, int V, int n, cons
     a.W = beam_width;
     a.nbest = nbest;
     a.max_len = max_len;
-    {
-        int dev = 0;
-        W2V2_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(g_stage_mu);
-        PinnedStage& st = g_stage[dev];
-        const size_t bytes = (size_t)n * sizeof(BeamSeg);
-        if (int e = pinned_stage_begin(st, bytes, (size_t)16 << 10)) return e;
-        memcpy(st.p, segs.data(), bytes);
-        if (int e = pinned_stage_upload(st, raw, bytes, s)) return e;
-    }
+    if (int e = staged_upload(SCRATCH_BEAM, s, raw, {{segs.data(), (size_t)n * sizeof(BeamSeg), 0}}, (size_t)16 << 10)) return e;
     // (work for the profile: about 4 fp64 operations per candidate and step; the logits read once by the lse pass)
     ProfScope ps(nullptr, FAM_CTC, 4.0 * (double)out * beam_width * V, 4.0 * (double)out * V, s);
     W2V2_LAUNCH(beam_lse_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);

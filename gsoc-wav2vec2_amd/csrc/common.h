@@ -6,6 +6,8 @@
 #include <stdio.h>
 
 #include <atomic>
+#include <initializer_list>
+#include <type_traits>
 
 #include <string>
 
@@ -393,9 +395,10 @@ int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int widt
 
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
 enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4, SCRATCH_BEAM = 5, SCRATCH_WINDOWS = 6,
-                   SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8, SCRATCH_EDIT = 9, SCRATCH_ALIGN_LONG = 10, SCRATCH_SCORE = 11, SCRATCH_SPOT = 12 };
+                   SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8, SCRATCH_EDIT = 9, SCRATCH_ALIGN_LONG = 10, SCRATCH_SCORE = 11, SCRATCH_SPOT = 12, SCRATCH_SLOTS = 13 };
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out);
-int stream_scratch_release();       // frees the calling device's scratch buffers
+int stream_scratch_release();       // frees the calling device's scratch buffers and staged-upload buffers
+inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }      // the parts of a workspace begin at multiples of 256 bytes
 // pinned staging of a small host table on its way to the device (shadow.hip): grow-only, and the previous upload out of it has
 // completed before it is rewritten.  One per owner, who serialises its users: a model; a device's entry of a library-wide map, under that map's lock.
 struct PinnedStage {
@@ -406,6 +409,22 @@ struct PinnedStage {
 int pinned_stage_begin(PinnedStage& st, size_t bytes, size_t min_bytes);             // waits for the previous upload; st.p then holds >= bytes (a new buffer: >= min_bytes)
 int pinned_stage_upload(PinnedStage& st, void* dst, size_t bytes, hipStream_t s);    // dst <- st.p[0, bytes) on s
 void pinned_stage_free(PinnedStage& st);
+// A family's host tables on their way into its workspace (shadow.hip), through a library-owned pinned buffer per (slot, device)
+// (a new one: >= min_bytes).  Waits (host-side) for the slot's previous upload on this device only: one lock per slot.
+// staged_fill: fill(stage) writes `bytes` bytes in place, which are then uploaded to dst on s.
+// staged_upload: the blocks, in ascending order of offset and not overlapping, go to their byte offsets, the gaps between them
+// are zeroed, and [0, end of the last block) is uploaded.
+int staged_fill_raw(int slot, hipStream_t s, void* dst, size_t bytes, size_t min_bytes, void (*fill)(void* stage, void* ctx), void* ctx);
+template <class F>
+int staged_fill(int slot, hipStream_t s, void* dst, size_t bytes, size_t min_bytes, F&& fill) {
+    return staged_fill_raw(slot, s, dst, bytes, min_bytes, [](void* stage, void* ctx) { (*static_cast<std::remove_reference_t<F>*>(ctx))(stage); },
+                           const_cast<void*>(static_cast<const void*>(&fill)));
+}
+struct StageBlock {
+    const void* src;
+    size_t bytes, offset;
+};
+int staged_upload(int slot, hipStream_t s, void* dst, std::initializer_list<StageBlock> blocks, size_t min_bytes);
 // one layer's q | k | v projections <-> the packed (H, 3H) kernel and (3H) bias (shadow.hip); unpack skips null targets
 int launch_qkv_pack(float* packed_w, float* packed_b, const float* const w[3], const float* const b[3], int H, hipStream_t s);
 int launch_qkv_pack_layers(float* const* packed_w, float* const* packed_b, const float* const* w, const float* const* b, int layers, int H, hipStream_t s);

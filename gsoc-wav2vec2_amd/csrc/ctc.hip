@@ -28,7 +28,7 @@
 // against ~1e-7 per step of the fp32 exp / log on differences above).  Inputs that break it: a frame in which a needed label has
 // softmax probability below e^-745 (fp64 exp flushes to 0), or CTC_NORM consecutive frames whose needed labels all sit below
 // 1e-77: that path is dropped where log space would have charged it its > 700 nats.
-#include "common.h"
+#include "ctc_lattice.h"
 
 namespace w2v2 {
 namespace {
@@ -56,10 +56,6 @@ struct CtcArgs {
     int B, T, V, U, blank, SP;
 };
 
-// Barrier of the recursion's steps: what must be visible across the block are the LDS exchange entries, so the wave waits for its LDS
-// traffic only.  __syncthreads() also drains vmcnt -- the step's fire-and-forget stores of alpha / beta to the workspace -- and a
-// store's round trip (~1 us) then becomes the step time (rounds 1-5 paid exactly that: 0.73 us per step).
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ int f64_exponent(double v) { return (int)((__double_as_longlong(v) >> 52) & 0x7FF); }
 __device__ __forceinline__ double shift2(double v, int sh) { return ldexp(v, sh < CTC_SHIFT_MIN ? CTC_SHIFT_MIN : sh); }
 // bring the pair (ev, od) x 2^E to the form where the larger mantissa lies in [1, 2); both zero (or subnormal): E = CTC_NOEXP

@@ -30,9 +30,6 @@
 #include "common.h"
 
 #include <algorithm>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <numeric>
 #include <vector>
 
@@ -144,10 +141,6 @@ __global__ __launch_bounds__(EDIT_WAVES * 64) void edit_ws_kernel(const int32_t*
     for (int p = w; p < count; p += W) edit_pair(tok, pairs[p], row, out);
 }
 
-// pinned staging of the pair table, per device; the previous call's copy out of it completes before it is rewritten
-std::mutex g_stage_mu;
-std::map<int, PinnedStage> g_stage;
-
 }  // namespace
 
 int launch_edit_distance(const int32_t* tokens, int64_t n_tokens, int n_pairs, const int64_t* hyp0, const int32_t* hyp_len,
@@ -188,26 +181,20 @@ int launch_edit_distance(const int32_t* tokens, int64_t n_tokens, int n_pairs, c
     const int ws_blocks = std::min((n_ws + EDIT_WAVES - 1) / EDIT_WAVES, EDIT_WS_WAVES / EDIT_WAVES);
     const int64_t ws_row = (ws_ref + 63) & ~63;
     // workspace: the table | the boundary rows of the workspace launch
-    const size_t tab_bytes = ((size_t)n_pairs * sizeof(EditPair) + 255) & ~(size_t)255;
+    const size_t tab_bytes = up256((size_t)n_pairs * sizeof(EditPair));
     const size_t ws_bytes = (size_t)ws_blocks * EDIT_WAVES * (size_t)ws_row * sizeof(uint32_t);
     void* raw = nullptr;
     if (int e = stream_scratch(SCRATCH_EDIT, s, tab_bytes + ws_bytes, &raw)) return e;
     const EditPair* pairs = static_cast<const EditPair*>(raw);
     uint32_t* ws = reinterpret_cast<uint32_t*>(static_cast<char*>(raw) + tab_bytes);
-    {
-        int dev = 0;
-        W2V2_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(g_stage_mu);
-        PinnedStage& st = g_stage[dev];
-        const size_t bytes = (size_t)n_pairs * sizeof(EditPair);
-        if (int e = pinned_stage_begin(st, bytes, (size_t)64 << 10)) return e;
-        EditPair* t = static_cast<EditPair*>(st.p);
+    auto fill = [&](void* stage) {                       // (the rows are written straight into the pinned stage)
+        EditPair* t = static_cast<EditPair*>(stage);
         for (int k = 0; k < n_pairs; ++k) {
             const int p = order[k];
             t[k] = EditPair{hyp0[p], ref0[p], hyp_len[p], ref_len[p], p, 0};
         }
-        if (int e = pinned_stage_upload(st, raw, bytes, s)) return e;
-    }
+    };
+    if (int e = staged_fill(SCRATCH_EDIT, s, raw, (size_t)n_pairs * sizeof(EditPair), (size_t)64 << 10, fill)) return e;
     // (work for the profile: ~10 integer operations per cell; the tokens are read once per stripe)
     ProfScope ps(nullptr, FAM_CTC, 10.0 * work, 0.0, s);
     if (n_ws > 0) W2V2_LAUNCH(edit_ws_kernel, dim3((unsigned)ws_blocks), dim3(EDIT_WAVES * 64), 0, s, tokens, pairs, n_ws, ws, ws_row, out);

@@ -7,8 +7,6 @@
 // (feature_extractor.py:92-95) -> Wav2Vec2Encoder.call (encoder.py:251-276) ->
 // TransformerLayer.call (encoder.py:111-134) -> lm_head.
 #include <algorithm>
-#include <map>
-#include <mutex>
 #include <string.h>
 
 #include <string>
@@ -599,10 +597,6 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
 // eps of Wav2Vec2Processor._normalize (processor.py: (x - mean) / sqrt(var + 1e-5))
 constexpr double kWaveNormEps = 1e-5;
 
-// pinned staging of w2v2_op_normalize_windows' table, per device (as beam.hip's)
-static std::mutex g_norm_stage_mu;
-static std::map<int, PinnedStage> g_norm_stage;
-
 // one piece of a packed stream: samples [src0, src0 + len) of the caller's buffer, computed as an utterance of its own; rows
 // [keep0, keep0 + keepn) of its frames go to the caller's output
 struct StreamPiece {
@@ -770,20 +764,11 @@ int w2v2_op_normalize_windows(const float* wave, int32_t n, const int64_t* sampl
         segs[i] = PackSeg{L, samples[i], sample0[i], 0, 0, 0, 0};
         L += samples[i];
     }
-    const size_t tab_bytes = ((size_t)n * sizeof(PackSeg) + 255) & ~(size_t)255;
+    const size_t tab_bytes = up256((size_t)n * sizeof(PackSeg));
     void* raw = nullptr;
     if (int e = stream_scratch(SCRATCH_WINDOWS, s, tab_bytes + (size_t)n * 2 * sizeof(double), &raw)) return e;
     double* stats = reinterpret_cast<double*>(static_cast<char*>(raw) + tab_bytes);
-    {
-        int dev = 0;
-        W2V2_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(g_norm_stage_mu);
-        PinnedStage& st = g_norm_stage[dev];
-        const size_t bytes = (size_t)n * sizeof(PackSeg);
-        if (int e = pinned_stage_begin(st, bytes, (size_t)16 << 10)) return e;
-        memcpy(st.p, segs.data(), bytes);
-        if (int e = pinned_stage_upload(st, raw, bytes, s)) return e;
-    }
+    if (int e = staged_upload(SCRATCH_WINDOWS, s, raw, {{segs.data(), (size_t)n * sizeof(PackSeg), 0}}, (size_t)16 << 10)) return e;
     const PackSeg* dsegs = static_cast<const PackSeg*>(raw);
     if (int e = launch_pack_stats(wave, dsegs, n, kWaveNormEps, stats, s)) return e;
     return launch_pack_scatter(wave, out, L, dsegs, n, s, stats);

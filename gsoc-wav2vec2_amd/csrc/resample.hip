@@ -20,11 +20,7 @@
 // kernel: consecutive outputs per lane, samples read from global memory with the same bounds; the same chain, the same bits.
 #include <algorithm>
 #include <cmath>
-#include <map>
-#include <mutex>
 #include <vector>
-
-#include <string.h>
 
 #include "common.h"
 
@@ -138,10 +134,6 @@ __global__ __launch_bounds__(RS_NT) void resample_kernel(RsArgs a) {
     // 3.
     for (int i = tid; i < cnt; i += RS_NT) y[i] = ys[i];
 }
-
-// pinned staging of the filter and segment tables, per device; the previous call's copy out of it completes before it is rewritten
-std::mutex g_stage_mu;
-std::map<int, PinnedStage> g_stage;
 
 // I0(x), the modified Bessel function of the first kind and order zero: its power series, sum_k ((x / 2)^k / k!)^2
 double bessel_i0(double x) {
@@ -269,16 +261,9 @@ int launch_resample(const float* in, int n, const int64_t* in0, const int64_t* i
     const size_t filt_bytes = ((size_t)n_filters * sizeof(RsFilt) + 15) & ~(size_t)15, seg_bytes = (size_t)n * sizeof(RsSeg);
     void* raw = nullptr;
     if (int e = stream_scratch(SCRATCH_RESAMPLE, s, filt_bytes + seg_bytes, &raw)) return e;
-    {
-        int dev = 0;
-        W2V2_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(g_stage_mu);
-        PinnedStage& st = g_stage[dev];
-        if (int e = pinned_stage_begin(st, filt_bytes + seg_bytes, (size_t)16 << 10)) return e;
-        memcpy(st.p, filts.data(), (size_t)n_filters * sizeof(RsFilt));
-        memcpy(static_cast<char*>(st.p) + filt_bytes, segs.data(), seg_bytes);
-        if (int e = pinned_stage_upload(st, raw, filt_bytes + seg_bytes, s)) return e;
-    }
+    if (int e = staged_upload(SCRATCH_RESAMPLE, s, raw,
+                              {{filts.data(), (size_t)n_filters * sizeof(RsFilt), 0}, {segs.data(), seg_bytes, filt_bytes}}, (size_t)16 << 10))
+        return e;
     RsArgs a{};
     a.in = in;
     a.out = out;

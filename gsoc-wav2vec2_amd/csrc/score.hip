@@ -2,8 +2,8 @@
 // it (the CTC forward recursion), for m (utterance, label string) pairs at once (w2v2_ctc_score).
 //
 // Definition (tests/score_reference.py implements exactly this in fp64 numpy).  x_t(v) is the fp32 logit widened to fp64;
-// lp_t(v) = x_t(v) - lse_t, lse_t the fp64 log-sum-exp of the frame computed as align.hip's align_lse_kernel computes it (fp32
-// max, then lane-strided fp64 sums and a fixed butterfly).  ext is the label string with blanks interleaved, S = 2U + 1 states,
+// lp_t(v) = x_t(v) - lse_t, lse_t the fp64 log-sum-exp of the frame (ctc_lattice.h: frame_lse, the one the aligners and the beam
+// search use).  ext is the label string with blanks interleaved, S = 2U + 1 states,
 // ext[2k] = blank, ext[2k + 1] = l_k.  lse() below is the log-sum-exp of its finite arguments, -inf when all are -inf.
 //   alpha_0(0) = lp_0(blank); alpha_0(1) = lp_0(l_0) if U >= 1; every other state -inf.
 //   alpha_t(s) = lse(alpha_{t-1}(s), alpha_{t-1}(s-1), [ext[s] != blank and ext[s] != ext[s-2]] alpha_{t-1}(s-2)) + lp_t(ext[s]).
@@ -21,25 +21,21 @@
 // Structure.  score_lse_kernel: one wave per frame, lse_t of every UTTERANCE (not pair) into the workspace.
 // score_alpha_kernel: one block per pair.  A thread owns P consecutive state pairs (2k blank, 2k + 1 label k) in registers; per
 // step the only value that crosses threads is the odd state of a thread's last pair, through a double-buffered LDS array behind
-// ONE LDS-only barrier (s_waitcnt lgkmcnt(0); s_barrier), and the P + 1 emissions and lse_t of a step are loaded PF steps
-// ahead (8, 8, 4, 1 for P = 1, 2, 4, 8: what 128 registers at 1024 threads leave) -- align.hip's sweep without the backpointers.  P is chosen from the pair's OWN label count (1, 2, 4 up to 255, 511, 1023
+// ONE lds_barrier, and the P + 1 emissions and lse_t of a step are loaded PF steps ahead (8, 8, 4, 1 for P = 1, 2, 4, 8: what
+// 128 registers at 1024 threads leave) -- align.hip's sweep without the backpointers, on lse2 and lse3 of ctc_lattice.h.
+// P is chosen from the pair's OWN label count (pairs_per_thread: 1, 2, 4 up to 255, 511, 1023
 // labels on 256 threads; 8 beyond, up to 1024 threads), the call launches one grid per P that occurs, and within a grid the pairs
 // are ordered by utterance so that an utterance's rows stay in L2 for its hypotheses.  A state's value is the same sequence of
 // fp64 operations whatever P, the block size or the neighbours: each pair is computed as if alone, and its bits do not depend
 // on the other pairs of the call, their order or repetition.  No atomics.
-#include "common.h"
+#include "ctc_lattice.h"
 
 #include <algorithm>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <numeric>
 #include <vector>
 
 namespace w2v2 {
 namespace {
-
-constexpr int SCORE_MAX_THREADS = 1024;
 
 struct ScoreUtt {
     int64_t row0;      // first logits row
@@ -65,56 +61,18 @@ struct ScoreArgs {
     int V, blank;
 };
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// lse_t of frame t of utterance blockIdx.y: one wave per frame, grid.x covers the longest utterance (as align_lse_kernel)
+// lse_t of frame t of utterance blockIdx.y: one wave per frame, grid.x covers the longest utterance
 __global__ __launch_bounds__(256) void score_lse_kernel(ScoreArgs a) {
     const ScoreUtt u = a.utts[blockIdx.y];
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= u.T) return;
-    const int lane = threadIdx.x & 63;
-    const float* __restrict__ r = a.logits + (u.row0 + t) * a.V;
-    float m = -INFINITY;
-    for (int v = lane; v < a.V; v += 64) m = fmaxf(m, r[v]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    double acc = 0.0;
-    for (int v = lane; v < a.V; v += 64) acc += exp((double)r[v] - (double)m);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (lane == 0) a.lse[u.lse0 + t] = (double)m + log(acc);
-}
-
-// number of threads of the block for which pred holds (wave ballots, then the waves in order)
-__device__ __forceinline__ int block_count(bool pred, int* red) {
-    const unsigned long long b = __ballot(pred);
-    __syncthreads();                                    // (red may still be read by the previous call)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
-    int c = 0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) c += red[i];
-    return c;
-}
-
-// lse of two / three values that are finite or -inf (never NaN, never +inf); -inf when all are
-__device__ __forceinline__ double lse2(double a, double b) {
-    const double hi = fmax(a, b), lo = fmin(a, b);
-    const double r = hi + log(1.0 + exp(lo - hi));
-    return hi > -__builtin_inf() ? r : -__builtin_inf();
-}
-__device__ __forceinline__ double lse3(double a, double b, double c) {
-    const double hi = fmax(a, b), lo = fmin(a, b);
-    const double m = fmax(hi, c), y = fmin(hi, c);
-    const double r = m + log(1.0 + exp(y - m) + exp(lo - m));
-    return m > -__builtin_inf() ? r : -__builtin_inf();
+    frame_lse(a.logits, a.V, u.row0, u.T, a.lse + u.lse0);
 }
 
 template <int P>
-__global__ __launch_bounds__(P == 8 ? SCORE_MAX_THREADS : 256) void score_alpha_kernel(ScoreArgs a, int pair0) {
+__global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void score_alpha_kernel(ScoreArgs a, int pair0) {
     constexpr int PF = P == 8 ? 1 : P == 4 ? 4 : 8;      // steps the emissions are loaded ahead (registers)
     constexpr double NEG = -__builtin_inf();
-    __shared__ double xv[2][SCORE_MAX_THREADS + 1];      // exchange: entry i + 1 = thread i's last odd state; entry 0 = "state -1"
-    __shared__ int red[SCORE_MAX_THREADS / 64];
+    __shared__ double xv[2][LATTICE_MAX_THREADS + 1];    // exchange: entry i + 1 = thread i's last odd state; entry 0 = "state -1"
+    __shared__ int red[LATTICE_MAX_THREADS / 64];
     __shared__ double fin[2];
 
     const ScorePair sg = a.pairs[pair0 + blockIdx.x];
@@ -165,7 +123,7 @@ __global__ __launch_bounds__(P == 8 ? SCORE_MAX_THREADS : 256) void score_alpha_
         ev[0] = (double)lg[blank] - l0;
         if (U >= 1) od[0] = (double)lg[lj[0]] - l0;
     }
-    for (int i = tid; i < 2 * (SCORE_MAX_THREADS + 1); i += NT) (&xv[0][0])[i] = NEG;
+    for (int i = tid; i < 2 * (LATTICE_MAX_THREADS + 1); i += NT) (&xv[0][0])[i] = NEG;
     __syncthreads();
     xv[0][tid + 1] = od[P - 1];
     float qb[PF], ql[PF][P];                             // x_t(blank), x_t(l_k) of the next PF steps
@@ -225,20 +183,7 @@ __global__ __launch_bounds__(P == 8 ? SCORE_MAX_THREADS : 256) void score_alpha_
     if (tid == 0) a.logp[sg.out] = U >= 1 ? lse2(fin[0], fin[1]) : fin[0];
 }
 
-// pinned staging of the tables, per device; the previous call's copy out of it completes before it is rewritten
-std::mutex g_stage_mu;
-std::map<int, PinnedStage> g_stage;
-
-inline int score_pairs_per_thread(int U) {
-    const int pairs = U + 1;
-    return pairs <= 256 ? 1 : pairs <= 512 ? 2 : pairs <= 1024 ? 4 : 8;
-}
-
-template <int P>
-void launch_alpha(const ScoreArgs& a, int pair0, int count, int Umax, hipStream_t s) {
-    const int nt = (((Umax + 1 + P - 1) / P + 63) / 64) * 64;
-    W2V2_LAUNCH(score_alpha_kernel<P>, dim3((unsigned)count), dim3((unsigned)nt), 0, s, a, pair0);
-}
+inline int score_pairs_per_thread(int U) { return pairs_per_thread(U + 1); }
 
 }  // namespace
 
@@ -282,8 +227,7 @@ int launch_ctc_score(const float* logits, int V, int n, const int64_t* row0, con
         pairs[i] = ScorePair{u.row0, u.lse0, label0[j], u.T, nlabels[j], j, 0};
     }
     // workspace: the utterance table | the pair table | lse (fp64, sum T_i)
-    const size_t utt_bytes = ((size_t)n * sizeof(ScoreUtt) + 255) & ~(size_t)255;
-    const size_t pair_bytes = ((size_t)m * sizeof(ScorePair) + 255) & ~(size_t)255;
+    const size_t utt_bytes = up256((size_t)n * sizeof(ScoreUtt)), pair_bytes = up256((size_t)m * sizeof(ScorePair));
     void* raw = nullptr;
     if (int e = stream_scratch(SCRATCH_SCORE, s, utt_bytes + pair_bytes + (size_t)out * sizeof(double), &raw)) return e;
     ScoreArgs a;
@@ -295,18 +239,10 @@ int launch_ctc_score(const float* logits, int V, int n, const int64_t* row0, con
     a.logp = logp;
     a.V = V;
     a.blank = blank;
-    {
-        int dev = 0;
-        W2V2_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(g_stage_mu);
-        PinnedStage& st = g_stage[dev];
-        const size_t bytes = utt_bytes + (size_t)m * sizeof(ScorePair);
-        if (int e = pinned_stage_begin(st, bytes, (size_t)64 << 10)) return e;
-        memset(st.p, 0, utt_bytes);
-        memcpy(st.p, utts.data(), (size_t)n * sizeof(ScoreUtt));
-        memcpy(static_cast<char*>(st.p) + utt_bytes, pairs.data(), (size_t)m * sizeof(ScorePair));
-        if (int e = pinned_stage_upload(st, raw, bytes, s)) return e;
-    }
+    if (int e = staged_upload(SCRATCH_SCORE, s, raw,
+                              {{utts.data(), (size_t)n * sizeof(ScoreUtt), 0}, {pairs.data(), (size_t)m * sizeof(ScorePair), utt_bytes}},
+                              (size_t)64 << 10))
+        return e;
     // (work for the profile: ~100 fp64 operations per state and step, the exp and log included; the logits read once by the lse pass)
     ProfScope ps(nullptr, FAM_CTC, 100.0 * work, 4.0 * (double)out * V, s);
     W2V2_LAUNCH(score_lse_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);
@@ -314,10 +250,10 @@ int launch_ctc_score(const float* logits, int V, int n, const int64_t* row0, con
         const int P = score_pairs_per_thread(pairs[i].U);
         int e = i, Umax = 0;
         for (; e < m && score_pairs_per_thread(pairs[e].U) == P; ++e) Umax = std::max(Umax, (int)pairs[e].U);
-        if (P == 1) launch_alpha<1>(a, i, e - i, Umax, s);
-        else if (P == 2) launch_alpha<2>(a, i, e - i, Umax, s);
-        else if (P == 4) launch_alpha<4>(a, i, e - i, Umax, s);
-        else launch_alpha<8>(a, i, e - i, Umax, s);
+        const int nt = (((Umax + 1 + P - 1) / P + 63) / 64) * 64;
+        dispatch_pairs(P, [&](auto p) {
+            W2V2_LAUNCH(score_alpha_kernel<decltype(p)::value>, dim3((unsigned)(e - i)), dim3((unsigned)nt), 0, s, a, i);
+        });
         i = e;
     }
     W2V2_HIP_CHECK(hipGetLastError());

@@ -22,11 +22,7 @@
 // repeated call gives the same bits.
 #include <algorithm>
 #include <cmath>
-#include <map>
-#include <mutex>
 #include <vector>
-
-#include <string.h>
 
 #include "common.h"
 
@@ -230,10 +226,6 @@ __global__ __launch_bounds__(CUTS_NT) void cuts_offset_kernel(CutArgs a) {
     if (threadIdx.x == 0) a.count[blockIdx.x] = running;
 }
 
-// pinned staging of the per-utterance table, per device; the previous call's copy out of it completes before it is rewritten
-std::mutex g_stage_mu;
-std::map<int, PinnedStage> g_stage;
-
 }  // namespace
 
 int launch_ctc_pause_cuts(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int delim,
@@ -260,9 +252,8 @@ int launch_ctc_pause_cuts(const float* logits, int V, int n, const int64_t* row0
         Tmax = std::max(Tmax, (int)frames[i]);
     }
     // workspace: the table | codes (sum T_i) | summary, carry_in (chunks) | counts, offsets (chunks)
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t tab_bytes = pad((size_t)n * sizeof(CutSeg)), code_bytes = pad((size_t)codes * sizeof(int32_t));
-    const size_t carry_bytes = pad((size_t)chunks * sizeof(Carry)), int_bytes = pad((size_t)chunks * sizeof(int32_t));
+    const size_t tab_bytes = up256((size_t)n * sizeof(CutSeg)), code_bytes = up256((size_t)codes * sizeof(int32_t));
+    const size_t carry_bytes = up256((size_t)chunks * sizeof(Carry)), int_bytes = up256((size_t)chunks * sizeof(int32_t));
     void* raw = nullptr;
     if (int e = stream_scratch(SCRATCH_CUTS, s, tab_bytes + code_bytes + 2 * carry_bytes + 2 * int_bytes, &raw)) return e;
     char* p = static_cast<char*>(raw);
@@ -283,16 +274,7 @@ int launch_ctc_pause_cuts(const float* logits, int V, int n, const int64_t* row0
     a.delim = delim;
     a.min_pause = min_pause;
     a.max_cuts = max_cuts;
-    {
-        int dev = 0;
-        W2V2_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(g_stage_mu);
-        PinnedStage& st = g_stage[dev];
-        const size_t bytes = (size_t)n * sizeof(CutSeg);
-        if (int e = pinned_stage_begin(st, bytes, (size_t)16 << 10)) return e;
-        memcpy(st.p, segs.data(), bytes);
-        if (int e = pinned_stage_upload(st, raw, bytes, s)) return e;
-    }
+    if (int e = staged_upload(SCRATCH_CUTS, s, raw, {{segs.data(), (size_t)n * sizeof(CutSeg), 0}}, (size_t)16 << 10)) return e;
     // (work for the profile: the logits read once by the frame pass; a comparison or two per logit)
     ProfScope ps(nullptr, FAM_CTC, 2.0 * (double)codes * V, 4.0 * (double)codes * V, s);
     // slots behind an utterance's pauses hold -1

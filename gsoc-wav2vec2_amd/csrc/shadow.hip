@@ -2,6 +2,7 @@
 // operand to on its own, materialised once so the GEMM streams 2 bytes per element instead of 4 and skips the
 // conversion.  Activations get their shadow from the producing kernel (GEMM / LayerNorm / conv0 / attention
 // epilogues); the kernels here serve the weights, which change only when variables are set or the optimizer steps.
+#include <cstring>
 #include <map>
 #include <tuple>
 #include <mutex>
@@ -196,6 +197,13 @@ namespace {
 struct StreamScratch { void* p = nullptr; size_t bytes = 0; };
 std::mutex g_scratch_mu;
 std::map<std::tuple<int, int, hipStream_t>, StreamScratch> g_scratch;
+// the pinned buffers of staged_upload, per (slot, device).  One lock per slot: an upload waits for the slot's previous one
+// (pinned_stage_begin) under it, and two families must not wait on each other's
+struct SlotStage {
+    std::mutex mu;
+    std::map<int, PinnedStage> dev;
+};
+SlotStage g_stage[SCRATCH_SLOTS];
 }  // namespace
 
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out) {
@@ -213,19 +221,28 @@ int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out) {
     return W2V2_OK;
 }
 
-// Release every scratch buffer of the calling thread's current device (w2v2_release_scratch in the C ABI): the entries are
-// otherwise kept for the life of the process.
+// Release every scratch buffer and every staged-upload buffer of the calling thread's current device (w2v2_release_scratch in the
+// C ABI): the entries are otherwise kept for the life of the process.
 int stream_scratch_release() {
     int dev = 0;
     W2V2_HIP_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_scratch_mu);
-    for (auto it = g_scratch.begin(); it != g_scratch.end();) {
-        if (std::get<1>(it->first) == dev) {
-            if (it->second.p) (void)hipFree(it->second.p);
-            it = g_scratch.erase(it);
-        } else {
-            ++it;
+    {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        for (auto it = g_scratch.begin(); it != g_scratch.end();) {
+            if (std::get<1>(it->first) == dev) {
+                if (it->second.p) (void)hipFree(it->second.p);
+                it = g_scratch.erase(it);
+            } else {
+                ++it;
+            }
         }
+    }
+    for (SlotStage& g : g_stage) {
+        std::lock_guard<std::mutex> lock(g.mu);
+        auto it = g.dev.find(dev);
+        if (it == g.dev.end()) continue;
+        pinned_stage_free(it->second);
+        g.dev.erase(it);
     }
     return W2V2_OK;
 }
@@ -257,6 +274,34 @@ void pinned_stage_free(PinnedStage& st) {
     }
     if (st.p) (void)hipHostFree(st.p);
     st = PinnedStage{};
+}
+
+int staged_fill_raw(int slot, hipStream_t s, void* dst, size_t bytes, size_t min_bytes, void (*fill)(void* stage, void* ctx), void* ctx) {
+    W2V2_REQUIRE(slot >= 0 && slot < SCRATCH_SLOTS, "staged upload: slot %d outside [0, %d)", slot, (int)SCRATCH_SLOTS);
+    int dev = 0;
+    W2V2_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_stage[slot].mu);
+    PinnedStage& st = g_stage[slot].dev[dev];
+    if (int e = pinned_stage_begin(st, bytes, min_bytes)) return e;
+    fill(st.p, ctx);
+    return pinned_stage_upload(st, dst, bytes, s);
+}
+
+int staged_upload(int slot, hipStream_t s, void* dst, std::initializer_list<StageBlock> blocks, size_t min_bytes) {
+    size_t total = 0;
+    for (const StageBlock& b : blocks) {
+        W2V2_REQUIRE(b.offset >= total, "staged upload: blocks overlap or are out of order (offset %zu behind %zu)", b.offset, total);
+        total = b.offset + b.bytes;
+    }
+    return staged_fill(slot, s, dst, total, min_bytes, [&](void* stage) {
+        char* p = static_cast<char*>(stage);
+        size_t end = 0;
+        for (const StageBlock& b : blocks) {
+            memset(p + end, 0, b.offset - end);
+            if (b.bytes) memcpy(p + b.offset, b.src, b.bytes);
+            end = b.offset + b.bytes;
+        }
+    });
 }
 
 int launch_to_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t s) {

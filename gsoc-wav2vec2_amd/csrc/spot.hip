@@ -39,9 +39,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <numeric>
 #include <type_traits>
 #include <vector>
@@ -80,7 +77,7 @@ struct SpotArgs {
     int V, blank, delim, max_hits;
 };
 
-// m_t of frame t of recording blockIdx.y: one wave per frame, grid.x covers the longest recording (as score_lse_kernel)
+// m_t of frame t of recording blockIdx.y: one wave per frame, grid.x covers the longest recording
 __global__ __launch_bounds__(256) void spot_max_kernel(SpotArgs a) {
     const SpotUtt u = a.utts[blockIdx.y];
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -360,10 +357,6 @@ __global__ __launch_bounds__(64) void spot_kernel(SpotArgs a, int pair0) {
     if (mine) a.count[sp.out] = n;
 }
 
-// pinned staging of the tables, per device; the previous call's copy out of it completes before it is rewritten
-std::mutex g_stage_mu;
-std::map<int, PinnedStage> g_stage;
-
 inline int spot_pairs_per_lane(int U) { return U <= 64 ? 1 : U <= 128 ? 2 : 4; }
 
 }  // namespace
@@ -418,8 +411,7 @@ int launch_ctc_spot(const float* logits, int V, int n, const int64_t* row0, cons
         pairs[i] = SpotPair{u.row0, u.m0, label0[j], trace_score ? trace0[j] : -1, min_score[j], u.T, nlabels[j], j, 0};
     }
     // workspace: the recording table | the pair table | m_t (fp32, sum T_i)
-    const size_t utt_bytes = ((size_t)n * sizeof(SpotUtt) + 255) & ~(size_t)255;
-    const size_t pair_bytes = ((size_t)m * sizeof(SpotPair) + 255) & ~(size_t)255;
+    const size_t utt_bytes = up256((size_t)n * sizeof(SpotUtt)), pair_bytes = up256((size_t)m * sizeof(SpotPair));
     void* raw = nullptr;
     if (int e = stream_scratch(SCRATCH_SPOT, s, utt_bytes + pair_bytes + (size_t)total * sizeof(float), &raw)) return e;
     SpotArgs a;
@@ -438,18 +430,10 @@ int launch_ctc_spot(const float* logits, int V, int n, const int64_t* row0, cons
     a.blank = blank;
     a.delim = delim;
     a.max_hits = max_hits;
-    {
-        int dev = 0;
-        W2V2_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(g_stage_mu);
-        PinnedStage& st = g_stage[dev];
-        const size_t bytes = utt_bytes + (size_t)m * sizeof(SpotPair);
-        if (int e = pinned_stage_begin(st, bytes, (size_t)64 << 10)) return e;
-        memset(st.p, 0, utt_bytes);
-        memcpy(st.p, utts.data(), (size_t)n * sizeof(SpotUtt));
-        memcpy(static_cast<char*>(st.p) + utt_bytes, pairs.data(), (size_t)m * sizeof(SpotPair));
-        if (int e = pinned_stage_upload(st, raw, bytes, s)) return e;
-    }
+    if (int e = staged_upload(SCRATCH_SPOT, s, raw,
+                              {{utts.data(), (size_t)n * sizeof(SpotUtt), 0}, {pairs.data(), (size_t)m * sizeof(SpotPair), utt_bytes}},
+                              (size_t)64 << 10))
+        return e;
     // (work for the profile: three compare-selects and an add per state and step; the logits read once by the max pass)
     ProfScope ps(nullptr, FAM_CTC, 4.0 * work, 4.0 * (double)total * V, s);
     W2V2_LAUNCH(spot_max_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);

@@ -70,8 +70,9 @@ typedef struct w2v2_model w2v2_model;
 
 const char* w2v2_last_error(void);
 const char* w2v2_version(void);
-/* Free the library-owned per-(device, stream) scratch buffers (split-K slabs, CTC alpha / beta, the aligners' workspaces) of the calling thread's
- * current device; they are otherwise kept, grow-only, for the life of the process.  The device must be idle. */
+/* Free the library-owned per-(device, stream) scratch buffers (split-K slabs, CTC alpha / beta, the aligners' workspaces) and the
+ * per-device pinned buffers their host tables are staged in, of the calling thread's current device; they are otherwise kept,
+ * grow-only, for the life of the process.  The device must be idle. */
 int w2v2_release_scratch(void);
 
 /* ---- model lifetime ------------------------------------------------------
