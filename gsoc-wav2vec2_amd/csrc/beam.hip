@@ -1,6 +1,6 @@
 // CTC prefix beam search: the n best transcripts of each of n utterances with their log-probabilities, optionally fused with a
 // character n-gram language model held as a dense table on the device, or with a word n-gram model and a lexicon (second part of
-// this header).  Model-free, like ctc.hip and align.hip.
+// this header), and with a phrase bias on top of either (third part).  Model-free, like ctc.hip and align.hip.
 //
 // Definition (tests/beam_reference.py implements exactly this).  x_t(v) is the fp32 logit widened to fp64, lp_t(v) = x_t(v) - lse_t
 // (lse_t: ctc_lattice.h, frame_lse), lse2(a, b) = max + log1p(exp(-|a - b|)) with -inf neutral.  A beam entry is a
@@ -65,6 +65,41 @@
 //    step; the c == d rule of an entry is evaluated ONCE, by the lane that writes the entry into the next beam, and kept with it
 //    (dlm, dstate; dstate -1 = dropped), so a step's delimiter candidates and the finalisation only read it; an entry that stays
 //    copies it.  lookup is a binary search per backoff level, state 0 indexed directly.  No barrier is added to a step.
+//
+// Phrase bias (contextual biasing, "hotwords"; w2v2_ctc_beam_search_biased; tests/bias_reference.py implements exactly
+// this from the prefix alone, by brute force over the phrase list, with no automaton).  On top of either search above.
+//  * A bias is a set of phrases.  Phrase h is a label string h_0 .. h_{m-1}, labels in [0, V), none the blank, with a boost b_h in
+//    nats per COUNTED label (finite, >= 0) and the weight w_h = b_h counted(h).  With `whole_words` (host) every phrase is wrapped in
+//    one leading and one trailing word delimiter; those two are not counted, every other label is, and the string in front of the
+//    first label of a prefix is one delimiter.
+//  * state(p): the longest suffix of the prefix p that is a prefix of some phrase, proper or whole; the empty string is the root.
+//    C(p): the sum of w_h over all i <= len(p) and all phrases h that p[:i] ends with: EVERY occurrence counts, overlapping and nested
+//    ones included (with the phrases NEW YORK and YORK the string NEW YORK earns both weights).
+//    phi(s) = (partial counted(s)) max{b_h : s is a PROPER prefix of h}, 0 where no such h exists and at the root: credit in advance
+//    for a phrase under way, which keeps it in the beam; partial in [0, 1], 1 by convention (not tuned), 0 = completed phrases only.
+//    The bias of a prefix is B(p) = C(p) + phi(state(p)).
+//  * Transition from state s by label c, s' = state(s + c):
+//      delta(s, c) = ([the sum of w_h, in phrase order, over the phrases h that s + c ends with] + phi(s')) - phi(s)
+//    formed in fp64 and rounded ONCE to fp32.  End of the utterance: final(s) = E(s) - phi(s), rounded once; E(s) = 0 without
+//    whole_words, else the sum of w_h over the phrases that s + delimiter ends with (the end closes a word).  So an unfinished phrase
+//    gives its credit back, at the label that leaves it or at the end, and the sum along a prefix plus final is C(p) (+ E).
+//  * Compiled on the host (wav2vec2.decoding.ContextBias): an Aho-Corasick automaton with its failure links resolved into dense tables
+//    next (n_states, V) int32, delta (n_states, V) fp32, final (n_states) fp32; state 0 the root; the blank's column next = s, delta = 0.
+//  * In the search every entry carries its state bst, a function of the prefix alone like lm; the empty prefix starts at start_state
+//    with lm = 0.  Every product or sum one fp64 operation, in this order:
+//      character table or none: lm(p + c) = ((lm(p) + alpha table[ctx, c]) + beta) + (double)delta[bst(p), c]
+//      word model             : the lm' of the rules above, for c == d and c != d alike, then + (double)delta[bst(p), c]; the cached dlm
+//                               stays the value of the word rule alone: the candidate adds its delta
+//      bst(p + c) = next[bst(p), c]
+//    Keys, the -inf drop, ties, the merging of p + c into an entry already in the beam (which keeps its own lm and bst) and bad rows
+//    are unchanged.  Finalisation, both forms: fin = lm (word model: after the open word and eos) + (double)final[bst]; total =
+//    score + fin; the final beam in descending total, equal totals by beam rank; the first nbest are returned.
+//  * In the kernel (beam_search_kernel<WORD, true>; the two <., false> instances are the searches above, instruction for
+//    instruction): bst lives in LDS arrays of its own (two halves of 64 ints beside the two beam buffers, and s_bst for the
+//    survivors' parents), so BeamBuf / BeamBufWord keep their layouts; the deltas of a thread's candidates are loaded at the top of
+//    the step beside lmv / wch (one fp32 per candidate from delta[bst[j] V + c], at most 16 per thread) and used after the match; the
+//    new state is read once, by the lane that writes the entry into the next beam, where word_end is evaluated; a stay copies it.  No
+//    barrier and no atomic is added to a step; every store is a plain vector store.
 #include "ctc_lattice.h"
 
 #include <algorithm>
@@ -111,6 +146,19 @@ struct BeamWordArgs : BeamArgs {
     double unk_penalty;
     int delim, constrained, score_eos;
 };
+
+// the device tables of a compiled phrase bias (w2v2_ctc_bias) behind the arguments of either form
+template <class Base>
+struct BeamBiasArgs : Base {
+    const int32_t* bnext;   // (n_states, V)
+    const float* bdelta;    // (n_states, V)
+    const float* bfinal;    // (n_states)
+    int bstart;
+};
+
+template <bool WORD, bool BIAS>
+using BeamKernelArgs = std::conditional_t<BIAS, BeamBiasArgs<std::conditional_t<WORD, BeamWordArgs, BeamArgs>>,
+                                          std::conditional_t<WORD, BeamWordArgs, BeamArgs>>;
 
 struct BeamBuf {
     double pb[BEAM_W], pnb[BEAM_W], tot[BEAM_W], lm[BEAM_W];
@@ -212,12 +260,14 @@ __device__ __forceinline__ void word_end(const BeamWordArgs& a, int wn, int st, 
 }
 
 // WORD: the word n-gram model with a lexicon in place of the character table (the header's second part)
-template <bool WORD>
-__global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t<WORD, BeamWordArgs, BeamArgs> a) {
+// BIAS: a phrase bias on top of either (the header's third part)
+template <bool WORD, bool BIAS>
+__global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamKernelArgs<WORD, BIAS> a) {
     constexpr double NEG = -__builtin_inf();
     using Buf = std::conditional_t<WORD, BeamBufWord, BeamBuf>;
     __shared__ Buf buf[2];
     __shared__ int s_wn[WORD ? BEAM_W : 1], s_st[WORD ? BEAM_W : 1];      // (WORD) wnode and lmstate of the survivors
+    __shared__ int bst[2][BIAS ? BEAM_W : 1], s_bst[BIAS ? BEAM_W : 1];   // (BIAS) bias state of the entries (half t & 1) and of the survivors' parents
     __shared__ double lpr[2][BEAM_RING][BEAM_V];            // lp of frames 8 (t / 8) + r, half (t / 8) & 1
     __shared__ u64 childmask[BEAM_W];
     __shared__ double spb[BEAM_W], spnb[BEAM_W], stot[BEAM_W], skey[BEAM_W];      // the stay candidates of a step
@@ -290,6 +340,7 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t
             B.dlm[0] = 0.0;
             B.dstate[0] = a.w.start_state;
         }
+        if constexpr (BIAS) bst[0][0] = a.bstart;
     }
     int nb = 1;
     __syncthreads();
@@ -316,12 +367,21 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t
         }
         // the language model's values of this thread's candidates
         // (WORD: their lexicon nodes: the child of the entry's node, -2 outside the lexicon, -1 dropped)
+        // (BIAS: their increments delta[bst, c], used after the match)
         float lmv[BEAM_KMAX];
         int wch[BEAM_KMAX];
+        float bdl[BIAS ? BEAM_KMAX : 1];
 #pragma unroll
         for (int k = 0; k < BEAM_KMAX; ++k) {
             lmv[k] = 0.f;
             wch[k] = -2;
+            if constexpr (BIAS) {
+                bdl[k] = 0.f;
+                if (k < nk) {
+                    const int j = jc[k] >> 8, c = jc[k] & 255;
+                    if (j < nb && c != blank) bdl[k] = a.bdelta[bst[t & 1][j] * V + c];
+                }
+            }
             if constexpr (WORD) {
                 if (k < nk) {
                     const int j = jc[k] >> 8, c = jc[k] & 255;
@@ -391,6 +451,7 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t
                     } else {
                         lmn = __dadd_rn(__dadd_rn(B.lm[j], __dmul_rn(alpha, (double)lmv[k])), beta);
                     }
+                    if constexpr (BIAS) lmn = __dadd_rn(lmn, (double)bdl[k]);
                     const double key = (pnbn + lmn) + 0.0;
                     if (key > NEG && keep) {
                         img[k] = key_image(key);
@@ -510,6 +571,10 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t
                             } else {
                                 s_lm[slot] = __dadd_rn(__dadd_rn(B.lm[j], __dmul_rn(alpha, (double)lmv[k])), beta);
                             }
+                            if constexpr (BIAS) {
+                                s_lm[slot] = __dadd_rn(s_lm[slot], (double)bdl[k]);
+                                s_bst[slot] = bst[t & 1][j];
+                            }
                         }
                     }
                     before_k += __popcll(bl);
@@ -551,6 +616,7 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t
                         N.dlm[cnt] = B.dlm[j];
                         N.dstate[cnt] = B.dstate[j];
                     }
+                    if constexpr (BIAS) bst[(t & 1) ^ 1][cnt] = bst[t & 1][j];
                 } else {
                     const int node = 1 + t * W + cnt;
                     nodes[node] = (u64)(uint32_t)B.node[j] << 32 | (u64)(uint32_t)c;
@@ -570,6 +636,7 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t
                         N.dlm[cnt] = dl;
                         N.dstate[cnt] = ds;
                     }
+                    if constexpr (BIAS) bst[(t & 1) ^ 1][cnt] = a.bnext[s_bst[r] * V + c];      // the new prefix' state, once
                 }
             }
         }
@@ -584,18 +651,26 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t
         __syncthreads();                                    // (also drains this step's node stores)
     }
 
-    if constexpr (WORD) {
-        // finalisation (wave 0: W <= 64): the open word ended, eos, then the entries in descending total, equal totals by beam rank
+    if constexpr (WORD || BIAS) {
+        // finalisation (wave 0: W <= 64): the open word ended, eos, the bias' end-of-utterance term, then the entries in descending
+        // total, equal totals by beam rank
         if (wave != 0) return;
         const Buf& B = buf[T & 1];
-        bool ok = lane < nb && B.dstate[lane] >= 0;
+        bool ok = lane < nb;
+        if constexpr (WORD) ok = ok && B.dstate[lane] >= 0;
         double tot = 0.0;
         if (ok) {
-            double fin = B.dlm[lane];
-            if (a.score_eos && a.w.eos >= 0) {
-                int nx;
-                fin = __dadd_rn(fin, __dmul_rn(alpha, word_lookup(a.w, B.dstate[lane], a.w.eos, &nx)));
+            double fin;
+            if constexpr (WORD) {
+                fin = B.dlm[lane];
+                if (a.score_eos && a.w.eos >= 0) {
+                    int nx;
+                    fin = __dadd_rn(fin, __dmul_rn(alpha, word_lookup(a.w, B.dstate[lane], a.w.eos, &nx)));
+                }
+            } else {
+                fin = B.lm[lane];
             }
+            if constexpr (BIAS) fin = __dadd_rn(fin, (double)a.bfinal[bst[T & 1][lane]]);
             tot = B.tot[lane] + fin;
         }
         int rank = 0;
@@ -646,10 +721,11 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(std::conditional_t
     }
 }
 
-// the checks, the workspace and the launches both entries share; `a` arrives with its language model fields set
-int beam_run(BeamWordArgs& a, bool word, const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank,
-             int beam_width, int nbest, float lm_alpha, float lm_beta, int max_len, int32_t* labels_out, int32_t* length, double* score,
-             double* total, hipStream_t s) {
+// the checks, the workspace and the launches the entries share; `a` arrives with its language model fields set; `bias` (checked by
+// the caller) or null
+int beam_run(BeamWordArgs& a, bool word, const w2v2_ctc_bias* bias, const float* logits, int V, int n, const int64_t* row0,
+             const int32_t* frames, int blank, int beam_width, int nbest, float lm_alpha, float lm_beta, int max_len,
+             int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s) {
     W2V2_REQUIRE(logits && row0 && frames && labels_out && length && score && total, "ctc_beam_search: null argument");
     W2V2_REQUIRE(n >= 1, "ctc_beam_search: %d utterances (need at least one)", n);
     W2V2_REQUIRE(V >= 1 && V <= W2V2_BEAM_MAX_VOCAB, "ctc_beam_search: vocabulary of %d entries; 1 to %d", V, W2V2_BEAM_MAX_VOCAB);
@@ -699,31 +775,37 @@ int beam_run(BeamWordArgs& a, bool word, const float* logits, int V, int n, cons
     // (work for the profile: about 4 fp64 operations per candidate and step; the logits read once by the lse pass)
     ProfScope ps(nullptr, FAM_CTC, 4.0 * (double)out * beam_width * V, 4.0 * (double)out * V, s);
     W2V2_LAUNCH(beam_lse_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);
-    if (word) W2V2_LAUNCH(beam_search_kernel<true>, dim3((unsigned)n), dim3(BEAM_NT), 0, s, a);
-    else W2V2_LAUNCH(beam_search_kernel<false>, dim3((unsigned)n), dim3(BEAM_NT), 0, s, static_cast<const BeamArgs&>(a));
+    if (bias && word) {
+        BeamBiasArgs<BeamWordArgs> b{};
+        static_cast<BeamWordArgs&>(b) = a;
+        b.bnext = bias->next_dev, b.bdelta = bias->delta_dev, b.bfinal = bias->final_dev, b.bstart = bias->start_state;
+        W2V2_LAUNCH((beam_search_kernel<true, true>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, b);
+    } else if (bias) {
+        BeamBiasArgs<BeamArgs> b{};
+        static_cast<BeamArgs&>(b) = a;
+        b.bnext = bias->next_dev, b.bdelta = bias->delta_dev, b.bfinal = bias->final_dev, b.bstart = bias->start_state;
+        W2V2_LAUNCH((beam_search_kernel<false, true>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, b);
+    } else if (word) {
+        W2V2_LAUNCH((beam_search_kernel<true, false>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, a);
+    } else {
+        W2V2_LAUNCH((beam_search_kernel<false, false>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, static_cast<const BeamArgs&>(a));
+    }
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }
 
-}  // namespace
-
-int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int beam_width,
-                           int nbest, const float* lm_table, int lm_order, float lm_alpha, float lm_beta, int max_len,
-                           int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s) {
+// the character form's own check and its fields of `a`
+int char_args(BeamWordArgs& a, int V, const float* lm_table, int lm_order) {
     W2V2_REQUIRE(lm_order >= 1 && lm_order <= 4, "ctc_beam_search: language model order %d; 1 to 4", lm_order);
-    BeamWordArgs a{};
     a.lm = lm_table;
     a.ctxmod = 1;
     if (lm_table && V >= 1 && V <= W2V2_BEAM_MAX_VOCAB)
         for (int k = 1; k < lm_order; ++k) a.ctxmod *= V;
-    return beam_run(a, false, logits, V, n, row0, frames, blank, beam_width, nbest, lm_alpha, lm_beta, max_len, labels_out, length, score,
-                    total, s);
+    return W2V2_OK;
 }
 
-int launch_ctc_beam_search_words(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank,
-                                 int beam_width, int nbest, const w2v2_word_lm* lm, int delim, float lm_alpha, float lm_beta,
-                                 float unk_penalty, int score_eos, int max_len, int32_t* labels_out, int32_t* length, double* score,
-                                 double* total, hipStream_t s) {
+// the word form's own checks and its fields of `a`
+int word_args(BeamWordArgs& a, int V, int blank, const w2v2_word_lm* lm, int delim, float unk_penalty, int score_eos) {
     W2V2_REQUIRE(lm, "ctc_beam_search_words: null language model");
     W2V2_REQUIRE(lm->child_dev && lm->word_at_dev && lm->arc0_dev && lm->arc_word_dev && lm->arc_logp_dev && lm->arc_next_dev &&
                      lm->bo_dev && lm->bstate_dev, "ctc_beam_search_words: null language model array");
@@ -741,7 +823,6 @@ int launch_ctc_beam_search_words(const float* logits, int V, int n, const int64_
     W2V2_REQUIRE(lm->n_arcs >= lm->n_words, "ctc_beam_search_words: %d arcs cannot hold the %d words of state 0", lm->n_arcs, lm->n_words);
     W2V2_REQUIRE(delim >= 0 && delim < V && delim != blank, "ctc_beam_search_words: word delimiter %d outside vocabulary %d or the blank", delim, V);
     W2V2_REQUIRE(!(unk_penalty != unk_penalty) && unk_penalty <= 0.f, "ctc_beam_search_words: unk_penalty must be <= 0 or -inf, not NaN");
-    BeamWordArgs a{};
     a.lm = nullptr;
     a.ctxmod = 1;
     a.w = *lm;
@@ -749,8 +830,47 @@ int launch_ctc_beam_search_words(const float* logits, int V, int n, const int64_
     a.unk_penalty = a.constrained ? 0.0 : (double)unk_penalty;
     a.delim = delim;
     a.score_eos = score_eos ? 1 : 0;
-    return beam_run(a, true, logits, V, n, row0, frames, blank, beam_width, nbest, lm_alpha, lm_beta, max_len, labels_out, length, score,
-                    total, s);
+    return W2V2_OK;
+}
+
+}  // namespace
+
+int launch_ctc_beam_search(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank, int beam_width,
+                           int nbest, const float* lm_table, int lm_order, float lm_alpha, float lm_beta, int max_len,
+                           int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s) {
+    BeamWordArgs a{};
+    if (int e = char_args(a, V, lm_table, lm_order)) return e;
+    return beam_run(a, false, nullptr, logits, V, n, row0, frames, blank, beam_width, nbest, lm_alpha, lm_beta, max_len, labels_out,
+                    length, score, total, s);
+}
+
+int launch_ctc_beam_search_words(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank,
+                                 int beam_width, int nbest, const w2v2_word_lm* lm, int delim, float lm_alpha, float lm_beta,
+                                 float unk_penalty, int score_eos, int max_len, int32_t* labels_out, int32_t* length, double* score,
+                                 double* total, hipStream_t s) {
+    BeamWordArgs a{};
+    if (int e = word_args(a, V, blank, lm, delim, unk_penalty, score_eos)) return e;
+    return beam_run(a, true, nullptr, logits, V, n, row0, frames, blank, beam_width, nbest, lm_alpha, lm_beta, max_len, labels_out,
+                    length, score, total, s);
+}
+
+int launch_ctc_beam_search_biased(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank,
+                                  int beam_width, int nbest, const float* lm_table, int lm_order, const w2v2_word_lm* word_lm, int delim,
+                                  float lm_alpha, float lm_beta, float unk_penalty, int score_eos, const w2v2_ctc_bias* bias, int max_len,
+                                  int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s) {
+    W2V2_REQUIRE(bias, "ctc_beam_search_biased: null bias");
+    W2V2_REQUIRE(bias->next_dev && bias->delta_dev && bias->final_dev, "ctc_beam_search_biased: null bias array");
+    W2V2_REQUIRE(bias->n_states >= 1 && bias->n_states <= W2V2_BIAS_MAX_STATES, "ctc_beam_search_biased: %d bias states; 1 to %d",
+                 bias->n_states, W2V2_BIAS_MAX_STATES);
+    W2V2_REQUIRE(bias->start_state >= 0 && bias->start_state < bias->n_states, "ctc_beam_search_biased: bias start state %d outside [0, %d)",
+                 bias->start_state, bias->n_states);
+    W2V2_REQUIRE(V < 1 || (int64_t)bias->n_states * V < ((int64_t)1 << 31),
+                 "ctc_beam_search_biased: bias of %d states times %d labels does not fit 31 bits", bias->n_states, V);
+    W2V2_REQUIRE(!(word_lm && lm_table), "ctc_beam_search_biased: both a word model and a character table given");
+    BeamWordArgs a{};
+    if (int e = word_lm ? word_args(a, V, blank, word_lm, delim, unk_penalty, score_eos) : char_args(a, V, lm_table, lm_order)) return e;
+    return beam_run(a, word_lm != nullptr, bias, logits, V, n, row0, frames, blank, beam_width, nbest, lm_alpha, lm_beta, max_len,
+                    labels_out, length, score, total, s);
 }
 
 }  // namespace w2v2

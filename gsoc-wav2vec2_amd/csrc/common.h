@@ -504,6 +504,11 @@ int launch_ctc_beam_search_words(const float* logits, int V, int n, const int64_
                                  int beam_width, int nbest, const w2v2_word_lm* lm, int delim, float lm_alpha, float lm_beta,
                                  float unk_penalty, int score_eos, int max_len, int32_t* labels_out, int32_t* length, double* score,
                                  double* total, hipStream_t s);
+// either search with a phrase bias (w2v2_ctc_beam_search_biased): the character form when word_lm is null, else the word form
+int launch_ctc_beam_search_biased(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int blank,
+                                  int beam_width, int nbest, const float* lm_table, int lm_order, const w2v2_word_lm* word_lm, int delim,
+                                  float lm_alpha, float lm_beta, float unk_penalty, int score_eos, const w2v2_ctc_bias* bias, int max_len,
+                                  int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s);
 
 // ---- device helpers ---------------------------------------------------------
 #ifdef __HIPCC__

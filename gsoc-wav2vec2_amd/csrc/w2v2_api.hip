@@ -570,6 +570,16 @@ int w2v2_ctc_beam_search_words(const float* logits, int32_t V, int32_t n, const 
                                         score_eos, max_len, labels_out, length, score, total, reinterpret_cast<hipStream_t>(stream));
 }
 
+int w2v2_ctc_beam_search_biased(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t blank,
+                                int32_t beam_width, int32_t nbest, const float* lm_table, int32_t lm_order, const w2v2_word_lm* word_lm,
+                                int32_t delim, float lm_alpha, float lm_beta, float unk_penalty, int32_t score_eos,
+                                const w2v2_ctc_bias* bias, int32_t max_len, int32_t* labels_out, int32_t* length, double* score,
+                                double* total, void* stream) {
+    return launch_ctc_beam_search_biased(logits, V, n, row0, frames, blank, beam_width, nbest, lm_table, lm_order, word_lm, delim, lm_alpha,
+                                         lm_beta, unk_penalty, score_eos, bias, max_len, labels_out, length, score, total,
+                                         reinterpret_cast<hipStream_t>(stream));
+}
+
 int w2v2_ctc_pause_cuts(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t blank,
                         int32_t delim, float margin, int32_t min_pause, int32_t max_cuts, int32_t* cut, int32_t* pause, int32_t* count,
                         void* stream) {

@@ -26,6 +26,7 @@ RESAMPLE_MAX_L = 4096            # W2V2_RESAMPLE_MAX_L, W2V2_RESAMPLE_MAX_TABLE:
 RESAMPLE_MAX_TABLE = 1 << 22
 EDIT_MAX_LEN = 65535             # W2V2_EDIT_MAX_LEN: tokens per sequence of w2v2_edit_distance
 WORDLM_MAX_ORDER = 5             # W2V2_WORDLM_MAX_ORDER: order of the word n-gram model of w2v2_ctc_beam_search_words
+BIAS_MAX_STATES = 1 << 20        # W2V2_BIAS_MAX_STATES: states of the phrase bias of w2v2_ctc_beam_search_biased
 
 
 class W2V2Config(C.Structure):
@@ -56,6 +57,11 @@ class W2V2WordLM(C.Structure):
     """struct w2v2_word_lm (include/w2v2.h): device arrays and sizes of a compiled word n-gram model and its lexicon."""
     _fields_ = [(k, C.c_void_p) for k in ("child", "word_at", "arc0", "arc_word", "arc_logp", "arc_next", "bo", "bstate")] + \
                [(k, C.c_int32) for k in ("n_nodes", "n_states", "n_arcs", "n_words", "order", "start_state", "unk", "eos")]
+
+
+class W2V2CtcBias(C.Structure):
+    """struct w2v2_ctc_bias (include/w2v2.h): device tables and sizes of a compiled phrase bias."""
+    _fields_ = [(k, C.c_void_p) for k in ("next", "delta", "final")] + [(k, C.c_int32) for k in ("n_states", "start_state")]
 
 
 class W2V2ResampleFilter(C.Structure):
@@ -94,6 +100,8 @@ PROTOTYPES = {
     "w2v2_ctc_beam_search": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_float, C.c_float, _I32, _P, _P, _P, _P, _P]),
     "w2v2_ctc_beam_search_words": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, C.POINTER(W2V2WordLM), _I32, C.c_float, C.c_float,
                                              C.c_float, _I32, _I32, _P, _P, _P, _P, _P]),
+    "w2v2_ctc_beam_search_biased": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _I32, C.POINTER(W2V2WordLM), _I32, C.c_float,
+                                              C.c_float, C.c_float, _I32, C.POINTER(W2V2CtcBias), _I32, _P, _P, _P, _P, _P]),
     "w2v2_ctc_pause_cuts": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, C.c_float, _I32, _I32, _P, _P, _P, _P]),
     "w2v2_edit_distance": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     "w2v2_resample_design": (C.c_int, [_I32, _I32, _I32, C.c_double, C.c_double, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32),

@@ -8,6 +8,9 @@ is a HIP kernel; the table is counted and smoothed on the host (it is built once
 ``WordNgramLM`` is the other kind of language model: a word-level backoff n-gram (read from an ARPA file or counted from text)
 with a lexicon that spells its words in the model's labels (w2v2_ctc_beam_search_words).
 
+``ContextBias`` is a list of phrases the search should prefer (contextual biasing, "hotwords"), compiled into an automaton that
+the kernel walks beside either language model or none (w2v2_ctc_beam_search_biased).
+
 ``ctc_score`` is the exact CTC log-probability of label sequences given logits (the sum over all frame paths, a HIP kernel);
 ``rescore`` replaces the beam's lower bounds in n-best lists by it; ``hypothesis_posteriors`` and ``word_confidence`` turn the
 rescored lists into probabilities of the hypotheses and of the best hypothesis' words (host code over a few numbers).
@@ -515,7 +518,231 @@ class WordNgramLM:
         return text
 
 
-def _check_args(V, beam_width, nbest, blank, lm):
+class ContextBias:
+    """Phrase boosting (contextual biasing, "hotwords") for ``beam_search``: a list of phrases the search should prefer, compiled
+    into an Aho-Corasick automaton with resolved failure links that the kernel reads as dense tables (exact
+    definition in csrc/beam.hip, third part of its header; tests/bias_reference.py computes it from the prefix alone).
+
+    A phrase ``h`` is a label string with a boost ``b_h`` >= 0 in nats per COUNTED label, weight ``w_h = b_h * counted(h)``.
+    ``whole_words`` wraps every phrase in one leading and one trailing ``delimiter`` (not counted), so that it matches whole words
+    only; the start and the end of the utterance count as delimiters.  The bias of a prefix ``p`` is ``B(p) = C(p) + phi(state(p))``:
+    ``C`` the summed weights of EVERY occurrence of every phrase in ``p`` (overlapping and nested phrases all count: with the
+    phrases NEW YORK and YORK the string NEW YORK earns both), ``state(p)`` the longest suffix of ``p`` that begins a phrase and
+    ``phi(s) = partial * counted(s) * max{b_h : s a proper prefix of h}`` a look-ahead credit that keeps a phrase under way in the
+    beam (``partial`` in [0, 1]; the default 1.0 is a convention -- the full per-label boost in advance -- not a tuned value; 0
+    rewards completed phrases only).  Credit for a phrase that is not finished is taken back, at the label that leaves it or at
+    the end of the utterance.
+
+    ``next`` (n_states, V) int32, ``delta`` (n_states, V) fp32, ``final`` (n_states) fp32, ``start_state``: the compiled tables
+    (numpy; state 0 the root; the blank's column is ``next = s``, ``delta = 0``).  ``delta`` and ``final`` are formed in fp64 --
+    ``(sum of w_h in phrase order + phi(s')) - phi(s)`` and ``E(s) - phi(s)`` -- and rounded to fp32 once."""
+
+    MAX_STATES = N.BIAS_MAX_STATES
+
+    def __init__(self, phrases, vocab_size, blank, delimiter=None, partial=1.0, whole_words=False):
+        """``phrases``: [(label ids, boost)]; see ``from_ids`` / ``from_phrases``"""
+        V, blank = int(vocab_size), int(blank)
+        if V < 2:
+            raise ValueError(f"vocabulary {V}; the blank and at least one label")
+        if not 0 <= blank < V:
+            raise ValueError(f"blank {blank} outside the vocabulary [0, {V})")
+        if delimiter is not None and (not 0 <= int(delimiter) < V or int(delimiter) == blank):
+            raise ValueError(f"word delimiter {delimiter} outside the vocabulary [0, {V}) or the blank")
+        if whole_words and delimiter is None:
+            raise ValueError("whole_words needs a word delimiter")
+        partial = float(partial)
+        if not 0.0 <= partial <= 1.0:                        # (NaN fails too)
+            raise ValueError(f"partial {partial} outside [0, 1]")
+        phrases = list(phrases)
+        if not phrases:
+            raise ValueError("the bias holds no phrase")
+        self.vocab_size, self.blank, self.partial, self.whole_words = V, blank, partial, bool(whole_words)
+        self.delimiter = None if delimiter is None else int(delimiter)
+        self.lead = 1 if self.whole_words else 0             # uncounted boundary labels at either end of a phrase
+        self.phrases, self.boosts = [], []
+        for i, (ids, b) in enumerate(phrases):
+            ids, b = tuple(int(c) for c in ids), float(b)
+            if not ids:
+                raise ValueError(f"phrase {i} has an empty spelling")
+            if any(not 0 <= c < V or c == blank for c in ids):
+                raise ValueError(f"phrase {i}: labels {ids} hold the blank or leave [0, {V})")
+            if not math.isfinite(b) or b < 0:
+                raise ValueError(f"phrase {i}: boost {b} is not a finite value >= 0")
+            self.phrases.append((self.delimiter,) * self.lead + ids + (self.delimiter,) * self.lead)
+            self.boosts.append(b)
+        self._dev = {}
+        self._compile()
+        self.validate()
+
+    @classmethod
+    def from_ids(cls, id_sequences, V, blank, delimiter=None, boost=2.0, partial=1.0, whole_words=False):
+        """The model-free form: ``id_sequences`` holds label sequences or ``(sequence, boost)`` pairs (``boost``: the others')."""
+        items = []
+        for x in id_sequences:
+            pair = isinstance(x, (tuple, list)) and len(x) == 2 and hasattr(x[0], "__len__")
+            items.append((x[0], x[1]) if pair else (x, boost))
+        return cls(items, V, blank, delimiter, partial, whole_words)
+
+    @classmethod
+    def from_phrases(cls, phrases, tokenizer, boost=2.0, partial=1.0, whole_words=True):
+        """``phrases``: strings or ``(string, boost)`` pairs, read as the tokenizer reads text (upper-cased, split at blanks and
+        hyphens); every word is spelled as ``WordNgramLM.spell`` spells it and the words are joined by the tokenizer's word
+        delimiter.  A phrase with a word the tokenizer cannot spell is a ValueError."""
+        from .processor import PAD_TOKEN, WORD_DELIMITER
+        vocab = tokenizer.get_vocab()
+        delim = vocab[WORD_DELIMITER]
+        items = []
+        for x in phrases:
+            text, b = (x, boost) if isinstance(x, str) else (x[0], x[1])
+            ids = []
+            for w in text.upper().replace("-", " ").split():
+                sp = WordNgramLM.spell(w, tokenizer)
+                if sp is None:
+                    raise ValueError(f"phrase `{text}`: the tokenizer cannot spell `{w}`")
+                ids += ([delim] if ids else []) + list(sp)
+            if not ids:
+                raise ValueError(f"phrase `{text}` has an empty spelling")
+            items.append((ids, b))
+        return cls(items, max(vocab.values()) + 1, vocab[PAD_TOKEN], delim, partial, whole_words)
+
+    # ---- compilation -----------------------------------------------------------------------------------------------------------
+    def _compile(self):
+        V, lead = self.vocab_size, self.lead
+        goto, depth, own = {}, [0], [[]]                     # the trie: (state, label) -> state; phrases that end at a state
+        for i, h in enumerate(self.phrases):
+            s = 0
+            for c in h:
+                nx = goto.get((s, c))
+                if nx is None:
+                    nx = len(depth)
+                    if nx + 1 > self.MAX_STATES:
+                        raise ValueError(f"the phrases need more than {self.MAX_STATES} automaton states")
+                    if (nx + 1) * V >= 2 ** 31:
+                        raise ValueError(f"the phrases need {nx + 1} or more states: states * vocabulary {V} reaches 2^31")
+                    goto[(s, c)] = nx
+                    depth.append(depth[s] + 1)
+                    own.append([])
+                s = nx
+            own[s].append(i)
+        ns = len(depth)
+        # best boost among the phrases a state is a PROPER prefix of
+        maxb = np.full(ns, -1.0)
+        for i, h in enumerate(self.phrases):
+            s = 0
+            for c in h:
+                maxb[s] = max(maxb[s], self.boosts[i])
+                s = goto[(s, c)]
+        counted = np.maximum(np.asarray(depth, np.float64) - lead, 0.0)
+        phi = np.where(maxb >= 0, (self.partial * counted) * np.maximum(maxb, 0.0), 0.0)
+        phi[0] = 0.0
+        # breadth first (states are numbered by insertion, so sort by depth): failure links resolved into the dense table
+        kids = [[] for _ in range(ns)]
+        for (s, c), nx in goto.items():
+            kids[s].append((c, nx))
+        nxt = np.zeros((ns, V), np.int32)
+        fail = np.zeros(ns, np.int64)
+        outs = [None] * ns                                   # phrase indices that end at the state's string, ascending
+        outs[0] = []
+        order = sorted(range(ns), key=lambda s: depth[s])
+        for s in order:
+            if s:
+                nxt[s] = nxt[fail[s]]
+                f = outs[fail[s]]
+                outs[s] = sorted(own[s] + f) if own[s] and f else (own[s] or f)
+            for c, k in kids[s]:
+                fail[k] = nxt[fail[s], c] if s else 0
+                nxt[s, c] = k
+        w = [b * float(len(h) - 2 * lead) for h, b in zip(self.phrases, self.boosts)]
+        osum = np.zeros(ns)
+        for s in range(ns):
+            acc = 0.0
+            for i in outs[s]:
+                acc = acc + w[i]
+            osum[s] = acc
+        delta = ((osum[nxt] + phi[nxt]) - phi[:, None]).astype(np.float32)
+        rows = np.arange(ns, dtype=np.int32)
+        nxt[:, self.blank] = rows
+        delta[:, self.blank] = 0.0
+        if self.whole_words:
+            final = (osum[nxt[:, self.delimiter]] - phi).astype(np.float32)
+            self.start_state = int(nxt[0, self.delimiter])
+        else:
+            final = (0.0 - phi).astype(np.float32)
+            self.start_state = 0
+        self.next, self.delta, self.final = np.ascontiguousarray(nxt), np.ascontiguousarray(delta), final
+        self.weights = w
+        self.n_states = ns
+        self._outs = outs
+
+    def validate(self):
+        """The compiled tables are what the kernel trusts: check them (ValueError)."""
+        ns, V = self.n_states, self.vocab_size
+        if not 1 <= ns <= self.MAX_STATES or ns * V >= 2 ** 31:
+            raise ValueError(f"{ns} automaton states; 1 to {self.MAX_STATES}, and states * vocabulary below 2^31")
+        if self.next.shape != (ns, V) or self.delta.shape != (ns, V) or self.final.shape != (ns,):
+            raise ValueError(f"the bias tables have shapes {self.next.shape}, {self.delta.shape}, {self.final.shape}; ({ns}, {V}) and ({ns},)")
+        if self.next.dtype != np.int32 or self.delta.dtype != np.float32 or self.final.dtype != np.float32:
+            raise ValueError("the bias tables must be int32 (next) and float32 (delta, final)")
+        if (self.next < 0).any() or (self.next >= ns).any():
+            raise ValueError("a next state is out of range")
+        if not (np.isfinite(self.delta).all() and np.isfinite(self.final).all()):
+            raise ValueError("the bias holds a non-finite value")
+        if not np.array_equal(self.next[:, self.blank], np.arange(ns)) or (self.delta[:, self.blank] != 0).any():
+            raise ValueError("the blank's column must stay in place and add nothing")
+        if not 0 <= self.start_state < ns:
+            raise ValueError(f"start state {self.start_state} outside [0, {ns})")
+
+    def uses_label(self, c):
+        return any(int(c) in h for h in self.phrases)
+
+    def device_arrays(self, device):
+        """(struct w2v2_ctc_bias, the tensors it points to) on ``device`` (uploaded on first use, then kept)"""
+        import torch
+        key = str(device)
+        if key not in self._dev:
+            self.validate()
+            t = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device) for k in ("next", "delta", "final")}
+            st = N.W2V2CtcBias()
+            for k, v in t.items():
+                setattr(st, k, v.data_ptr())
+            st.n_states, st.start_state = self.n_states, self.start_state
+            self._dev[key] = (st, t)
+        return self._dev[key]
+
+    def score(self, ids):
+        """(the bias of the transcript ``ids`` at the end of an utterance -- the table values along it and ``final``, summed in
+        fp64 in the search's order: what the search adds to ``total`` beside the language model -- and the matches: a list of
+        (phrase index, position of its first counted label in ``ids``, position of its last), by last position, then phrase)"""
+        s, acc, matches = self.start_state, 0.0, []
+        lead = self.lead
+
+        def fired(state, end):                               # `end`: position of the phrase's last label, a boundary delimiter included
+            for i in self._outs[state]:
+                n = len(self.phrases[i])
+                matches.append((i, end - n + 1 + lead, end - lead))
+
+        for k, c in enumerate(ids):
+            c = int(c)
+            if not 0 <= c < self.vocab_size or c == self.blank:
+                raise ValueError(f"label {c} at position {k} is the blank or outside [0, {self.vocab_size})")
+            acc = acc + float(self.delta[s, c])
+            s = int(self.next[s, c])
+            fired(s, k)
+        if self.whole_words:
+            fired(int(self.next[s, self.delimiter]), len(ids))
+        return acc + float(self.final[s]), matches
+
+
+def _check_args(V, beam_width, nbest, blank, lm, bias=None):
+    if bias is not None:
+        if not isinstance(bias, ContextBias):
+            raise ValueError("`bias` must be a ContextBias")
+        if bias.vocab_size != V:
+            raise ValueError(f"the bias has vocabulary {bias.vocab_size}, the logits {V}")
+        if bias.blank != blank or bias.uses_label(blank):
+            raise ValueError(f"blank {blank} is a label of the bias' phrases (the bias was built with blank {bias.blank})")
+        if isinstance(lm, WordNgramLM) and bias.delimiter is not None and bias.delimiter != lm.delimiter:
+            raise ValueError(f"the bias has word delimiter {bias.delimiter}, the language model {lm.delimiter}")
     if not 1 <= V <= N.BEAM_MAX_VOCAB:
         raise ValueError(f"vocabulary {V}; the beam search takes at most {N.BEAM_MAX_VOCAB}")
     if not 1 <= beam_width <= N.BEAM_MAX_WIDTH:
@@ -536,13 +763,15 @@ def _check_args(V, beam_width, nbest, blank, lm):
             raise ValueError(f"the language model has vocabulary {lm.vocab_size}, the logits {V}")
 
 
-def beam_search(logits, beam_width=16, nbest=1, blank=0, frame_lengths=None, lm=None):
+def beam_search(logits, beam_width=16, nbest=1, blank=0, frame_lengths=None, lm=None, bias=None):
     """CTC prefix beam search; per utterance a list of at most ``nbest`` ``Hypothesis(ids, score, total)``, best first.
 
     ``logits``: what ``forced_align`` accepts -- a list of (T_i, V) tensors (views of one storage, as ``predict_packed``
     returns them, are read in place) or a (B, T, V) tensor with ``frame_lengths``.  ``lm``: a ``CharNgramLM``, a
     ``WordNgramLM`` (whose word delimiter and weights are the object's; see there for the constrained mode, in which an
-    utterance may return an empty list) or None.
+    utterance may return an empty list) or None.  ``bias``: a ``ContextBias`` (phrases to prefer, with any ``lm``; its bonuses are
+    part of ``total``, and the final beam is ordered by ``total`` after the end-of-utterance term) or None, which takes exactly the
+    search without one.
 
     ``score`` is the log of the summed probability of the frame paths that spell the transcript AND whose prefixes stayed in
     the beam at every frame: a LOWER bound of the transcript's exact CTC log-probability (``-ctc_loss``), equal to it only
@@ -555,7 +784,7 @@ def beam_search(logits, beam_width=16, nbest=1, blank=0, frame_lengths=None, lm=
     base, row0, lens = _logits_base(logits, frame_lengths)
     n, V = len(lens), int(base.shape[1])
     beam_width, nbest, blank = int(beam_width), int(nbest), int(blank)
-    _check_args(V, beam_width, nbest, blank, lm)
+    _check_args(V, beam_width, nbest, blank, lm, bias)
     dev = base.device
     max_len = max(lens)
     labels = torch.empty((n, nbest, max_len), dtype=torch.int32, device=dev)
@@ -565,6 +794,19 @@ def beam_search(logits, beam_width=16, nbest=1, blank=0, frame_lengths=None, lm=
     row0_h = np.asarray(row0, np.int64)
     frames_h = np.asarray(lens, np.int32)
     lib = N.load()
+    if bias is not None:
+        import ctypes
+        word = isinstance(lm, WordNgramLM)
+        bst, _keep_bias = bias.device_arrays(dev)
+        st, _keep = lm.device_arrays(dev) if word else (None, None)
+        table = lm.device_table(dev) if lm is not None and not word else None
+        N.check(lib.w2v2_ctc_beam_search_biased(N.ptr(base), V, n, N.ptr(row0_h), N.ptr(frames_h), blank, beam_width, nbest, N.ptr(table),
+                                                1 if lm is None or word else lm.order, ctypes.byref(st) if word else None,
+                                                lm.delimiter if word else 0, lm.alpha if lm is not None else 0.0,
+                                                lm.beta if lm is not None else 0.0, lm.unk_penalty if word else 0.0,
+                                                int(lm.score_eos) if word else 0, ctypes.byref(bst), max_len, N.ptr(labels), N.ptr(length),
+                                                N.ptr(score), N.ptr(total), N.current_stream()), "w2v2_ctc_beam_search_biased")
+        return _hypotheses(n, nbest, labels, length, score, total)
     if isinstance(lm, WordNgramLM):
         import ctypes
         st, _keep = lm.device_arrays(dev)
@@ -665,7 +907,8 @@ def ctc_score(logits, labels, blank=0, frame_lengths=None, utterance=None):
 def rescore(logits, hypotheses, blank=0, frame_lengths=None):
     """The n-best lists of ``beam_search`` (one list of ``Hypothesis`` per utterance of ``logits``) with exact scores: ONE
     ``ctc_score`` call over every hypothesis of every utterance.  ``score`` becomes the exact CTC log-probability; ``total``
-    keeps its language-model part, ``exact + (old total - old score)``; a hypothesis without a beam score (NaN: the greedy
+    keeps its language-model part, ``exact + (old total - old score)`` -- with a ``ContextBias`` that part holds the bonuses of the
+    completed phrases and the end-of-utterance term, so biased lists need nothing else here --; a hypothesis without a beam score (NaN: the greedy
     path) gets ``score = total = exact``.  Each list is sorted again by ``total``, best first, equal totals in their old order.
     Exact scores are comparable across a list and across utterances; the beam's were lower bounds, each pruned differently."""
     lists = [list(h) for h in hypotheses]

@@ -270,7 +270,7 @@ def _collapse(path, blank):
 
 def decode_long(logits, tokenizer=None, beam_width=16, nbest=1, lm=None, blank=0, delimiter_id=None, timestamps=False,
                 pause_margin=2.0, min_pause=10, min_frames=250, max_frames=1500, seconds_per_frame=0.02, rescore=False,
-                confidence=False, posterior_scale=1.0):
+                confidence=False, posterior_scale=1.0, bias=None):
     """Transcripts of long recordings from their logits: one ``LongTranscript`` per recording (a single (T, V) tensor gives one
     result, a list gives a list).  Model-free, like ``beam_search``.
 
@@ -284,7 +284,8 @@ def decode_long(logits, tokenizer=None, beam_width=16, nbest=1, lm=None, blank=0
     decode the collapse of the whole equals the concatenation of the collapses of the pieces, and ``ids`` is the
     concatenation of the segments' best hypotheses; ``text`` decodes ``ids`` without grouping.  A language model sees every
     segment as an utterance: a ``WordNgramLM`` restarts from its start state at each segment and scores ``</s>`` at each
-    segment's end when its ``score_eos`` is set; no LM state or beam entry is carried across a cut.
+    segment's end when its ``score_eos`` is set; no LM state or beam entry is carried across a cut.  ``bias`` (a ``ContextBias``)
+    likewise restarts at its start state in every segment and settles its end-of-utterance term at every segment's end.
 
     ``rescore=True``: the segments' n-best lists go through ONE ``wav2vec2.decoding.rescore`` call (exact scores, lists ordered
     by the exact totals) before anything is made of them.  ``confidence=True`` (implies ``rescore``; needs a beam with
@@ -312,6 +313,8 @@ def decode_long(logits, tokenizer=None, beam_width=16, nbest=1, lm=None, blank=0
         raise ValueError("timestamps without a tokenizer: pass delimiter_id")
     if beam_width is None and lm is not None:
         raise ValueError("the greedy path takes no language model")
+    if beam_width is None and bias is not None:
+        raise ValueError("the greedy path takes no phrase bias")
     if confidence and (beam_width is None or nbest < 2):
         raise ValueError("confidence=True needs a beam search with nbest >= 2: a posterior is taken over a list")
     if confidence and delimiter_id is None:
@@ -326,7 +329,7 @@ def decode_long(logits, tokenizer=None, beam_width=16, nbest=1, lm=None, blank=0
     if beam_width is None:
         hyps = [[Hypothesis(_collapse(p.argmax(dim=1).cpu().numpy(), blank), float("nan"), float("nan"))] for p in pieces]
     else:
-        hyps = beam_search(pieces, beam_width=beam_width, nbest=nbest, blank=blank, lm=lm)
+        hyps = beam_search(pieces, beam_width=beam_width, nbest=nbest, blank=blank, lm=lm, bias=bias)
     if rescore or confidence:
         hyps = rescore_lists(pieces, hyps, blank=blank)
     if confidence:

@@ -815,11 +815,12 @@ class Wav2Vec2ForCTC(TFKerasModel):
         return spans[0] if single else spans
 
     def transcribe(self, waveforms, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False, sampling_rate=None, normalize=False,
-                   rescore=False, confidence=False, posterior_scale=1.0):
+                   rescore=False, confidence=False, posterior_scale=1.0, bias=None):
         """Text: `predict_packed(waveforms)`, then the CTC prefix beam search on the packed logits in place
         (wav2vec2.decoding.beam_search; blank = config.pad_id), ids -> text with `tokenizer` (a Wav2Vec2Processor(is_tokenizer=True);
         "|" -> space, as its `decode`).  `lm`: a wav2vec2.decoding.CharNgramLM, a wav2vec2.decoding.WordNgramLM (a word n-gram model
         with a lexicon; in its constrained mode an utterance can end without a hypothesis: an empty text) or None.
+        `bias`: a wav2vec2.decoding.ContextBias (phrases the search should prefer, with any `lm`) or None; not for the greedy path.
         `beam_width=None` is the greedy path for comparison: the argmax of every frame on the device, then `tokenizer.decode`.  With `timestamps=True` the best hypothesis
         of each utterance goes through the forced alignment (wav2vec2.alignment) and the result carries its WordSpans (none for
         an empty transcript).  Returns one wav2vec2.decoding.Transcript(text, hypotheses, texts, words) per utterance; see
@@ -842,13 +843,15 @@ class Wav2Vec2ForCTC(TFKerasModel):
         if beam_width is None:
             if lm is not None:
                 raise ValueError("the greedy path takes no language model")
+            if bias is not None:
+                raise ValueError("the greedy path takes no phrase bias")
             hyps = []
             for l in logits:
                 path = l.argmax(dim=1).cpu().numpy()
                 keep = np.flatnonzero((path != blank) & (np.concatenate(([True], path[1:] != path[:-1]))))
                 hyps.append([Hypothesis(tuple(int(v) for v in path[keep]), float("nan"), float("nan"))])
         else:
-            hyps = beam_search(logits, beam_width=beam_width, nbest=nbest, blank=blank, lm=lm)
+            hyps = beam_search(logits, beam_width=beam_width, nbest=nbest, blank=blank, lm=lm, bias=bias)
         if rescore or confidence:
             hyps = rescore_lists(logits, hyps, blank=blank)
         if confidence:
@@ -873,7 +876,7 @@ class Wav2Vec2ForCTC(TFKerasModel):
             out.append(Transcript(texts[0] if texts else "", h, texts, w))
         return out
 
-    def evaluate(self, waveforms, references, tokenizer, beam_width=16, nbest=1, lm=None, sampling_rate=None, normalize=False):
+    def evaluate(self, waveforms, references, tokenizer, beam_width=16, nbest=1, lm=None, sampling_rate=None, normalize=False, bias=None):
         """Error rates: `transcribe(waveforms, tokenizer, ...)`, then the word and character error rates of the best hypotheses
         against `references` (one text per waveform) and, with `nbest > 1`, the oracle word error rate of the n-best lists
         (wav2vec2.metrics: wer, cer, oracle_wer; the edit distances run on the device).  The texts are compared as they are: no
@@ -883,11 +886,11 @@ class Wav2Vec2ForCTC(TFKerasModel):
         if isinstance(references, str) or len(references) != len(waveforms):
             raise ValueError("one reference per waveform")
         transcripts = self.transcribe(waveforms, tokenizer, beam_width=beam_width, nbest=nbest, lm=lm, sampling_rate=sampling_rate,
-                                      normalize=normalize)
+                                      normalize=normalize, bias=bias)
         return evaluate_transcripts(transcripts, references, nbest)
 
     def evaluate_long(self, waveform, references, tokenizer, beam_width=16, nbest=1, lm=None, window_s=20.0, margin_s=2.0,
-                      normalize=True, max_stream_s=1200.0, sampling_rate=None, **cut_options):
+                      normalize=True, max_stream_s=1200.0, sampling_rate=None, bias=None, **cut_options):
         """`evaluate` over `transcribe_long`: the word and character error rates of each recording's concatenated text against
         its reference.  `waveform` is one recording or a list of them, `references` one text or a list to match.  A recording's
         n-best lists belong to its segments, which have no references of their own, so `oracle_wer` is None here."""
@@ -896,7 +899,7 @@ class Wav2Vec2ForCTC(TFKerasModel):
             references = [references]
         transcripts = self.transcribe_long(waveform, tokenizer, beam_width=beam_width, nbest=nbest, lm=lm, window_s=window_s,
                                            margin_s=margin_s, normalize=normalize, max_stream_s=max_stream_s,
-                                           sampling_rate=sampling_rate, **cut_options)
+                                           sampling_rate=sampling_rate, bias=bias, **cut_options)
         if not isinstance(transcripts, list):
             transcripts = [transcripts]
         if len(references) != len(transcripts):
@@ -905,12 +908,13 @@ class Wav2Vec2ForCTC(TFKerasModel):
 
     def transcribe_long(self, waveform, tokenizer, beam_width=16, nbest=1, lm=None, timestamps=False, window_s=20.0, margin_s=2.0,
                         normalize=True, max_stream_s=1200.0, sampling_rate=None, rescore=False, confidence=False, posterior_scale=1.0,
-                        **cut_options):
+                        bias=None, **cut_options):
         """Text of recordings of any length: `predict_long(waveform, ...)`, then `wav2vec2.longform.decode_long` on the stitched
         logits with blank = config.pad_id, the tokenizer's word delimiter and the frame period of the conv strides: the logits
         are cut at pauses between words, all segments go through one beam search (and one forced alignment with
         `timestamps=True`), and the pieces are concatenated.  `cut_options`: decode_long's pause_margin, min_pause, min_frames,
-        max_frames.  A language model sees each segment as an utterance (a WordNgramLM restarts at every segment).  Returns one
+        max_frames.  A language model sees each segment as an utterance (a WordNgramLM restarts at every segment, and so does a
+        ContextBias given as `bias`).  Returns one
         wav2vec2.longform.LongTranscript(text, ids, score, total, words, segments) per recording.  `sampling_rate`: as
         `predict_long`; the times stay seconds of the recording.  `rescore`, `confidence`, `posterior_scale`: as `transcribe`,
         per segment; with `confidence=True` the result is decode_long's ScoredLongTranscript."""
@@ -919,4 +923,4 @@ class Wav2Vec2ForCTC(TFKerasModel):
         seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
         return decode_long(logits, tokenizer, beam_width=beam_width, nbest=nbest, lm=lm, blank=self.config.pad_id, timestamps=timestamps,
                            seconds_per_frame=seconds_per_frame, rescore=rescore, confidence=confidence, posterior_scale=posterior_scale,
-                           **cut_options)
+                           bias=bias, **cut_options)

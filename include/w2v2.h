@@ -402,6 +402,36 @@ int w2v2_ctc_beam_search_words(const float* logits_dev, int32_t V, int32_t n, co
                                float lm_alpha, float lm_beta, float unk_penalty, int32_t score_eos, int32_t max_len,
                                int32_t* labels_out_dev, int32_t* length_dev, double* score_dev, double* total_dev, void* stream);
 
+/* Either search with a PHRASE BIAS (contextual biasing, "hotwords"; DESIGN.md §20, exact definition in csrc/beam.hip): hypotheses that
+ * spell given phrases are preferred while the search runs.  The bias is an Aho-Corasick automaton over labels with its failure links
+ * resolved, compiled on the host (wav2vec2.decoding.ContextBias) into dense device tables:
+ *   next_dev      (n_states, V) int32: the state after a label (the longest suffix of the prefix that begins a phrase); state 0 the root
+ *   delta_dev     (n_states, V) fp32: what that label adds to the hypothesis' LM score: the boosts of the phrases it completes plus the
+ *                 change of the partial credit of the phrase under way
+ *   final_dev     (n_states) fp32: added after the last frame (partial credit of an unfinished phrase is given back)
+ *   start_state   the state of the empty prefix
+ * The blank's column is never read.  Every entry of the beam carries its state; a new label c from state s adds (double)delta[s][c]
+ * after the language model's own term and moves to next[s][c]; after the last frame (and, in the word form, after the open word and
+ * eos) (double)final[s] is added and the final beam is re-ordered by descending total, equal totals by beam rank.
+ * The language model is the character table (lm_table_dev, lm_order; NULL: none) when word_lm == NULL, else the word model (delim,
+ * unk_penalty, score_eos as in w2v2_ctc_beam_search_words; delim is ignored without a word model).  `bias` is required: the calls
+ * without one are the two entries above.  W2V2_EINVAL with a message, before anything is launched: a null bias or a null array in
+ * it, n_states outside [1, W2V2_BIAS_MAX_STATES], start_state outside [0, n_states), n_states * V >= 2^31, word_lm and lm_table_dev
+ * both given, and every check of the entry of the chosen form.  The CONTENTS of the tables are trusted (the Python class validates
+ * them).  Outputs, addressing, limits, scratch and the treatment of bad logits are w2v2_ctc_beam_search's. */
+#define W2V2_BIAS_MAX_STATES (1 << 20)
+typedef struct w2v2_ctc_bias {
+    const int32_t* next_dev;
+    const float* delta_dev;
+    const float* final_dev;
+    int32_t n_states, start_state;
+} w2v2_ctc_bias;
+int w2v2_ctc_beam_search_biased(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host,
+                                int32_t blank, int32_t beam_width, int32_t nbest, const float* lm_table_dev, int32_t lm_order,
+                                const w2v2_word_lm* word_lm, int32_t delim, float lm_alpha, float lm_beta, float unk_penalty,
+                                int32_t score_eos, const w2v2_ctc_bias* bias, int32_t max_len, int32_t* labels_out_dev,
+                                int32_t* length_dev, double* score_dev, double* total_dev, void* stream);
+
 /* Pause cuts (exact definition in csrc/segment.hip and, in numpy, tests/longform_reference.py): where the logits
  * of a long recording can be cut into utterance-sized pieces for w2v2_ctc_beam_search and w2v2_ctc_align.  Model-free, with their
  * addressing:  utterance i: logits_dev rows [row0_host[i], row0_host[i] + frames_host[i]) of V fp32.
