@@ -18,9 +18,18 @@
 // An utterance is feasible only if T >= U + R, R = #{k >= 1: l_k = l_{k-1}}: otherwise score = -inf, token = label_index = -1 and
 // frame_logp = NaN.  A label outside [0, V) or equal to the blank (labels are on the device): score = NaN, the same -1 / NaN rows.
 //
+// The star (w2v2_ctc_align_star; tests/align_star_reference.py): a wildcard label that absorbs whatever is spoken
+// where the transcript has a gap.  Its id is V, as if the logits had one more column, with the raw-logit emission
+//   xs_t = (double)m_t + (double)star_score,   m_t = the fp32 maximum of the frame's V logits (the blank included; fmaxf, so a NaN
+//   logit is ignored: ctc_lattice.h, frame_lse_max), star_score <= 0 an fp32 argument in nats per frame.
+// Nothing in the recursion changes: ext[2k + 1] = V is a state like any other, the skip rule and R treat V like any id, the star
+// takes at least one frame, and the comparison order, the ties, the end state and T >= U + R stay.  On a star frame token[t] = V,
+// label_index[t] = k, frame_logp[t] = (float)(xs_t - lse_t).  score = delta_end - sum_t lse_t as before: with a star it is the
+// score of a path, no longer the log-probability of a label string.  A label < 0, > V or equal to the blank: the NaN utterance.
+//
 // Structure.  lds_barrier, frame_lse and block_count are ctc_lattice.h's; the step and the backtrace below have a copy in
 // align_long.hip, which must stay the same operations in the same order.  align_lse_kernel: one wave per frame, lse_t into the
-// workspace.  align_viterbi_kernel: one block per utterance.
+// workspace (align_lse_star_kernel: and xs_t beside it).  align_viterbi_kernel: one block per utterance.
 // A thread owns P consecutive state pairs in registers as fp64; per step the only value that crosses threads is the odd state of
 // a thread's last pair, through a double-buffered LDS array behind ONE lds_barrier (the step's fire-and-forget backpointer stores
 // are not drained).  The P + 1 emissions a step needs are loaded PF steps ahead.  Backpointers: a thread collects its 4P bits of
@@ -30,6 +39,10 @@
 // sweep the same block backtracks: the state moves down by at most 2 per step, so the backpointer words of the next C frames lie
 // in a window of C frames x C pairs; the block loads that window into LDS, one lane walks it, and the block writes the C frames'
 // outputs (token, label index, frame_logp) in parallel.  No atomics: two identical calls give identical bits.
+// STAR is a compile-time flag of the sweep kernel; the STAR = false instantiation is the star-free code.  With it a thread keeps a
+// bit mask of its pairs that hold the star, xs_t is loaded PF steps ahead like x_t(blank) (one block-uniform fp64), an odd state
+// adds xs_t where the mask is set, and a star pair's per-lane logits load reads the blank's column and is discarded, so that no
+// address leaves the row.
 #include "ctc_lattice.h"
 
 #include <algorithm>
@@ -65,8 +78,17 @@ __global__ __launch_bounds__(256) void align_lse_kernel(AlignArgs a) {
     frame_lse(a.logits, a.V, sg.row0, sg.T, a.lse + sg.out0);
 }
 
-template <int P>
-__global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_viterbi_kernel(AlignArgs a) {
+// ... and xs_t = m_t + star_score into xs, indexed like lse
+__global__ __launch_bounds__(256) void align_lse_star_kernel(AlignArgs a, double* xs, float star_score) {
+    const AlignSeg sg = a.segs[blockIdx.y];
+    float m;
+    const int t = frame_lse_max(a.logits, a.V, sg.row0, sg.T, a.lse + sg.out0, m);
+    if (t >= 0 && (threadIdx.x & 63) == 0) xs[sg.out0 + t] = (double)m + (double)star_score;
+}
+
+template <int P, bool STAR>
+__global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_viterbi_kernel(AlignArgs a, const double* xs) {
+    // (xs: the star's emission per frame, indexed like a.lse; read only with STAR)
     constexpr int G = 8 / P;                 // steps per backpointer word
     constexpr int PF = P == 8 ? 2 : 8;       // steps the emissions are loaded ahead (a multiple of G; P = 8: registers)
     constexpr double NEG = -__builtin_inf();
@@ -85,7 +107,7 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_vite
 
     // labels of the thread's pairs (the blank past U), the skip flags, and the two per-utterance checks
     int lj[P];
-    unsigned skipm = 0;
+    unsigned skipm = 0, starm = 0;                       // starm (STAR): the pairs whose label is the star
     bool bad = false;
 #pragma unroll
     for (int j = 0; j < P; ++j) {
@@ -93,9 +115,16 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_vite
         lj[j] = blank;
         if (k < U) {
             const int l = lab[k];
-            bad |= l < 0 || l >= V || l == blank;
+            if constexpr (STAR) bad |= l < 0 || l > V || l == blank;
+            else bad |= l < 0 || l >= V || l == blank;
             if (k >= 1 && l != lab[k - 1]) skipm |= 1u << j;
             lj[j] = l;
+            if constexpr (STAR) {
+                if (l == V) {
+                    starm |= 1u << j;
+                    lj[j] = blank;                       // (the column this pair loads and discards)
+                }
+            }
         }
     }
     const int nbad = block_count(bad, red);
@@ -123,21 +152,28 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_vite
     if (tid == 0) {
         ev[0] = (double)lg[blank];
         if (U >= 1) od[0] = (double)lg[lj[0]];
+        if constexpr (STAR) {
+            if (starm & 1u) od[0] = xs[sg.out0];
+        }
     }
     for (int i = tid; i < 2 * (LATTICE_MAX_THREADS + 1); i += NT) (&xv[0][0])[i] = NEG;
     __syncthreads();
     xv[0][tid + 1] = od[P - 1];
     uint32_t* __restrict__ bpw = a.bp + sg.bp0 + tid;
     float qb[PF], ql[PF][P];                             // x_t(blank), x_t(l_k) of the next PF steps
+    const double* __restrict__ xsr = STAR ? xs + sg.out0 : nullptr;
+    double qs[STAR ? PF : 1];                            // xs_t of the next PF steps (STAR)
+    qs[0] = 0.0;
 #pragma unroll
     for (int i = 0; i < PF; ++i) {
         const float* __restrict__ row = lg + (int64_t)min(1 + i, T - 1) * V;
         qb[i] = row[blank];
+        if constexpr (STAR) qs[i] = xsr[min(1 + i, T - 1)];
 #pragma unroll
         for (int j = 0; j < P; ++j) ql[i][j] = row[lj[j]];
     }
     uint32_t word = 0;
-    auto step = [&](int t, float yb, const float* yl, int slot) {
+    auto step = [&](int t, float yb, const float* yl, double ys, int slot) {
         lds_barrier();
         const double nb = xv[(t - 1) & 1][tid];          // delta_{t-1}(2 k0 - 1)
         const double xb = (double)yb;
@@ -153,7 +189,8 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_vite
             if (ev[j] > mo) { mo = ev[j]; bo = 1; }
             if ((skipm >> j & 1u) && po > mo) { mo = po; bo = 2; }
             const int k = k0 + j;
-            od[j] = k < U ? mo + (double)yl[j] : NEG;
+            if constexpr (STAR) od[j] = k < U ? mo + ((starm >> j & 1u) ? ys : (double)yl[j]) : NEG;
+            else od[j] = k < U ? mo + (double)yl[j] : NEG;
             ev[j] = k <= U ? me + xb : NEG;
             bits |= (be | bo << 2) << (4 * j);
         }
@@ -165,13 +202,14 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_vite
     for (; t0 + PF <= T; t0 += PF) {
 #pragma unroll
         for (int i = 0; i < PF; ++i) {
-            step(t0 + i, qb[i], ql[i], i % G);
+            step(t0 + i, qb[i], ql[i], qs[STAR ? i : 0], i % G);
             if (i % G == G - 1) {
                 bpw[(int64_t)((t0 + i - 1) / G) * NT] = word;
                 word = 0;
             }
             const float* __restrict__ row = lg + (int64_t)min(t0 + i + PF, T - 1) * V;      // (block-uniform row, per-lane column)
             qb[i] = row[blank];
+            if constexpr (STAR) qs[i] = xsr[min(t0 + i + PF, T - 1)];
 #pragma unroll
             for (int j = 0; j < P; ++j) ql[i][j] = row[lj[j]];
         }
@@ -179,7 +217,7 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_vite
 #pragma unroll
     for (int i = 0; i < PF; ++i) {
         if (t0 + i < T) {                                // (block-uniform)
-            step(t0 + i, qb[i], ql[i], i % G);
+            step(t0 + i, qb[i], ql[i], qs[STAR ? i : 0], i % G);
             if (i % G == G - 1 || t0 + i == T - 1) {
                 bpw[(int64_t)((t0 + i - 1) / G) * NT] = word;
                 word = 0;
@@ -242,7 +280,8 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_vite
             const int64_t o = sg.out0 + t;
             a.token[o] = tok;
             a.label_index[o] = (s & 1) ? (s >> 1) : -1;
-            a.frame_logp[o] = (float)((double)lg[(int64_t)t * V + tok] - a.lse[o]);
+            if constexpr (STAR) a.frame_logp[o] = (float)((tok == V ? xsr[t] : (double)lg[(int64_t)t * V + tok]) - a.lse[o]);
+            else a.frame_logp[o] = (float)((double)lg[(int64_t)t * V + tok] - a.lse[o]);
         }
         if (t_lo == 0) break;
         t_hi = t_lo;
@@ -251,14 +290,17 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_vite
 
 }  // namespace
 
-int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
-                     const int64_t* label0, const int32_t* nlabels, int blank, int32_t* token, int32_t* label_index,
-                     float* frame_logp, double* score, hipStream_t s) {
+namespace {
+
+int align_launch(bool star, float star_score, const float* logits, int V, int n, const int64_t* row0, const int32_t* frames,
+                 const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank, int32_t* token, int32_t* label_index,
+                 float* frame_logp, double* score, hipStream_t s) {
     W2V2_REQUIRE(logits && row0 && frames && labels && label0 && nlabels && token && label_index && frame_logp && score,
                  "ctc_align: null argument");
     W2V2_REQUIRE(n >= 1, "ctc_align: %d utterances (need at least one)", n);
     W2V2_REQUIRE(V >= 1, "ctc_align: vocabulary of %d entries", V);
     W2V2_REQUIRE(blank >= 0 && blank < V, "ctc_align: blank index %d outside vocabulary %d", blank, V);
+    W2V2_REQUIRE(!star || star_score <= 0.f, "ctc_align: star_score %g (a log-domain penalty per frame: <= 0, not NaN)", (double)star_score);
     int Umax = 0, Tmax = 0;
     for (int i = 0; i < n; ++i) {
         W2V2_REQUIRE(frames[i] >= 1, "ctc_align: utterance %d has %d frames (need at least one)", i, frames[i]);
@@ -280,17 +322,19 @@ int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, con
         out += frames[i];
         words += (int64_t)((frames[i] - 1 + G - 1) / G) * nt;
     }
-    // workspace: the table | lse (fp64, sum T_i) | backpointer words
+    // workspace: the table | lse (fp64, sum T_i) | xs (the same, star calls only) | backpointer words
     const size_t tab_bytes = up256((size_t)n * sizeof(AlignSeg)), lse_bytes = up256((size_t)out * sizeof(double));
+    const size_t xs_bytes = star ? lse_bytes : 0;
     void* raw = nullptr;
-    if (int e = stream_scratch(SCRATCH_ALIGN, s, tab_bytes + lse_bytes + (size_t)std::max<int64_t>(words, 1) * sizeof(uint32_t), &raw))
+    if (int e = stream_scratch(SCRATCH_ALIGN, s, tab_bytes + lse_bytes + xs_bytes + (size_t)std::max<int64_t>(words, 1) * sizeof(uint32_t), &raw))
         return e;
     AlignArgs a;
     a.logits = logits;
     a.labels = labels;
     a.segs = static_cast<const AlignSeg*>(raw);
     a.lse = reinterpret_cast<double*>(static_cast<char*>(raw) + tab_bytes);
-    a.bp = reinterpret_cast<uint32_t*>(static_cast<char*>(raw) + tab_bytes + lse_bytes);
+    double* xs = star ? reinterpret_cast<double*>(static_cast<char*>(raw) + tab_bytes + lse_bytes) : nullptr;
+    a.bp = reinterpret_cast<uint32_t*>(static_cast<char*>(raw) + tab_bytes + lse_bytes + xs_bytes);
     a.token = token;
     a.label_index = label_index;
     a.frame_logp = frame_logp;
@@ -301,12 +345,33 @@ int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, con
     if (int e = staged_upload(SCRATCH_ALIGN, s, raw, {{segs.data(), (size_t)n * sizeof(AlignSeg), 0}}, (size_t)16 << 10)) return e;
     // (work for the profile: the sweep's ~12 fp64 operations per state and step; the logits read once by the lse pass)
     ProfScope ps(nullptr, FAM_CTC, 12.0 * (double)out * (2.0 * Umax + 1.0), 4.0 * (double)out * V, s);
-    W2V2_LAUNCH(align_lse_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);
-    dispatch_pairs(P, [&](auto p) {
-        W2V2_LAUNCH(align_viterbi_kernel<decltype(p)::value>, dim3((unsigned)n), dim3((unsigned)a.nt), 0, s, a);
-    });
+    if (star) {
+        W2V2_LAUNCH(align_lse_star_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a, xs, star_score);
+        dispatch_pairs(P, [&](auto p) {
+            W2V2_LAUNCH((align_viterbi_kernel<decltype(p)::value, true>), dim3((unsigned)n), dim3((unsigned)a.nt), 0, s, a, (const double*)xs);
+        });
+    } else {
+        W2V2_LAUNCH(align_lse_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);
+        dispatch_pairs(P, [&](auto p) {
+            W2V2_LAUNCH((align_viterbi_kernel<decltype(p)::value, false>), dim3((unsigned)n), dim3((unsigned)a.nt), 0, s, a, (const double*)xs);
+        });
+    }
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
+}
+
+}  // namespace
+
+int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
+                     const int64_t* label0, const int32_t* nlabels, int blank, int32_t* token, int32_t* label_index,
+                     float* frame_logp, double* score, hipStream_t s) {
+    return align_launch(false, 0.f, logits, V, n, row0, frames, labels, label0, nlabels, blank, token, label_index, frame_logp, score, s);
+}
+
+int launch_ctc_align_star(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
+                          const int64_t* label0, const int32_t* nlabels, int blank, float star_score, int32_t* token,
+                          int32_t* label_index, float* frame_logp, double* score, hipStream_t s) {
+    return align_launch(true, star_score, logits, V, n, row0, frames, labels, label0, nlabels, blank, token, label_index, frame_logp, score, s);
 }
 
 }  // namespace w2v2

@@ -30,6 +30,10 @@
 // block writing the outputs); flagged recordings get their -1 / NaN rows here.  Backpointers: 2 bits per state in align.hip's word
 // layout, word (g, q (sp / P) + tid) = step group g of thread tid of strip q, i.e. column pair / P of a row of strips x (sp / P)
 // words; pf is a multiple of 8, so a step group never straddles a panel.  All backpointer, carry and column indices are 64-bit.
+//
+// The star (w2v2_ctc_align_long_star): align.hip's, operation for operation.  The pre-pass writes xs_t beside lse_t
+// (align_long_lse_star_kernel), the init kernel admits the label V, and the tile and finish kernels carry align.hip's compile-time
+// STAR flag: the mask of star pairs, xs_t loaded PD steps ahead, V and xs_t - lse_t on star frames.  STAR = false is the star-free code.
 #include "ctc_lattice.h"
 
 #include <algorithm>
@@ -81,9 +85,18 @@ __global__ __launch_bounds__(256) void align_long_lse_kernel(LongArgs a) {
     frame_lse(a.logits, a.V, sg.row0, sg.T, a.lse + sg.out0);
 }
 
+// ... and xs_t = m_t + star_score into xs, indexed like lse
+__global__ __launch_bounds__(256) void align_long_lse_star_kernel(LongArgs a, double* xs, float star_score) {
+    const LongSeg sg = a.segs[blockIdx.y];
+    float m;
+    const int t = frame_lse_max(a.logits, a.V, sg.row0, sg.T, a.lse + sg.out0, m);
+    if (t >= 0 && (threadIdx.x & 63) == 0) xs[sg.out0 + t] = (double)m + (double)star_score;
+}
+
 // one block per recording: the two checks that span strips (integer counts: any order gives the same flag), then the carry row at
-// frame 0: delta_0(0) = x_0(blank), delta_0(1) = x_0(l_0), every other state -inf
-__global__ __launch_bounds__(256) void align_long_init_kernel(LongArgs a) {
+// frame 0: delta_0(0) = x_0(blank), delta_0(1) = x_0(l_0) (xs_0 for the star), every other state -inf
+template <bool STAR>
+__global__ __launch_bounds__(256) void align_long_init_kernel(LongArgs a, const double* xs) {
     constexpr double NEG = -__builtin_inf();
     __shared__ long long red[2][4];
     const LongSeg sg = a.segs[blockIdx.x];
@@ -92,7 +105,8 @@ __global__ __launch_bounds__(256) void align_long_init_kernel(LongArgs a) {
     long long nbad = 0, rep = 0;
     for (int64_t k = tid; k < U; k += 256) {
         const int l = lab[k];
-        nbad += l < 0 || l >= V || l == blank;
+        if constexpr (STAR) nbad += l < 0 || l > V || l == blank;
+        else nbad += l < 0 || l >= V || l == blank;
         rep += k >= 1 && l == lab[k - 1];
     }
 #pragma unroll
@@ -113,12 +127,18 @@ __global__ __launch_bounds__(256) void align_long_init_kernel(LongArgs a) {
     const float* __restrict__ lg = a.logits + sg.row0 * V;
     double* __restrict__ cr = a.carry + sg.carry0;
     const int64_t S = 2 * (int64_t)U + 1;
-    for (int64_t s = tid; s < S; s += 256) cr[s] = s == 0 ? (double)lg[blank] : s == 1 ? (double)lg[lab[0]] : NEG;
+    if constexpr (STAR) {
+        for (int64_t s = tid; s < S; s += 256)
+            cr[s] = s == 0 ? (double)lg[blank] : s == 1 ? (lab[0] == V ? xs[sg.out0] : (double)lg[lab[0]]) : NEG;
+    } else {
+        for (int64_t s = tid; s < S; s += 256) cr[s] = s == 0 ? (double)lg[blank] : s == 1 ? (double)lg[lab[0]] : NEG;
+    }
 }
 
 // tile tile0 + blockIdx.x of the table: align.hip's sweep over one panel for one strip
-template <int P>
-__global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_long_tile_kernel(LongArgs a, int64_t tile0) {
+template <int P, bool STAR>
+__global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_long_tile_kernel(LongArgs a, int64_t tile0, const double* xs) {
+    // (xs: the star's emission per frame, indexed like a.lse; read only with STAR)
     constexpr int G = 8 / P;                 // steps per backpointer word
     constexpr int PD = P == 8 ? 2 : 8;       // steps the emissions and the column are loaded ahead (a multiple of G)
     constexpr double NEG = -__builtin_inf();
@@ -139,7 +159,7 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_long
     const int nod = act ? (int)max((int64_t)-1, min((int64_t)P, (int64_t)U - k0)) : -1;
     double* __restrict__ cr = a.carry + sg.carry0;
     int lj[P];
-    unsigned skipm = 0;
+    unsigned skipm = 0, starm = 0;                       // starm (STAR): the pairs whose label is the star
     double ev[P], od[P];                                 // delta(2k), delta(2k + 1) of the thread's pairs
 #pragma unroll
     for (int j = 0; j < P; ++j) {
@@ -152,6 +172,12 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_long
             const int l = lab[k];
             if (k >= 1 && l != lab[k - 1]) skipm |= 1u << j;     // (the first pair of a strip: the label of the strip below)
             lj[j] = l;
+            if constexpr (STAR) {
+                if (l == V) {
+                    starm |= 1u << j;
+                    lj[j] = blank;                       // (the column this pair loads and discards)
+                }
+            }
             od[j] = cr[2 * k + 1];
         }
     }
@@ -165,16 +191,20 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_long
     const bool wcol = tl.q + 1 < sg.strips && tid == a.wps - 1;      // the strip's last thread, when a strip above reads the column
     xv[0][tid + 1] = od[P - 1];                          // (tb - 1 is even)
     float qb[PD], ql[PD][P];                             // x_t(blank), x_t(l_k) of the next PD steps
+    const double* __restrict__ xsr = STAR ? xs + sg.out0 : nullptr;
+    double qs[STAR ? PD : 1];                            // xs_t of the next PD steps (STAR)
+    qs[0] = 0.0;
 #pragma unroll
     for (int i = 0; i < PD; ++i) {
         const float* __restrict__ row = lg + (int64_t)min(tb + i, T - 1) * V;
         qb[i] = row[blank];
+        if constexpr (STAR) qs[i] = xsr[min(tb + i, T - 1)];
 #pragma unroll
         for (int j = 0; j < P; ++j) ql[i][j] = row[lj[j]];
     }
     uint32_t word = 0;
     int cb = tb;                                         // first step of the current chunk
-    auto step = [&](int t, float yb, const float* yl, int slot) {
+    auto step = [&](int t, float yb, const float* yl, double ys, int slot) {
         lds_barrier();
         const double nb = *(tid ? &xv[(t - 1) & 1][tid] : &cl[t - cb]);      // delta_{t-1}(2 k0 - 1)
         const double xb = (double)yb;
@@ -189,7 +219,8 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_long
             uint32_t bo = 0;
             if (ev[j] > mo) { mo = ev[j]; bo = 1; }
             if ((skipm >> j & 1u) && po > mo) { mo = po; bo = 2; }
-            od[j] = j < nod ? mo + (double)yl[j] : NEG;
+            if constexpr (STAR) od[j] = j < nod ? mo + ((starm >> j & 1u) ? ys : (double)yl[j]) : NEG;
+            else od[j] = j < nod ? mo + (double)yl[j] : NEG;
             ev[j] = j <= nod ? me + xb : NEG;
             bits |= (be | bo << 2) << (4 * j);
         }
@@ -209,13 +240,14 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_long
         for (; t0 + PD <= ce; t0 += PD) {
 #pragma unroll
             for (int i = 0; i < PD; ++i) {
-                step(t0 + i, qb[i], ql[i], i % G);
+                step(t0 + i, qb[i], ql[i], qs[STAR ? i : 0], i % G);
                 if (i % G == G - 1) {
                     if (act) bpw[(int64_t)((t0 + i - 1) / G) * W] = word;
                     word = 0;
                 }
                 const float* __restrict__ row = lg + (int64_t)min(t0 + i + PD, T - 1) * V;      // (block-uniform row, per-lane column)
                 qb[i] = row[blank];
+                if constexpr (STAR) qs[i] = xsr[min(t0 + i + PD, T - 1)];
 #pragma unroll
                 for (int j = 0; j < P; ++j) ql[i][j] = row[lj[j]];
             }
@@ -225,7 +257,7 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_long
 #pragma unroll
     for (int i = 0; i < PD; ++i) {
         if (t0 + i < te) {                               // (block-uniform)
-            step(t0 + i, qb[i], ql[i], i % G);
+            step(t0 + i, qb[i], ql[i], qs[STAR ? i : 0], i % G);
             if (i % G == G - 1 || t0 + i == te - 1) {
                 if (act) bpw[(int64_t)((t0 + i - 1) / G) * W] = word;
                 word = 0;
@@ -242,8 +274,8 @@ __global__ __launch_bounds__(P == 8 ? LATTICE_MAX_THREADS : 256) void align_long
 }
 
 // one block per recording: end state, score, backtrace (align.hip's, on rows of strips x wps words), or the -1 / NaN rows
-template <int P>
-__global__ __launch_bounds__(256) void align_long_finish_kernel(LongArgs a) {
+template <int P, bool STAR>
+__global__ __launch_bounds__(256) void align_long_finish_kernel(LongArgs a, const double* xs) {
     constexpr int G = 8 / P;
     constexpr double NEG = -__builtin_inf();
     __shared__ uint32_t win[LATTICE_WIN_WORDS];          // backtrace window of backpointer words
@@ -319,7 +351,8 @@ __global__ __launch_bounds__(256) void align_long_finish_kernel(LongArgs a) {
             const int64_t o = sg.out0 + t;
             a.token[o] = tok;
             a.label_index[o] = (s & 1) ? (int)(s >> 1) : -1;
-            a.frame_logp[o] = (float)((double)lg[(int64_t)t * V + tok] - a.lse[o]);
+            if constexpr (STAR) a.frame_logp[o] = (float)((tok == V ? xs[o] : (double)lg[(int64_t)t * V + tok]) - a.lse[o]);
+            else a.frame_logp[o] = (float)((double)lg[(int64_t)t * V + tok] - a.lse[o]);
         }
         if (t_lo == 0) break;
         t_hi = t_lo;
@@ -330,11 +363,11 @@ __global__ __launch_bounds__(256) void align_long_finish_kernel(LongArgs a) {
 struct LongPlan {
     int sp, pf, P, G, nt, wps, Tmax, Umax;
     int64_t frames, tiles, diagonals;
-    size_t tile_bytes, seg_bytes, lse_bytes, flag_bytes, carry_bytes, col_bytes, bp_bytes;
+    size_t tile_bytes, seg_bytes, lse_bytes, xs_bytes, flag_bytes, carry_bytes, col_bytes, bp_bytes;
     int64_t total;          // INT64_MAX when it does not fit
 };
 
-int long_plan(int n, const int32_t* frames, const int32_t* nlabels, int strip_pairs, int panel_frames, LongPlan& pl) {
+int long_plan(int n, const int32_t* frames, const int32_t* nlabels, int strip_pairs, int panel_frames, bool star, LongPlan& pl) {
     W2V2_REQUIRE(frames && nlabels, "ctc_align_long: null argument");
     W2V2_REQUIRE(n >= 1, "ctc_align_long: %d recordings (need at least one)", n);
     W2V2_REQUIRE(strip_pairs == 0 || (strip_pairs >= 64 && strip_pairs <= 8192 && strip_pairs % 64 == 0),
@@ -376,11 +409,12 @@ int long_plan(int n, const int32_t* frames, const int32_t* nlabels, int strip_pa
     pl.tile_bytes = up256(std::max<unsigned __int128>(tiles, 1) * sizeof(LongTile));
     pl.seg_bytes = up256((unsigned __int128)n * sizeof(LongSeg));
     pl.lse_bytes = up256(out * sizeof(double));
+    pl.xs_bytes = star ? pl.lse_bytes : 0;
     pl.flag_bytes = up256((unsigned __int128)n * sizeof(int32_t));
     pl.carry_bytes = up256(carry * sizeof(double));
     pl.col_bytes = up256(col * sizeof(double));
     pl.bp_bytes = up256(std::max<unsigned __int128>(words, 1) * sizeof(uint32_t));
-    const unsigned __int128 total = (unsigned __int128)pl.tile_bytes + pl.seg_bytes + pl.lse_bytes + pl.flag_bytes + pl.carry_bytes +
+    const unsigned __int128 total = (unsigned __int128)pl.tile_bytes + pl.seg_bytes + pl.lse_bytes + pl.xs_bytes + pl.flag_bytes + pl.carry_bytes +
                                     pl.col_bytes + pl.bp_bytes;
     if (total < lim) pl.total = (int64_t)total;
     return W2V2_OK;
@@ -388,23 +422,24 @@ int long_plan(int n, const int32_t* frames, const int32_t* nlabels, int strip_pa
 
 }  // namespace
 
-int64_t ctc_align_long_workspace(int n, const int32_t* frames, const int32_t* nlabels, int strip_pairs, int panel_frames) {
+int64_t ctc_align_long_workspace(int n, const int32_t* frames, const int32_t* nlabels, int strip_pairs, int panel_frames, bool star) {
     LongPlan pl;
-    if (int e = long_plan(n, frames, nlabels, strip_pairs, panel_frames, pl)) return e;
+    if (int e = long_plan(n, frames, nlabels, strip_pairs, panel_frames, star, pl)) return e;
     return pl.total;
 }
 
 int launch_ctc_align_long(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
                           const int64_t* label0, const int32_t* nlabels, int blank, int32_t* token, int32_t* label_index,
                           float* frame_logp, double* score, int strip_pairs, int panel_frames, int64_t max_workspace_bytes,
-                          hipStream_t s) {
+                          hipStream_t s, bool star, float star_score) {
     W2V2_REQUIRE(logits && row0 && frames && labels && label0 && nlabels && token && label_index && frame_logp && score,
                  "ctc_align_long: null argument");
     W2V2_REQUIRE(V >= 1, "ctc_align_long: vocabulary of %d entries", V);
     W2V2_REQUIRE(blank >= 0 && blank < V, "ctc_align_long: blank index %d outside vocabulary %d", blank, V);
     W2V2_REQUIRE(max_workspace_bytes >= 0, "ctc_align_long: max_workspace_bytes %lld is negative", (long long)max_workspace_bytes);
+    W2V2_REQUIRE(!star || star_score <= 0.f, "ctc_align_long: star_score %g (a log-domain penalty per frame: <= 0, not NaN)", (double)star_score);
     LongPlan pl;
-    if (int e = long_plan(n, frames, nlabels, strip_pairs, panel_frames, pl)) return e;
+    if (int e = long_plan(n, frames, nlabels, strip_pairs, panel_frames, star, pl)) return e;
     for (int i = 0; i < n; ++i)
         W2V2_REQUIRE(row0[i] >= 0 && label0[i] >= 0, "ctc_align_long: recording %d has a negative offset", i);
     const int64_t cap = max_workspace_bytes ? max_workspace_bytes : LONG_DEFAULT_CAP;
@@ -438,7 +473,7 @@ int launch_ctc_align_long(const float* logits, int V, int n, const int64_t* row0
                 for (int q = 0; q < segs[i].strips; ++q) tiles[(size_t)next[(size_t)(p + q)]++] = LongTile{i, p, q, 0};
     }
 
-    // workspace: the tiles | the recordings | lse | flags | carry rows | boundary columns | backpointer words
+    // workspace: the tiles | the recordings | lse | xs (star calls only) | flags | carry rows | boundary columns | backpointer words
     void* raw = nullptr;
     if (int e = stream_scratch(SCRATCH_ALIGN_LONG, s, (size_t)pl.total, &raw)) return e;
     char* base = static_cast<char*>(raw);
@@ -451,6 +486,9 @@ int launch_ctc_align_long(const float* logits, int V, int n, const int64_t* row0
     base += pl.seg_bytes;
     a.lse = reinterpret_cast<double*>(base);
     base += pl.lse_bytes;
+    double* xsw = star ? reinterpret_cast<double*>(base) : nullptr;
+    const double* xs = xsw;
+    base += pl.xs_bytes;
     a.flag = reinterpret_cast<int32_t*>(base);
     base += pl.flag_bytes;
     a.carry = reinterpret_cast<double*>(base);
@@ -476,16 +514,24 @@ int launch_ctc_align_long(const float* logits, int V, int n, const int64_t* row0
     double work = 0.0;
     for (int i = 0; i < n; ++i) work += 12.0 * (double)frames[i] * (2.0 * nlabels[i] + 1.0);
     ProfScope ps(nullptr, FAM_CTC, work, 4.0 * (double)pl.frames * V, s);
-    W2V2_LAUNCH(align_long_lse_kernel, dim3((unsigned)((pl.Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);
-    W2V2_LAUNCH(align_long_init_kernel, dim3((unsigned)n), dim3(256), 0, s, a);
-    for (int64_t d = 0; d < pl.diagonals; ++d) {
-        const int64_t off = first[(size_t)d], count = first[(size_t)d + 1] - off;
-        if (!count) continue;
+    auto run = [&](auto st) {
+        constexpr bool STAR = decltype(st)::value;
+        if constexpr (STAR) W2V2_LAUNCH(align_long_lse_star_kernel, dim3((unsigned)((pl.Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a, xsw, star_score);
+        else W2V2_LAUNCH(align_long_lse_kernel, dim3((unsigned)((pl.Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);
+        W2V2_LAUNCH(align_long_init_kernel<STAR>, dim3((unsigned)n), dim3(256), 0, s, a, xs);
+        for (int64_t d = 0; d < pl.diagonals; ++d) {
+            const int64_t off = first[(size_t)d], count = first[(size_t)d + 1] - off;
+            if (!count) continue;
+            dispatch_pairs(pl.P, [&](auto p) {
+                W2V2_LAUNCH((align_long_tile_kernel<decltype(p)::value, STAR>), dim3((unsigned)count), dim3((unsigned)pl.nt), 0, s, a, off, xs);
+            });
+        }
         dispatch_pairs(pl.P, [&](auto p) {
-            W2V2_LAUNCH(align_long_tile_kernel<decltype(p)::value>, dim3((unsigned)count), dim3((unsigned)pl.nt), 0, s, a, off);
+            W2V2_LAUNCH((align_long_finish_kernel<decltype(p)::value, STAR>), dim3((unsigned)n), dim3(256), 0, s, a, xs);
         });
-    }
-    dispatch_pairs(pl.P, [&](auto p) { W2V2_LAUNCH(align_long_finish_kernel<decltype(p)::value>, dim3((unsigned)n), dim3(256), 0, s, a); });
+    };
+    if (star) run(std::true_type());
+    else run(std::false_type());
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }

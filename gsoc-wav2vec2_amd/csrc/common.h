@@ -461,14 +461,20 @@ int launch_ctc_x(Profiler* prof, const float* logits, int B, int T, int V, const
 int launch_ctc_align(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
                      const int64_t* label0, const int32_t* nlabels, int blank, int32_t* token, int32_t* label_index,
                      float* frame_logp, double* score, hipStream_t s);
+// ... with the star, the wildcard label V (w2v2_ctc_align_star; the definition in align.hip): star_score <= 0
+int launch_ctc_align_star(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
+                          const int64_t* label0, const int32_t* nlabels, int blank, float star_score, int32_t* token,
+                          int32_t* label_index, float* frame_logp, double* score, hipStream_t s);
 // ... of whole recordings (align_long.hip; w2v2_ctc_align_long): the same addressing and outputs, any label count; the plane of
 // frames x states runs as tiles of panel_frames steps x strip_pairs state pairs (0 = the defaults), one launch per anti-diagonal.
-// ctc_align_long_workspace: the bytes of scratch such a call needs (host only; a negative W2V2_E* for bad shapes)
+// ctc_align_long_workspace: the bytes of scratch such a call needs (host only; a negative W2V2_E* for bad shapes).  star: the
+// label V is the star with that star_score (w2v2_ctc_align_long_star), and the workspace holds xs_t as well
 int launch_ctc_align_long(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
                           const int64_t* label0, const int32_t* nlabels, int blank, int32_t* token, int32_t* label_index,
                           float* frame_logp, double* score, int strip_pairs, int panel_frames, int64_t max_workspace_bytes,
-                          hipStream_t s);
-int64_t ctc_align_long_workspace(int n, const int32_t* frames, const int32_t* nlabels, int strip_pairs, int panel_frames);
+                          hipStream_t s, bool star = false, float star_score = 0.f);
+int64_t ctc_align_long_workspace(int n, const int32_t* frames, const int32_t* nlabels, int strip_pairs, int panel_frames,
+                                 bool star = false);
 // exact CTC scoring (score.hip; w2v2_ctc_score): the same addressing of the logits; pair j = utterance utt_of[j] against labels
 // [label0_j, label0_j + nlabels_j); one fp64 log-probability per pair, in the caller's order
 int launch_ctc_score(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int m, const int32_t* utt_of,

@@ -52,6 +52,26 @@ __device__ __forceinline__ void frame_lse(const float* logits, int V, int64_t ro
     if (lane == 0) lse[t] = (double)m + log(acc);
 }
 
+// frame_lse that also yields the frame's maximum (the star emission of the aligners): the same operations in the
+// same order, so lse[t] has frame_lse's bits.  Returns the wave's frame t (-1: none) and, in every lane, m = the fp32 maximum of
+// the frame's V logits (fmaxf: a NaN logit is ignored; -inf when all are NaN).
+__device__ __forceinline__ int frame_lse_max(const float* logits, int V, int64_t row0, int T, double* lse, float& m) {
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    m = -INFINITY;
+    if (t >= T) return -1;
+    const int lane = threadIdx.x & 63;
+    const float* __restrict__ r = logits + (row0 + t) * V;
+    for (int v = lane; v < V; v += 64) m = fmaxf(m, r[v]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    double acc = 0.0;
+    for (int v = lane; v < V; v += 64) acc += exp((double)r[v] - (double)m);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane == 0) lse[t] = (double)m + log(acc);
+    return t;
+}
+
 // number of threads of the block for which pred holds (wave ballots, then the waves in order)
 __device__ __forceinline__ int block_count(bool pred, int* red) {
     const unsigned long long b = __ballot(pred);

@@ -528,6 +528,13 @@ int w2v2_ctc_align(const float* logits, int32_t V, int32_t n, const int64_t* row
                             reinterpret_cast<hipStream_t>(stream));
 }
 
+int w2v2_ctc_align_star(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
+                        const int64_t* label0, const int32_t* nlabels, int32_t blank, float star_score, int32_t* token,
+                        int32_t* label_index, float* frame_logp, double* score, void* stream) {
+    return launch_ctc_align_star(logits, V, n, row0, frames, labels, label0, nlabels, blank, star_score, token, label_index, frame_logp,
+                                 score, reinterpret_cast<hipStream_t>(stream));
+}
+
 int w2v2_ctc_align_long(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, const int32_t* labels,
                         const int64_t* label0, const int32_t* nlabels, int32_t blank, int32_t* token, int32_t* label_index,
                         float* frame_logp, double* score, int32_t strip_pairs, int32_t panel_frames, int64_t max_workspace_bytes,
@@ -539,6 +546,19 @@ int w2v2_ctc_align_long(const float* logits, int32_t V, int32_t n, const int64_t
 int64_t w2v2_ctc_align_long_workspace(int32_t n, const int32_t* frames, const int32_t* nlabels, int32_t strip_pairs,
                                       int32_t panel_frames) {
     return ctc_align_long_workspace(n, frames, nlabels, strip_pairs, panel_frames);
+}
+
+int w2v2_ctc_align_long_star(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames,
+                             const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int32_t blank, float star_score,
+                             int32_t* token, int32_t* label_index, float* frame_logp, double* score, int32_t strip_pairs,
+                             int32_t panel_frames, int64_t max_workspace_bytes, void* stream) {
+    return launch_ctc_align_long(logits, V, n, row0, frames, labels, label0, nlabels, blank, token, label_index, frame_logp, score,
+                                 strip_pairs, panel_frames, max_workspace_bytes, reinterpret_cast<hipStream_t>(stream), true, star_score);
+}
+
+int64_t w2v2_ctc_align_long_star_workspace(int32_t n, const int32_t* frames, const int32_t* nlabels, int32_t strip_pairs,
+                                           int32_t panel_frames) {
+    return ctc_align_long_workspace(n, frames, nlabels, strip_pairs, panel_frames, true);
 }
 
 int w2v2_ctc_score(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t m, const int32_t* utt_of,

@@ -692,26 +692,35 @@ class Wav2Vec2ForCTC(TFKerasModel):
 
     call = __call__
 
-    def align(self, waveforms, transcripts, tokenizer=None, delimiter_id=None, sampling_rate=None, normalize=False):
+    def align(self, waveforms, transcripts, tokenizer=None, delimiter_id=None, sampling_rate=None, normalize=False, star=None,
+              free_ends=False, star_score=-0.5):
         """Word timestamps: `predict_packed(waveforms)`, then the CTC forced alignment of each transcript on the packed logits
         in place (wav2vec2.alignment: forced_align, token_spans, word_spans; blank = config.pad_id).  A transcript is text,
         encoded with `tokenizer` (a Wav2Vec2Processor(is_tokenizer=True)), or a sequence of ids, used as it is.  Frame f lies at
         f * prod(strides) / 16000 s.  The word delimiter is the tokenizer's "|" unless `delimiter_id` is given.  Returns one list
         of WordSpan(text, start_s, end_s, score) per utterance.  Runs in the precision modes predict_packed accepts.
         `sampling_rate`, `normalize`: as `predict_packed`.  A frame is prod(strides) samples of the 16 kHz audio whatever the
-        rate of the input, so the times stay seconds of the recording."""
-        from .alignment import forced_align, token_spans, word_spans
+        rate of the input, so the times stay seconds of the recording.
+
+        Partial transcripts: with `star` (say "*") a whitespace-separated word of a text transcript equal to it
+        is the star, a wildcard that absorbs whatever is spoken there (at least one frame; the word delimiter next to it is
+        dropped); id transcripts may hold the star's id, config.vocab_size, directly.  `free_ends=True` puts a star before the
+        first and after the last label: speech before and after the transcript.  Either one switches the star on:
+        forced_align(..., star_score=star_score), and the returned lists hold a WordSpan(star or "*", ...) per star, so the
+        caller sees where the unknown speech lies.  `star_score` (<= 0, nats per frame; -0.5 is a convention, not a tuned value)
+        is what a star frame pays on top of the frame's best token.  Without `star` and `free_ends` nothing changes."""
+        from .alignment import forced_align, token_spans, word_spans, star_transcript
         from .processor import WORD_DELIMITER
         if isinstance(transcripts, str) or len(transcripts) != len(waveforms):
             raise ValueError("one transcript per waveform")
+        use_star = star is not None or free_ends
+        V = self.config.vocab_size
         ids = []
         for i, tr in enumerate(transcripts):
-            if isinstance(tr, str):
-                if tokenizer is None:
-                    raise ValueError(f"transcript {i} is text: pass the tokenizer that encodes it")
-                ids.append(list(tokenizer(tr)))
-            else:
-                ids.append([int(x) for x in tr])
+            if isinstance(tr, str) and tokenizer is None:
+                raise ValueError(f"transcript {i} is text: pass the tokenizer that encodes it")
+            ids.append(star_transcript(tr, V, tokenizer, star, free_ends))
+        use_star = use_star or any(V in l for l in ids)          # (an id transcript that holds the star's id)
         vocab = None
         if tokenizer is not None:
             tokens = tokenizer.get_vocab()
@@ -721,11 +730,16 @@ class Wav2Vec2ForCTC(TFKerasModel):
         if delimiter_id is None:
             raise ValueError("ids without a tokenizer: pass delimiter_id")
         seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
-        alignments = forced_align(self.predict_packed(waveforms, sampling_rate, normalize), ids, blank=self.config.pad_id)
-        return [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab) for a in alignments]
+        logits = self.predict_packed(waveforms, sampling_rate, normalize)
+        if not use_star:
+            alignments = forced_align(logits, ids, blank=self.config.pad_id)
+            return [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab) for a in alignments]
+        alignments = forced_align(logits, ids, blank=self.config.pad_id, star_score=star_score)
+        star_text = "*" if star is None else star
+        return [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab, star_id=V, star_text=star_text) for a in alignments]
 
     def align_long(self, waveform, transcript, tokenizer=None, delimiter_id=None, window_s=20.0, margin_s=2.0, normalize=True,
-                   max_stream_s=1200.0, sampling_rate=None):
+                   max_stream_s=1200.0, sampling_rate=None, star=None, free_ends=False, star_score=-0.5):
         """Word timestamps of whole recordings and their texts: `predict_long(waveform, ...)`, then the forced alignment of each
         transcript on the stitched logits without a limit on its length (wav2vec2.alignment.forced_align_long; blank =
         config.pad_id), then token_spans / word_spans.  `waveform`: one recording or a list of them; `transcript`: one transcript
@@ -733,9 +747,11 @@ class Wav2Vec2ForCTC(TFKerasModel):
         `align`.  Returns the list of WordSpan(text, start_s, end_s, score) of the recording (a list of such lists for a list),
         the times in seconds of the recording exactly as `align` states them.  `window_s` ... `sampling_rate`: as `predict_long`.
         The alignment's workspace grows with frames x labels (about 5 GB for an hour of speech); wav2vec2.alignment's
-        `split_at_pauses` cuts the result into utterance-sized pieces."""
+        `split_at_pauses` cuts the result into utterance-sized pieces.  `star`, `free_ends`, `star_score`: as `align`, for
+        recordings whose text has gaps (a preface, an aside, an untranscribed speaker); `split_at_pauses(..., star_text=star)`
+        then cuts at the star words."""
         import torch
-        from .alignment import forced_align_long, token_spans, word_spans
+        from .alignment import forced_align_long, token_spans, word_spans, star_transcript
         from .processor import WORD_DELIMITER
         single = isinstance(waveform, (np.ndarray, torch.Tensor)) and getattr(waveform, "ndim", 0) == 1
         if single:
@@ -744,14 +760,14 @@ class Wav2Vec2ForCTC(TFKerasModel):
             waveform, transcripts = list(waveform), transcript
         if isinstance(transcripts, str) or len(transcripts) != len(waveform):
             raise ValueError("one transcript per recording")
+        use_star = star is not None or free_ends
+        V = self.config.vocab_size
         ids = []
         for i, tr in enumerate(transcripts):
-            if isinstance(tr, str):
-                if tokenizer is None:
-                    raise ValueError(f"transcript {i} is text: pass the tokenizer that encodes it")
-                ids.append(list(tokenizer(tr)))
-            else:
-                ids.append([int(x) for x in tr])
+            if isinstance(tr, str) and tokenizer is None:
+                raise ValueError(f"transcript {i} is text: pass the tokenizer that encodes it")
+            ids.append(star_transcript(tr, V, tokenizer, star, free_ends))
+        use_star = use_star or any(V in l for l in ids)          # (an id transcript that holds the star's id)
         vocab = None
         if tokenizer is not None:
             tokens = tokenizer.get_vocab()
@@ -762,8 +778,14 @@ class Wav2Vec2ForCTC(TFKerasModel):
             raise ValueError("ids without a tokenizer: pass delimiter_id")
         seconds_per_frame = float(np.prod(self.config.strides)) / 16000.0
         logits = self.predict_long(waveform, window_s, margin_s, normalize, max_stream_s, sampling_rate)
-        alignments = forced_align_long(logits, ids, blank=self.config.pad_id)
-        words = [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab) for a in alignments]
+        if use_star:
+            alignments = forced_align_long(logits, ids, blank=self.config.pad_id, star_score=star_score)
+            star_text = "*" if star is None else star
+            words = [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab, star_id=V, star_text=star_text)
+                     for a in alignments]
+        else:
+            alignments = forced_align_long(logits, ids, blank=self.config.pad_id)
+            words = [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab) for a in alignments]
         return words[0] if single else words
 
     def score(self, waveforms, transcripts, tokenizer=None, sampling_rate=None, normalize=False):

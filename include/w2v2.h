@@ -291,6 +291,29 @@ int w2v2_ctc_align_long(const float* logits_dev, int32_t V, int32_t n, const int
 int64_t w2v2_ctc_align_long_workspace(int32_t n, const int32_t* frames_host, const int32_t* nlabels_host, int32_t strip_pairs,
                                       int32_t panel_frames);
 
+/* Forced alignment with a wildcard label, the "star", for transcripts that do not spell everything that is spoken (DESIGN.md §21,
+ * exact definition in csrc/align.hip).  The three calls are w2v2_ctc_align, w2v2_ctc_align_long and
+ * w2v2_ctc_align_long_workspace with one more label id: V, the star, as if the logits had one more column whose raw-logit value at
+ * frame t is max_v logits[t][v] + star_score (the fp32 maximum over all V columns, the blank included, widened to fp64 before the
+ * sum).  A star may stand anywhere in a label string and absorbs whatever is spoken there; it occupies at least one frame, and the
+ * recursion, its ties, the end state and the feasibility rule frames_i >= nlabels_i + repeats (V counts like any id) are unchanged.
+ *   star_score   fp32, <= 0, nats per frame: a star frame costs what the greedy path pays for the frame, plus star_score.  NaN or
+ *                > 0 is W2V2_EINVAL.
+ *   outputs      on a star frame token = V, label_index = k, frame_logp = (float)(max + star_score - lse).  score is the score of
+ *                the path: with a star in the labels it is no longer the log-probability of a label string.
+ * A label < 0, > V or equal to the blank gives the NaN utterance.  Labels without a star give w2v2_ctc_align's bits.  The workspace
+ * of the _long call holds one more fp64 per frame than w2v2_ctc_align_long's. */
+int w2v2_ctc_align_star(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host,
+                        const int32_t* labels_dev, const int64_t* label0_host, const int32_t* nlabels_host, int32_t blank,
+                        float star_score, int32_t* token_dev, int32_t* label_index_dev, float* frame_logp_dev, double* score_dev,
+                        void* stream);
+int w2v2_ctc_align_long_star(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host,
+                             const int32_t* labels_dev, const int64_t* label0_host, const int32_t* nlabels_host, int32_t blank,
+                             float star_score, int32_t* token_dev, int32_t* label_index_dev, float* frame_logp_dev,
+                             double* score_dev, int32_t strip_pairs, int32_t panel_frames, int64_t max_workspace_bytes, void* stream);
+int64_t w2v2_ctc_align_long_star_workspace(int32_t n, const int32_t* frames_host, const int32_t* nlabels_host, int32_t strip_pairs,
+                                           int32_t panel_frames);
+
 /* Exact CTC scoring (exact definition in csrc/score.hip): the log-probability of a label string given an utterance's
  * logits, summed over every frame path that spells it (-ctc_loss in fp64), for m (utterance, label string) pairs in one call.
  * Model-free, like w2v2_ctc_align, and with its addressing of the utterances; asynchronous on `stream`.

@@ -9,8 +9,12 @@ transcript of about --labels-per-s labels per second of audio, with a share --re
   call_ms       one forced_align() call from Python (label checks, label upload, the kernels, the score copy back)
   ref_ms        the fp64 numpy reference (tests/align_reference.py) over the same set, on the host
   packed_ms     the packed fp32 forward of the set, for scale
+  star_*        the star row (w2v2_ctc_align_star): star_same_labels_kernel_ms is the star entry point on the very
+                same star-free labels; star_kernel_ms on the transcripts in which every --star-every-th word (a word: 5 labels)
+                is replaced by one star
 
     python tools/align_bench.py [--n 64] [--steps 20] [--warmup 3] [--labels-per-s 15] [--repeat 0.03] [--ref-n 64]
+                                [--star-every 20] [--star-score -0.5]
 """
 import argparse
 import json
@@ -49,6 +53,8 @@ def main():
     ap.add_argument("--labels-per-s", type=float, default=15.0)
     ap.add_argument("--repeat", type=float, default=0.03)
     ap.add_argument("--ref-n", type=int, default=64, help="utterances the host reference is timed on (0: skip)")
+    ap.add_argument("--star-every", type=int, default=20, help="every this many words one becomes a star (0: no star row)")
+    ap.add_argument("--star-score", type=float, default=-0.5)
     args = ap.parse_args()
 
     import torch
@@ -103,17 +109,47 @@ def main():
         N.check(lib.w2v2_ctc_align(N.ptr(base), cfg.vocab_size, n, N.ptr(row0_h), N.ptr(frames_h), N.ptr(lab_dev), N.ptr(label0),
                                    N.ptr(nlab), cfg.pad_id, N.ptr(tok), N.ptr(li), N.ptr(flp), N.ptr(sc), N.current_stream()))
 
-    for _ in range(args.warmup):
-        kernel()
-    torch.cuda.synchronize()
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    for a, b in ev:
-        a.record()
-        kernel()
-        b.record()
-    torch.cuda.synchronize()
-    kt = sorted(a.elapsed_time(b) for a, b in ev)
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        for a, b in ev:
+            a.record()
+            fn()
+            b.record()
+        torch.cuda.synchronize()
+        return sorted(a.elapsed_time(b) for a, b in ev)
+
+    kt = timed(kernel)
     kernel_ms = float(np.median(kt))
+
+    # the star row: the star entry point on the same labels, and on transcripts with every star_every-th word a star
+    star = {}
+    if args.star_every:
+        WORD = 5
+        slabels = []
+        for l in labels:
+            out = []
+            for w in range(0, len(l), WORD):
+                out.extend([cfg.vocab_size] if (w // WORD) % args.star_every == args.star_every - 1 else l[w:w + WORD])
+            slabels.append(out)
+        sflat = np.concatenate([np.asarray(l, np.int32) for l in slabels])
+        slab_dev = torch.from_numpy(sflat).cuda()
+        slabel0 = np.cumsum([0] + [len(l) for l in slabels[:-1]]).astype(np.int64)
+        snlab = np.asarray([len(l) for l in slabels], np.int32)
+
+        def star_kernel(ld, l0, nl):
+            N.check(lib.w2v2_ctc_align_star(N.ptr(base), cfg.vocab_size, n, N.ptr(row0_h), N.ptr(frames_h), N.ptr(ld), N.ptr(l0), N.ptr(nl),
+                                            cfg.pad_id, args.star_score, N.ptr(tok), N.ptr(li), N.ptr(flp), N.ptr(sc), N.current_stream()))
+
+        st = timed(lambda: star_kernel(slab_dev, slabel0, snlab))
+        star_frames = int((tok == cfg.vocab_size).sum().item())
+        ss = timed(lambda: star_kernel(lab_dev, label0, nlab))
+        star = {"stars": int((sflat == cfg.vocab_size).sum()), "star_labels": int(snlab.sum()), "star_frames": star_frames,
+                "star_kernel_ms": round(float(np.median(st)), 3), "star_kernel_ms_min": round(st[0], 3),
+                "star_same_labels_kernel_ms": round(float(np.median(ss)), 3), "star_same_labels_kernel_ms_min": round(ss[0], 3)}
+        kernel()                                                 # (tok below: the star-free paths)
 
     ct = []
     for _ in range(max(3, args.steps // 4)):
@@ -128,6 +164,7 @@ def main():
            "kernel_ms": round(kernel_ms, 3), "kernel_ms_min": round(kt[0], 3),
            "us_per_step": round(kernel_ms * 1e3 / max(frames), 3), "call_ms": round(call_ms, 3),
            "packed_ms": round(packed_ms, 2), "align_over_packed": round(kernel_ms / packed_ms, 4), "target_ms": 2.0}
+    res.update(star)
     if args.ref_n:
         import align_reference as AR
         hosts = [l.cpu().numpy() for l in logits[:args.ref_n]]

@@ -12,12 +12,15 @@ it is the planted one, and every timed geometry is checked against it.  Per geom
   us_per_step     ms / ((panels + strips) * panel_frames): the time per sequential step of the diagonal schedule, next to the
                   0.415 us per step of the one-block aligner (profiles/align.md)
   path_ok         the path equals the planted one
+  star_*          the star row (w2v2_ctc_align_long_star): star_same_labels_ms is the star entry point on the very
+                  same star-free labels (star_same_labels_path_ok: it finds the planted path too); star_ms on the transcript in which
+                  every --star-every-th word (a word: 5 labels) is replaced by one star
 
 and at the end the geometry with the smallest median and the hour's budget: the forward that produces the logits of the hour
 takes 0.57 s.
 
     python tools/align_long_bench.py [--frames 180000] [--labels 54000] [--strips 1024,2048,8192] [--panels 512,1024,2048]
-                                     [--steps 3] [--warmup 1] [--default]
+                                     [--steps 3] [--warmup 1] [--default] [--star-every 20] [--star-score -0.5]
 """
 import argparse
 import json
@@ -59,6 +62,8 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--default", action="store_true", help="time the library's default geometry (0, 0) as well")
+    ap.add_argument("--star-every", type=int, default=20, help="every this many words one becomes a star (0: no star row)")
+    ap.add_argument("--star-score", type=float, default=-0.5)
     args = ap.parse_args()
 
     import torch
@@ -76,6 +81,24 @@ def main():
     flp = torch.empty(T, dtype=torch.float32, device="cuda")
     sc = torch.empty(1, dtype=torch.float64, device="cuda")
     lib = N.load()
+    if args.star_every:
+        WORD = 5
+        slabels = np.concatenate([np.asarray([V], np.int32) if (w // WORD) % args.star_every == args.star_every - 1 else labels[w:w + WORD]
+                                  for w in range(0, U, WORD)])
+        slab_dev = torch.from_numpy(slabels).cuda()
+        snlab_h = np.asarray([slabels.size], np.int32)
+
+    def timed(call):
+        for _ in range(args.warmup):
+            call()
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        for a, b in ev:
+            a.record()
+            call()
+            b.record()
+        torch.cuda.synchronize()
+        return sorted(a.elapsed_time(b) for a, b in ev)
 
     grid = [(int(s), int(p)) for s in args.strips.split(",") for p in args.panels.split(",")]
     if args.default:
@@ -87,17 +110,22 @@ def main():
                                             N.ptr(nlab_h), blank, N.ptr(tok), N.ptr(li), N.ptr(flp), N.ptr(sc), sp, pf, 0,
                                             N.current_stream()), "w2v2_ctc_align_long")
 
+        def star_call(ld, nl):
+            N.check(lib.w2v2_ctc_align_long_star(N.ptr(base), V, 1, N.ptr(row0), N.ptr(frames_h), N.ptr(ld), N.ptr(label0), N.ptr(nl),
+                                                 blank, args.star_score, N.ptr(tok), N.ptr(li), N.ptr(flp), N.ptr(sc), sp, pf, 0,
+                                                 N.current_stream()), "w2v2_ctc_align_long_star")
+
+        star = {}
+        if args.star_every:
+            st = timed(lambda: star_call(slab_dev, snlab_h))
+            star_frames = int((tok == V).sum().item())
+            tok.fill_(-7)
+            ss = timed(lambda: star_call(lab_dev, nlab_h))
+            star = {"stars": int((slabels == V).sum()), "star_frames": star_frames, "star_ms": round(float(np.median(st)), 2),
+                    "star_ms_min": round(st[0], 2), "star_same_labels_ms": round(float(np.median(ss)), 2),
+                    "star_same_labels_ms_min": round(ss[0], 2), "star_same_labels_path_ok": bool(torch.equal(tok, want))}
         tok.fill_(-7)
-        for _ in range(args.warmup):
-            call()
-        torch.cuda.synchronize()
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-        for a, b in ev:
-            a.record()
-            call()
-            b.record()
-        torch.cuda.synchronize()
-        ms = sorted(a.elapsed_time(b) for a, b in ev)
+        ms = timed(call)
         res = {"strip_pairs": sp, "panel_frames": pf,
                "workspace": int(lib.w2v2_ctc_align_long_workspace(1, N.ptr(frames_h), N.ptr(nlab_h), sp, pf)),
                "ms": round(float(np.median(ms)), 2), "ms_min": round(ms[0], 2), "path_ok": bool(torch.equal(tok, want)),
@@ -106,6 +134,7 @@ def main():
             strips, panels = -(-(U + 1) // sp), -(-(T - 1) // pf)
             res.update(strips=strips, panels=panels, launches=strips + panels - 1 + 3,
                        us_per_step=round(res["ms"] * 1e3 / ((panels + strips) * pf), 3))
+        res.update(star)
         rows.append(res)
         print(json.dumps(res), flush=True)
     best = min((r for r in rows if r["strip_pairs"]), key=lambda r: r["ms"])
