@@ -179,6 +179,8 @@ int launch_gemm(Profiler* prof, const float* A, int64_t lda, int64_t strideA, co
 // fp32 GEMM on the LDS-ring kernels (gemm_f32_sw.hip): tile 0 = 256 x 128, 1 = 128 x 128, 2 = 64 x 64; persist: at most two blocks per CU,
 // each looping over its tiles.  launch_gemm routes to them; gemm_f32_ring_ok says whether a shape fits.
 void gemm_f32_force_ring(int route);      // this thread's next launch_gemm calls: 0 | 1 | 2 as gemm_f32.hip's RING_DEFAULT, -1 = by shape
+bool gemm_f32_ring_form_ok(const float* bias, const float* residual, int act);      // the ring kernels have an instance for this epilogue
+void gemm_f32_ring_launches(int64_t* counts /* [4]: 256 x 128, 128 x 128, 64 x 64, 64 x 64 quarters */);      // launches so far, this process
 bool gemm_f32_ring_ok(int tile, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb, int64_t strideB,
                       int M, int N, int K);
 int launch_gemm_f32_ring(int tile, bool persist, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb,
@@ -214,6 +216,9 @@ int launch_gemm_split_sw(Profiler* prof, int fmt, const uint16_t* A16, int64_t p
 
 // selftest.hip: counts the float patterns on which erf_select / tanh_select differ from the device library's erff / tanhf
 int launch_check_select_forms(unsigned long long* mismatches_dev /* [2] */, hipStream_t s);
+// ... and those on which gelu_erf_epi (the fp32 GEMM epilogue) / gelu_erf_select differ from gelu_erf; y = gelu_erf(x) element-wise
+int launch_check_gelu_epilogue(unsigned long long* mismatches_dev /* [2] */, hipStream_t s);
+int launch_gelu_reference(const float* x, float* y, int64_t n, hipStream_t s);
 
 // Optional bf16 shadows of the operands (precision mode 1).  A shadow holds nearest-even bf16 roundings of the fp32
 // tensor -- exactly what the kernel would round to itself -- so using one changes speed, never results.
@@ -562,6 +567,35 @@ __device__ __forceinline__ float gelu_tanh_select(float x) {     // == gelu_tanh
 }
 __device__ __forceinline__ float gelu_erf_select(float x) {      // == gelu_erf(x), bit for bit
     return 0.5f * x * (1.0f + erf_select(x * 0.70710678118654752440f));
+}
+// gelu_erf for the fp32 GEMM epilogue (gemm_epilogue.h): gelu_erf_select with the library expf of the 1 - exp(-q) arm written out
+// (the compiler's own expansion: -q log2(e) in two terms, v_exp_f32 of the fraction, v_ldexp_f32 by the integer part) WITHOUT its two
+// range selects.  The overflow select (q < -88.7 -> inf) cannot fire on a selected arm: q >= 1 wherever |z| >= 1.  The underflow select
+// (q > 103.3 -> 0) is what keeps a huge or infinite z from producing inf - inf; clamping |z| to 4 in front of the q chain does the same
+// with one v_min_f32: q(4) = 18.1 and 1 - exp(-q) rounds to 1 from q = 17.33 on, which is the library's value for every |z| >= 4.
+// A NaN passes the clamp as 4, and the final 0.5 x (...) is NaN all the same.  Bit for bit gelu_erf over all 2^32 patterns:
+// selftest.hip (w2v2_op_check_gelu_epilogue), tests/test_gemm_gelu_epilogue_gpu.py.
+__device__ __forceinline__ float gelu_erf_epi(float x) {
+    const float z = x * 0.70710678118654752440f, az = fabsf(z), t = z * z;
+    float p = __builtin_fmaf(t, -0x1.268bc2p-11f, 0x1.420828p-8f);
+    p = __builtin_fmaf(t, p, -0x1.b5937p-6f);
+    p = __builtin_fmaf(t, p, 0x1.ce077cp-4f);
+    p = __builtin_fmaf(t, p, -0x1.81266p-2f);
+    p = __builtin_fmaf(t, p, 0x1.06ebap-3f);
+    const float small = __builtin_fmaf(az, p, az);
+    const float ac = __builtin_fminf(az, 4.0f);
+    float q = __builtin_fmaf(ac, 0x1.1d3156p-16f, -0x1.8d129p-12f);
+    q = __builtin_fmaf(ac, q, 0x1.f9a6d2p-9f);
+    q = __builtin_fmaf(ac, q, -0x1.8c3164p-6f);
+    q = __builtin_fmaf(ac, q, 0x1.b4e9c8p-4f);
+    q = __builtin_fmaf(ac, q, 0x1.4515fap-1f);
+    q = __builtin_fmaf(ac, q, 0x1.078e5p-3f);
+    q = __builtin_fmaf(ac, q, ac);
+    const float ph = q * -0x1.715476p+0f;                                        // exp(-q) = 2^(ph + pl)
+    const float pl = __builtin_fmaf(q, -0x1.4ae0bep-26f, __builtin_fmaf(q, -0x1.715476p+0f, -ph));
+    const float e = __builtin_rintf(ph);
+    const float large = 1.0f - __builtin_amdgcn_ldexpf(__builtin_amdgcn_exp2f((ph - e) + pl), (int)e);
+    return 0.5f * x * (1.0f + copysignf(az < 1.0f ? small : large, z));
 }
 __device__ __forceinline__ float gelu_tanh(float x) {
     const float c = 0.79788456080286535588f;  // sqrt(2/pi)

@@ -421,7 +421,7 @@ thread_local int tl_ring = -1;      // w2v2_op_gemm_variant: forces the ring rou
 // The LDS-ring kernels (gemm_f32_sw.hip) for the shapes that took gemm_f32_dma_kernel's 256 x 128 x 16, 128 x 128 x 32 and
 // 64 x 64 x 32 instances (the split-K slabs keep the last): 0 = those instances, 1 = the ring kernels with one tile per block, 2 = the ring kernels with a persistent grid.
 constexpr int RING_DEFAULT = 2;
-int ring_route() { return tl_ring >= 0 ? tl_ring : tune_int("W2V2_GEMM_RING", RING_DEFAULT); }
+int ring_route_any() { return tl_ring >= 0 ? tl_ring : tune_int("W2V2_GEMM_RING", RING_DEFAULT); }
 
 }  // namespace
 
@@ -454,6 +454,8 @@ int launch_gemm_ex(Profiler* prof, const float* A, int64_t lda, int64_t strideA,
                       ((reinterpret_cast<uintptr_t>(B) & 15) == 0);
     ProfScope ps(prof, FAM_GEMM, 2.0 * M * (double)N * K * nbatch,
                  4.0 * nbatch * ((double)M * K + (double)M * N) + 4.0 * (double)K * N, s);
+    // (the ring kernels hold one instance per epilogue form the models use; the other forms, tanh GELU among them, keep the double buffer)
+    auto ring_route = [&]() { return gemm_f32_ring_form_ok(bias, residual, act) ? ring_route_any() : 0; };
     int cfg = forced_cfg();
     const bool by_shape = cfg < 0;      // (a forced W2V2_GEMM_CFG names a gemm_f32_dma_kernel / gemm_f32_kernel instance)
     // default: the LDS-DMA 128x128 kernel with 8 waves (2x4, each wave 64x32), 2 blocks per CU = 4 waves

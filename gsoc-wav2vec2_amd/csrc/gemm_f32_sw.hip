@@ -12,6 +12,8 @@
 //   * s_setprio(1) over the K loop: a block's MFMA waves outrank the other block's epilogue on the SIMD.
 // Every output element consumes the same k pairs in the same order ({k, k+4} in each 8-wide block, k blocks ascending)
 // from a zeroed accumulator, and the epilogue is gemm_epilogue: results are bit-identical to gemm_f32_dma_kernel.
+// The epilogue's form (bias, exact GELU, residual) is a template argument: one instance per form the models use (ring_form below);
+// any other combination, tanh GELU included, stays on gemm_f32_dma_kernel, whose epilogue takes its switches at run time.
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "gemm_sw_common.h"
@@ -27,7 +29,7 @@ struct GemmRingArgs {
     const float* bias;
     const float* residual;
     int64_t lda, ldb, ldc, strideA, strideB, strideC;
-    int M, N, K, act;
+    int M, N, K;
     int tiles_m, tiles_n, nbatch;
     int gm;          // grouped tile order (common.h::grouped_tile); 0 = linear order
     int total;       // tiles of this launch: tiles_m x tiles_n x nbatch, or a prefix of that order (the split launch below)
@@ -49,7 +51,9 @@ struct RingCfg {
 // (waves_per_eu(4): two 8-wave blocks per CU need <= 128 VGPRs; the 256 x 128 instance otherwise takes 132 and one block per CU)
 // QUAD: tiles_m x tiles_n is the grid of (2 BM) x (2 BN) tiles; this launch runs tiles first, first + 1, ... of ITS order, four
 // BM x BN quarters each (the rest of an order whose first `first` tiles ran at the large tile; M and N are multiples of the large tile).
-template <int WM, int WN, int BKT, int BM, int BN, int NS, bool QUAD = false>
+// BIAS / GELU / RES: the epilogue's form.  As run-time values they had to be laundered through asm against loop unswitching, which left
+// both GELU arms and the residual path in every instance (256 x 128: two spilled VGPRs); as constants each instance holds its own path only.
+template <int WM, int WN, int BKT, int BM, int BN, int NS, bool QUAD, bool BIAS, bool GELU, bool RES>
 __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(4))) void gemm_f32_ring_kernel(GemmRingArgs g) {
     using R_ = RingCfg<WM, WN, BKT, BM, BN, NS>;
     constexpr int NW = R_::NW, PPA = R_::PPA, PPB = R_::PPB, P = R_::P, STAGE = R_::STAGE;
@@ -191,6 +195,8 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(4))
     int s = 0, cst = 0;                                  // step of the stream, ring stage it reads
     for (int ci = 0; ci < ntl; ++ci) {
         zero();
+        int z, m0, n0;      // (worked out in front of the K loop, under the DMA in flight: the epilogue starts without tile_of's divisions)
+        tile_of(ci, z, m0, n0);
         for (int kt = 0; kt < nk; ++kt, ++s) {
             const bool more = s + NS - 1 < nsteps;
             if (more) issue_step();                      // into the stage read at step s - 1 (every wave passed the barrier since)
@@ -201,28 +207,25 @@ __global__ __launch_bounds__(WM* WN * 64) __attribute__((amdgpu_waves_per_eu(4))
             cst = cst + 1 == NS ? 0 : cst + 1;
         }
         // epilogue of tile ci, with the next tile's first K tiles in flight: bias -> activation -> + residual -> store
-        int z, m0, n0;
-        tile_of(ci, z, m0, n0);
         const int64_t tile_off = (int64_t)z * g.strideC + (int64_t)(m0 + wm * WTM) * g.ldc + (n0 + wn * WTN);
-        // (the epilogue's loop-invariant switches are laundered through asm: otherwise the compiler unswitches the tile loop on
-        //  them, and hoists the per-element store offsets, which depend on ldc and the lane only, out of it: 64+ registers held
-        //  live across the K loop, 255 VGPRs and scratch at 256 x 128)
-        int act = g.act, ldc = (int)g.ldc, eli = li, elh = lh;
-        const float* res = g.residual;
-        const float* bias = g.bias;
-        asm volatile("" : "+s"(act), "+s"(res), "+s"(bias), "+s"(ldc), "+v"(eli), "+v"(elh));
+        // (ldc and the lane coordinates are laundered through asm: otherwise the compiler hoists the per-element store offsets, which
+        //  depend on them only, out of the tile loop: 64+ registers held live across the K loop, 255 VGPRs and scratch at 256 x 128)
+        int ldc = (int)g.ldc, eli = li, elh = lh;
+        asm volatile("" : "+s"(ldc), "+v"(eli), "+v"(elh));
         __builtin_amdgcn_s_setprio(0);
-        gemm_epilogue<MT, NTL, false>(acc, g.C + tile_off, nullptr, res ? res + tile_off : nullptr, bias ? bias + (n0 + wn * WTN) : nullptr,
-                                     ldc, g.M - (m0 + wm * WTM), g.N - (n0 + wn * WTN), act, eli, elh);
+        gemm_epilogue<MT, NTL, false, RES && MT * NTL <= 2>(acc, g.C + tile_off, nullptr, RES ? g.residual + tile_off : nullptr, BIAS ? g.bias + (n0 + wn * WTN) : nullptr,
+                                     ldc, g.M - (m0 + wm * WTM), g.N - (n0 + wn * WTN), GELU ? 1 : 0, eli, elh);
         __builtin_amdgcn_s_setprio(1);
     }
     __builtin_amdgcn_s_setprio(0);
 }
 
+std::atomic<int64_t> g_ring_launches[4];      // 256 x 128, 128 x 128, 64 x 64, 64 x 64 quarters (gemm_f32_ring_launches)
+
 // split launch (nbatch == 1, M and N multiples of the large tile): `first` tiles of the order, group height gm, run at the large tile
 // (!QUAD: limit = first), the other tiles as quarters (QUAD).  first < 0: the whole problem.
-template <int WM, int WN, int BKT, int BM, int BN, int NS, bool QUAD = false>
-int launch_ring(GemmRingArgs& g, bool persist, hipStream_t s, int64_t first = -1, int gm = 0) {
+template <int WM, int WN, int BKT, int BM, int BN, int NS, bool QUAD, bool BIAS, bool GELU, bool RES>
+int launch_ring_form(GemmRingArgs& g, bool persist, hipStream_t s, int64_t first, int gm) {
     using R_ = RingCfg<WM, WN, BKT, BM, BN, NS>;
     static_assert(2 * R_::LDS <= 160 * 1024, "two blocks per CU");
     constexpr int TM = QUAD ? 2 * BM : BM, TN = QUAD ? 2 * BN : BN;
@@ -249,16 +252,44 @@ int launch_ring(GemmRingArgs& g, bool persist, hipStream_t s, int64_t first = -1
     g.gm = first > 0 ? gm : g.nbatch == 1 ? tile_group_rows(g.tiles_m, g.tiles_n, (int64_t)BM * g.K * 4, BM == 256 ? 96 : 32 * PER_CU) : 0;
     static std::atomic<bool> attr_set{false};
     if (!attr_set) {
-        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_ring_kernel<WM, WN, BKT, BM, BN, NS, QUAD>),
+        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_ring_kernel<WM, WN, BKT, BM, BN, NS, QUAD, BIAS, GELU, RES>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, R_::LDS));
         attr_set = true;
     }
-    W2V2_LAUNCH((gemm_f32_ring_kernel<WM, WN, BKT, BM, BN, NS, QUAD>), dim3(grid), dim3(WM * WN * 64), R_::LDS, s, g);
+    W2V2_LAUNCH((gemm_f32_ring_kernel<WM, WN, BKT, BM, BN, NS, QUAD, BIAS, GELU, RES>), dim3(grid), dim3(WM * WN * 64), R_::LDS, s, g);
     W2V2_HIP_CHECK(hipGetLastError());
+    g_ring_launches[QUAD ? 3 : BM == 256 ? 0 : BM == 128 ? 1 : 2].fetch_add(1, std::memory_order_relaxed);
+    return W2V2_OK;
+}
+
+// the epilogue forms with an instance: plain, bias, bias + exact GELU, bias + residual, residual, exact GELU (the bias-free conv layers);
+// -1: none, the caller keeps gemm_f32_dma_kernel
+int ring_form(const float* bias, const float* residual, int act) {
+    if (act == 1) return residual ? -1 : bias ? 2 : 5;
+    if (act != 0) return -1;
+    return residual ? (bias ? 3 : 4) : (bias ? 1 : 0);
+}
+
+template <int WM, int WN, int BKT, int BM, int BN, int NS, bool QUAD = false>
+int launch_ring(GemmRingArgs& g, int act, bool persist, hipStream_t s, int64_t first = -1, int gm = 0) {
+    switch (ring_form(g.bias, g.residual, act)) {
+        case 0: return launch_ring_form<WM, WN, BKT, BM, BN, NS, QUAD, false, false, false>(g, persist, s, first, gm);
+        case 1: return launch_ring_form<WM, WN, BKT, BM, BN, NS, QUAD, true, false, false>(g, persist, s, first, gm);
+        case 2: return launch_ring_form<WM, WN, BKT, BM, BN, NS, QUAD, true, true, false>(g, persist, s, first, gm);
+        case 3: return launch_ring_form<WM, WN, BKT, BM, BN, NS, QUAD, true, false, true>(g, persist, s, first, gm);
+        case 4: return launch_ring_form<WM, WN, BKT, BM, BN, NS, QUAD, false, false, true>(g, persist, s, first, gm);
+        case 5: return launch_ring_form<WM, WN, BKT, BM, BN, NS, QUAD, false, true, false>(g, persist, s, first, gm);
+    }
+    W2V2_REQUIRE(false, "gemm ring: no instance for this epilogue (bias %d, residual %d, act %d)", g.bias != nullptr, g.residual != nullptr, act);
     return W2V2_OK;
 }
 
 }  // namespace
+
+bool gemm_f32_ring_form_ok(const float* bias, const float* residual, int act) { return ring_form(bias, residual, act) >= 0; }
+void gemm_f32_ring_launches(int64_t* counts) {
+    for (int i = 0; i < 4; ++i) counts[i] = g_ring_launches[i].load(std::memory_order_relaxed);
+}
 
 bool gemm_f32_ring_ok(int tile, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb, int64_t strideB,
                       int M, int N, int K) {
@@ -278,13 +309,13 @@ int launch_gemm_f32_ring(int tile, bool persist, const float* A, int64_t lda, in
     GemmRingArgs g;
     g.A = A; g.B = B; g.C = C; g.bias = bias; g.residual = residual;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.strideA = strideA; g.strideB = strideB; g.strideC = strideC;
-    g.M = M; g.N = N; g.K = K; g.act = act; g.nbatch = nbatch;
-    if (tile == 0) return launch_ring<4, 2, 16, 256, 128, 3>(g, persist, s);      // 72 KiB: two blocks per CU
-    if (tile == 1) return launch_ring<2, 4, 16, 128, 128, 4>(g, persist, s);      // 64 KiB
+    g.M = M; g.N = N; g.K = K; g.nbatch = nbatch;
+    if (tile == 0) return launch_ring<4, 2, 16, 256, 128, 3>(g, act, persist, s);      // 72 KiB: two blocks per CU
+    if (tile == 1) return launch_ring<2, 4, 16, 128, 128, 4>(g, act, persist, s);      // 64 KiB
     // 64 x 64, four waves of 32 x 32 (the tail rows and the small problems).  48 KiB: three blocks per CU, so the 528 tail tiles of
     // N = 768 at B = 32 are all resident at once, as with the double buffer; the 64-KiB 32 x 4 ring runs them in two rounds and loses
     // (instances 16 x 4 / 5 / 6 and 32 x 4 measured and dropped: profiles/ring_tail_ab.md).
-    return launch_ring<2, 2, 32, 64, 64, 3>(g, persist, s);
+    return launch_ring<2, 2, 32, 64, 64, 3>(g, act, persist, s);
 }
 
 // One GEMM as two launches that split the 128 x 128 tile order (XCD runs, grouped rows) at `main_tiles`: the first main_tiles tiles on
@@ -299,10 +330,10 @@ int launch_gemm_f32_ring_split(bool persist, int64_t main_tiles, const float* A,
     GemmRingArgs g;
     g.A = A; g.B = B; g.C = C; g.bias = bias; g.residual = residual;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.strideA = 0; g.strideB = 0; g.strideC = 0;
-    g.M = M; g.N = N; g.K = K; g.act = act; g.nbatch = 1;
+    g.M = M; g.N = N; g.K = K; g.nbatch = 1;
     const int gm = tile_group_rows(M / 128, N / 128, (int64_t)128 * K * 4, 64);
-    if (int e = launch_ring<2, 4, 16, 128, 128, 4>(g, persist, s, main_tiles, gm)) return e;
-    return launch_ring<2, 2, 32, 64, 64, 3, true>(g, false, s, main_tiles, gm);
+    if (int e = launch_ring<2, 4, 16, 128, 128, 4>(g, act, persist, s, main_tiles, gm)) return e;
+    return launch_ring<2, 2, 32, 64, 64, 3, true>(g, act, false, s, main_tiles, gm);
 }
 
 }  // namespace w2v2

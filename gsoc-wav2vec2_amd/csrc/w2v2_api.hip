@@ -750,6 +750,17 @@ int w2v2_op_gemm_split(const float* A, int64_t lda, int64_t strideA, const float
 int w2v2_op_check_select_forms(uint64_t* mismatches, void* stream) {
     return launch_check_select_forms(reinterpret_cast<unsigned long long*>(mismatches), reinterpret_cast<hipStream_t>(stream));
 }
+int w2v2_op_check_gelu_epilogue(uint64_t* mismatches, void* stream) {
+    return launch_check_gelu_epilogue(reinterpret_cast<unsigned long long*>(mismatches), reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_gelu_reference(const float* x, float* y, int64_t n, void* stream) {
+    return launch_gelu_reference(x, y, n, reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_gemm_ring_launches(int64_t* counts) {
+    W2V2_REQUIRE(counts, "op_gemm_ring_launches: null argument");
+    gemm_f32_ring_launches(counts);
+    return W2V2_OK;
+}
 int w2v2_op_split_planes(const float* x, uint16_t* planes, int64_t plane_stride, int64_t n, int32_t fmt, int32_t* range_flag, void* stream) {
     W2V2_REQUIRE(fmt == PF_BF16X3 || fmt == PF_F16X2, "op_split_planes: unknown plane format %d", fmt);
     return launch_split_planes(x, planes, plane_stride, n, fmt, range_flag, reinterpret_cast<hipStream_t>(stream));

@@ -171,6 +171,9 @@ PROTOTYPES = {
     "w2v2_crc32c_extend": (C.c_uint32, [C.c_uint32, _P, C.c_uint64]),
     "w2v2_op_weight_grad_bf16": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P]),
     "w2v2_op_check_select_forms": (C.c_int, [_P, _P]),
+    "w2v2_op_check_gelu_epilogue": (C.c_int, [_P, _P]),
+    "w2v2_op_gelu_reference": (C.c_int, [_P, _P, _I64, _P]),
+    "w2v2_op_gemm_ring_launches": (C.c_int, [C.POINTER(_I64)]),
     "w2v2_op_split_planes": (C.c_int, [_P, _P, _I64, _I64, _I32, _P, _P]),
     "w2v2_op_split_weight": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P]),
     "w2v2_op_gemm_split_planes": (C.c_int, [_I32, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),

@@ -685,7 +685,9 @@ int w2v2_op_gemm(const float* A_dev, int64_t lda, int64_t strideA,
                  int32_t M, int32_t N, int32_t K, int32_t nbatch, int32_t act, void* stream);
 /* w2v2_op_gemm with the fp32 kernel family pinned, for bit-for-bit comparisons: variant -1 by shape (= w2v2_op_gemm),
  * 0 the double-buffered LDS-DMA kernels only, 1 the LDS-ring kernels where the shape routes to them, 2 the same with a
- * persistent grid (csrc/gemm_f32_sw.hip). */
+ * persistent grid (csrc/gemm_f32_sw.hip).  The ring kernels have an instance per epilogue form the models use (plain, bias,
+ * bias + exact GELU, exact GELU, bias + residual, residual): with any other form, tanh GELU or GELU + residual among them,
+ * variants 1 and 2 run the double-buffered kernels as variant 0 does (the same bits). */
 int w2v2_op_gemm_variant(const float* A_dev, int64_t lda, int64_t strideA,
                          const float* B_dev, int64_t ldb,
                          float* C_dev, int64_t ldc, int64_t strideC,
@@ -749,6 +751,16 @@ int w2v2_op_gemm_split_planes(int32_t fmt, const uint16_t* A16_dev, int64_t plan
  * and the device library's erff / tanhf on all 2^32 float bit patterns; mismatches_dev[0] / [1] receive the number of patterns whose
  * results differ in any bit (NaNs compare equal).  Both must be 0: the forms are drop-in for the fp32 path's GELU. */
 int w2v2_op_check_select_forms(uint64_t* mismatches_dev, void* stream);
+
+/* The same sweep for the exact GELU of the fp32 GEMM epilogue (csrc/common.h: gelu_erf_epi) and for gelu_erf_select, each against
+ * 0.5 x (1 + erff(x / sqrt 2)) with the library erff: mismatches_dev[0] / [1], both must be 0 (NaNs compare equal). */
+int w2v2_op_check_gelu_epilogue(uint64_t* mismatches_dev, void* stream);
+/* y[i] = 0.5 x[i] (1 + erff(x[i] / sqrt 2)) through the library erff, n elements: the element-wise reference of the epilogue tests. */
+int w2v2_op_gelu_reference(const float* x_dev, float* y_dev, int64_t n, void* stream);
+/* Launches of the LDS-ring fp32 GEMM instances by this process so far (host memory): counts[0] 256 x 128, [1] 128 x 128, [2] 64 x 64,
+ * [3] 64 x 64 quarters of a split launch.  Diagnostic only (one relaxed atomic add per launch): tests read it before and after a call
+ * to see which instances the call reached. */
+int w2v2_op_gemm_ring_launches(int64_t* counts);
 
 /* The weight-gradient form of the same GEMM: C_z (M, N) = A_z^T B_z with A given TRANSPOSED, (K, M) fp32 row-major with
  * row stride lda (>= M), and per-batch strides on A, B and C (split-K: batch z covers rows [z K, (z+1) K) of both
