@@ -319,6 +319,31 @@ ForwardPlan w2v2_plan_forward(const w2v2_model* m, int B, int64_t L, bool planes
 }
 
 // ---- GEMM routing ---------------------------------------------------------------------------------------------------------------
+// C = act(A Bw + bias) + res for a GEMM that is not plane-fed, on the route the mode selects: the six-product split kernel (modes
+// bf16x3 / f16x2, shapes it takes), the fp32 MFMA, or -- `sh` -- the bf16 kernel with the shadows A16 / C16 and the weight's.  Raw
+// pointers; a form the caller's forward did not write is passed as null, and a route that would read it is an error, not a stale read.
+// Shared by the inference forward (gemm() below) and the training forward (w2v2_train.hip).
+int w2v2_gemm_route(w2v2_model* m, bool sh, hipStream_t s, const float* A, const uint16_t* A16, int64_t lda, int64_t strideA, const float* Bw,
+                    int64_t ldb, float* Cc, uint16_t* C16, int64_t ldc, int64_t strideC, const float* bias, const float* res, int M, int N, int K,
+                    int nbatch, int act_) {
+    Profiler* pf = m->prof;
+    if (w2v2_use_split_gemm(m, A, lda, strideA, ldb, M, N, K, nbatch)) {
+        W2V2_REQUIRE(A, "forward: the six-product GEMM (M=%d N=%d K=%d) reads an fp32 A this forward did not write", M, N, K);
+        const uint16_t* planes = nullptr;
+        if (int e = w2v2_split_planes(m, Bw, K, N, s, &planes)) return e;
+        return launch_gemm_split(pf, A, lda, strideA, planes, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, s);
+    }
+    if (!sh) {
+        W2V2_REQUIRE(A, "forward: the fp32 GEMM (M=%d N=%d K=%d) reads an fp32 A this forward did not write", M, N, K);
+        return launch_gemm(pf, A, lda, strideA, Bw, ldb, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, s);
+    }
+    GemmShadows x;
+    x.A16 = A16; x.B16 = m->w16[Bw]; x.C16 = C16; x.ldb16 = K;
+    W2V2_REQUIRE(A || (A16 && gemm_bf16_streams_a16(K, lda, strideA)),
+                 "forward: the bf16 GEMM (M=%d N=%d K=%d) cannot stream A's shadow and this forward wrote no fp32 A", M, N, K);
+    return launch_gemm_bf16_x(pf, A, lda, strideA, Bw, ldb, 0, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, x, s);
+}
+
 // One tensor as a GEMM sees it: the forms this forward fills (ForwardPlan) and the buffers of the three forms (null where the
 // model has none).  gemm() masks the buffers by the forms, so a call site names buffers and a plan field, never a condition.
 struct Tens {
@@ -353,23 +378,9 @@ static int gemm(w2v2_model* m, const ForwardPlan& plan, hipStream_t s, bool plan
             return e;
         return (Cpl && !planes_only) ? split_out() : W2V2_OK;
     }
-    int e;
-    if (w2v2_use_split_gemm(m, A.f32, lda, strideA, ldb, M, N, K, nbatch)) {
-        W2V2_REQUIRE(A.forms & F32, "forward: the six-product GEMM (M=%d N=%d K=%d) reads an fp32 A this forward did not write", M, N, K);
-        const uint16_t* planes = nullptr;
-        if (int e2 = w2v2_split_planes(m, Bw, K, N, s, &planes)) return e2;
-        e = launch_gemm_split(pf, A.f32, lda, strideA, planes, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, s);
-    } else if (!plan.sh) {
-        W2V2_REQUIRE(A.forms & F32, "forward: the fp32 GEMM (M=%d N=%d K=%d) reads an fp32 A this forward did not write", M, N, K);
-        e = launch_gemm(pf, A.f32, lda, strideA, Bw, ldb, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, s);
-    } else {
-        GemmShadows x;
-        x.A16 = ForwardPlan::b16(A.forms, A.b16); x.B16 = m->w16[Bw]; x.C16 = ForwardPlan::b16(C.forms, C.b16); x.ldb16 = K;
-        W2V2_REQUIRE((A.forms & F32) || (x.A16 && gemm_bf16_streams_a16(K, lda, strideA)),
-                     "forward: the bf16 GEMM (M=%d N=%d K=%d) cannot stream A's shadow and this forward wrote no fp32 A", M, N, K);
-        e = launch_gemm_bf16_x(pf, A.f32, lda, strideA, Bw, ldb, 0, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, x, s);
-    }
-    if (e) return e;
+    if (int e = w2v2_gemm_route(m, plan.sh, s, ForwardPlan::f32(A.forms, A.f32), ForwardPlan::b16(A.forms, A.b16), lda, strideA, Bw, ldb, Cc,
+                                ForwardPlan::b16(C.forms, C.b16), ldc, strideC, bias, res, M, N, K, nbatch, act_))
+        return e;
     return Cpl ? split_out() : W2V2_OK;
 }
 

@@ -151,6 +151,24 @@ struct ForwardPlan {
 };
 struct PackedPlan;      // forward.hip: the tables of a packed stream
 
+// ---- the training plan (w2v2_train.hip::plan_train; DESIGN.md, "The training plan") -------------------------------------------------
+// What a training forward decided, once, before its first launch.  The forward runs from it, the workspace is built for it, and the
+// backward takes every mode-dependent decision from the copy TrainState keeps -- never from the model's settings at backward time.
+struct TrainPlan {
+    int precision = 0;                       // the mode and the shadow option the forward ran with: the backward refuses any other
+    bool opt_shadows = false;
+    int B = 0, T = 0;
+    int64_t BT = 0;
+    bool sh = false, attn16 = false;         // mode bf16 with shadows; ... and the bf16 attention kernels (q|k|v kept as bf16 only)
+    // kept as bf16 only (no fp32 copy written): dropout(GELU(u)); u (in the first half of its buffer); the attention output; prenorm: a, t2
+    bool ffn16_only = false, u16_only = false, ctx16_only = false, ln16_only = false;
+    bool lean_ws = true;                     // the fp32 buffers of the above are not even allocated (tools-only knob W2V2_LEAN_WS)
+    bool prenorm = false;
+    int act = 1, act_ew = 1;                 // GELU form of the GEMM epilogues / of the element-wise kernels
+    int u_round = 0;                         // the element-wise kernels round an fp32 u to bf16 on the way in (mode bf16)
+    bool lse_log2 = false;                   // the attention forward saved lse2 = -(m C2 + log2 l) (bf16 kernels), not the natural lse
+};
+
 // implemented in w2v2_api.hip
 int w2v2_ensure_workspace(w2v2_model* m, int B, int64_t L);
 int w2v2_ws_alloc(w2v2_model* m, float** out, int64_t floats);           // a buffer that lives as long as the workspace
@@ -170,6 +188,10 @@ int w2v2_ensure_pos16(w2v2_model* m, int B, int T, hipStream_t s);        // ker
 int w2v2_split_planes(w2v2_model* m, const float* W, int K, int N, hipStream_t s, const uint16_t** planes);
 // whether GEMM (M, N, K) x nbatch with this A should take the split kernel in the model's current precision mode
 bool w2v2_use_split_gemm(const w2v2_model* m, const float* A, int64_t lda, int64_t strideA, int64_t ldb, int M, int N, int K, int nbatch);
+// a GEMM that is not plane-fed, on the mode's route (six-product split / fp32 / bf16 with shadows when `sh`); null = form not written
+int w2v2_gemm_route(w2v2_model* m, bool sh, hipStream_t s, const float* A, const uint16_t* A16, int64_t lda, int64_t strideA, const float* Bw,
+                    int64_t ldb, float* Cc, uint16_t* C16, int64_t ldc, int64_t strideC, const float* bias, const float* res, int M, int N, int K,
+                    int nbatch, int act_);
 // precision modes 2 / 3 with W2V2_OPT_SPLIT_PLANES: the plane buffers of a (B, L) forward in the mode's format; the LDS images (and,
 // f16x2, the accumulator scale) of the (K, N) fp32 matrix W
 int w2v2_ensure_planes(w2v2_model* m, int B, int64_t L, int fmt);

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "model.h"
+#include "train.h"
 
 namespace w2v2 {
 
@@ -910,6 +911,70 @@ int w2v2_op_frame_lengths(const int32_t* mask, int32_t* frame_len, int32_t B, in
                           const int32_t* kernal_sizes, const int32_t* strides, int32_t num_layers, void* stream) {
     return launch_frame_lengths(nullptr, mask, frame_len, B, L, kernal_sizes, strides, num_layers,
                                 reinterpret_cast<hipStream_t>(stream));
+}
+// ---- op-level entry points of the training kernels (train.h): the tests drive them one kernel at a time ----
+int64_t w2v2_ln_bwd_ws_floats(int64_t rows, int32_t C) { return ln_bwd_ws_floats(rows, C); }
+int w2v2_op_layer_norm_bwd(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma,
+                           float* dbeta, int64_t rows, int32_t C, float eps, float* ws, void* stream) {
+    return launch_ln_bwd(x, gamma, dy, dx, dgamma, dbeta, rows, C, eps, ws, reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_attention_train(const float* qkv, const int32_t* frame_len, float* ctx, float* lse, int32_t B, int32_t T,
+                            int32_t H, int32_t heads, float p, uint64_t seed, uint32_t stream_id, void* stream) {
+    AttnTrain tr{p, seed, stream_id, lse};
+    return launch_attention_train(nullptr, qkv, frame_len, ctx, B, T, H, heads, tr, reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_attention_bwd(const float* qkv, const int32_t* frame_len, const float* ctx, const float* lse,
+                          const float* dctx, float* dqkv, float* dvec_ws, int32_t B, int32_t T, int32_t H,
+                          int32_t heads, float p, uint64_t seed, uint32_t stream_id, void* stream) {
+    AttnTrain tr{p, seed, stream_id, const_cast<float*>(lse)};
+    return launch_attention_bwd(nullptr, qkv, frame_len, ctx, dctx, dqkv, dvec_ws, B, T, H, heads, tr,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_layer_norm_dropout(const float* x, const float* residual, float* t1, float* y, uint16_t* y16, const float* gamma, const float* beta,
+                               int64_t rows, int32_t C, float eps, float p, uint64_t seed, uint32_t stream_id, void* stream) {
+    return launch_layer_norm_drop(nullptr, x, residual, t1, y, y16, gamma, beta, rows, C, eps, p, seed, stream_id, reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_dropout(const float* x, const float* residual, float* y, int64_t n, int32_t act, float p,
+                    uint64_t seed, uint32_t stream_id, void* stream) {
+    return launch_dropout_fwd(x, residual, y, n, act, p, seed, stream_id, reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_pos_conv_ex(const float* x, const float* wg, const float* bias, const int32_t* frame_len, float* y, float* pre_act,
+                        int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, int32_t act, int32_t pad_left, int32_t add_residual,
+                        void* stream) {
+    return launch_pos_conv_ex(nullptr, x, wg, bias, frame_len, y, pre_act, B, T, H, K, groups, act, pad_left, add_residual,
+                              reinterpret_cast<hipStream_t>(stream));
+}
+int64_t w2v2_op_pos_conv_bf16_pack_elems(int32_t B, int32_t T, int32_t H, int32_t K) { return pos_conv_bf16_pack_elems(B, T, H, K); }
+int w2v2_op_pos_conv_weight_shadow(const float* wg, uint16_t* w16, int32_t K, int32_t cg, int32_t groups, void* stream) {
+    return launch_pos_conv_weight_shadow(wg, w16, K, cg, groups, reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_pos_conv_bf16(const float* x, const uint16_t* w16, const float* bias, const int32_t* frame_len, float* y, float* pre_act,
+                          uint16_t* pack16, float* xz_ws, int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, int32_t act,
+                          int32_t pad_left, int32_t add_residual, void* stream) {
+    return launch_pos_conv_bf16(nullptr, x, w16, bias, frame_len, y, pre_act, pack16, xz_ws, B, T, H, K, groups, act, pad_left, add_residual,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_pos_conv_flip_regroup(const float* wg, float* wg_t, int32_t K, int32_t cg, int32_t groups, void* stream) {
+    return launch_pos_conv_flip_regroup(wg, wg_t, K, cg, groups, reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_op_pos_conv_dw(const float* xz, const float* dc, float* dwg, int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups,
+                        void* stream) {
+    return launch_pos_conv_dw(nullptr, xz, dc, dwg, nullptr, B, T, H, K, groups, reinterpret_cast<hipStream_t>(stream));
+}
+int w2v2_pos_conv_dw_bf16_ws_floats(int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, int64_t* sizes4, int32_t* slabs_S) {
+    W2V2_REQUIRE(sizes4 && B > 0 && T > 0 && K > 0 && groups > 0 && H > 0 && H % groups == 0, "pos_conv_dw_bf16_ws_floats: bad argument");
+    int S = 0;
+    pos_conv_dw_bf16_ws_floats(B, T, H, K, groups, sizes4, &S);
+    if (slabs_S) *slabs_S = S;
+    return W2V2_OK;
+}
+int w2v2_op_pos_conv_dw_bf16(const float* xz, const float* dc, float* dwg, float* pack32, float* slabs, float* red_ws, float* dc_pad,
+                             int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, void* stream) {
+    return launch_pos_conv_dw_bf16(nullptr, xz, dc, dwg, pack32, slabs, red_ws, B, T, H, K, groups, reinterpret_cast<hipStream_t>(stream), dc_pad);
+}
+int w2v2_op_weight_norm_bwd(const float* weight_v, const float* weight_g, const float* dwg, float* dweight_v, float* dweight_g, int32_t K,
+                            int32_t cg, int32_t H, int32_t groups, void* stream) {
+    return launch_weight_norm_bwd(weight_v, weight_g, dwg, dweight_v, dweight_g, K, cg, H, groups, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -36,7 +36,9 @@ struct LayerSave {
 struct TrainState {
     int B = 0, T = 0;
     int64_t L = 0;
-    int lean = 0;                       // LEAN_* set the shape-dependent buffers were built with (ensure_train_ws)
+    // The plan the shape-dependent buffers were built for (ensure_train_ws) and, once `forward_done`, the plan of the completed forward
+    // the backward differentiates.  The two agree in everything the buffers depend on: a forward whose plan needs other buffers rebuilds.
+    TrainPlan plan;
     int64_t alloc_bytes = 0;            // bytes behind `allocs`
     std::vector<void*> allocs;          // shape-dependent buffers: rebuilt when (B, L) changes
     std::vector<void*> persist;         // shape-independent buffers (gradients, Adam moments, transposed kernels, slab scratch):
@@ -73,12 +75,7 @@ struct TrainState {
     uint16_t *dy16_h = nullptr, *dy16_f = nullptr, *dy16_3h = nullptr, *dy16_ctx = nullptr;
     float* cs_ws = nullptr;           // (slabs + 1, widest N): per-slab column sums of dY from the weight-gradient GEMM
     int64_t cs_floats = 0;
-    bool forward_done = false;
-    bool ffn16_only = false;                      // the last forward wrote dropout(GELU(u)) only as bf16 (no fp32 l.gd)
-    bool ctx16_only = false;                      // ... and the attention output only as bf16 (no fp32 l.ctx: the backward reads O and dO as bf16)
-    bool u16_only = false;                        // ... and the FFN pre-activation u only as bf16 (in the first half of l.u's storage)
-    bool ln16_only = false;                       // ... and (prenorm) the two in-layer LayerNorm outputs a, t2 only as bf16
-    bool x16_valid = false, x16_attn = false;     // the last forward wrote the per-layer bf16 shadows (/ ctx16 from the bf16 attention)
+    bool forward_done = false;                    // a completed training forward stands behind `plan` and the saved activations
     // gradient buckets for overlapping the data-parallel all-reduce with the backward: completion order
     //   0 = lm_head, 1 .. N = encoder layers N-1 .. 0, N+1 = everything in front of layer 0 in the flat buffer
     std::vector<hipEvent_t> bucket_ev;
@@ -98,7 +95,7 @@ struct TrainState {
     float* red_ws_side = nullptr;     // the side stream's own reduction scratch (red_ws belongs to the main stream's kernels)
     // Deferred folds (train.h: FoldBatch): the partial rows of a layer's gradients live until the layer's one fold launch, so each
     // deferred producer has its own scratch -- split-K slabs of the four weight gradients (0 = FFN down, 1 = FFN up, 2 = out-projection,
-    // 3 = q|k|v; 33 x the kernel's size each: ~0.9 GB for base, 1.7 GB for large) and the per-block column sums of LayerNorm 2 / the FFN
+    // 3 = q|k|v; site_slab_count + 1 slabs of the kernel's size each: ensure_site_scratch) and the per-block column sums of LayerNorm 2 / the FFN
     // dropout backward / LayerNorm 1 (site_ws).  The attention backward's column partials already have theirs (attn_colpart).
     float* site_slabs[4] = {nullptr, nullptr, nullptr, nullptr};
     int64_t site_slab_floats[4] = {0, 0, 0, 0};
@@ -238,7 +235,8 @@ static int ensure_site_scratch(w2v2_model* m, bool side, bool defer_cols, bool d
         const int64_t H = m->cfg.hidden_size, F = m->cfg.intermediate_size;
         const int64_t site_elems[4] = {F * H, H * F, H * H, 3 * H * H};
         for (int k = 0; k < 4; ++k) {
-            t->site_slab_floats[k] = site_slab_count(site_elems[k]) * site_elems[k];
+            // (+ 1: S slabs, a leftover-row slab and the fold's partial scratch behind them -- weight_grad's `nslabs + 1` -- always fit)
+            t->site_slab_floats[k] = (site_slab_count(site_elems[k]) + 1) * site_elems[k];
             if (int e = p_alloc(t, &t->site_slabs[k], t->site_slab_floats[k])) return e;
         }
     }
@@ -253,9 +251,63 @@ static int ensure_site_scratch(w2v2_model* m, bool side, bool defer_cols, bool d
 // weight gradients, which all stream the bf16 shadow -- so their fp32 copies (a, t2) are neither written nor allocated.  (Postnorm: t2 is
 // also the FFN's residual and stays fp32.)
 enum : int { LEAN_QKV = 1, LEAN_CTX = 2, LEAN_GD = 4, LEAN_U_HALF = 8, LEAN_LN = 16 };
-static int ensure_train_ws(w2v2_model* m, int B, int64_t L, int T, int lean) {
+static int lean_mask(const TrainPlan& p) {
+    if (!p.lean_ws) return 0;
+    return (p.attn16 ? LEAN_QKV : 0) | (p.ctx16_only ? LEAN_CTX : 0) | (p.ffn16_only ? LEAN_GD : 0) | (p.u16_only ? LEAN_U_HALF : 0) |
+           (p.ln16_only ? LEAN_LN : 0);
+}
+// the same fact as w2v2_train_storage reports it: what the forward keeps as bf16 only (allocated in fp32 or not)
+static int storage_mask(const TrainPlan& p) {
+    return (p.attn16 ? W2V2_TRAIN_BF16_QKV : 0) | (p.ctx16_only ? W2V2_TRAIN_BF16_CTX : 0) | (p.ffn16_only ? W2V2_TRAIN_BF16_FFN : 0) |
+           (p.u16_only ? W2V2_TRAIN_BF16_U : 0) | (p.ln16_only ? W2V2_TRAIN_BF16_LN : 0);
+}
+
+// The plan of a training forward over (B, L): every mode-dependent decision of the step, one line each, here and nowhere else.  Reads
+// m->w16_valid and m->w16p, so it runs behind w2v2_ensure_shadows (which refreshes the bf16 weight shadows after an optimizer step).
+static TrainPlan plan_train(const w2v2_model* m, int B, int64_t L) {
+    const w2v2_config& c = m->cfg;
+    const int H = c.hidden_size, F = c.intermediate_size;
+    TrainPlan p;
+    p.precision = m->precision;
+    p.opt_shadows = m->opt_shadows;
+    p.B = B;
+    p.T = (int)w2v2_num_frames(m, L);
+    p.BT = (int64_t)B * p.T;
+    p.prenorm = c.attention_norm_type == 1;
+    // Mode bf16: the same bf16 shadows as the inference forward (forward.hip).  Every producer of a forward GEMM operand -- conv0, GEMM
+    // epilogues, LayerNorm, dropout, attention -- also writes the nearest-even bf16 copy, so the forward GEMMs stream 2-byte operands
+    // by LDS-DMA instead of converting fp32 in registers; results are bit-identical either way.
+    p.sh = m->precision == 1 && m->opt_shadows;
+    // the bf16 attention kernels (forward and backward) read q | k | v only as bf16: the projection then writes just that shadow
+    p.attn16 = p.sh && attention_bf16_supported(H / c.num_heads);
+    // ... and they save lse2 = -(m C2 + log2 l) where the fp32 kernels save the natural lse (launch_attention_train_x picks by the mode)
+    p.lse_log2 = m->precision == 1 && attention_bf16_supported(H / c.num_heads);
+    // FFN hidden activation dropout(GELU(u)) as bf16 only: needs the shadow paths on both sides (forward GEMM by LDS-DMA, weight gradient
+    // in the transposing-read form, whole 128-tiles) and the plain bf16 copies of the FFN kernels for the data gradients
+    p.ffn16_only = p.sh && m->w16_valid && F % 128 == 0 && H % 128 == 0 && (p.BT * F) % 4 == 0 && !m->w16p.empty();
+    // u = t2 W1 + b1 as bf16 only (what a mixed_bfloat16 Dense hands to its activation): the up-projection writes ONLY the bf16 copy (302 MB
+    // of fp32 stores per layer gone at B = 32) and GELU + dropout, GELU' in the backward read that ...
+    p.u16_only = p.ffn16_only && tune_int("W2V2_U16", 1) != 0;
+    // ... while the shadow-free path of the mode rounds the fp32 u on the way into the same kernels, so both agree bit for bit
+    p.u_round = m->precision == 1 ? 1 : 0;
+    // The attention output O: its readers are the out-projection GEMM and that GEMM's weight gradient (both stream the bf16 shadow) and
+    // D = rowsum(dO o O) of the attention backward, which is defined on the bf16 values -- no fp32 copy is written
+    p.ctx16_only = p.ffn16_only && p.attn16 && tune_int("W2V2_CTX16", 1) != 0;
+    // Prenorm: a = LN1(x) and t2 = LN2(t1) are read only by GEMMs that stream their shadows (the same conditions): written only as bf16
+    // (196 MB of fp32 stores per layer gone at 16 x 480000).  Postnorm: t2 is also the FFN's residual and stays fp32
+    p.ln16_only = p.prenorm && p.ffn16_only && p.attn16 && tune_int("W2V2_LN16", 1) != 0;
+    // (tools-only build: W2V2_LEAN_WS = 0 allocates every fp32 buffer, as rounds 2-4 did, for A/B runs)
+    p.lean_ws = tune_int("W2V2_LEAN_WS", 1) != 0;
+    p.act = c.is_gelu_approx ? 2 : 1;
+    // element-wise kernels in mode bf16 evaluate exact GELU / GELU' through the 5-term erf the bf16 GEMM epilogue uses (act 3)
+    p.act_ew = (p.act == 1 && m->precision == 1) ? 3 : p.act;
+    return p;
+}
+
+static int ensure_train_ws(w2v2_model* m, const TrainPlan& plan, int64_t L) {
     TrainState* t = get_state(m);
-    if (t->B == B && t->L == L && t->B > 0 && t->lean == lean) return W2V2_OK;
+    const int B = plan.B, T = plan.T, lean = lean_mask(plan);
+    if (t->B == B && t->L == L && t->B > 0 && lean_mask(t->plan) == lean) return W2V2_OK;
     if (int e = ensure_persistent(m)) return e;
     const w2v2_config& c = m->cfg;
     const int64_t H = c.hidden_size, F = c.intermediate_size, BT = (int64_t)B * T;
@@ -346,7 +398,7 @@ static int ensure_train_ws(w2v2_model* m, int B, int64_t L, int T, int lean) {
     t->B = B;
     t->L = L;
     t->T = T;
-    t->lean = lean;
+    t->plan = plan;
     return W2V2_OK;
 }
 
@@ -412,9 +464,10 @@ static int weight_grad(w2v2_model* m, const float* A, const float* dY, int M, in
     TrainState* t = m->train;
     if (!red_ws) red_ws = t->red_ws;       // (the side stream passes its own: TrainState::red_ws_side)
     bool fused_bias = false;
-    // slab scratch: the shared one, or this site's own (33 Kin Nout floats: S <= 32 slabs; the deferred fold needs no partial scratch
-    // behind them).  The slab-count rule below keeps using TrainState::slab_floats either way, so S does not depend on the site.
+    // slab scratch: the shared one, or this site's own (S <= 32 slabs, a leftover-row slab and the fold's partial scratch behind them).
+    // The slab-count rule below keeps using TrainState::slab_floats either way, so S does not depend on the site.
     float* const slabs = (site && site->slabs) ? site->slabs : t->slabs;
+    const int64_t slab_cap = (site && site->slabs) ? site->slab_floats : t->slab_floats;      // floats behind `slabs`: what the capacity checks look at
     FoldBatch* const defer = (site && site->slabs) ? site->defer : nullptr;
     const bool unpack = site && site->unpackH > 0;
     // dW = sum of `nrows` slabs: behind the GEMM, or as a job of the layer's fold launch.  (`unpack`: even a single slab goes through the
@@ -429,7 +482,25 @@ static int weight_grad(w2v2_model* m, const float* A, const float* dY, int M, in
                          "weight_grad: the unpacking fold does not fit this shape");
             return one.flush(s);
         }
+        // (the one-chunk partial scratch lives behind the slabs: every caller has checked that nrows + 1 slabs fit `slab_cap`)
         return launch_colsum(slabs, dW, nrows, Kin * Nout, slabs + (int64_t)nrows * Kin * Nout, 0, s);
+    };
+    // db = column sums of the fp32 dY, where no GEMM took them along
+    auto bias_colsum = [&]() -> int {
+        if (!db) return W2V2_OK;
+        W2V2_REQUIRE(dY, "weight_grad: the bias gradient needs the fp32 dY");
+        return launch_colsum(dY, db, M, Nout, red_ws, 0, s);
+    };
+    // The whole weight gradient on the transposing-read kernel (both bf16 shadows; no fp32 operand is touched): S slabs of Kp rows as
+    // `x` describes them, their fold, the bias column sum -- for the uneven-slab and the ragged branch below
+    auto tr_slabs = [&](int S, int Kp, const GemmShadows& x) -> int {
+        W2V2_REQUIRE(S == 1 || (int64_t)(S + 1) * Kin * Nout <= slab_cap, "weight_grad: slab scratch too small");
+        if (int e = launch_gemm_bf16_x(m->prof, nullptr, Kin, (int64_t)Kp * Kin, nullptr, Nout, (int64_t)Kp * Nout, (S == 1 && !unpack) ? dW : slabs, Nout,
+                                       (int64_t)Kin * Nout, nullptr, nullptr, Kin, Nout, Kp, S, 0, x, s))
+            return e;
+        if (S > 1 || unpack)
+            if (int e = fold_slabs(S)) return e;
+        return bias_colsum();
     };
     if (dW) {
         // dW (Kin, Nout) = A^T dY over the M = B T rows: few output tiles and a very long K, so the rows are cut into S slabs
@@ -469,20 +540,10 @@ static int weight_grad(w2v2_model* m, const float* A, const float* dY, int M, in
             const int S = (int)std::min<int64_t>(cap, units_all / 3);      // (a slab is at least three K tiles: the kernel's pipeline depth)
             if (S >= 1) {
                 const int64_t q = units_all / S;
-                const int Kp = (int)(q * kq);
                 GemmShadows x;
                 x.transA = true; x.A16 = A16; x.B16p = dY16; x.kextra = (int)(units_all % S);
                 if (M % kq != 0) { x.validK = M; x.b_zero_row = true; }
-                if (int e = launch_gemm_bf16_x(m->prof, nullptr, Kin, (int64_t)Kp * Kin, nullptr, Nout, (int64_t)Kp * Nout, (S == 1 && !unpack) ? dW : slabs, Nout,
-                                               (int64_t)Kin * Nout, nullptr, nullptr, Kin, Nout, Kp, S, 0, x, s))
-                    return e;
-                if (S > 1 || unpack)
-                    if (int e = fold_slabs(S)) return e;
-                if (db) {
-                    W2V2_REQUIRE(dY, "weight_grad: the bias gradient needs the fp32 dY");
-                    if (int e = launch_colsum(dY, db, M, Nout, red_ws, 0, s)) return e;
-                }
-                return W2V2_OK;
+                return tr_slabs(S, (int)(q * kq), x);
             }
         }
         // That kernel reads rows past M as zero (GemmShadows::validK), so any M splits into S slabs of ceil(M / 64 / S) K tiles with
@@ -493,20 +554,9 @@ static int weight_grad(w2v2_model* m, const float* A, const float* dY, int M, in
             int S = (int)(units_all < cap ? units_all : cap);
             int64_t per = (units_all + S - 1) / S;
             while (S > 1 && (int64_t)(S - 1) * per >= units_all) { --S; per = (units_all + S - 1) / S; }     // (no empty slab)
-            const int Kp = (int)(per * kq);
-            W2V2_REQUIRE(S == 1 || (int64_t)(S + 1) * Kin * Nout <= t->slab_floats, "weight_grad: slab scratch too small");
             GemmShadows x;
             x.transA = true; x.A16 = A16; x.B16p = dY16; x.validK = M;
-            if (int e = launch_gemm_bf16_x(m->prof, nullptr, Kin, (int64_t)Kp * Kin, nullptr, Nout, (int64_t)Kp * Nout, (S == 1 && !unpack) ? dW : slabs, Nout,
-                                           (int64_t)Kin * Nout, nullptr, nullptr, Kin, Nout, Kp, S, 0, x, s))
-                return e;
-            if (S > 1 || unpack)
-                if (int e = fold_slabs(S)) return e;
-            if (db) {
-                W2V2_REQUIRE(dY, "weight_grad: the bias gradient needs the fp32 dY");
-                if (int e = launch_colsum(dY, db, M, Nout, red_ws, 0, s)) return e;
-            }
-            return W2V2_OK;
+            return tr_slabs(S, (int)(per * kq), x);
         }
         const int64_t units0 = M / kq;
         int64_t units = units0;
@@ -521,7 +571,7 @@ static int weight_grad(w2v2_model* m, const float* A, const float* dY, int M, in
         }
         const int Mq = (int)(units * kq), R = M - Mq;
         const int nslabs = S + (R ? 1 : 0);
-        W2V2_REQUIRE(nslabs == 1 || (int64_t)(nslabs + 1) * Kin * Nout <= t->slab_floats, "weight_grad: slab scratch too small");
+        W2V2_REQUIRE(nslabs == 1 || (int64_t)(nslabs + 1) * Kin * Nout <= slab_cap, "weight_grad: slab scratch too small");
         float* dst = (nslabs == 1 && !unpack) ? dW : slabs;
         const int Kp = S ? Mq / S : 0;
         if (S) {
@@ -563,11 +613,7 @@ static int weight_grad(w2v2_model* m, const float* A, const float* dY, int M, in
             if (int e = launch_colsum(t->cs_ws, db, nslabs, Nout, red_ws, 0, s)) return e;
         }
     }
-    if (db && !fused_bias) {
-        W2V2_REQUIRE(dY, "weight_grad: the bias gradient needs the fp32 dY");
-        if (int e = launch_colsum(dY, db, M, Nout, red_ws, 0, s)) return e;
-    }
-    return W2V2_OK;
+    return fused_bias ? W2V2_OK : bias_colsum();
 }
 
 extern "C" {
@@ -628,53 +674,24 @@ int w2v2_train_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, c
     const int T = (int)Tll;
     const int H = c.hidden_size, F = c.intermediate_size;
     const int64_t BT = (int64_t)B * T;
-    // Precision mode 1: the same bf16 shadows as the inference forward (forward.hip).  Every producer of a forward GEMM
-    // operand -- conv0, GEMM epilogues, LayerNorm, dropout, attention -- also writes the nearest-even bf16 copy, so the
-    // forward GEMMs stream 2-byte operands by LDS-DMA instead of converting fp32 in registers.  The shadow buffers are
-    // transient scratch (the backward works from the saved fp32 activations); results are bit-identical either way.
-    const bool sh = m->precision == 1 && m->opt_shadows;
-    if (sh)       // (also refreshes the bf16 weight shadows after an optimizer step: m->w16_valid, which the decisions below read)
+    if (m->precision == 1 && m->opt_shadows)       // (also refreshes the bf16 weight shadows after an optimizer step: m->w16_valid, which the plan reads)
         if (int e = w2v2_ensure_shadows(m, B, T, s)) return e;
-    const bool attn16 = sh && attention_bf16_supported(H / c.num_heads);
-    // FFN hidden activations as bf16 only: needs the shadow paths on both sides (forward GEMM by LDS-DMA, weight gradient in
-    // the transposing-read form, whole 128-tiles) and the plain bf16 copies of the FFN kernels for the data gradients
-    const bool ffn16_only = sh && m->w16_valid && F % 128 == 0 && H % 128 == 0 && (BT * F) % 4 == 0 && !m->w16p.empty();
-    // Precision mode 1 keeps the FFN pre-activation u = t2 W1 + b1 as bf16 (what a mixed_bfloat16 Dense hands to its activation): on
-    // the shadow path the up-projection writes ONLY the bf16 copy (its bf16 epilogue; 302 MB of fp32 stores per layer gone at B = 32)
-    // and GELU + dropout, GELU' in the backward read that; the shadow-free path of the mode rounds the fp32 u on the way into the
-    // same kernels, so both paths agree bit for bit.
-    const bool u16_only = ffn16_only && tune_int("W2V2_U16", 1) != 0;
-    // The attention output O: its readers are the out-projection GEMM and that GEMM's weight gradient (both stream the bf16 shadow)
-    // and D = rowsum(dO o O) of the attention backward, which is defined on the bf16 values -- no fp32 copy is written.
-    const bool ctx16_only = ffn16_only && attn16 && tune_int("W2V2_CTX16", 1) != 0;
-    // Prenorm: a = LN1(x) and t2 = LN2(t1) are read only by GEMMs that stream their shadows (forward GEMM by LDS-DMA, weight gradient in the
-    // transposing-read form: the same conditions as above): written only as bf16 (196 MB of fp32 stores per layer gone at 16 x 480000)
-    const bool ln16_only = c.attention_norm_type == 1 && ffn16_only && attn16 && tune_int("W2V2_LN16", 1) != 0;
-    // (tools-only build: W2V2_LEAN_WS = 0 allocates everything, as rounds 2-4 did, for A/B runs)
-    const int lean = tune_int("W2V2_LEAN_WS", 1) == 0 ? 0
-                     : (attn16 ? LEAN_QKV : 0) | (ctx16_only ? LEAN_CTX : 0) | (ffn16_only ? LEAN_GD : 0) | (u16_only ? LEAN_U_HALF : 0) |
-                       (ln16_only ? LEAN_LN : 0);
-    if (int e = ensure_train_ws(m, B, L, T, lean)) return e;
+    const TrainPlan plan = plan_train(m, B, L);
+    if (int e = ensure_train_ws(m, plan, L)) return e;
     TrainState* t = m->train;
+    t->forward_done = false;           // (until this forward completes there is nothing for a backward to differentiate)
     Profiler* pf = m->prof;
-    const int act = c.is_gelu_approx ? 2 : 1;
-    // element-wise kernels in precision mode 1 evaluate exact GELU / GELU' through the 5-term erf the bf16 GEMM epilogue uses (act 3)
-    const int act_ew = (act == 1 && m->precision == 1) ? 3 : act;
+    const bool sh = plan.sh, attn16 = plan.attn16, ffn16_only = plan.ffn16_only, u16_only = plan.u16_only, ctx16_only = plan.ctx16_only,
+               ln16_only = plan.ln16_only, prenorm = plan.prenorm;
+    const int act = plan.act, act_ew = plan.act_ew;
     const float eps = c.layer_norm_eps, p = dropout_p;
     t->p = p;
     t->seed = seed;
+    // (the non-plane-fed routes of the inference forward's gemm(): six-product split, fp32, bf16 with shadows -- forward.hip)
     auto gemm = [&](const float* A, const uint16_t* A16, int64_t lda, int64_t strideA, const float* Bw, int64_t ldb, float* Cc,
                     uint16_t* C16, int64_t ldc, int64_t strideC, const float* bias, const float* res, int M, int N, int K,
                     int nbatch, int act_) -> int {
-        if (w2v2_use_split_gemm(m, A, lda, strideA, ldb, M, N, K, nbatch)) {      // precision mode 2 (gemm_split.hip)
-            const uint16_t* planes = nullptr;
-            if (int e = w2v2_split_planes(m, Bw, K, N, s, &planes)) return e;
-            return launch_gemm_split(pf, A, lda, strideA, planes, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, s);
-        }
-        if (!sh) return launch_gemm(pf, A, lda, strideA, Bw, ldb, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, s);
-        GemmShadows x;
-        x.A16 = A16; x.B16 = m->w16[Bw]; x.C16 = C16; x.ldb16 = K;
-        return launch_gemm_bf16_x(pf, A, lda, strideA, Bw, ldb, 0, Cc, ldc, strideC, bias, res, M, N, K, nbatch, act_, x, s);
+        return w2v2_gemm_route(m, sh, s, A, A16, lda, strideA, Bw, ldb, Cc, C16, ldc, strideC, bias, res, M, N, K, nbatch, act_);
     };
     auto S16 = [&](uint16_t* p16) -> uint16_t* { return sh ? p16 : nullptr; };
 
@@ -710,7 +727,6 @@ int w2v2_train_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, c
                                           c.num_conv_pos_embeddings / 2, 1, s)) {
         return e;
     }
-    const bool prenorm = c.attention_norm_type == 1;
     // postnorm: hs[0] = dropout(LN(posout));  prenorm: hs[0] = dropout(posout)   (encoder.py:267-270)
     {
         const float* pre = m->posout;
@@ -722,11 +738,6 @@ int w2v2_train_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, c
         // postnorm: layer 0's q|k|v GEMM reads this tensor -> shadow
         if (int e = launch_dropout_fwd_x(pre, nullptr, h0, (sh && !prenorm) ? m->hs16[0] : nullptr, BT * H, 0, p, seed, DS_ENCODER_IN, s)) return e;
     }
-    t->ffn16_only = ffn16_only;       // (decided in front of the workspace, which leaves out the fp32 buffers these modes never write)
-    t->u16_only = u16_only;
-    t->ctx16_only = ctx16_only;
-    t->ln16_only = ln16_only;
-    const int u_round = m->precision == 1 ? 1 : 0;
     for (int i = 0; i < c.num_layers; ++i) {
         const std::string b = "encoder/layers/" + std::to_string(i);
         LayerSave& l = t->layers[i];
@@ -779,7 +790,7 @@ int w2v2_train_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, c
                              m->P(b + "/feed_forward/intermediate_dense/bias"), nullptr, (int)BT, F, H, 1, 0))
                 return e;
             EwBf16 uin;
-            uin.a16 = u16; uin.round_in = u_round;
+            uin.a16 = u16; uin.round_in = plan.u_round;
             if (int e = launch_dropout_fwd_x(u16_only ? nullptr : l.u, nullptr, ffn16_only ? nullptr : l.gd, S16(l.gd16), BT * F, act_ew, p, seed,
                                              layer_stream(i, 2), s, uin))
                 return e;
@@ -813,29 +824,51 @@ int w2v2_train_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, c
     if (int e = gemm(t->hdf, S16(m->enc16), H, 0, m->P("lm_head/kernel"), c.vocab_size, logits_out, nullptr, c.vocab_size, 0,
                      m->P("lm_head/bias"), nullptr, (int)BT, c.vocab_size, H, 1, 0))
         return e;
+    t->plan = plan;                    // what the backward reads: the per-layer X shadows (and hs16) hold this forward's activations iff plan.sh
     t->forward_done = true;
-    t->x16_valid = sh;                 // the per-layer X shadows (and hs16) hold this forward's activations
-    t->x16_attn = attn16;
     return W2V2_OK;
 }
 
-int w2v2_train_backward(w2v2_model* m, const float* dlogits, void* stream) {
-    W2V2_REQUIRE(m && dlogits, "train_backward: null argument");
-    TrainState* t = m->train;
-    if (!t || !t->forward_done) {
-        set_error("train_backward: no training forward to differentiate");
-        return W2V2_ESTATE;
-    }
-    const w2v2_config& c = m->cfg;
-    PrecisionScope precision(m->precision);
-    StepProfScope step_prof(m->prof);          // the training-only kernels' launchers find the profiler here (common.h)
-    // dX = dY W^T reads the fp32 transposed copy WT ([out][in]) as its B operand; in precision mode 1 with shadows the bf16
-    // copy of W itself ([in][out] = (N, K) for this GEMM) is the B shadow -- no transpose needed.  Bit-identical results.
-    const bool shb = m->precision == 1 && m->opt_shadows && m->w16_valid;
+}  // extern "C"
+
+// ---- the backward: w2v2_train_backward sets up one BwdCtx and runs four stages over it -------------------------------------------------
+// head -> encoder layers -> encoder input, positional conv, spec-augment -> feature projection.  Every mode-dependent decision comes from
+// `plan`, the plan of the forward being differentiated (TrainState::plan), never from the model's settings at backward time.
+struct BwdCtx {
+    w2v2_model* m;
+    TrainState* t;
+    const TrainPlan& plan;
+    hipStream_t s;
+    int B, T, H, F;
+    int64_t BT;
+    float eps, p;
+    uint64_t seed;
+    const int32_t* flen;
+    // dX = dY W^T reads the fp32 transposed copy WT ([out][in]) as its B operand; in mode bf16 with shadows the bf16 copy of W itself
+    // ([in][out] = (N, K) for this GEMM) is the B shadow -- no transpose needed.  Bit-identical results.  `shb` also says that the
+    // forward's X shadows and the dY shadows below are there for the weight-gradient GEMMs (plan.sh is part of it).
+    bool shb;
+    // bf16 shadows of dY (written by its producer) for the data-gradient GEMMs: only where the consumer will take them
+    uint16_t *s16h, *s16f, *s16q;
+    float *dh, *tmp, *tmp2, *tmp3;            // (BT, H) gradient scratch: TrainState::gh
+    // weight-gradient side stream (TrainState::wg_stream) and deferred folds (train.h: FoldBatch) of the encoder layers
+    bool side_on = false;
+    int defer_mode = 0;
+    FoldBatch fold;
+    FoldBatch* fb = nullptr;
+    float *ln2_ws = nullptr, *ln1_ws = nullptr;
+    bool wg_pending[4] = {false, false, false, false};
+    bool wg_used = false;
+    // head -> layers (prenorm): the encoder LayerNorm's backward already summed dh's columns into the top layer's b2 gradient / wrote dh's shadow
+    float* head_b2 = nullptr;
+    bool head_dh16 = false;
+
+    float* G(const std::string& n) const { return is_trainable(m, n) ? grad_of(m, n) : nullptr; }
+    bool dx_shadowed(const float* W) const { return shb && m->w16p.find(W) != m->w16p.end(); }
     // A16: the producer's bf16 shadow of A (or null): with it both operands stream by LDS-DMA (gemm_bf16.hip source 5)
-    auto gemm_dx = [&](const float* A, const uint16_t* A16, int64_t lda, const float* WT, const float* W, float* Cc, int64_t ldc,
-                       const float* res, int M, int N, int K, hipStream_t st, uint16_t* C16 = nullptr) -> int {
-        // (C16: bf16 shadow of the result, only from the shadow branch -- callers ask for it only when `dx_shadowed(W)`)
+    // (C16: bf16 shadow of the result, only from the shadow branch -- callers ask for it only when `dx_shadowed(W)`)
+    int gemm_dx(const float* A, const uint16_t* A16, int64_t lda, const float* WT, const float* W, float* Cc, int64_t ldc, const float* res, int M,
+                int N, int K, hipStream_t st, uint16_t* C16 = nullptr) const {
         if (shb) {
             auto it = m->w16p.find(W);
             if (it != m->w16p.end()) {
@@ -847,57 +880,18 @@ int w2v2_train_backward(w2v2_model* m, const float* dlogits, void* stream) {
                 return launch_gemm_bf16_x(m->prof, A, lda, 0, WT, N, 0, Cc, ldc, 0, nullptr, res, M, N, K, 1, 0, x, st);
             }
         }
-        if (w2v2_use_split_gemm(m, A, lda, 0, N, M, N, K, 1)) {                   // precision mode 2: planes of the transposed copy
+        if (w2v2_use_split_gemm(m, A, lda, 0, N, M, N, K, 1)) {                   // mode bf16x3: planes of the transposed copy
             const uint16_t* planes = nullptr;
             if (int e = w2v2_split_planes(m, WT, K, N, st, &planes)) return e;
             return launch_gemm_split(m->prof, A, lda, 0, planes, Cc, ldc, 0, nullptr, res, M, N, K, 1, 0, st);
         }
         return launch_gemm(m->prof, A, lda, 0, WT, N, Cc, ldc, 0, nullptr, res, M, N, K, 1, 0, st);
-    };
-    auto dx_shadowed = [&](const float* W) { return shb && m->w16p.find(W) != m->w16p.end(); };
-    // bf16 shadows of dY (written by its producer) for the data-gradient GEMMs: only where the consumer will take them
-    const int dhead = c.hidden_size / c.num_heads;
-    uint16_t* const s16h = shb ? t->dy16_h : nullptr;
-    uint16_t* const s16f = shb ? t->dy16_f : nullptr;
-    uint16_t* const s16q = (shb && attention_bf16_supported(dhead)) ? t->dy16_3h : nullptr;
-    if (shb && ((int64_t)t->B * t->T) % 64 != 0) {
-        // Ragged row count: the weight-gradient GEMMs read the missing rows of their last K tile from the zero row behind each dY
-        // shadow.  Re-assert the invariant on THIS stream every backward (three rows, a few KB): nothing may have padded into them.
-        hipStream_t st0 = reinterpret_cast<hipStream_t>(stream);
-        const int64_t BT0 = (int64_t)t->B * t->T;
-        W2V2_HIP_CHECK(hipMemsetAsync(t->dy16_h + BT0 * c.hidden_size, 0, (size_t)c.hidden_size * 2, st0));
-        W2V2_HIP_CHECK(hipMemsetAsync(t->dy16_f + BT0 * c.intermediate_size, 0, (size_t)c.intermediate_size * 2, st0));
-        W2V2_HIP_CHECK(hipMemsetAsync(t->dy16_3h + BT0 * 3 * c.hidden_size, 0, (size_t)3 * c.hidden_size * 2, st0));
     }
-    const bool xs = shb && t->x16_valid;             // X shadows of the forward are there for the weight-gradient GEMMs
-    // the forward kept the FFN hidden activations only as bf16: the backward must then run entirely on the shadow paths
-    const bool f16 = t->ffn16_only;
-    W2V2_REQUIRE(!f16 || (xs && t->dy16_f && t->dy16_h), "train_backward: the forward ran with bf16 shadows (FFN activations kept as bf16 only); "
-                                                      "precision / W2V2_BF16_SHADOWS must not change before the backward");
-    for (size_t i = 0; i < m->params.size(); ++i)
-        if (t->trainable[i] && m->params[i].name.compare(0, 18, "feature_extractor/") == 0) {
-            set_error("train_backward: `%s` is trainable, but the conv feature extractor has no backward "
-                      "(the reference freezes it, main.py:234-237); call freeze_feature_extractor()", m->params[i].name.c_str());
-            return W2V2_ESTATE;
-        }
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    Profiler* pf = m->prof;
-    const int B = t->B, T = t->T, H = c.hidden_size, F = c.intermediate_size, V = c.vocab_size;
-    const int64_t BT = (int64_t)B * T;
-    const int act = c.is_gelu_approx ? 2 : 1;
-    // element-wise kernels in precision mode 1 evaluate exact GELU / GELU' through the 5-term erf the bf16 GEMM epilogue uses (act 3)
-    const int act_ew = (act == 1 && m->precision == 1) ? 3 : act;
-    const float eps = c.layer_norm_eps, p = t->p;
-    const uint64_t seed = t->seed;
-    const int32_t* flen = t->have_mask ? m->frame_len : nullptr;
-    // With the shadows on, the weight-gradient GEMMs take the LDS-DMA / transposing-read kernel, which has no fp32 dY in
-    // registers to sum for the bias gradient: the PRODUCER of each dY leaves its column sums instead (dropout backward,
-    // LayerNorm backward), and weight_grad is called without a bias target.  `bias_from_producer` says that happened.
-    // Deferred folds of the encoder layers (train.h: FoldBatch; W2V2_OPT_DEFER_FOLDS): `fb` is set below, once the side-stream decision is known
-    FoldBatch fold;
-    FoldBatch* fb = nullptr;
-    auto dropout_bwd_bias = [&](const float* u, const float* dy, float* dx, uint16_t* dx16, int64_t rows, int cols, int act_, uint32_t stream_id,
-                                float* bias_grad, bool* bias_done, const EwBf16& in = EwBf16{}, bool deferrable = false) -> int {
+    // With the shadows on, the weight-gradient GEMMs take the LDS-DMA / transposing-read kernel, which has no fp32 dY in registers to
+    // sum for the bias gradient: the PRODUCER of each dY leaves its column sums instead (dropout backward, LayerNorm backward), and
+    // weight_grad is called without a bias target.  `bias_done` says that happened.
+    int dropout_bwd_bias(const float* u, const float* dy, float* dx, uint16_t* dx16, int64_t rows, int cols, int act_, uint32_t stream_id, float* bias_grad,
+                         bool* bias_done, const EwBf16& in = EwBf16{}, bool deferrable = false) {
         *bias_done = false;
         if (shb && bias_grad) {
             *bias_done = true;
@@ -906,67 +900,15 @@ int w2v2_train_backward(w2v2_model* m, const float* dlogits, void* stream) {
                                              d ? fb : nullptr);
         }
         return launch_dropout_bwd_x(u, dy, dx, dx16, rows * cols, act_, p, seed, stream_id, s, in);
-    };
-    // Gradient buffer at the start of a backward.  Rounds 1-5 zeroed all of it every step (360 MB / 1.25 GB: the runtime's fill kernels,
-    // 0.23 / 0.8 ms per step and the only framework kernels left in it).  Every producer below STORES its gradient (no accumulation
-    // into the buffer: folds, column sums and GEMM epilogues overwrite), so a slot needs zeros only if nothing will write it this time:
-    //   * slots of variables that are not trainable, and the 16-byte padding between slots: zero since allocation, never written;
-    //   * masked_spec_embed when this step has no spec-augment mask;
-    //   * everything, conservatively, when the trainable set changed since the last backward (a slot that was written before keeps
-    //     its last gradient) or when stochastic depth dropped a layer (its branch's gradients are not computed: zeros).
-    // tests/test_train_gpu.py poisons the buffer with NaN before its gradient checks: a trainable slot nobody wrote shows up there.
-    {
-        uint64_t sig = 1469598103934665603ull;
-        for (size_t i = 0; i < t->trainable.size(); ++i) sig = (sig ^ (uint64_t)(t->trainable[i] ? 0x9E : 0x3C)) * 1099511628211ull;
-        bool dropped = false;
-        for (int i = 0; i < c.num_layers; ++i) dropped = dropped || t->layers[i].keep == 0.f;
-        if (sig != t->trainable_sig || dropped || t->grads_need_clear) {
-            W2V2_HIP_CHECK(hipMemsetAsync(t->grads, 0, (size_t)t->gtotal * 4, s));
-            t->trainable_sig = sig;
-            t->grads_need_clear = dropped;        // (the step after a dropped layer starts from zeros as well: its slots hold nothing new)
-        } else if (!t->have_spec) {
-            auto it = m->index.find("masked_spec_embed");
-            if (it != m->index.end() && t->trainable[it->second])
-                W2V2_HIP_CHECK(hipMemsetAsync(t->grads + t->goff[it->second], 0, (size_t)m->params[it->second].numel * 4, s));
-        }
     }
-    if (int e = refresh_transposes(m, s)) return e;
-    const int nbuckets = c.num_layers + 2;
-    while ((int)t->bucket_ev.size() < nbuckets) {
-        hipEvent_t ev;
-        W2V2_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        t->bucket_ev.push_back(ev);
-    }
-    // ---- weight-gradient side stream (TrainState::wg_stream): the bf16 shadow path only -- there every dY a weight gradient reads is a
-    // shadow with a known next writer (the wait points below); the other paths keep one stream.
-    // (tools-only build: W2V2_WGRAD_STREAM = 0 / 1 overrides the option for A/B runs)
-    const int wg_knob = tune_int("W2V2_WGRAD_STREAM", -1);
-    const bool side_on = shb && t->x16_valid && t->x16_attn && t->attn_colpart && (wg_knob < 0 ? m->opt_wgrad_stream : wg_knob != 0);
-    if (side_on && !t->wg_stream) {
-        int lo = 0, hi = 0;
-        W2V2_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));           // (lo = the numerically largest = least urgent)
-        W2V2_HIP_CHECK(hipStreamCreateWithPriority(&t->wg_stream, hipStreamNonBlocking, lo));
-        W2V2_HIP_CHECK(hipEventCreateWithFlags(&t->wg_fork, hipEventDisableTiming));
-        W2V2_HIP_CHECK(hipEventCreateWithFlags(&t->wg_main, hipEventDisableTiming));
-        for (int k = 0; k < 4; ++k) W2V2_HIP_CHECK(hipEventCreateWithFlags(&t->wg_join[k], hipEventDisableTiming));
-    }
-    // (the side stream keeps the folds behind their GEMMs: its weight gradients run ahead of / behind the main stream's position)
-    // (tools-only build: W2V2_DEFER_FOLDS = 0 none, 1 the column-sum folds only -- slab sums behind their GEMMs --, 2 everything.
-    //  One box, arms interleaved, profiles/r05_ab_defer_folds.txt: base step 33.80 / 33.55 / 33.50 ms, large-robust 98.38 / 97.94 / 97.74)
-    const int defer_mode = (!side_on && m->opt_defer_folds) ? tune_int("W2V2_DEFER_FOLDS", 2) : 0;
-    if (defer_mode != 0) fb = &fold;
-    if (int e = ensure_site_scratch(m, side_on, defer_mode != 0, defer_mode == 2)) return e;
-    auto wg_site = [&](int k) {
+    WgSite wg_site(int k) {
         WgSite w;
         if (defer_mode == 2) { w.slabs = t->site_slabs[k]; w.slab_floats = t->site_slab_floats[k]; w.defer = fb; }
         return w;
-    };
-    float* const ln2_ws = fb ? t->site_ws[0] : t->red_ws;
-    float* const ln1_ws = fb ? t->site_ws[2] : t->red_ws;
-    bool wg_pending[4] = {false, false, false, false};
-    bool wg_used = false;
+    }
     // side(site, f): run f(stream, reduction scratch) -- a weight gradient -- behind everything the main stream has enqueued so far
-    auto side = [&](int site, auto&& f) -> int {
+    template <class Fn>
+    int side(int site, Fn&& f) {
         if (!side_on) return f(s, t->red_ws);
         W2V2_HIP_CHECK(hipEventRecord(t->wg_fork, s));
         W2V2_HIP_CHECK(hipStreamWaitEvent(t->wg_stream, t->wg_fork, 0));
@@ -974,18 +916,18 @@ int w2v2_train_backward(w2v2_model* m, const float* dlogits, void* stream) {
         W2V2_HIP_CHECK(hipEventRecord(t->wg_join[site], t->wg_stream));
         wg_pending[site] = wg_used = true;
         return W2V2_OK;
-    };
+    }
     // the main stream is about to overwrite what site's weight gradient reads
-    auto side_wait = [&](int site) -> int {
+    int side_wait(int site) {
         if (wg_pending[site]) {
             W2V2_HIP_CHECK(hipStreamWaitEvent(s, t->wg_join[site], 0));
             wg_pending[site] = false;
         }
         return W2V2_OK;
-    };
+    }
     // bucket k's slice of the flat buffer is final once this is recorded (w2v2_train_bucket_wait): with the side stream in use the
     // event goes THERE, after the side stream has caught up with the main stream's position (LayerNorm / bias gradients come from it)
-    auto bucket_done = [&](int k) -> int {
+    int bucket_done(int k) {
         if (wg_used) {
             W2V2_HIP_CHECK(hipEventRecord(t->wg_main, s));
             W2V2_HIP_CHECK(hipStreamWaitEvent(t->wg_stream, t->wg_main, 0));
@@ -994,342 +936,323 @@ int w2v2_train_backward(w2v2_model* m, const float* dlogits, void* stream) {
         }
         W2V2_HIP_CHECK(hipEventRecord(t->bucket_ev[k], s));
         return W2V2_OK;
-    };
-    auto G = [&](const std::string& n) { return is_trainable(m, n) ? grad_of(m, n) : nullptr; };
-    // does anything below the head train?
-    bool below_head = false;
-    for (size_t i = 0; i < m->params.size(); ++i)
-        if (t->trainable[i] && m->params[i].name.compare(0, 8, "lm_head/") != 0) below_head = true;
+    }
+    // the two branches of an encoder layer, written once for both norms (below)
+    int qkv_weight_grad(const std::string& b, const float* attn_in, const uint16_t* attn_in16, bool only16, hipStream_t st, float* rws);
+    int ffn_branch_bwd(int i, LayerSave& l, const std::string& b, const float* dy, const uint16_t* dy16, bool b2_done, float* dx, const float* res);
+    bool do16_only(const std::string& b) const;
+    int attn_branch_bwd(int i, LayerSave& l, const std::string& b, const float* dt1, const float* attn_in, const uint16_t* attn_in16, bool do_tail,
+                        float* dx, const float* res);
+};
 
-    // ---- head ----
-    if (int e = weight_grad(m, t->hdf, dlogits, (int)BT, H, V, G("lm_head/kernel"), G("lm_head/bias"), s)) return e;
-    if (int e = bucket_done(0)) return e;
-    if (!below_head) {                          // stage 1 of the reference: only lm_head trains (main.py:210)
-        for (int k = 1; k < nbuckets; ++k)
-            if (int e = bucket_done(k)) return e;
+// ---- head: lm_head's gradients (bucket 0), then dh = d loss / d hs[N] ----
+static int bwd_head(BwdCtx& x, const float* dlogits, bool below_head) {
+    w2v2_model* m = x.m;
+    TrainState* t = x.t;
+    const w2v2_config& c = m->cfg;
+    const int H = x.H, V = c.vocab_size;
+    const int64_t BT = x.BT;
+    hipStream_t s = x.s;
+    if (int e = weight_grad(m, t->hdf, dlogits, (int)BT, H, V, x.G("lm_head/kernel"), x.G("lm_head/bias"), s)) return e;
+    if (int e = x.bucket_done(0)) return e;
+    if (!below_head) return W2V2_OK;          // stage 1 of the reference: only lm_head trains (main.py:210)
+    if (int e = launch_gemm(m->prof, dlogits, V, 0, t->WlmT, H, x.tmp, H, 0, nullptr, nullptr, (int)BT, H, V, 1, 0, s)) return e;
+    if (!x.plan.prenorm) return launch_dropout_bwd(nullptr, x.tmp, x.dh, BT * H, 0, x.p, x.seed, DS_HEAD, s);
+    // prenorm: hdf = dropout(LN_enc(hs[N]))   (encoder.py:274-275)
+    if (int e = launch_dropout_bwd(nullptr, x.tmp, x.tmp2, BT * H, 0, x.p, x.seed, DS_HEAD, s)) return e;
+    float* dg = x.G("encoder/layer_norm/gamma");
+    float* db = x.G("encoder/layer_norm/beta");
+    // (round 5: this pass also leaves dh's bf16 shadow -- a separate rounding kernel before -- and, on the shadow path, the column
+    //  sums of dh = the top layer's down-projection bias gradient: see `b2_done` in bwd_layers)
+    const bool top16 = x.s16h && (BT * H) % 4 == 0 && (reinterpret_cast<uintptr_t>(x.dh) & 15) == 0;
+    x.head_b2 = (x.shb && tune_int("W2V2_B2_FROM_LN", 1) != 0 && c.num_layers > 0 && t->layers[c.num_layers - 1].keep != 0.f)
+                    ? x.G("encoder/layers/" + std::to_string(c.num_layers - 1) + "/feed_forward/output_dense/bias") : nullptr;
+    if (int e = launch_ln_bwd_x(m->hs[c.num_layers], m->P("encoder/layer_norm/gamma"), x.tmp2, x.dh, top16 ? x.s16h : nullptr, dg ? dg : t->dummy,
+                                db ? db : t->dummy + H, BT, H, x.eps, t->red_ws, s, x.head_b2))
+        return e;
+    x.head_dh16 = top16;
+    return W2V2_OK;
+}
+
+// packed q|k|v projection: dW (H, 3H) -> the three (H, H) kernels, db (3H) -> the three biases.  only16: dqkv exists only as bf16
+// (+ the attention backward's column partials for the bias gradient)
+int BwdCtx::qkv_weight_grad(const std::string& b, const float* attn_in, const uint16_t* attn_in16, bool only16, hipStream_t st, float* rws) {
+    float* dWqkv = t->dwqkv;
+    float* dbqkv = dWqkv + (int64_t)3 * H * H;
+    const char* names[3] = {"q_proj", "k_proj", "v_proj"};
+    float* gw3[3];
+    float* gb3[3];
+    bool all6 = true;
+    for (int j = 0; j < 3; ++j) {
+        gw3[j] = G(b + "/attention/" + names[j] + "/kernel");
+        gb3[j] = G(b + "/attention/" + names[j] + "/bias");
+        all6 = all6 && gw3[j] && gb3[j];
+    }
+    if (fb && only16 && all6 && H % 4 == 0 && fold.tab.n + 2 <= FOLD_MAX_JOBS) {
+        // deferred: the layer's fold launch sums the (H, 3H) slabs straight into the three (H, H) kernels and the attention backward's
+        // column partials into the three biases (group g of the wide job = columns [g H, (g + 1) H) of the 3H-wide partial rows)
+        WgSite site = wg_site(3);
+        site.unpackH = H;
+        for (int j = 0; j < 3; ++j) site.unpack3[j] = gw3[j];
+        if (int e = weight_grad(m, attn_in, nullptr, (int)BT, H, 3 * H, dWqkv, nullptr, st, s16q ? attn_in16 : nullptr, s16q, s16q != nullptr, rws, &site))
+            return e;
+        W2V2_REQUIRE(fb->add_wide(t->attn_colpart, attention_colpart_rows(B, T), H, (int64_t)3 * H, 3, gb3[0], gb3[1], gb3[2]),
+                     "train_backward: fold table full");
         return W2V2_OK;
     }
-    float *dh = t->gh[0], *tmp = t->gh[1], *tmp2 = t->gh[2], *tmp3 = t->gh[3];
-    const bool prenorm = c.attention_norm_type == 1;
-    float* head_b2 = nullptr;      // prenorm: the encoder LayerNorm's backward already summed dh's columns into the top layer's b2 gradient
-    bool head_dh16 = false;        // ... and wrote dh's bf16 shadow
-    if (int e = launch_gemm(pf, dlogits, V, 0, t->WlmT, H, tmp, H, 0, nullptr, nullptr, (int)BT, H, V, 1, 0, s)) return e;
-    if (!prenorm) {
-        if (int e = launch_dropout_bwd(nullptr, tmp, dh, BT * H, 0, p, seed, DS_HEAD, s)) return e;
-    } else {   // hdf = dropout(LN_enc(hs[N]))   (encoder.py:274-275)
-        if (int e = launch_dropout_bwd(nullptr, tmp, tmp2, BT * H, 0, p, seed, DS_HEAD, s)) return e;
-        float* dg = G("encoder/layer_norm/gamma");
-        float* db = G("encoder/layer_norm/beta");
-        // (round 5: this pass also leaves dh's bf16 shadow -- a separate rounding kernel before -- and, on the shadow path, the column
-        //  sums of dh = the top layer's down-projection bias gradient: see `b2_done` in the prenorm loop)
-        const bool top16 = s16h && (BT * H) % 4 == 0 && (reinterpret_cast<uintptr_t>(dh) & 15) == 0;
-        head_b2 = (shb && tune_int("W2V2_B2_FROM_LN", 1) != 0 && c.num_layers > 0 && t->layers[c.num_layers - 1].keep != 0.f)
-                      ? G("encoder/layers/" + std::to_string(c.num_layers - 1) + "/feed_forward/output_dense/bias") : nullptr;
-        if (int e = launch_ln_bwd_x(m->hs[c.num_layers], m->P("encoder/layer_norm/gamma"), tmp2, dh, top16 ? s16h : nullptr, dg ? dg : t->dummy,
-                                    db ? db : t->dummy + H, BT, H, eps, t->red_ws, s, head_b2))
-            return e;
-        head_dh16 = top16;
+    if (int e = weight_grad(m, attn_in, only16 ? nullptr : t->g3h, (int)BT, H, 3 * H, dWqkv, only16 ? nullptr : dbqkv, st, s16q ? attn_in16 : nullptr, s16q,
+                            s16q != nullptr, rws))
+        return e;
+    if (only16)
+        if (int e = launch_colsum_fold(t->attn_colpart, dbqkv, attention_colpart_rows(B, T), 3 * H, st)) return e;
+    if (H % 4 == 0) return launch_qkv_unpack(dWqkv, dbqkv, gw3, gb3, H, st);
+    for (int j = 0; j < 3; ++j) {
+        if (gw3[j])
+            W2V2_HIP_CHECK(hipMemcpy2DAsync(gw3[j], (size_t)H * 4, dWqkv + j * H, (size_t)3 * H * 4, (size_t)H * 4, (size_t)H, hipMemcpyDeviceToDevice, st));
+        if (gb3[j]) W2V2_HIP_CHECK(hipMemcpyAsync(gb3[j], dbqkv + j * H, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
     }
+    return W2V2_OK;
+}
 
-    // dqkv only as bf16 (+ per-block column sums for the bias gradient) when all three of its readers can do without the fp32 copy
-    auto dqkv16_only = [&](int i, const uint16_t* attn_in16) {
-        return xs && s16q && t->x16_attn && t->attn_colpart && attn_in16 && H % 128 == 0 && dx_shadowed(m->qkv_w[i]);
-    };
-    auto qkv_weight_grad = [&](const std::string& b, const float* attn_in, const uint16_t* attn_in16, bool only16, hipStream_t s, float* rws) -> int {
-        // packed q|k|v projection: dW (H, 3H) -> the three (H, H) kernels, db (3H) -> the three biases
-        float* dWqkv = t->dwqkv;
-        float* dbqkv = dWqkv + (int64_t)3 * H * H;
-        const char* names[3] = {"q_proj", "k_proj", "v_proj"};
-        float* gw3[3];
-        float* gb3[3];
-        bool all6 = true;
-        for (int j = 0; j < 3; ++j) {
-            gw3[j] = G(b + "/attention/" + names[j] + "/kernel");
-            gb3[j] = G(b + "/attention/" + names[j] + "/bias");
-            all6 = all6 && gw3[j] && gb3[j];
-        }
-        if (fb && only16 && all6 && H % 4 == 0 && fold.tab.n + 2 <= FOLD_MAX_JOBS) {
-            // deferred: the layer's fold launch sums the (H, 3H) slabs straight into the three (H, H) kernels and the attention backward's
-            // column partials into the three biases (group g of the wide job = columns [g H, (g + 1) H) of the 3H-wide partial rows)
-            WgSite site = wg_site(3);
-            site.unpackH = H;
-            for (int j = 0; j < 3; ++j) site.unpack3[j] = gw3[j];
-            if (int e = weight_grad(m, attn_in, nullptr, (int)BT, H, 3 * H, dWqkv, nullptr, s, (xs && s16q) ? attn_in16 : nullptr, s16q, s16q != nullptr,
-                                    rws, &site))
-                return e;
-            W2V2_REQUIRE(fb->add_wide(t->attn_colpart, attention_colpart_rows(B, T), H, (int64_t)3 * H, 3, gb3[0], gb3[1], gb3[2]),
-                         "train_backward: fold table full");
-            return W2V2_OK;
-        }
-        if (int e = weight_grad(m, attn_in, only16 ? nullptr : t->g3h, (int)BT, H, 3 * H, dWqkv, only16 ? nullptr : dbqkv, s,
-                                (xs && s16q) ? attn_in16 : nullptr, s16q, s16q != nullptr, rws))
-            return e;
-        if (only16)
-            if (int e = launch_colsum_fold(t->attn_colpart, dbqkv, attention_colpart_rows(B, T), 3 * H, s)) return e;
-        if (H % 4 == 0) return launch_qkv_unpack(dWqkv, dbqkv, gw3, gb3, H, s);
-        for (int j = 0; j < 3; ++j) {
-            float* gw = G(b + "/attention/" + names[j] + "/kernel");
-            float* gb = G(b + "/attention/" + names[j] + "/bias");
-            if (gw)
-                W2V2_HIP_CHECK(hipMemcpy2DAsync(gw, (size_t)H * 4, dWqkv + j * H, (size_t)3 * H * 4, (size_t)H * 4, (size_t)H,
-                                                hipMemcpyDeviceToDevice, s));
-            if (gb) W2V2_HIP_CHECK(hipMemcpyAsync(gb, dbqkv + j * H, (size_t)H * 4, hipMemcpyDeviceToDevice, s));
-        }
-        return W2V2_OK;
-    };
-
-    // dgd = dY W2^T (the down-projection's data gradient) into t->gf, then du = dropout-backward(dgd) * GELU'(u) with its column sums
+// FFN branch of layer i, f = dropout(GELU(in W1 + b1)) W2 + b2, for both norms: given dy = d loss / d f (fp32, and its bf16 shadow dy16 or
+// null) it leaves the four FFN gradients and dx = d loss / d `in` (+ res, the residual path's gradient, if given).  b2_done: the kernel
+// that produced dy already left its column sums in the down-projection's bias gradient.
+int BwdCtx::ffn_branch_bwd(int i, LayerSave& l, const std::string& b, const float* dy, const uint16_t* dy16, bool b2_done, float* dx,
+                          const float* res) {
+    const bool f16 = plan.ffn16_only;
+    const float* W1 = m->P(b + "/feed_forward/intermediate_dense/kernel");
+    const float* W2 = m->P(b + "/feed_forward/output_dense/kernel");
+    const WgSite ws0 = wg_site(0), ws1 = wg_site(1);
+    W2V2_REQUIRE(!f16 || dy16, "train_backward: no bf16 shadow of the FFN output's gradient");
+    // (dy16 is null or the H-wide dY shadow of TrainState, whose row BT stays zero: weight_grad's dy16_zero_row.  Without dy16 the
+    //  weight gradient takes no shadow at all, so gd16 is passed only along with it)
+    if (int e = side(0, [&](hipStream_t st, float* rws) {
+            return weight_grad(m, f16 ? nullptr : l.gd, dy, (int)BT, F, H, G(b + "/feed_forward/output_dense/kernel"),
+                               b2_done ? nullptr : G(b + "/feed_forward/output_dense/bias"), st, (shb && dy16) ? l.gd16 : nullptr, dy16, dy16 != nullptr,
+                               rws, &ws0);
+        }))
+        return e;
+    // du = dgd * keep/(1-p) * GELU'(u)   (+ its column sums = the up-projection's bias gradient)
+    bool b1_done = false;
+    float* const gb1 = G(b + "/feed_forward/intermediate_dense/bias");
+    // (f16: du is needed only as bf16 -- both consumers stream the shadow -- unless its fp32 column sums are still to be taken)
+    const bool du16_only = f16 && (!gb1 || shb) && dx_shadowed(W1);
+    float* const du = du16_only ? nullptr : t->gf;
+    if (int e = side_wait(1)) return e;              // (du / its shadow: read by the layer above's up-projection weight gradient)
+    // dgd = dy W2^T (the down-projection's data gradient) into t->gf, then du = dropout-backward(dgd) * GELU'(u) with its column sums
     // (the up-projection's bias gradient) as one element-wise pass.  (In round 2 that pass rode in the GEMM's epilogue; with the GEMM
     // on the 128 x 256 kernel the separate pass at the HBM roofline is faster: profiles/r03_gemm_bf16_study.md.)
-    auto ffn_hidden_grad = [&](int i, LayerSave& l, const std::string& b, const float* dy, const uint16_t* dy16, bool du16_only, float* gb1,
-                               bool* b1_done) -> int {
-        const float* W2 = m->P(b + "/feed_forward/output_dense/kernel");
-        *b1_done = false;
-        EwBf16 in;
-        in.round_in = m->precision == 1 ? 1 : 0;
-        if (t->u16_only) {
-            // the forward kept u only as bf16; the gradient of the hidden activation is written only as bf16 too (the data-gradient
-            // GEMM's bf16 epilogue, into the buffer du's shadow will occupy) and GELU' x dropout-backward runs on it in place
-            W2V2_REQUIRE(s16f && dx_shadowed(W2), "train_backward: the forward kept u as bf16 only, which needs the shadow path for the down-projection's data gradient");
-            if (int e = gemm_dx(dy, dy16, H, l.W2T, W2, nullptr, F, nullptr, (int)BT, F, H, s, s16f)) return e;
-            in.a16 = reinterpret_cast<const uint16_t*>(l.u); in.b16 = s16f;
-            return dropout_bwd_bias(nullptr, nullptr, du16_only ? nullptr : t->gf, s16f, BT, F, act_ew, layer_stream(i, 2), gb1, b1_done, in, true);
-        }
+    EwBf16 in;
+    in.round_in = plan.u_round;
+    if (plan.u16_only) {
+        // the forward kept u only as bf16; the gradient of the hidden activation is written only as bf16 too (the data-gradient
+        // GEMM's bf16 epilogue, into the buffer du's shadow will occupy) and GELU' x dropout-backward runs on it in place
+        W2V2_REQUIRE(s16f && dx_shadowed(W2), "train_backward: the forward kept u as bf16 only, which needs the shadow path for the down-projection's data gradient");
+        if (int e = gemm_dx(dy, dy16, H, l.W2T, W2, nullptr, F, nullptr, (int)BT, F, H, s, s16f)) return e;
+        in.a16 = reinterpret_cast<const uint16_t*>(l.u); in.b16 = s16f;
+        if (int e = dropout_bwd_bias(nullptr, nullptr, du, s16f, BT, F, plan.act_ew, layer_stream(i, 2), gb1, &b1_done, in, true)) return e;
+    } else {
         if (int e = gemm_dx(dy, dy16, H, l.W2T, W2, t->gf, F, nullptr, (int)BT, F, H, s)) return e;
-        return dropout_bwd_bias(l.u, t->gf, du16_only ? nullptr : t->gf, s16f, BT, F, act_ew, layer_stream(i, 2), gb1, b1_done, in, true);
+        if (int e = dropout_bwd_bias(l.u, t->gf, du, s16f, BT, F, plan.act_ew, layer_stream(i, 2), gb1, &b1_done, in, true)) return e;
+    }
+    if (int e = side(1, [&](hipStream_t st, float* rws) {
+            return weight_grad(m, l.t2, du, (int)BT, H, F, G(b + "/feed_forward/intermediate_dense/kernel"), b1_done ? nullptr : gb1, st,
+                               shb ? l.t2_16 : nullptr, s16f, s16f != nullptr, rws, &ws1);
+        }))
+        return e;
+    return gemm_dx(du, s16f, F, l.W1T, W1, dx, H, res, (int)BT, H, F, s);
+}
+
+// d_o (the gradient of the out-projection's output) is read only as bf16 when both of its GEMMs stream shadows and its column sums come
+// from the producer: the dropout backward that makes it then rides in the tail of the LayerNorm backward that produces dt1
+bool BwdCtx::do16_only(const std::string& b) const {
+    return shb && plan.attn16 && s16h && H % 128 == 0 && (BT * H) % 4 == 0 && dx_shadowed(m->P(b + "/attention/out_proj/kernel"));
+}
+
+// Attention branch of layer i, t1 = dropout(attn(attn_in) Wo + bo) + residual, for both norms: given dt1 (in tmp3) it leaves the eight
+// attention gradients and dx = d loss / d attn_in (+ res, if given).  attn_in / attn_in16: what the q|k|v projection read (prenorm
+// l.a / l.a16, postnorm hs[i] / hs16[i]).  do_tail: the LayerNorm backward that produced dt1 already left d_o's shadow in s16h and its
+// column sums in the out-projection's bias gradient.  Scratch: d_o in tmp, dctx in tmp2 (the caller's earlier tenants are dead).
+int BwdCtx::attn_branch_bwd(int i, LayerSave& l, const std::string& b, const float* dt1, const float* attn_in, const uint16_t* attn_in16,
+                           bool do_tail, float* dx, const float* res) {
+    const float* Wo = m->P(b + "/attention/out_proj/kernel");
+    const WgSite ws2 = wg_site(2);
+    const bool o16 = do16_only(b);
+    float* const gbo = G(b + "/attention/out_proj/bias");
+    bool bo_done = do_tail && gbo;
+    float* d_o = tmp;
+    if (!do_tail)
+        if (int e = dropout_bwd_bias(nullptr, dt1, o16 ? nullptr : d_o, s16h, BT, H, 0, layer_stream(i, 1), gbo, &bo_done)) return e;
+    float* dctx = tmp2;
+    // (the bf16 attention backward reads dctx and q | k | v as bf16: the GEMM leaves the dctx shadow, the forward left qkv16)
+    uint16_t* const dctx16 = (s16q && dx_shadowed(Wo)) ? t->dy16_ctx : nullptr;
+    // (c16: the forward kept O only as bf16 -- dctx is then written only as bf16 too and the backward reads both as bf16)
+    const bool c16 = plan.ctx16_only;
+    W2V2_REQUIRE(!c16 || (dctx16 && shb), "train_backward: the forward kept the attention output as bf16 only, which needs the shadow paths");
+    if (int e = gemm_dx(o16 ? nullptr : d_o, s16h, H, l.WoT, Wo, c16 ? nullptr : dctx, H, nullptr, (int)BT, H, H, s, dctx16)) return e;
+    AttnTrain tr{p, seed, layer_stream(i, 0), l.lse, plan.attn16 ? l.keep_bits : nullptr};
+    // dqkv only as bf16 (+ per-block column sums for the bias gradient) when all three of its readers can do without the fp32 copy
+    const bool q16 = shb && s16q && plan.attn16 && t->attn_colpart && attn_in16 && H % 128 == 0 && dx_shadowed(m->qkv_w[i]);
+    auto out_weight_grad = [&](hipStream_t st, float* rws) {
+        return weight_grad(m, c16 ? nullptr : l.ctx, o16 ? nullptr : d_o, (int)BT, H, H, G(b + "/attention/out_proj/kernel"), bo_done ? nullptr : gbo, st,
+                           (shb && plan.attn16) ? l.ctx16 : nullptr, s16h, s16h != nullptr, rws, &ws2);
     };
+    // (side stream: the out-projection's weight gradient goes out BEFORE the attention backward, to run under it)
+    if (side_on)
+        if (int e = side(2, out_weight_grad)) return e;
+    if (int e = side_wait(3)) return e;                  // (dqkv / its shadow / the column partials: the layer above's q|k|v weight gradient)
+    if (int e = launch_attention_bwd(m->prof, plan.attn16 ? nullptr : l.qkv, flen, c16 ? nullptr : l.ctx, c16 ? nullptr : dctx, q16 ? nullptr : t->g3h, t->dvec,
+                                     B, T, H, m->cfg.num_heads, tr, s, s16q, plan.attn16 ? l.qkv16 : nullptr, dctx16, q16 ? t->attn_colpart : nullptr,
+                                     c16 ? l.ctx16 : nullptr))
+        return e;
+    // (one stream: the out-projection's weight gradient runs here, not before its data gradient: the attention backward has just read O, so
+    //  the GEMM finds it in the Infinity Cache instead of streaming it from HBM cold; d_o / its shadow are untouched until below)
+    if (!side_on)
+        if (int e = out_weight_grad(s, t->red_ws)) return e;
+    if (int e = side(3, [&](hipStream_t st, float* rws) { return qkv_weight_grad(b, attn_in, attn_in16, q16, st, rws); })) return e;
+    if (dx == d_o && !o16)
+        if (int e = side_wait(2)) return e;              // (prenorm: dx goes where the fp32 d_o lives, which the out-projection's weight gradient reads)
+    return gemm_dx(q16 ? nullptr : t->g3h, s16q, 3 * H, l.WqkvT, m->qkv_w[i], dx, H, res, (int)BT, H, 3 * H, s);
+}
+
+// ---- encoder layers N-1 .. 0 (buckets 1 .. N): dh = d loss / d (layer output) comes in and goes out in x.dh.  The two branch functions
+// above do the work for both norms; the norm decides where the LayerNorm backward passes sit and which buffers they read and write ----
+static int bwd_layers(BwdCtx& x) {
+    w2v2_model* m = x.m;
+    TrainState* t = x.t;
+    const w2v2_config& c = m->cfg;
+    const TrainPlan& plan = x.plan;
+    const int H = x.H;
+    const int64_t BT = x.BT;
+    hipStream_t s = x.s;
+    float *dh = x.dh, *tmp = x.tmp, *tmp2 = x.tmp2, *dt1 = x.tmp3;
+    uint16_t* const s16h = x.s16h;
     const bool fuse_do_tail = !tune_int("W2V2_NO_DO_TAIL", 0);
-    bool dh16_valid = head_dh16;
-    // b2_done: the kernel that produced dh (the encoder LayerNorm's backward for the top layer, the LayerNorm-1 backward of layer i + 1
-    // below) also left its column sums -- dh is the dY of this layer's down-projection, so they are its bias gradient -- and the
-    // weight gradient needs no separate pass over the fp32 dh (two launches and a 98 MB read per layer at 16 x 480000)
-    bool b2_done = head_b2 != nullptr;
-    if (prenorm && !dh16_valid && s16h && (BT * H) % 4 == 0 && (reinterpret_cast<uintptr_t>(dh) & 15) == 0) {
+    // prenorm: dh's bf16 shadow lives in s16h between layers (written by the pass that produced dh; s16h is free again by then) ...
+    bool dh16_valid = x.head_dh16;
+    // ... and b2_done: that pass (the encoder LayerNorm's backward for the top layer, the LayerNorm-1 backward of layer i + 1) also left
+    // dh's column sums -- dh is the dY of this layer's down-projection, so they are its bias gradient -- and the weight gradient needs
+    // no separate pass over the fp32 dh (two launches and a 98 MB read per layer at 16 x 480000)
+    bool b2_done = x.head_b2 != nullptr;
+    if (plan.prenorm && !dh16_valid && s16h && (BT * H) % 4 == 0 && (reinterpret_cast<uintptr_t>(dh) & 15) == 0) {
         // the last layer's output gradient arrives in fp32 only: round it once so that its down-projection GEMMs stream shadows too
         if (int e = launch_to_bf16(dh, s16h, BT * H, s)) return e;
         dh16_valid = true;
     }
-    for (int i = c.num_layers - 1; i >= 0 && prenorm; --i) {
-        // prenorm layer (encoder.py:111-134):  t1 = x + drop(attn(LN1(x)));  out = t1 + keep * FFN(LN2(t1))
+    for (int i = c.num_layers - 1; i >= 0; --i) {
         const std::string b = "encoder/layers/" + std::to_string(i);
         LayerSave& l = t->layers[i];
-        const WgSite ws0 = wg_site(0), ws1 = wg_site(1), ws2 = wg_site(2);
-        const float* x = i == 0 ? t->hs0 : m->hs[i];
-        float* dt1 = tmp3;
-        // dh's bf16 shadow (written by the previous iteration's closing axpby into s16h, which is free again by then)
-        const uint16_t* dh16 = dh16_valid ? s16h : nullptr;
-        bool bo_done = false;
-        float* const gbo = G(b + "/attention/out_proj/bias");
-        // (d_o is read only as bf16 when both of its GEMMs stream shadows and its column sums come from the producer: the
-        //  dropout backward that makes it then rides in the tail of the LayerNorm backward that produces dt1)
-        const bool do16_only = xs && t->x16_attn && s16h && H % 128 == 0 && (BT * H) % 4 == 0 && dx_shadowed(m->P(b + "/attention/out_proj/kernel"));
-        bool do_tail = do16_only && shb && fuse_do_tail;
-        const LnDropTail do_drop{p, seed, layer_stream(i, 1)};
-        if (l.keep != 0.f) {
-            W2V2_REQUIRE(!f16 || dh16, "train_backward: no bf16 shadow of the layer's output gradient");
-            if (int e = side(0, [&](hipStream_t st, float* rws) {
-                    return weight_grad(m, f16 ? nullptr : l.gd, dh, (int)BT, F, H, G(b + "/feed_forward/output_dense/kernel"),
-                                       b2_done ? nullptr : G(b + "/feed_forward/output_dense/bias"), st, (xs && dh16) ? l.gd16 : nullptr, dh16,
-                                       dh16 != nullptr && dh16 == s16h, rws, &ws0);
-                }))
+        const bool keep = l.keep != 0.f;
+        float* const gbo = x.G(b + "/attention/out_proj/bias");
+        // (do_tail: d_o's shadow and column sums come from the LayerNorm backward that produces dt1 -- see do16_only)
+        bool do_tail = x.do16_only(b) && fuse_do_tail;
+        const LnDropTail do_drop{x.p, x.seed, layer_stream(i, 1)};
+        float* const do_sum = do_tail ? (gbo ? gbo : t->dummy + 2 * H) : nullptr;
+        float* dg1 = x.G(b + "/layer_norm/gamma");
+        float* db1 = x.G(b + "/layer_norm/beta");
+        float* dg2 = x.G(b + "/final_layer_norm/gamma");
+        float* db2 = x.G(b + "/final_layer_norm/beta");
+        if (plan.prenorm) {
+            // prenorm layer (encoder.py:111-134):  t1 = x + drop(attn(LN1(x)));  out = t1 + keep * FFN(LN2(t1))
+            const float* xin = i == 0 ? t->hs0 : m->hs[i];
+            if (keep) {
+                // the FFN's dY is dh itself; d LN2(t1) goes to tmp
+                if (int e = x.ffn_branch_bwd(i, l, b, dh, dh16_valid ? s16h : nullptr, b2_done, tmp, nullptr)) return e;
+                // dt1 = dh (residual) + LN2-backward(tmp), one pass (+ d_o's shadow and column sums where nothing reads d_o in fp32;
+                // dh16 in s16h is dead by now -- once the down-projection's weight gradient has read it)
+                if (int e = x.side_wait(0)) return e;
+                if (int e = launch_ln_bwd_x(l.t1, m->P(b + "/final_layer_norm/gamma"), tmp, dt1, do_tail ? s16h : nullptr, dg2 ? dg2 : t->dummy,
+                                            db2 ? db2 : t->dummy + H, BT, H, x.eps, x.ln2_ws, s, do_sum, dh, do_tail ? &do_drop : nullptr, x.fb))
+                    return e;
+            } else {
+                W2V2_HIP_CHECK(hipMemcpyAsync(dt1, dh, (size_t)BT * H * 4, hipMemcpyDeviceToDevice, s));
+                do_tail = false;
+            }
+            // d LN1(x) goes to tmp (where the fp32 d_o lived)
+            if (int e = x.attn_branch_bwd(i, l, b, dt1, l.a, l.a16, do_tail, tmp, nullptr)) return e;
+            // dh = dt1 (residual) + LN1-backward(tmp), one pass (+ the shadow the next iteration's down-projection GEMMs stream)
+            dh16_valid = s16h && H % 4 == 0 && (reinterpret_cast<uintptr_t>(dt1) & 15) == 0;
+            if (int e = x.side_wait(2)) return e;                  // (d_o's shadow in s16h: the out-projection's weight gradient)
+            if (int e = x.side_wait(0)) return e;                  // (dh in fp32, when the down-projection's weight gradient read that)
+            // (+ the column sums of dh: the down-projection bias gradient of layer i - 1, unless stochastic depth dropped that layer's FFN)
+            float* const next_b2 = (x.shb && tune_int("W2V2_B2_FROM_LN", 1) != 0 && i > 0 && t->layers[i - 1].keep != 0.f)
+                                       ? x.G("encoder/layers/" + std::to_string(i - 1) + "/feed_forward/output_dense/bias") : nullptr;
+            if (int e = launch_ln_bwd_x(xin, m->P(b + "/layer_norm/gamma"), tmp, dh, dh16_valid ? s16h : nullptr, dg1 ? dg1 : t->dummy,
+                                        db1 ? db1 : t->dummy + H, BT, H, x.eps, x.ln1_ws, s, next_b2, dt1, nullptr, x.fb))
                 return e;
-            bool b1_done = false;
-            float* const gb1 = G(b + "/feed_forward/intermediate_dense/bias");
-            // (f16: du is needed only as bf16 -- both consumers stream the shadow -- unless its fp32 column sums are still to be taken)
-            const bool du16_only = f16 && (!gb1 || shb) && dx_shadowed(m->P(b + "/feed_forward/intermediate_dense/kernel"));
-            float* const du = du16_only ? nullptr : t->gf;
-            if (int e = side_wait(1)) return e;              // (du / its shadow: read by the layer above's up-projection weight gradient)
-            if (int e = ffn_hidden_grad(i, l, b, dh, dh16, du16_only, gb1, &b1_done)) return e;
-            if (int e = side(1, [&](hipStream_t st, float* rws) {
-                    return weight_grad(m, l.t2, du, (int)BT, H, F, G(b + "/feed_forward/intermediate_dense/kernel"),
-                                       b1_done ? nullptr : gb1, st, xs ? l.t2_16 : nullptr, s16f, s16f != nullptr, rws, &ws1);
-                }))
-                return e;
-            if (int e = gemm_dx(du, s16f, F, l.W1T, m->P(b + "/feed_forward/intermediate_dense/kernel"), tmp, H, nullptr, (int)BT, H, F, s)) return e;
-            float* dg2 = G(b + "/final_layer_norm/gamma");
-            float* db2 = G(b + "/final_layer_norm/beta");
-            // dt1 = dh (residual) + LN2-backward(tmp), one pass (+ d_o's shadow and column sums where nothing reads d_o in fp32;
-            // dh16 in s16h is dead by now -- once the down-projection's weight gradient has read it)
-            if (int e = side_wait(0)) return e;
-            if (int e = launch_ln_bwd_x(l.t1, m->P(b + "/final_layer_norm/gamma"), tmp, dt1, do_tail ? s16h : nullptr, dg2 ? dg2 : t->dummy,
-                                        db2 ? db2 : t->dummy + H, BT, H, eps, ln2_ws, s, do_tail ? (gbo ? gbo : t->dummy + 2 * H) : nullptr, dh,
-                                        do_tail ? &do_drop : nullptr, fb))
-                return e;
-            bo_done = do_tail && gbo;
+            b2_done = next_b2 != nullptr;
         } else {
-            W2V2_HIP_CHECK(hipMemcpyAsync(dt1, dh, (size_t)BT * H * 4, hipMemcpyDeviceToDevice, s));
-            do_tail = false;
+            // postnorm layer:  t1 = x + drop(attn(x));  t2 = LN1(t1);  t3 = t2 + keep * FFN(t2);  out = LN2(t3)
+            float *dt3 = tmp, *dt2 = tmp2;
+            // (dt3 is the dY of the FFN down-projection: its column sums are that layer's bias gradient, its shadow goes to s16h)
+            float* const gb2 = (x.shb && keep) ? x.G(b + "/feed_forward/output_dense/bias") : nullptr;
+            uint16_t* const dt3_16 = (keep && H % 4 == 0) ? s16h : nullptr;
+            if (int e = x.side_wait(2)) return e;                  // (tmp / s16h still hold the d_o the layer above's out-projection weight gradient reads)
+            if (int e = launch_ln_bwd_x(l.t3, m->P(b + "/final_layer_norm/gamma"), dh, dt3, dt3_16, dg2 ? dg2 : t->dummy, db2 ? db2 : t->dummy + H, BT, H,
+                                        x.eps, x.ln2_ws, s, gb2, nullptr, nullptr, x.fb))
+                return e;
+            if (keep) {
+                // dt2 = d FFN input + dt3 (the residual branch)
+                if (int e = x.ffn_branch_bwd(i, l, b, dt3, dt3_16, gb2 != nullptr, dt2, dt3)) return e;
+            } else {
+                W2V2_HIP_CHECK(hipMemcpyAsync(dt2, dt3, (size_t)BT * H * 4, hipMemcpyDeviceToDevice, s));
+            }
+            if (int e = x.side_wait(0)) return e;                  // (dt3 in tmp / s16h: the down-projection's weight gradient; d_o goes there next)
+            if (int e = launch_ln_bwd_x(l.t1, m->P(b + "/layer_norm/gamma"), dt2, dt1, do_tail ? s16h : nullptr, dg1 ? dg1 : t->dummy,
+                                        db1 ? db1 : t->dummy + H, BT, H, x.eps, x.ln1_ws, s, do_sum, nullptr, do_tail ? &do_drop : nullptr, x.fb))
+                return e;
+            // dh = d attention input + dt1 (residual); dt3 and dt2 are dead: d_o and dctx take their buffers
+            const uint16_t* const hs16_i = m->hs16.size() > (size_t)i ? m->hs16[i] : nullptr;
+            if (int e = x.attn_branch_bwd(i, l, b, dt1, m->hs[i], hs16_i, do_tail, dh, dt1)) return e;
         }
-        float* d_o = tmp;
-        if (!do_tail)
-            if (int e = dropout_bwd_bias(nullptr, dt1, do16_only ? nullptr : d_o, s16h, BT, H, 0, layer_stream(i, 1), gbo, &bo_done)) return e;
-        float* dctx = tmp2;
-        // (the bf16 attention backward reads dctx and q | k | v as bf16: the GEMM leaves the dctx shadow, the forward left qkv16)
-        uint16_t* const dctx16 = (s16q && dx_shadowed(m->P(b + "/attention/out_proj/kernel"))) ? t->dy16_ctx : nullptr;
-        // (c16: the forward kept O only as bf16 -- dctx is then written only as bf16 too and the backward reads both as bf16)
-        const bool c16 = t->ctx16_only;
-        W2V2_REQUIRE(!c16 || (dctx16 && xs && t->x16_attn), "train_backward: the forward kept the attention output as bf16 only, which needs the shadow paths");
-        if (int e = gemm_dx(do16_only ? nullptr : d_o, s16h, H, l.WoT, m->P(b + "/attention/out_proj/kernel"), c16 ? nullptr : dctx, H, nullptr, (int)BT, H, H, s, dctx16)) return e;
-        AttnTrain tr{p, seed, layer_stream(i, 0), l.lse, t->x16_attn ? l.keep_bits : nullptr};
-        const bool q16 = dqkv16_only(i, l.a16);
-        auto out_weight_grad = [&](hipStream_t st, float* rws) {
-            return weight_grad(m, t->ctx16_only ? nullptr : l.ctx, do16_only ? nullptr : d_o, (int)BT, H, H, G(b + "/attention/out_proj/kernel"), bo_done ? nullptr : gbo, st,
-                               (xs && t->x16_attn) ? l.ctx16 : nullptr, s16h, s16h != nullptr, rws, &ws2);
-        };
-        // (side stream: the out-projection's weight gradient goes out BEFORE the attention backward, to run under it)
-        if (side_on)
-            if (int e = side(2, out_weight_grad)) return e;
-        if (int e = side_wait(3)) return e;                  // (dqkv / its shadow / the column partials: the layer above's q|k|v weight gradient)
-        if (int e = launch_attention_bwd(pf, t->x16_attn ? nullptr : l.qkv, flen, c16 ? nullptr : l.ctx, c16 ? nullptr : dctx, q16 ? nullptr : t->g3h, t->dvec, B, T, H, c.num_heads, tr,
-                                         s, s16q, t->x16_attn ? l.qkv16 : nullptr, dctx16, q16 ? t->attn_colpart : nullptr, c16 ? l.ctx16 : nullptr))
-            return e;
-        // (one stream: the out-projection's weight gradient runs here, not before its data gradient: the attention backward has just read O, so
-        //  the GEMM finds it in the Infinity Cache instead of streaming it from HBM cold; d_o / its shadow are untouched until below)
-        if (!side_on)
-            if (int e = out_weight_grad(s, t->red_ws)) return e;
-        if (int e = side(3, [&](hipStream_t st, float* rws) { return qkv_weight_grad(b, l.a, l.a16, q16, st, rws); })) return e;
-        if (!do16_only)
-            if (int e = side_wait(2)) return e;              // (d_o in fp32 lives in tmp)
-        if (int e = gemm_dx(q16 ? nullptr : t->g3h, s16q, 3 * H, l.WqkvT, m->qkv_w[i], tmp, H, nullptr, (int)BT, H, 3 * H, s)) return e;
-        float* dg1 = G(b + "/layer_norm/gamma");
-        float* db1 = G(b + "/layer_norm/beta");
-        // dh = dt1 (residual) + LN1-backward(tmp), one pass (+ the shadow the next iteration's down-projection GEMMs stream)
-        dh16_valid = s16h && H % 4 == 0 && (reinterpret_cast<uintptr_t>(dt1) & 15) == 0;
-        if (int e = side_wait(2)) return e;                  // (d_o's shadow in s16h: the out-projection's weight gradient)
-        if (int e = side_wait(0)) return e;                  // (dh in fp32, when the down-projection's weight gradient read that)
-        // (+ the column sums of dh: the down-projection bias gradient of layer i - 1, unless stochastic depth dropped that layer's FFN)
-        float* const next_b2 = (shb && tune_int("W2V2_B2_FROM_LN", 1) != 0 && i > 0 && t->layers[i - 1].keep != 0.f)
-                                   ? G("encoder/layers/" + std::to_string(i - 1) + "/feed_forward/output_dense/bias") : nullptr;
-        if (int e = launch_ln_bwd_x(x, m->P(b + "/layer_norm/gamma"), tmp, dh, dh16_valid ? s16h : nullptr, dg1 ? dg1 : t->dummy,
-                                    db1 ? db1 : t->dummy + H, BT, H, eps, ln1_ws, s, next_b2, dt1, nullptr, fb))
-            return e;
-        b2_done = next_b2 != nullptr;
-        if (int e = fold.flush(s)) return e;                 // (the layer's deferred folds: its gradients are final behind this launch)
-        if (int e = bucket_done(c.num_layers - i)) return e;
+        if (int e = x.fold.flush(s)) return e;                 // (the layer's deferred folds: its gradients are final behind this launch)
+        if (int e = x.bucket_done(c.num_layers - i)) return e;
     }
+    return W2V2_OK;
+}
 
-    for (int i = c.num_layers - 1; i >= 0 && !prenorm; --i) {
-        const std::string b = "encoder/layers/" + std::to_string(i);
-        LayerSave& l = t->layers[i];
-        const WgSite ws0 = wg_site(0), ws1 = wg_site(1), ws2 = wg_site(2);
-        // hs[i+1] = LN(t3)
-        float* dt3 = tmp;
-        float* dg2 = G(b + "/final_layer_norm/gamma");
-        float* db2 = G(b + "/final_layer_norm/beta");
-        // (dt3 is the dY of the FFN down-projection: its column sums are that layer's bias gradient)
-        float* const gb2 = (shb && l.keep != 0.f) ? G(b + "/feed_forward/output_dense/bias") : nullptr;
-        if (int e = side_wait(2)) return e;                  // (tmp / s16h still hold the d_o the layer above's out-projection weight gradient reads)
-        if (int e = launch_ln_bwd_x(l.t3, m->P(b + "/final_layer_norm/gamma"), dh, dt3, (l.keep != 0.f && H % 4 == 0) ? s16h : nullptr,
-                                    dg2 ? dg2 : t->dummy, db2 ? db2 : t->dummy + H, BT, H, eps, ln2_ws, s, gb2, nullptr, nullptr, fb))
-            return e;
-        float* dt2 = tmp2;
-        if (l.keep != 0.f) {
-            // t3 = t2 + f,  f = gd W2 + b2
-            if (int e = side(0, [&](hipStream_t st, float* rws) {
-                    return weight_grad(m, f16 ? nullptr : l.gd, dt3, (int)BT, F, H, G(b + "/feed_forward/output_dense/kernel"),
-                                       gb2 ? nullptr : G(b + "/feed_forward/output_dense/bias"), st, xs ? l.gd16 : nullptr, H % 4 == 0 ? s16h : nullptr,
-                                       s16h != nullptr, rws, &ws0);
-                }))
-                return e;
-            // du = dgd * keep/(1-p) * GELU'(u)   (+ its column sums = the up-projection's bias gradient)
-            bool b1_done = false;
-            float* const gb1 = G(b + "/feed_forward/intermediate_dense/bias");
-            // (f16: du is needed only as bf16 -- both consumers stream the shadow, the column sums come from the producer)
-            const bool du16_only = f16 && (!gb1 || shb) && dx_shadowed(m->P(b + "/feed_forward/intermediate_dense/kernel"));
-            float* const du = du16_only ? nullptr : t->gf;
-            if (int e = side_wait(1)) return e;              // (du / its shadow: read by the layer above's up-projection weight gradient)
-            if (int e = ffn_hidden_grad(i, l, b, dt3, H % 4 == 0 ? s16h : nullptr, du16_only, gb1, &b1_done)) return e;
-            if (int e = side(1, [&](hipStream_t st, float* rws) {
-                    return weight_grad(m, l.t2, du, (int)BT, H, F, G(b + "/feed_forward/intermediate_dense/kernel"),
-                                       b1_done ? nullptr : gb1, st, xs ? l.t2_16 : nullptr, s16f, s16f != nullptr, rws, &ws1);
-                }))
-                return e;
-            // dt2 = du W1^T + dt3 (the residual branch)
-            if (int e = gemm_dx(du, s16f, F, l.W1T, m->P(b + "/feed_forward/intermediate_dense/kernel"), dt2, H, dt3, (int)BT, H, F, s)) return e;
-        } else {
-            W2V2_HIP_CHECK(hipMemcpyAsync(dt2, dt3, (size_t)BT * H * 4, hipMemcpyDeviceToDevice, s));
-        }
-        // t2 = LN(t1)
-        float* dt1 = tmp3;
-        float* dg1 = G(b + "/layer_norm/gamma");
-        float* db1 = G(b + "/layer_norm/beta");
-        // t1 = dropout(o) + x,  o = ctx Wo + bo
-        float* d_o = tmp;     // dt3 (and its shadow) is dead
-        bool bo_done = false;
-        float* const gbo = G(b + "/attention/out_proj/bias");
-        // (d_o is read only as bf16 when both of its GEMMs stream shadows and its column sums come from the producer: the
-        //  dropout backward that makes it then rides in the tail of the LayerNorm backward that produces dt1)
-        const bool do16_only = xs && t->x16_attn && s16h && H % 128 == 0 && (BT * H) % 4 == 0 && dx_shadowed(m->P(b + "/attention/out_proj/kernel"));
-        const bool do_tail = do16_only && shb && fuse_do_tail;
-        const LnDropTail do_drop{p, seed, layer_stream(i, 1)};
-        if (int e = side_wait(0)) return e;                  // (dt3 in tmp / s16h: the down-projection's weight gradient; d_o goes there next)
-        if (int e = launch_ln_bwd_x(l.t1, m->P(b + "/layer_norm/gamma"), dt2, dt1, do_tail ? s16h : nullptr, dg1 ? dg1 : t->dummy,
-                                    db1 ? db1 : t->dummy + H, BT, H, eps, ln1_ws, s, do_tail ? (gbo ? gbo : t->dummy + 2 * H) : nullptr, nullptr,
-                                    do_tail ? &do_drop : nullptr, fb))
-            return e;
-        bo_done = do_tail && gbo;
-        if (!do_tail)
-            if (int e = dropout_bwd_bias(nullptr, dt1, do16_only ? nullptr : d_o, s16h, BT, H, 0, layer_stream(i, 1), gbo, &bo_done)) return e;
-        float* dctx = tmp2;   // dt2 is dead
-        // (the bf16 attention backward reads dctx and q | k | v as bf16: the GEMM leaves the dctx shadow, the forward left qkv16)
-        uint16_t* const dctx16 = (s16q && dx_shadowed(m->P(b + "/attention/out_proj/kernel"))) ? t->dy16_ctx : nullptr;
-        const bool c16 = t->ctx16_only;
-        W2V2_REQUIRE(!c16 || (dctx16 && xs && t->x16_attn), "train_backward: the forward kept the attention output as bf16 only, which needs the shadow paths");
-        if (int e = gemm_dx(do16_only ? nullptr : d_o, s16h, H, l.WoT, m->P(b + "/attention/out_proj/kernel"), c16 ? nullptr : dctx, H, nullptr, (int)BT, H, H, s, dctx16)) return e;
-        AttnTrain tr{p, seed, layer_stream(i, 0), l.lse, t->x16_attn ? l.keep_bits : nullptr};
-        const uint16_t* const hs16_i = m->hs16.size() > (size_t)i ? m->hs16[i] : nullptr;
-        const bool q16 = dqkv16_only(i, hs16_i);
-        auto out_weight_grad = [&](hipStream_t st, float* rws) {
-            return weight_grad(m, t->ctx16_only ? nullptr : l.ctx, do16_only ? nullptr : d_o, (int)BT, H, H, G(b + "/attention/out_proj/kernel"), bo_done ? nullptr : gbo, st,
-                               (xs && t->x16_attn) ? l.ctx16 : nullptr, s16h, s16h != nullptr, rws, &ws2);
-        };
-        // (side stream: the out-projection's weight gradient goes out BEFORE the attention backward, to run under it)
-        if (side_on)
-            if (int e = side(2, out_weight_grad)) return e;
-        if (int e = side_wait(3)) return e;                  // (dqkv / its shadow / the column partials: the layer above's q|k|v weight gradient)
-        if (int e = launch_attention_bwd(pf, t->x16_attn ? nullptr : l.qkv, flen, c16 ? nullptr : l.ctx, c16 ? nullptr : dctx, q16 ? nullptr : t->g3h, t->dvec, B, T, H, c.num_heads, tr,
-                                         s, s16q, t->x16_attn ? l.qkv16 : nullptr, dctx16, q16 ? t->attn_colpart : nullptr, c16 ? l.ctx16 : nullptr))
-            return e;
-        if (!side_on)
-            if (int e = out_weight_grad(s, t->red_ws)) return e;
-        if (int e = side(3, [&](hipStream_t st, float* rws) { return qkv_weight_grad(b, m->hs[i], hs16_i, q16, st, rws); })) return e;
-        // dx = dqkv Wqkv^T + dt1 (residual)
-        if (int e = gemm_dx(q16 ? nullptr : t->g3h, s16q, 3 * H, l.WqkvT, m->qkv_w[i], dh, H, dt1, (int)BT, H, 3 * H, s)) return e;
-        if (int e = fold.flush(s)) return e;                 // (the layer's deferred folds: its gradients are final behind this launch)
-        if (int e = bucket_done(c.num_layers - i)) return e;
-    }
+// ---- encoder input, positional conv, spec-augment: x.dh = d loss / d hs[0] comes in, *dhd = d loss / d (dropped projection) goes out ----
+static int bwd_encoder_input(BwdCtx& x, float** dhd) {
+    w2v2_model* m = x.m;
+    TrainState* t = x.t;
+    const w2v2_config& c = m->cfg;
+    Profiler* pf = m->prof;
+    const int B = x.B, T = x.T, H = x.H;
+    const int64_t BT = x.BT;
+    hipStream_t s = x.s;
+    float *dh = x.dh, *tmp = x.tmp, *tmp2 = x.tmp2, *tmp3 = x.tmp3;
     // (the scratch the layers' gradients flowed through is reused from here on, and the last weight gradient below shares the slabs)
     for (int k = 0; k < 4; ++k)
-        if (int e = side_wait(k)) return e;
-    // ---- encoder input: postnorm hs[0] = dropout(LN(posout));  prenorm hs0 = dropout(posout) ----
+        if (int e = x.side_wait(k)) return e;
+    // postnorm hs[0] = dropout(LN(posout));  prenorm hs0 = dropout(posout)
     float* dpos = tmp2;
-    if (prenorm) {
-        if (int e = launch_dropout_bwd(nullptr, dh, dpos, BT * H, 0, p, seed, DS_ENCODER_IN, s)) return e;
+    if (x.plan.prenorm) {
+        if (int e = launch_dropout_bwd(nullptr, dh, dpos, BT * H, 0, x.p, x.seed, DS_ENCODER_IN, s)) return e;
     } else {
-        if (int e = launch_dropout_bwd(nullptr, dh, tmp, BT * H, 0, p, seed, DS_ENCODER_IN, s)) return e;
-        float* dg = G("encoder/layer_norm/gamma");
-        float* db = G("encoder/layer_norm/beta");
+        if (int e = launch_dropout_bwd(nullptr, dh, tmp, BT * H, 0, x.p, x.seed, DS_ENCODER_IN, s)) return e;
+        float* dg = x.G("encoder/layer_norm/gamma");
+        float* db = x.G("encoder/layer_norm/beta");
         if (int e = launch_ln_bwd(m->posout, m->P("encoder/layer_norm/gamma"), tmp, dpos, dg ? dg : t->dummy, db ? db : t->dummy + H, BT, H,
-                                  eps, t->red_ws, s))
+                                  x.eps, t->red_ws, s))
             return e;
     }
     // ---- positional conv: posout = xz + GELU(c),  c = conv(xz; W_eff) + bias ----
     const int K = c.num_conv_pos_embeddings, Gr = c.num_conv_pos_embedding_groups, cg = H / Gr;
     float* dc = tmp;
-    if (int e = launch_dropout_bwd(t->pos_c, dpos, dc, BT * H, act_ew, 0.f, 0, 0, s)) return e;       // dc = dpos * GELU'(c)
-    if (float* gb = G("encoder/pos_conv_embed/conv/bias"))
+    if (int e = launch_dropout_bwd(t->pos_c, dpos, dc, BT * H, x.plan.act_ew, 0.f, 0, 0, s)) return e;       // dc = dpos * GELU'(c)
+    if (float* gb = x.G("encoder/pos_conv_embed/conv/bias"))
         if (int e = launch_colsum(dc, gb, BT, H, t->red_ws, 0, s)) return e;
     const float* enc_x = t->have_spec ? t->hm : t->hd;
     const float* xz = enc_x;
-    if (flen) {
-        if (int e = launch_mask_rows(enc_x, flen, tmp3, B, T, H, s)) return e;
+    if (x.flen) {
+        if (int e = launch_mask_rows(enc_x, x.flen, tmp3, B, T, H, s)) return e;
         xz = tmp3;
     }
-    float* gv = G("encoder/pos_conv_embed/conv/weight_v");
-    float* gg = G("encoder/pos_conv_embed/conv/weight_g");
+    float* gv = x.G("encoder/pos_conv_embed/conv/weight_v");
+    float* gg = x.G("encoder/pos_conv_embed/conv/weight_g");
     if (gv || gg) {
         if (w2v2_pos_conv_bf16_ok(m) && B <= 64) {
-            // precision mode 1: batched transposed-A GEMM on the bf16 pipe (one (K cg, og) slab per sample and group, summed after);
+            // mode bf16: batched transposed-A GEMM on the bf16 pipe (one (K cg, og) slab per sample and group, summed after);
             // the frames are padded to a multiple of 64 with zero rows of dc (T = 1499 at 480000 samples)
             const int Tk = (T + 63) / 64 * 64;
             if (!t->pos_pack32) {
@@ -1367,36 +1290,165 @@ int w2v2_train_backward(w2v2_model* m, const float* dlogits, void* stream) {
         return e;
     }
     if (int e = launch_axpby(dxz, dpos, dxz, BT * H, 1.f, 1.f, s)) return e;
-    if (flen)
-        if (int e = launch_mask_rows(dxz, flen, dxz, B, T, H, s)) return e;
+    if (x.flen)
+        if (int e = launch_mask_rows(dxz, x.flen, dxz, B, T, H, s)) return e;
     // ---- spec-augment ----
-    float* dhd = dxz;
+    *dhd = dxz;
     if (t->have_spec) {
         if (int e = launch_spec_aug_bwd(dxz, t->spec_mask, tmp, tmp2, BT, H, s)) return e;
-        if (float* ge = G("masked_spec_embed"))
+        if (float* ge = x.G("masked_spec_embed"))
             if (int e = launch_colsum(tmp2, ge, BT, H, t->red_ws, 0, s)) return e;
-        dhd = tmp;
+        *dhd = tmp;
     }
-    // ---- feature projection: hd = dropout(ln512 Wp + bp),  ln512 = LN(conv_out) ----
-    float* dproj = tmp3;
-    if (int e = launch_dropout_bwd(nullptr, dhd, dproj, BT * H, 0, p, seed, DS_FEATURE_PROJECTION, s)) return e;
+    return W2V2_OK;
+}
+
+// ---- feature projection: hd = dropout(ln512 Wp + bp),  ln512 = LN(conv_out) ----
+static int bwd_projection(BwdCtx& x, const float* dhd) {
+    w2v2_model* m = x.m;
+    TrainState* t = x.t;
+    const w2v2_config& c = m->cfg;
+    const int H = x.H;
+    const int64_t BT = x.BT;
+    hipStream_t s = x.s;
+    float* dproj = x.tmp3;
+    if (int e = launch_dropout_bwd(nullptr, dhd, dproj, BT * H, 0, x.p, x.seed, DS_FEATURE_PROJECTION, s)) return e;
     const int C = c.filter_sizes[c.num_conv_layers - 1];
-    if (int e = weight_grad(m, m->ln512, dproj, (int)BT, C, H, G("feature_projection/projection/kernel"),
-                            G("feature_projection/projection/bias"), s))
+    if (int e = weight_grad(m, m->ln512, dproj, (int)BT, C, H, x.G("feature_projection/projection/kernel"),
+                            x.G("feature_projection/projection/bias"), s))
         return e;
-    float* dgp = G("feature_projection/layer_norm/gamma");
-    float* dbp = G("feature_projection/layer_norm/beta");
+    float* dgp = x.G("feature_projection/layer_norm/gamma");
+    float* dbp = x.G("feature_projection/layer_norm/beta");
     if (dgp || dbp) {
-        float* dln = tmp2;       // (BT, C) fits a (BT, H) buffer when C <= H; otherwise use the FFN scratch
+        float* dln = x.tmp2;       // (BT, C) fits a (BT, H) buffer when C <= H; otherwise use the FFN scratch
         if (C > H) dln = t->gf;
-        if (int e = gemm_dx(dproj, nullptr, H, t->WpT, m->P("feature_projection/projection/kernel"), dln, C, nullptr, (int)BT, C, H, s)) return e;
-        float* dxc = C > H ? t->g3h : tmp;    // gradient w.r.t. the frozen conv output: computed and dropped
+        if (int e = x.gemm_dx(dproj, nullptr, H, t->WpT, m->P("feature_projection/projection/kernel"), dln, C, nullptr, (int)BT, C, H, s)) return e;
+        float* dxc = C > H ? t->g3h : x.tmp;    // gradient w.r.t. the frozen conv output: computed and dropped
         if (int e = launch_ln_bwd(m->conv[c.num_conv_layers - 1], m->P("feature_projection/layer_norm/gamma"), dln, dxc,
-                                  dgp ? dgp : t->dummy, dbp ? dbp : t->dummy + C, BT, C, eps, t->red_ws, s))
+                                  dgp ? dgp : t->dummy, dbp ? dbp : t->dummy + C, BT, C, x.eps, t->red_ws, s))
             return e;
     }
-    return bucket_done(nbuckets - 1);
+    return W2V2_OK;
 }
+
+static const char* precision_name(int p) {
+    static const char* const names[] = {"fp32", "bf16", "bf16x3", "f16x2"};
+    return p >= 0 && p < 4 ? names[p] : "?";
+}
+
+extern "C" {
+
+int w2v2_train_backward(w2v2_model* m, const float* dlogits, void* stream) {
+    W2V2_REQUIRE(m && dlogits, "train_backward: null argument");
+    TrainState* t = m->train;
+    if (!t || !t->forward_done) {
+        set_error("train_backward: no training forward to differentiate");
+        return W2V2_ESTATE;
+    }
+    const w2v2_config& c = m->cfg;
+    const TrainPlan& plan = t->plan;
+    // The saved activations are in the forms, and the saved lse in the domain, of the mode the forward ran in (TrainPlan): a backward in
+    // another mode would read buffers that were never written, or a log2-domain lse as a natural one.  Refused before the first launch.
+    if (m->precision != plan.precision || m->opt_shadows != plan.opt_shadows) {
+        set_error("train_backward: the forward ran with precision %s, bf16_shadows %s; the model is now set to precision %s, bf16_shadows %s -- "
+                  "restore the settings or run the forward again",
+                  precision_name(plan.precision), plan.opt_shadows ? "on" : "off", precision_name(m->precision), m->opt_shadows ? "on" : "off");
+        return W2V2_ESTATE;
+    }
+    const bool shb = plan.sh && m->w16_valid;
+    // (a variable set between the forward and the backward invalidates the bf16 weight shadows the bf16-only activations depend on)
+    W2V2_REQUIRE(!plan.ffn16_only || shb, "train_backward: a variable changed since the forward, which kept activations as bf16 only; run the forward again");
+    for (size_t i = 0; i < m->params.size(); ++i)
+        if (t->trainable[i] && m->params[i].name.compare(0, 18, "feature_extractor/") == 0) {
+            set_error("train_backward: `%s` is trainable, but the conv feature extractor has no backward "
+                      "(the reference freezes it, main.py:234-237); call freeze_feature_extractor()", m->params[i].name.c_str());
+            return W2V2_ESTATE;
+        }
+    PrecisionScope precision(plan.precision);
+    StepProfScope step_prof(m->prof);          // the training-only kernels' launchers find the profiler here (common.h)
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int H = c.hidden_size, F = c.intermediate_size;
+    const int64_t BT = plan.BT;
+    BwdCtx x{m, t, plan, s, plan.B, plan.T, H, F, BT, c.layer_norm_eps, t->p, t->seed, t->have_mask ? m->frame_len : nullptr, shb,
+             shb ? t->dy16_h : nullptr, shb ? t->dy16_f : nullptr, (shb && attention_bf16_supported(H / c.num_heads)) ? t->dy16_3h : nullptr,
+             t->gh[0], t->gh[1], t->gh[2], t->gh[3]};
+    if (shb && BT % 64 != 0) {
+        // Ragged row count: the weight-gradient GEMMs read the missing rows of their last K tile from the zero row behind each dY
+        // shadow.  Re-assert the invariant on THIS stream every backward (three rows, a few KB): nothing may have padded into them.
+        W2V2_HIP_CHECK(hipMemsetAsync(t->dy16_h + BT * H, 0, (size_t)H * 2, s));
+        W2V2_HIP_CHECK(hipMemsetAsync(t->dy16_f + BT * F, 0, (size_t)F * 2, s));
+        W2V2_HIP_CHECK(hipMemsetAsync(t->dy16_3h + BT * 3 * H, 0, (size_t)3 * H * 2, s));
+    }
+    // Gradient buffer at the start of a backward.  Rounds 1-5 zeroed all of it every step (360 MB / 1.25 GB: the runtime's fill kernels,
+    // 0.23 / 0.8 ms per step and the only framework kernels left in it).  Every producer below STORES its gradient (no accumulation
+    // into the buffer: folds, column sums and GEMM epilogues overwrite), so a slot needs zeros only if nothing will write it this time:
+    //   * slots of variables that are not trainable, and the 16-byte padding between slots: zero since allocation, never written;
+    //   * masked_spec_embed when this step has no spec-augment mask;
+    //   * everything, conservatively, when the trainable set changed since the last backward (a slot that was written before keeps
+    //     its last gradient) or when stochastic depth dropped a layer (its branch's gradients are not computed: zeros).
+    // tests/test_train_gpu.py poisons the buffer with NaN before its gradient checks: a trainable slot nobody wrote shows up there.
+    {
+        uint64_t sig = 1469598103934665603ull;
+        for (size_t i = 0; i < t->trainable.size(); ++i) sig = (sig ^ (uint64_t)(t->trainable[i] ? 0x9E : 0x3C)) * 1099511628211ull;
+        bool dropped = false;
+        for (int i = 0; i < c.num_layers; ++i) dropped = dropped || t->layers[i].keep == 0.f;
+        if (sig != t->trainable_sig || dropped || t->grads_need_clear) {
+            W2V2_HIP_CHECK(hipMemsetAsync(t->grads, 0, (size_t)t->gtotal * 4, s));
+            t->trainable_sig = sig;
+            t->grads_need_clear = dropped;        // (the step after a dropped layer starts from zeros as well: its slots hold nothing new)
+        } else if (!t->have_spec) {
+            auto it = m->index.find("masked_spec_embed");
+            if (it != m->index.end() && t->trainable[it->second])
+                W2V2_HIP_CHECK(hipMemsetAsync(t->grads + t->goff[it->second], 0, (size_t)m->params[it->second].numel * 4, s));
+        }
+    }
+    if (int e = refresh_transposes(m, s)) return e;
+    const int nbuckets = c.num_layers + 2;
+    while ((int)t->bucket_ev.size() < nbuckets) {
+        hipEvent_t ev;
+        W2V2_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        t->bucket_ev.push_back(ev);
+    }
+    // ---- weight-gradient side stream (TrainState::wg_stream): the bf16 shadow path only -- there every dY a weight gradient reads is a
+    // shadow with a known next writer (the wait points of the stages); the other paths keep one stream.
+    // (tools-only build: W2V2_WGRAD_STREAM = 0 / 1 overrides the option for A/B runs)
+    const int wg_knob = tune_int("W2V2_WGRAD_STREAM", -1);
+    x.side_on = shb && plan.attn16 && t->attn_colpart && (wg_knob < 0 ? m->opt_wgrad_stream : wg_knob != 0);
+    if (x.side_on && !t->wg_stream) {
+        int lo = 0, hi = 0;
+        W2V2_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));           // (lo = the numerically largest = least urgent)
+        W2V2_HIP_CHECK(hipStreamCreateWithPriority(&t->wg_stream, hipStreamNonBlocking, lo));
+        W2V2_HIP_CHECK(hipEventCreateWithFlags(&t->wg_fork, hipEventDisableTiming));
+        W2V2_HIP_CHECK(hipEventCreateWithFlags(&t->wg_main, hipEventDisableTiming));
+        for (int k = 0; k < 4; ++k) W2V2_HIP_CHECK(hipEventCreateWithFlags(&t->wg_join[k], hipEventDisableTiming));
+    }
+    // Deferred folds of the encoder layers (W2V2_OPT_DEFER_FOLDS).  The side stream keeps the folds behind their GEMMs: its weight
+    // gradients run ahead of / behind the main stream's position.
+    // (tools-only build: W2V2_DEFER_FOLDS = 0 none, 1 the column-sum folds only -- slab sums behind their GEMMs --, 2 everything.
+    //  One box, arms interleaved, profiles/r05_ab_defer_folds.txt: base step 33.80 / 33.55 / 33.50 ms, large-robust 98.38 / 97.94 / 97.74)
+    x.defer_mode = (!x.side_on && m->opt_defer_folds) ? tune_int("W2V2_DEFER_FOLDS", 2) : 0;
+    if (x.defer_mode != 0) x.fb = &x.fold;
+    if (int e = ensure_site_scratch(m, x.side_on, x.defer_mode != 0, x.defer_mode == 2)) return e;
+    x.ln2_ws = x.fb ? t->site_ws[0] : t->red_ws;
+    x.ln1_ws = x.fb ? t->site_ws[2] : t->red_ws;
+    // does anything below the head train?
+    bool below_head = false;
+    for (size_t i = 0; i < m->params.size(); ++i)
+        if (t->trainable[i] && m->params[i].name.compare(0, 8, "lm_head/") != 0) below_head = true;
+
+    if (int e = bwd_head(x, dlogits, below_head)) return e;
+    if (!below_head) {                          // stage 1 of the reference: only lm_head trains (main.py:210)
+        for (int k = 1; k < nbuckets; ++k)
+            if (int e = x.bucket_done(k)) return e;
+        return W2V2_OK;
+    }
+    if (int e = bwd_layers(x)) return e;
+    float* dhd = nullptr;
+    if (int e = bwd_encoder_input(x, &dhd)) return e;
+    if (int e = bwd_projection(x, dhd)) return e;
+    return x.bucket_done(nbuckets - 1);
+}
+
 
 /* Gradient buckets: slices of the flat buffer in the order the backward completes them.  Data-parallel callers enqueue
  * one all-reduce per bucket on a communication stream that waits (w2v2_train_bucket_wait) for that bucket only, so the
@@ -1407,8 +1459,7 @@ int w2v2_train_storage(const w2v2_model* m, int32_t* mask, int64_t* workspace_by
     *mask = 0;
     *workspace_bytes = t ? t->alloc_bytes : 0;
     if (t && t->B > 0)
-        *mask = (t->x16_attn ? W2V2_TRAIN_BF16_QKV : 0) | (t->ctx16_only ? W2V2_TRAIN_BF16_CTX : 0) | (t->ffn16_only ? W2V2_TRAIN_BF16_FFN : 0) |
-                (t->u16_only ? W2V2_TRAIN_BF16_U : 0) | (t->ln16_only ? W2V2_TRAIN_BF16_LN : 0);
+        *mask = storage_mask(t->plan);
     return W2V2_OK;
 }
 
@@ -1542,70 +1593,6 @@ int w2v2_adam_step(w2v2_model* m, float lr, float beta1, float beta2, float eps,
     t->transposes_fresh = false;
     m->finalized = false;
     return w2v2_finalize(m, stream);     // re-derive the effective positional kernel and the packed q|k|v
-}
-
-int64_t w2v2_ln_bwd_ws_floats(int64_t rows, int32_t C) { return ln_bwd_ws_floats(rows, C); }
-int w2v2_op_layer_norm_bwd(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma,
-                           float* dbeta, int64_t rows, int32_t C, float eps, float* ws, void* stream) {
-    return launch_ln_bwd(x, gamma, dy, dx, dgamma, dbeta, rows, C, eps, ws, reinterpret_cast<hipStream_t>(stream));
-}
-int w2v2_op_attention_train(const float* qkv, const int32_t* frame_len, float* ctx, float* lse, int32_t B, int32_t T,
-                            int32_t H, int32_t heads, float p, uint64_t seed, uint32_t stream_id, void* stream) {
-    AttnTrain tr{p, seed, stream_id, lse};
-    return launch_attention_train(nullptr, qkv, frame_len, ctx, B, T, H, heads, tr, reinterpret_cast<hipStream_t>(stream));
-}
-int w2v2_op_attention_bwd(const float* qkv, const int32_t* frame_len, const float* ctx, const float* lse,
-                          const float* dctx, float* dqkv, float* dvec_ws, int32_t B, int32_t T, int32_t H,
-                          int32_t heads, float p, uint64_t seed, uint32_t stream_id, void* stream) {
-    AttnTrain tr{p, seed, stream_id, const_cast<float*>(lse)};
-    return launch_attention_bwd(nullptr, qkv, frame_len, ctx, dctx, dqkv, dvec_ws, B, T, H, heads, tr,
-                                reinterpret_cast<hipStream_t>(stream));
-}
-int w2v2_op_layer_norm_dropout(const float* x, const float* residual, float* t1, float* y, uint16_t* y16, const float* gamma, const float* beta,
-                               int64_t rows, int32_t C, float eps, float p, uint64_t seed, uint32_t stream_id, void* stream) {
-    return launch_layer_norm_drop(nullptr, x, residual, t1, y, y16, gamma, beta, rows, C, eps, p, seed, stream_id, reinterpret_cast<hipStream_t>(stream));
-}
-int w2v2_op_dropout(const float* x, const float* residual, float* y, int64_t n, int32_t act, float p,
-                    uint64_t seed, uint32_t stream_id, void* stream) {
-    return launch_dropout_fwd(x, residual, y, n, act, p, seed, stream_id, reinterpret_cast<hipStream_t>(stream));
-}
-int w2v2_op_pos_conv_ex(const float* x, const float* wg, const float* bias, const int32_t* frame_len, float* y, float* pre_act,
-                        int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, int32_t act, int32_t pad_left, int32_t add_residual,
-                        void* stream) {
-    return launch_pos_conv_ex(nullptr, x, wg, bias, frame_len, y, pre_act, B, T, H, K, groups, act, pad_left, add_residual,
-                              reinterpret_cast<hipStream_t>(stream));
-}
-int64_t w2v2_op_pos_conv_bf16_pack_elems(int32_t B, int32_t T, int32_t H, int32_t K) { return pos_conv_bf16_pack_elems(B, T, H, K); }
-int w2v2_op_pos_conv_weight_shadow(const float* wg, uint16_t* w16, int32_t K, int32_t cg, int32_t groups, void* stream) {
-    return launch_pos_conv_weight_shadow(wg, w16, K, cg, groups, reinterpret_cast<hipStream_t>(stream));
-}
-int w2v2_op_pos_conv_bf16(const float* x, const uint16_t* w16, const float* bias, const int32_t* frame_len, float* y, float* pre_act,
-                          uint16_t* pack16, float* xz_ws, int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, int32_t act,
-                          int32_t pad_left, int32_t add_residual, void* stream) {
-    return launch_pos_conv_bf16(nullptr, x, w16, bias, frame_len, y, pre_act, pack16, xz_ws, B, T, H, K, groups, act, pad_left, add_residual,
-                                reinterpret_cast<hipStream_t>(stream));
-}
-int w2v2_op_pos_conv_flip_regroup(const float* wg, float* wg_t, int32_t K, int32_t cg, int32_t groups, void* stream) {
-    return launch_pos_conv_flip_regroup(wg, wg_t, K, cg, groups, reinterpret_cast<hipStream_t>(stream));
-}
-int w2v2_op_pos_conv_dw(const float* xz, const float* dc, float* dwg, int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups,
-                        void* stream) {
-    return launch_pos_conv_dw(nullptr, xz, dc, dwg, nullptr, B, T, H, K, groups, reinterpret_cast<hipStream_t>(stream));
-}
-int w2v2_pos_conv_dw_bf16_ws_floats(int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, int64_t* sizes4, int32_t* slabs_S) {
-    W2V2_REQUIRE(sizes4 && B > 0 && T > 0 && K > 0 && groups > 0 && H > 0 && H % groups == 0, "pos_conv_dw_bf16_ws_floats: bad argument");
-    int S = 0;
-    pos_conv_dw_bf16_ws_floats(B, T, H, K, groups, sizes4, &S);
-    if (slabs_S) *slabs_S = S;
-    return W2V2_OK;
-}
-int w2v2_op_pos_conv_dw_bf16(const float* xz, const float* dc, float* dwg, float* pack32, float* slabs, float* red_ws, float* dc_pad,
-                             int32_t B, int32_t T, int32_t H, int32_t K, int32_t groups, void* stream) {
-    return launch_pos_conv_dw_bf16(nullptr, xz, dc, dwg, pack32, slabs, red_ws, B, T, H, K, groups, reinterpret_cast<hipStream_t>(stream), dc_pad);
-}
-int w2v2_op_weight_norm_bwd(const float* weight_v, const float* weight_g, const float* dwg, float* dweight_v, float* dweight_g, int32_t K,
-                            int32_t cg, int32_t H, int32_t groups, void* stream) {
-    return launch_weight_norm_bwd(weight_v, weight_g, dwg, dweight_v, dweight_g, K, cg, H, groups, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

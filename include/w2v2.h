@@ -554,6 +554,7 @@ int w2v2_resample(const float* in_dev, int32_t n, const int64_t* in0_host, const
  *   call (tensorflow_addons.py:381).  Saves what the backward needs.
  * w2v2_train_backward: given d loss / d logits (B, T, V) fills the flat gradient buffer (zero for
  *   frozen variables).  w2v2_grad_buffer exposes that buffer for the data-parallel all-reduce (SUM).
+ *   The precision mode and W2V2_OPT_BF16_SHADOWS must be what the forward ran with: W2V2_ESTATE otherwise.
  * w2v2_adam_step: Keras Adam, p -= lr sqrt(1-b2^t)/(1-b1^t) m / (sqrt(v) + eps), then re-derives the
  *   tensors w2v2_finalize builds. */
 int w2v2_set_trainable(w2v2_model* m, const char* name_prefix, int trainable);

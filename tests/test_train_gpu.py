@@ -579,6 +579,54 @@ def test_bf16_training_shadows_do_not_change_results(env):
         assert np.abs(g - g1).max() <= 2e-5 * max(np.abs(g).max(), 1e-6), (n, float(np.abs(g - g1).max()), float(np.abs(g).max()))
 
 
+def test_backward_refuses_a_precision_change_since_the_forward(env):
+    """The saved activations are in the forms, and the attention's saved lse in the domain (log2 for the bf16 kernels, natural for
+    fp32), of the mode the forward ran in.  A backward after set_precision or a toggled "bf16_shadows" would read them wrongly, so
+    it is refused with both settings named; with the setting restored, a fresh forward + backward gives the gradient buffer of a
+    model that was never toggled, bit for bit."""
+    import wav2vec2
+    _, torch, dev = env
+    B, L = 2, 4000
+    x = V.hash_normal("train/wave_plan", B * L, 8).reshape(B, L)
+
+    def step(m, tr):
+        logits = tr.forward(x, step_seed=7)
+        tr.backward(torch.sin(logits))
+        g = tr.grad_buffer().clone()
+        torch.cuda.synchronize()
+        return g
+
+    def trainer():
+        m, cfg, w = build("tiny_base", L)
+        return m, wav2vec2.Trainer(m, None, dropout=0.1, apply_spec_augment=False, seed=1)
+
+    ref = {}
+    for precision in ("fp32", "bf16"):
+        m, tr = trainer()
+        m.set_precision(precision)
+        ref[precision] = step(m, tr)
+        assert float(ref[precision].abs().max()) > 0
+    m, tr = trainer()
+    for first, then in (("fp32", "bf16"), ("bf16", "fp32")):
+        m.set_precision(first)
+        logits = tr.forward(x, step_seed=7)
+        m.set_precision(then)
+        with pytest.raises(RuntimeError) as err:
+            tr.backward(torch.sin(logits))
+        assert f"precision {first}" in str(err.value) and f"precision {then}" in str(err.value), str(err.value)
+        m.set_precision(first)
+        assert torch.equal(step(m, tr), ref[first])
+    m.set_precision("bf16")
+    logits = tr.forward(x, step_seed=7)
+    m.set_option("bf16_shadows", False)
+    with pytest.raises(RuntimeError) as err:
+        tr.backward(torch.sin(logits))
+    assert "bf16_shadows on" in str(err.value) and "bf16_shadows off" in str(err.value), str(err.value)
+    m.set_option("bf16_shadows", True)
+    assert torch.equal(step(m, tr), ref["bf16"])
+    m.set_precision("fp32")
+
+
 def test_stage1_only_lm_head_trains(env):
     import wav2vec2
     g = H.golden("tiny_base")
@@ -710,6 +758,46 @@ def test_weight_gradient_slabs_with_awkward_row_counts(env, precision):
         grads_close(tr, ref_grads, rtol=5e-4)
     else:
         grads_close(tr, ref_grads, rtol=8e-2)
+    # Deferred folds (each site's own slab scratch) at B T = 32 x 64 + 5 = 2053 rows: one output tile, so the FFN and out-projection
+    # weight gradients take S = 32 slabs plus the leftover-row slab -- 33, with the fold's scratch a 34th: the most a site ever holds.
+    # Bit for bit the gradients of the run with "defer_folds" off (shared scratch).
+    _, torch, dev = env
+    L2, Hh, F = 400 + 320 * 2052, cfg.hidden_size, cfg.intermediate_size
+    assert cfg.num_frames(L2) == 2053
+    kq, blocks = (32, 2048) if precision == "fp32" else (64, 512)
+    for Kin, Nout in ((F, Hh), (Hh, F), (Hh, Hh)):
+        assert _weight_grad_slabs(2053, Kin, Nout, kq, blocks, 33 * max(F * Hh, 3 * Hh * Hh)) == 33
+    x2 = V.hash_normal("train/wave_2053", L2, 8).reshape(1, L2)
+    res = []
+    for flag in (False, True):
+        m.set_option("defer_folds", flag)
+        logits = tr.forward(x2, step_seed=5)
+        tr.backward(torch.sin(logits))
+        res.append(tr.grad_buffer().clone())
+        torch.cuda.synchronize()
+    assert float(res[0].abs().max()) > 0 and bool(torch.isfinite(res[0]).all())
+    assert torch.equal(res[0], res[1]), int((res[0] != res[1]).sum())
+
+
+def _weight_grad_slabs(M, Kin, Nout, kq, max_blocks, shared_slab_floats):
+    """Host mirror of weight_grad's slab rule (csrc/w2v2_train.hip) where the bf16 transposing-read form does not apply (fp32, or dims
+    that are not whole 128-tiles): S equal slabs of whole kq-row units, S a divisor of the unit count, plus one slab of leftover rows."""
+    tiles = -(-Kin // 128) * -(-Nout // 128)
+    cap = 32
+    while cap > 1 and (tiles * cap > max_blocks or (cap + 2) * Kin * Nout > shared_slab_floats):
+        cap -= 1
+    units0 = M // kq
+    S, units = (1 if units0 else 0), units0
+    for drop in range(16):
+        u = units0 - drop
+        if u <= 0:
+            break
+        d = next((cand for cand in range(cap, 1, -1) if u % cand == 0), 1)
+        if d > S:
+            S, units = d, u
+        if 2 * d >= cap:
+            break
+    return S + (1 if M - units * kq else 0)
 
 
 def test_bf16x3_training_matches_fp32_path(env):

@@ -11,6 +11,9 @@ Runs a fixed matrix and prints one JSON object per entry:
   packed      predict_packed of three utterances of unequal length (cuts of the fixture's first row) in fp32 / bf16x3 / f16x2,
               same options
   train       one training forward + backward in fp32 / bf16 / bf16x3 with dropout 0 and 0.1, fixed seed, spec-augment off
+  train_plan  tiny_base, tiny_robust and base dims at 3 x 24080 samples (B T = 225, ragged): spec-augment on, a dropped layer,
+              bf16_shadows off, defer_folds off / on, wgrad_stream on, only lm_head / only layer 0 trainable; each entry also holds
+              Trainer.activation_storage() (`storage`, `storage_bytes`)
 
 Each object holds the sha256 of the output bytes (`out`; train entries: the logits, and `grads` = the flat gradient buffer), the
 per-family kernel-launch counts (`kernels`, profile_read() after a profile_reset()) and the sorted taps for which activation()
@@ -73,10 +76,74 @@ def build(name):
     return m, cfg, wave, mask
 
 
+def train_plan_cases(cfg):
+    """(precisions, options, keyword) of the training-step matrix: every switch the backward's decisions depend on."""
+    n = cfg.num_layers
+    drop = np.ones(n, dtype=np.float32)
+    drop[max(0, n - 2)] = 0.0                                   # one dropped layer that is not the last
+    all3, two = ("fp32", "bf16", "bf16x3"), ("fp32", "bf16")
+    return [(all3, {}, dict(spec=True)),
+            (all3, {}, dict(sd_keep=drop)),
+            (("bf16",), dict(bf16_shadows=False), {}),
+            (two, dict(defer_folds=False), {}),
+            (two, dict(defer_folds=True), {}),
+            (("bf16",), dict(wgrad_stream=True), {}),
+            (two, {}, dict(trainable="lm_head/")),              # stage 1
+            (two, {}, dict(trainable="encoder/layers/0/"))]
+
+
+def train_plan(emit):
+    """Training forward + backward of tiny_base, tiny_robust (postnorm + group norm, prenorm + layer norm + mask) and base dims at a
+    ragged row count (3 x 24080 samples: B T = 225, H % 128 == 0) over train_plan_cases; each entry also records activation_storage()."""
+    import helpers as H
+    import torch
+    import wav2vec2
+    from wav2vec2 import variables as V
+    from wav2vec2.spec_augment import compute_mask_indices
+    from wav2vec2.training import Trainer
+    for name in ("tiny_base", "tiny_robust", "base_sample_padded"):
+        if name == "base_sample_padded":
+            cfg, mask = H.case_config(name), None
+            wave = V.hash_normal("fingerprint/train_plan", 3 * 24080, 8).reshape(3, 24080)
+            m = wav2vec2.Wav2Vec2ForCTC(cfg, input_shape=wave.shape)
+            m.set_weights(H.case_weights(name))
+        else:
+            m, cfg, wave, mask = build(name)
+        defaults = {k: m.get_option(k) for k in ("bf16_shadows", "defer_folds", "wgrad_stream")}
+        T = cfg.num_frames(wave.shape[1])
+        spec = compute_mask_indices((wave.shape[0], T), 0.05, 10, rng=np.random.RandomState(4))
+        for precisions, opts, kw in train_plan_cases(cfg):
+            for precision in precisions:
+                m.set_precision(precision)
+                for k, v in opts.items():
+                    m.set_option(k, v)
+                if "trainable" in kw:
+                    m.set_trainable("", False)
+                    m.set_trainable(kw["trainable"], True)
+                else:
+                    m.set_trainable("", True)
+                    m.freeze_feature_extractor()
+                tr = Trainer(m, None, seed=0, dropout=0.1, apply_spec_augment=False)
+                m.profile_reset()
+                sd_keep = kw.get("sd_keep", np.ones(cfg.num_layers, dtype=np.float32))
+                logits = tr.forward(wave, attention_mask=mask, spec_mask=spec if kw.get("spec") else None, sd_keep=sd_keep, step_seed=1234)
+                tr.backward(torch.sin(logits))
+                names, nbytes = tr.activation_storage()
+                tag = dict(opts, **{k: (v if isinstance(v, (str, bool)) else [float(x) for x in v]) for k, v in kw.items()})
+                emit(dict(fixture=name, form="train_plan", precision=precision, **tag), m, [], out=sha(logits), grads=sha(tr.grad_buffer()),
+                     storage=sorted(names), storage_bytes=nbytes)
+                for k, v in defaults.items():
+                    m.set_option(k, v)
+        del m
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fixtures", default=",".join(FIXTURES))
     ap.add_argument("--skip-train", action="store_true")
+    ap.add_argument("--skip-forward", action="store_true", help="only the train entries of --fixtures (and the train_plan matrix)")
+    ap.add_argument("--skip-train-plan", action="store_true")
     args = ap.parse_args()
 
     import torch
@@ -102,7 +169,7 @@ def main():
                [f"layer{i}" for i in range(cfg.num_layers)] + ["encoder_out"]
         L = wave.shape[1]
         utterances = [wave[0, :L], wave[0, :(2 * L) // 3], wave[0, :L // 2 + 37]]
-        for precision in ("fp32", "bf16", "bf16x3", "f16x2"):
+        for precision in () if args.skip_forward else ("fp32", "bf16", "bf16x3", "f16x2"):
             m.set_precision(precision)
             for opts in option_sets(precision):
                 for k, v in opts.items():
@@ -130,6 +197,8 @@ def main():
                      grads=sha(tr.grad_buffer()))
         del m
         torch.cuda.empty_cache()
+    if not (args.skip_train or args.skip_train_plan):
+        train_plan(emit)
 
 
 if __name__ == "__main__":
