@@ -149,9 +149,25 @@ struct AdamChunk {
     float* p;
     int64_t goff;
     int n;
+    int decay;      // adamw_multi: the chunk's variable takes the decoupled weight decay (w2v2_set_decay_flags); 0 by default
 };
 int launch_adam_multi(const AdamChunk* chunks_dev, int nchunks, const float* grads, float* m, float* v, float lr_t, float b1,
                       float b2, float eps, hipStream_t s);
+// ---- optimizer: accumulation, global-norm clipping, AdamW, skipped steps ----
+// What w2v2_grad_norm leaves in device memory for adamw_multi: the host never reads it inside a step (w2v2_optimizer_stats does).
+using OptStats = w2v2_opt_stats;      // (include/w2v2.h: w2v2_op_grad_norm writes the same record)
+constexpr int OPT_CHUNK = 4096;     // elements per chunk of the table (and per block of grad_sumsq)
+// mode 0 store: acc = g; 1 add: acc += g; 2 finish: g += acc -- over the trainable chunks only (acc has the gradient buffer's layout)
+int launch_grad_accumulate(const AdamChunk* chunks_dev, int nchunks, float* grads, float* acc, int mode, hipStream_t s);
+// Global norm of the gradient, two launches: grad_sumsq (one block per chunk -> partial[k] fp64, flag[k] = non-finite seen) and
+// grad_norm_finish (one block folds them and writes *stats).  chunks_dev null: the raw buffer g[0 .. n) cut into OPT_CHUNK-element
+// chunks (nchunks = ceil(n / OPT_CHUNK)); else the chunks' slices of `g` (n unused).  partial: nchunks doubles; flag: nchunks ints.
+int launch_grad_norm(const AdamChunk* chunks_dev, int nchunks, const float* g, int64_t n, double* partial, int32_t* flag,
+                     float max_norm, int skip_nonfinite, OptStats* stats, hipStream_t s);
+// adam_multi's sibling: g' = g * stats->scale; p = p (1 - lr wd [chunk decays]) - lr_t m / (sqrt(v) + eps); nothing is touched when
+// stats->skip.  scale == 1, wd == 0, skip == 0: the bits of launch_adam_multi.
+int launch_adamw_multi(const AdamChunk* chunks_dev, int nchunks, const float* grads, float* m, float* v, const OptStats* stats,
+                       float lr, float weight_decay, float lr_t, float b1, float b2, float eps, hipStream_t s);
 // bf16-stored inputs of the element-wise dropout kernels (precision mode 1 keeps the FFN pre-activation u and the gradient of the
 // FFN hidden activation only as bf16): a16 stands in for x (forward) / u (backward), b16 for dy (backward; it may be the dx16 the
 // call writes -- in place); round_in = the fp32 inputs are rounded to bf16 on the way in (the shadow-free path of the same mode,

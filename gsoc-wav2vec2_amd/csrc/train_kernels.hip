@@ -712,6 +712,187 @@ __global__ void adam_multi_kernel(const AdamChunk* __restrict__ chunks, const fl
     }
 }
 
+// ---- optimizer: accumulation, global-norm clipping, AdamW, skipped steps ----------------------------------------------
+// All four run over the chunk table of adam_multi_kernel (trainable variables only: a frozen slot is never read or written), 16 bytes
+// per lane over a chunk's whole float4s and scalar accesses for its last n % 4 elements.  No float atomics: every sum has one order.
+
+// a chunk's slice is read as float4 when its first element is 16-byte aligned (gradient slots are; a variable's storage almost always)
+__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// inf or NaN: the exponent field is all ones (an integer test: a float compare may be folded away under fast-math assumptions)
+__device__ __forceinline__ int nonfinite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+__global__ void grad_accumulate_kernel(const AdamChunk* __restrict__ chunks, float* __restrict__ grads, float* __restrict__ accum, int mode) {
+    const AdamChunk c = chunks[blockIdx.x];
+    float* __restrict__ g = grads + c.goff;
+    float* __restrict__ a = accum + c.goff;
+    const int n4 = c.n >> 2;           // (both buffers are 16-byte aligned at every slot)
+    for (int i = threadIdx.x; i < n4; i += EW_THREADS) {
+        const float4 gv = reinterpret_cast<const float4*>(g)[i];
+        if (mode == 0) {
+            reinterpret_cast<float4*>(a)[i] = gv;
+        } else {
+            const float4 av = reinterpret_cast<const float4*>(a)[i];
+            const float4 r = make_float4(av.x + gv.x, av.y + gv.y, av.z + gv.z, av.w + gv.w);
+            reinterpret_cast<float4*>(mode == 1 ? a : g)[i] = r;
+        }
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < c.n; i += EW_THREADS) {
+        if (mode == 0) a[i] = g[i];
+        else (mode == 1 ? a : g)[i] = a[i] + g[i];
+    }
+}
+
+// One block per chunk.  Thread t squares and adds, in fp64 and in index order, the float4s t, t + 256, ... of the chunk and then its share of
+// the scalar tail; the 256 partial sums fold in a fixed LDS tree (the pattern of the normalisation statistics).  fp64: a
+// gradient element of 1e18 squares to 1e36 without overflow, and the sum of 9e7 non-negative terms keeps 1e-15 relative accuracy.
+__global__ void grad_sumsq_kernel(const AdamChunk* __restrict__ chunks, const float* __restrict__ grads, int64_t n_raw,
+                                  double* __restrict__ partial, int32_t* __restrict__ flag) {
+    __shared__ double red[EW_THREADS];
+    int64_t off;
+    int n;
+    if (chunks) {
+        const AdamChunk c = chunks[blockIdx.x];
+        off = c.goff;
+        n = c.n;
+    } else {
+        off = (int64_t)blockIdx.x * OPT_CHUNK;
+        n = (int)(n_raw - off < OPT_CHUNK ? n_raw - off : OPT_CHUNK);
+    }
+    const float* __restrict__ g = grads + off;
+    const int n4 = aligned16(g) ? n >> 2 : 0;
+    double acc = 0.0;
+    int bad = 0;
+    // the chunk's (at most four) float4s of this thread: all loads in flight before the first add; a float4 past the end reads as
+    // zeros, whose squares leave the sum as it is
+    constexpr int VPT = OPT_CHUNK / (4 * EW_THREADS);
+    float4 v[VPT];
+#pragma unroll
+    for (int k = 0; k < VPT; ++k) {
+        const int i = threadIdx.x + k * EW_THREADS;
+        v[k] = i < n4 ? reinterpret_cast<const float4*>(g)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < VPT; ++k) {
+        bad |= nonfinite_bits(v[k].x) | nonfinite_bits(v[k].y) | nonfinite_bits(v[k].z) | nonfinite_bits(v[k].w);
+        acc += (double)v[k].x * (double)v[k].x;
+        acc += (double)v[k].y * (double)v[k].y;
+        acc += (double)v[k].z * (double)v[k].z;
+        acc += (double)v[k].w * (double)v[k].w;
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < n; i += EW_THREADS) {
+        const float v = g[i];
+        bad |= nonfinite_bits(v);
+        acc += (double)v * (double)v;
+    }
+    red[threadIdx.x] = acc;
+    bad = __syncthreads_or(bad);
+    for (int w = EW_THREADS / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = red[0];
+        flag[blockIdx.x] = bad;
+    }
+}
+
+// One block.  Thread t adds partials t, t + 256, ... in that order, then the same LDS tree: one fixed order for a given chunk count.
+__global__ void grad_norm_finish_kernel(const double* __restrict__ partial, const int32_t* __restrict__ flag, int nchunks, float max_norm,
+                                        int skip_nonfinite, OptStats* __restrict__ stats) {
+    __shared__ double red[EW_THREADS];
+    double acc = 0.0;
+    int bad = 0;
+    // eight loads in flight per thread (one block alone on the chip pays every load's latency); added in index order as before,
+    // a partial past the end as +0
+    constexpr int U = 8;
+    for (int base = threadIdx.x; base < nchunks; base += U * EW_THREADS) {
+        double pv[U];
+        int fv[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const int i = base + k * EW_THREADS;
+            pv[k] = i < nchunks ? partial[i] : 0.0;
+            fv[k] = i < nchunks ? flag[i] : 0;
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            acc += pv[k];
+            bad |= fv[k];
+        }
+    }
+    red[threadIdx.x] = acc;
+    bad = __syncthreads_or(bad);
+    for (int w = EW_THREADS / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double sumsq = red[0];
+        const double norm64 = sqrt(sumsq);
+        const float norm = (float)norm64;
+        // torch.nn.utils.clip_grad_norm_: max_norm / (norm + 1e-6), clamped to 1.  A non-finite norm gives a NaN / zero factor, as there.
+        float scale = 1.0f;
+        if (max_norm > 0.f) {
+            const double r = (double)max_norm / (norm64 + 1e-6);
+            scale = (float)(r > 1.0 ? 1.0 : r);
+        }
+        const int skip = (skip_nonfinite && (bad || nonfinite_bits(norm))) ? 1 : 0;
+        stats->sumsq = sumsq;
+        stats->norm = norm;
+        stats->scale = scale;
+        stats->nonfinite = bad ? 1 : 0;
+        stats->skip = skip;
+        stats->skipped_total += skip;
+    }
+}
+
+// adam_multi_kernel with the gradient scaled by the clip factor, decoupled weight decay and the skip decision, both read from the
+// device-resident OptStats (one uniform load each: the host never sees them).  The update is written term for term like
+// adam_multi_kernel's -- the scaled gradient in a statement of its own, so no product is fused across it -- and with scale == 1 and a
+// decay factor of exactly 1, g * 1 and the fused p * 1 - q round as g and p - q do: the same bits (tests/test_optimizer_gpu.py).
+__device__ __forceinline__ void adamw_update(float& p, float g, float& m, float& v, float scale, float keep, float lr_t, float b1, float b2,
+                                             float eps) {
+    const float gi = g * scale;
+    const float mi = b1 * m + (1.0f - b1) * gi;
+    const float vi = b2 * v + (1.0f - b2) * gi * gi;
+    m = mi;
+    v = vi;
+    const float q = lr_t * mi / (sqrtf(vi) + eps);
+    p = p * keep - q;
+}
+__global__ void adamw_multi_kernel(const AdamChunk* __restrict__ chunks, const float* __restrict__ grads, float* __restrict__ am,
+                                   float* __restrict__ av, const OptStats* __restrict__ stats, float lr, float wd, float lr_t, float b1,
+                                   float b2, float eps) {
+    if (stats->skip) return;          // a skipped step reads no gradient and no moment: parameters, m and v keep their bits
+    const float scale = stats->scale;
+    const AdamChunk c = chunks[blockIdx.x];
+    float* __restrict__ p = c.p;
+    const float* __restrict__ g = grads + c.goff;
+    float* __restrict__ m = am + c.goff;
+    float* __restrict__ v = av + c.goff;
+    const float keep = c.decay ? 1.0f - lr * wd : 1.0f;
+    const int n4 = aligned16(p) ? c.n >> 2 : 0;
+    for (int i = threadIdx.x; i < n4; i += EW_THREADS) {
+        float4 pv = reinterpret_cast<float4*>(p)[i];
+        const float4 gv = reinterpret_cast<const float4*>(g)[i];
+        float4 mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+        adamw_update(pv.x, gv.x, mv.x, vv.x, scale, keep, lr_t, b1, b2, eps);
+        adamw_update(pv.y, gv.y, mv.y, vv.y, scale, keep, lr_t, b1, b2, eps);
+        adamw_update(pv.z, gv.z, mv.z, vv.z, scale, keep, lr_t, b1, b2, eps);
+        adamw_update(pv.w, gv.w, mv.w, vv.w, scale, keep, lr_t, b1, b2, eps);
+        reinterpret_cast<float4*>(m)[i] = mv;
+        reinterpret_cast<float4*>(v)[i] = vv;
+        reinterpret_cast<float4*>(p)[i] = pv;
+    }
+    for (int i = (n4 << 2) + threadIdx.x; i < c.n; i += EW_THREADS) {
+        float pi = p[i], mi = m[i], vi = v[i];
+        adamw_update(pi, g[i], mi, vi, scale, keep, lr_t, b1, b2, eps);
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = pi;
+    }
+}
+
 // y[row] = mask[row] ? embed : x[row]      (spec_augment.py:127, tf.where(mask, spec_embed, x))
 __global__ void spec_aug_fwd_kernel(const float* __restrict__ x, const uint8_t* __restrict__ mask,
                                     const float* __restrict__ embed, float* __restrict__ y, int64_t rows, int H) {
@@ -1013,6 +1194,35 @@ int launch_adam_multi(const AdamChunk* chunks_dev, int nchunks, const float* gra
     W2V2_REQUIRE(chunks_dev && nchunks > 0 && grads && m && v, "adam_multi: bad argument");
     ProfScope ps(tl_step_prof, FAM_OPTIMIZER, 0.0, 28.0 * 4096.0 * nchunks, s);
     W2V2_LAUNCH(adam_multi_kernel, dim3(nchunks), dim3(EW_THREADS), 0, s, chunks_dev, grads, m, v, lr_t, b1, b2, eps);
+    W2V2_HIP_CHECK(hipGetLastError());
+    return W2V2_OK;
+}
+
+int launch_grad_accumulate(const AdamChunk* chunks_dev, int nchunks, float* grads, float* acc, int mode, hipStream_t s) {
+    W2V2_REQUIRE(chunks_dev && nchunks > 0 && grads && acc && mode >= 0 && mode <= 2, "grad_accumulate: bad argument");
+    ProfScope ps(tl_step_prof, FAM_OPTIMIZER, 0.0, (mode == 0 ? 8.0 : 12.0) * OPT_CHUNK * nchunks, s);
+    W2V2_LAUNCH(grad_accumulate_kernel, dim3(nchunks), dim3(EW_THREADS), 0, s, chunks_dev, grads, acc, mode);
+    W2V2_HIP_CHECK(hipGetLastError());
+    return W2V2_OK;
+}
+
+int launch_grad_norm(const AdamChunk* chunks_dev, int nchunks, const float* g, int64_t n, double* partial, int32_t* flag, float max_norm,
+                     int skip_nonfinite, OptStats* stats, hipStream_t s) {
+    W2V2_REQUIRE(nchunks > 0 && nchunks <= (1 << 28) && g && partial && flag && stats, "grad_norm: bad argument");      // (chunk indices stay far from INT_MAX)
+    W2V2_REQUIRE(chunks_dev || (n > 0 && nchunks == (int)((n + OPT_CHUNK - 1) / OPT_CHUNK)), "grad_norm: %d chunks do not tile %lld elements",
+                 nchunks, (long long)n);
+    ProfScope ps(tl_step_prof, FAM_OPTIMIZER, 0.0, 4.0 * OPT_CHUNK * nchunks, s);
+    W2V2_LAUNCH(grad_sumsq_kernel, dim3(nchunks), dim3(EW_THREADS), 0, s, chunks_dev, g, n, partial, flag);
+    W2V2_LAUNCH(grad_norm_finish_kernel, dim3(1), dim3(EW_THREADS), 0, s, partial, flag, nchunks, max_norm, skip_nonfinite, stats);
+    W2V2_HIP_CHECK(hipGetLastError());
+    return W2V2_OK;
+}
+
+int launch_adamw_multi(const AdamChunk* chunks_dev, int nchunks, const float* grads, float* m, float* v, const OptStats* stats, float lr,
+                       float weight_decay, float lr_t, float b1, float b2, float eps, hipStream_t s) {
+    W2V2_REQUIRE(chunks_dev && nchunks > 0 && grads && m && v && stats, "adamw_multi: bad argument");
+    ProfScope ps(tl_step_prof, FAM_OPTIMIZER, 0.0, 28.0 * OPT_CHUNK * nchunks, s);
+    W2V2_LAUNCH(adamw_multi_kernel, dim3(nchunks), dim3(EW_THREADS), 0, s, chunks_dev, grads, m, v, stats, lr, weight_decay, lr_t, b1, b2, eps);
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }

@@ -976,5 +976,23 @@ int w2v2_op_weight_norm_bwd(const float* weight_v, const float* weight_g, const 
                             int32_t cg, int32_t H, int32_t groups, void* stream) {
     return launch_weight_norm_bwd(weight_v, weight_g, dwg, dweight_v, dweight_g, K, cg, H, groups, reinterpret_cast<hipStream_t>(stream));
 }
+int w2v2_op_grad_norm(const float* g, int64_t n, float max_norm, int32_t skip_nonfinite, w2v2_opt_stats* stats_out, void* stream) {
+    W2V2_REQUIRE(g && stats_out && n > 0 && n <= ((int64_t)OPT_CHUNK << 28), "op_grad_norm: bad argument");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int nchunks = (int)((n + OPT_CHUNK - 1) / OPT_CHUNK);
+    void* ws = nullptr;
+    W2V2_HIP_CHECK(hipMalloc(&ws, (size_t)nchunks * (sizeof(double) + sizeof(int32_t))));
+    int e = W2V2_OK;
+    if (hipMemsetAsync(stats_out, 0, sizeof(w2v2_opt_stats), s) != hipSuccess) {
+        set_error("op_grad_norm: cannot clear the record");
+        e = W2V2_EHIP;
+    }
+    if (!e)
+        e = launch_grad_norm(nullptr, nchunks, g, n, reinterpret_cast<double*>(ws), reinterpret_cast<int32_t*>(reinterpret_cast<double*>(ws) + nchunks),
+                             max_norm, skip_nonfinite ? 1 : 0, stats_out, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(ws);
+    return e;
+}
 
 }  // extern "C"

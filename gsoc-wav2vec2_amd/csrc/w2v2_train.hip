@@ -60,6 +60,13 @@ struct TrainState {
     AdamChunk* adam_chunks = nullptr;        // device table for the single-launch Adam; rebuilt when `trainable` changes
     int adam_nchunks = 0;
     bool adam_table_fresh = false;
+    // accumulation, clipping, AdamW, skipped steps: every buffer below is allocated by the first call that needs it
+    std::vector<char> decay;                 // per variable: takes the decoupled weight decay (w2v2_set_decay_flags); empty = none
+    float* grad_acc = nullptr;               // gtotal floats: the micro-step sum of w2v2_grad_accumulate
+    double* norm_partial = nullptr;          // norm_cap doubles, then norm_cap int32 flags: grad_sumsq's output per chunk
+    int norm_cap = 0;
+    OptStats* opt_stats = nullptr;           // the device-resident record w2v2_grad_norm writes and w2v2_adamw_step reads
+    bool norm_fresh = false;                 // a w2v2_grad_norm has run since the last backward / accumulate-finish
     std::vector<int64_t> goff;
     int64_t gtotal = 0;
     std::vector<char> trainable;
@@ -149,6 +156,8 @@ void w2v2_train_destroy(w2v2_model* m) {
     for (void* p : m->train->persist) (void)hipFree(p);
     m->train->persist.clear();
     if (m->train->adam_chunks) (void)hipFree(m->train->adam_chunks);
+    for (void* p : {(void*)m->train->grad_acc, (void*)m->train->norm_partial, (void*)m->train->opt_stats})
+        if (p) (void)hipFree(p);
     if (m->train->pos_w16_t) (void)hipFree(m->train->pos_w16_t);
     for (hipEvent_t ev : m->train->bucket_ev) (void)hipEventDestroy(ev);
     if (m->train->wg_stream) (void)hipStreamDestroy(m->train->wg_stream);
@@ -1367,6 +1376,7 @@ int w2v2_train_backward(w2v2_model* m, const float* dlogits, void* stream) {
     PrecisionScope precision(plan.precision);
     StepProfScope step_prof(m->prof);          // the training-only kernels' launchers find the profiler here (common.h)
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    t->norm_fresh = false;                     // the OptStats of an earlier gradient say nothing about this one (w2v2_adamw_step)
     const int H = c.hidden_size, F = c.intermediate_size;
     const int64_t BT = plan.BT;
     BwdCtx x{m, t, plan, s, plan.B, plan.T, H, F, BT, c.layer_norm_eps, t->p, t->seed, t->have_mask ? m->frame_len : nullptr, shb,
@@ -1518,6 +1528,7 @@ int w2v2_adam_reset(w2v2_model* m, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     W2V2_HIP_CHECK(hipMemsetAsync(t->adam_m, 0, (size_t)t->gtotal * 4, s));
     W2V2_HIP_CHECK(hipMemsetAsync(t->adam_v, 0, (size_t)t->gtotal * 4, s));
+    if (t->opt_stats) W2V2_HIP_CHECK(hipMemsetAsync(&t->opt_stats->skipped_total, 0, sizeof(int64_t), s));   // a fresh optimizer has skipped nothing
     return W2V2_OK;
 }
 
@@ -1559,6 +1570,29 @@ int w2v2_get_grad(w2v2_model* m, const char* name, float* host_dst, int64_t nume
     return W2V2_OK;
 }
 
+// The device table of trainable 4096-element chunks every optimizer kernel runs over; rebuilt when the trainable set or the decay
+// flags changed.
+static int ensure_chunk_table(w2v2_model* m, TrainState* t) {
+    if (t->adam_table_fresh) return W2V2_OK;
+    std::vector<AdamChunk> host;
+    for (size_t i = 0; i < m->params.size(); ++i) {
+        if (!t->trainable[i]) continue;
+        const Param& p = m->params[i];
+        const int decay = !t->decay.empty() && t->decay[i];
+        for (int64_t o = 0; o < p.numel; o += 4096)
+            host.push_back(AdamChunk{p.dev + o, t->goff[i] + o, (int)(p.numel - o < 4096 ? p.numel - o : 4096), decay});
+    }
+    if (t->adam_chunks) (void)hipFree(t->adam_chunks);
+    t->adam_chunks = nullptr;
+    t->adam_nchunks = (int)host.size();
+    if (!host.empty()) {
+        W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&t->adam_chunks), host.size() * sizeof(AdamChunk)));
+        W2V2_HIP_CHECK(hipMemcpy(t->adam_chunks, host.data(), host.size() * sizeof(AdamChunk), hipMemcpyHostToDevice));
+    }
+    t->adam_table_fresh = true;
+    return W2V2_OK;
+}
+
 int w2v2_adam_step(w2v2_model* m, float lr, float beta1, float beta2, float eps, int64_t step, void* stream) {
     W2V2_REQUIRE(m && step >= 1, "adam_step: bad argument");
     TrainState* t = m->train;
@@ -1570,29 +1604,122 @@ int w2v2_adam_step(w2v2_model* m, float lr, float beta1, float beta2, float eps,
     StepProfScope step_prof(m->prof);
     // Keras: lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t);  p -= lr_t * m / (sqrt(v) + eps)
     const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
-    if (!t->adam_table_fresh) {
-        std::vector<AdamChunk> host;
-        for (size_t i = 0; i < m->params.size(); ++i) {
-            if (!t->trainable[i]) continue;
-            const Param& p = m->params[i];
-            for (int64_t o = 0; o < p.numel; o += 4096)
-                host.push_back(AdamChunk{p.dev + o, t->goff[i] + o, (int)(p.numel - o < 4096 ? p.numel - o : 4096)});
-        }
-        if (t->adam_chunks) (void)hipFree(t->adam_chunks);
-        t->adam_chunks = nullptr;
-        t->adam_nchunks = (int)host.size();
-        if (!host.empty()) {
-            W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&t->adam_chunks), host.size() * sizeof(AdamChunk)));
-            W2V2_HIP_CHECK(hipMemcpy(t->adam_chunks, host.data(), host.size() * sizeof(AdamChunk), hipMemcpyHostToDevice));
-        }
-        t->adam_table_fresh = true;
-    }
+    if (int e = ensure_chunk_table(m, t)) return e;
     if (t->adam_nchunks > 0)
         if (int e = launch_adam_multi(t->adam_chunks, t->adam_nchunks, t->grads, t->adam_m, t->adam_v, (float)lr_t, beta1, beta2, eps, s))
             return e;
     t->transposes_fresh = false;
     m->finalized = false;
     return w2v2_finalize(m, stream);     // re-derive the effective positional kernel and the packed q|k|v
+}
+
+/* ---- accumulation, global-norm clipping, AdamW, skipped steps ---- */
+
+int w2v2_set_decay_flags(w2v2_model* m, const uint8_t* flags, int32_t n) {
+    W2V2_REQUIRE(m && flags, "set_decay_flags: null argument");
+    W2V2_REQUIRE(n == (int32_t)m->params.size(), "set_decay_flags: %d flags for %d variables", n, (int)m->params.size());
+    TrainState* t = get_state(m);
+    if (t->decay.empty()) t->decay.assign(m->params.size(), 0);
+    bool changed = false;
+    for (int32_t i = 0; i < n; ++i) {
+        const char f = flags[i] ? 1 : 0;
+        changed |= t->decay[i] != f;
+        t->decay[i] = f;
+    }
+    if (changed) t->adam_table_fresh = false;
+    return W2V2_OK;
+}
+
+// the gradient buffer and the chunk table of a model that has run a backward
+static int optimizer_ready(w2v2_model* m, const char* who, TrainState** out) {
+    TrainState* t = m ? m->train : nullptr;
+    if (!t || !t->grads) {
+        set_error("%s: no gradients", who);
+        return W2V2_ESTATE;
+    }
+    *out = t;
+    return ensure_chunk_table(m, t);
+}
+
+int w2v2_grad_accumulate(w2v2_model* m, int32_t mode, void* stream) {
+    W2V2_REQUIRE(m && mode >= W2V2_ACCUM_STORE && mode <= W2V2_ACCUM_FINISH, "grad_accumulate: bad argument");
+    TrainState* t = nullptr;
+    if (int e = optimizer_ready(m, "grad_accumulate", &t)) return e;
+    if (!t->grad_acc) {
+        W2V2_REQUIRE(mode == W2V2_ACCUM_STORE, "grad_accumulate: nothing has been stored yet (the first micro-step is W2V2_ACCUM_STORE)");
+        W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&t->grad_acc), (size_t)t->gtotal * 4));
+        W2V2_HIP_CHECK(hipMemset(t->grad_acc, 0, (size_t)t->gtotal * 4));     // (a slot that turns trainable inside an accumulation adds zeros)
+    }
+    if (mode == W2V2_ACCUM_FINISH) t->norm_fresh = false;      // the gradient changes under an earlier norm
+    if (t->adam_nchunks == 0) return W2V2_OK;
+    StepProfScope step_prof(m->prof);
+    return launch_grad_accumulate(t->adam_chunks, t->adam_nchunks, t->grads, t->grad_acc, mode, reinterpret_cast<hipStream_t>(stream));
+}
+
+static int ensure_opt_stats(TrainState* t) {
+    if (!t->opt_stats) {
+        const OptStats zero{0.0, 0.f, 1.f, 0, 0, 0};
+        W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&t->opt_stats), sizeof(OptStats)));
+        W2V2_HIP_CHECK(hipMemcpy(t->opt_stats, &zero, sizeof(OptStats), hipMemcpyHostToDevice));
+    }
+    return W2V2_OK;
+}
+
+int w2v2_grad_norm(w2v2_model* m, float max_norm, int32_t skip_nonfinite, void* stream) {
+    W2V2_REQUIRE(m, "grad_norm: null model");
+    TrainState* t = nullptr;
+    if (int e = optimizer_ready(m, "grad_norm", &t)) return e;
+    W2V2_REQUIRE(t->adam_nchunks > 0, "grad_norm: no variable is trainable");
+    if (int e = ensure_opt_stats(t)) return e;
+    if (t->norm_cap < t->adam_nchunks) {
+        // (freeing synchronises with the kernels that may still read the old scratch; the table changes between stages, not steps)
+        if (t->norm_partial) (void)hipFree(t->norm_partial);
+        t->norm_partial = nullptr;
+        t->norm_cap = 0;
+        W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&t->norm_partial), (size_t)t->adam_nchunks * (sizeof(double) + sizeof(int32_t))));
+        t->norm_cap = t->adam_nchunks;
+    }
+    StepProfScope step_prof(m->prof);
+    if (int e = launch_grad_norm(t->adam_chunks, t->adam_nchunks, t->grads, 0, t->norm_partial,
+                                 reinterpret_cast<int32_t*>(t->norm_partial + t->norm_cap), max_norm, skip_nonfinite ? 1 : 0, t->opt_stats,
+                                 reinterpret_cast<hipStream_t>(stream)))
+        return e;
+    t->norm_fresh = true;
+    return W2V2_OK;
+}
+
+int w2v2_adamw_step(w2v2_model* m, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream) {
+    W2V2_REQUIRE(m && step >= 1 && weight_decay >= 0.f, "adamw_step: bad argument");
+    TrainState* t = nullptr;
+    if (int e = optimizer_ready(m, "adamw_step", &t)) return e;
+    if (!t->norm_fresh) {
+        set_error("adamw_step: no w2v2_grad_norm since the last backward (it leaves the clip factor and the skip decision this call reads)");
+        return W2V2_ESTATE;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    StepProfScope step_prof(m->prof);
+    // lr_t as in w2v2_adam_step; t counts the calls, skipped ones included (the host does not know the skip: DESIGN 22)
+    const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
+    if (int e = launch_adamw_multi(t->adam_chunks, t->adam_nchunks, t->grads, t->adam_m, t->adam_v, t->opt_stats, lr, weight_decay, (float)lr_t,
+                                   beta1, beta2, eps, s))
+        return e;
+    t->transposes_fresh = false;
+    m->finalized = false;
+    return w2v2_finalize(m, stream);
+}
+
+int w2v2_optimizer_stats(w2v2_model* m, float* norm, float* scale, int32_t* skipped_last, int64_t* skipped_total, void* stream) {
+    W2V2_REQUIRE(m && norm && scale && skipped_last && skipped_total, "optimizer_stats: null argument");
+    OptStats st{0.0, 0.f, 1.f, 0, 0, 0};
+    if (m->train && m->train->opt_stats) {
+        W2V2_HIP_CHECK(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+        W2V2_HIP_CHECK(hipMemcpy(&st, m->train->opt_stats, sizeof(OptStats), hipMemcpyDeviceToHost));
+    }
+    *norm = st.norm;
+    *scale = st.scale;
+    *skipped_last = st.skip;
+    *skipped_total = st.skipped_total;
+    return W2V2_OK;
 }
 
 }  // extern "C"

@@ -69,6 +69,12 @@ class W2V2ResampleFilter(C.Structure):
     _fields_ = [("table", C.c_void_p), ("L", C.c_int32), ("M", C.c_int32), ("K", C.c_int32), ("lead", C.c_int32)]
 
 
+class W2V2OptStats(C.Structure):
+    """struct w2v2_opt_stats (include/w2v2.h): the record w2v2_grad_norm / w2v2_op_grad_norm leave in device memory."""
+    _fields_ = [("sumsq", C.c_double), ("norm", C.c_float), ("scale", C.c_float), ("nonfinite", C.c_int32), ("skip", C.c_int32),
+                ("skipped_total", C.c_int64)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/w2v2.h
 _P = C.c_void_p
 _I32 = C.c_int32
@@ -136,6 +142,12 @@ PROTOTYPES = {
     "w2v2_get_grad": (C.c_int, [_P, C.c_char_p, _P, _I64, _P]),
     "w2v2_train_storage": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I64)]),
     "w2v2_adam_step": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, _I64, _P]),
+    "w2v2_grad_accumulate": (C.c_int, [_P, _I32, _P]),
+    "w2v2_set_decay_flags": (C.c_int, [_P, _P, _I32]),
+    "w2v2_grad_norm": (C.c_int, [_P, C.c_float, _I32, _P]),
+    "w2v2_adamw_step": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I64, _P]),
+    "w2v2_optimizer_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(_I32), C.POINTER(_I64), _P]),
+    "w2v2_op_grad_norm": (C.c_int, [_P, _I64, C.c_float, _I32, _P, _P]),
     "w2v2_ln_bwd_ws_floats": (_I64, [_I64, _I32]),
     "w2v2_op_layer_norm_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I32, C.c_float, _P, _P]),
     "w2v2_op_attention_train": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, C.c_float, C.c_uint64, C.c_uint32, _P]),

@@ -9,7 +9,9 @@ all-reduce of the gradients across data-parallel ranks (RCCL), Adam with Keras d
 
 Everything numeric runs in the HIP library (w2v2_train_forward / w2v2_ctc_loss / w2v2_train_backward /
 w2v2_adam_step); this class only sequences the calls, draws the host-side randomness the reference also
-draws on the host, and issues the collective.
+draws on the host, and issues the collective.  What fine-tuning recipes add to that step -- gradient accumulation, clipping
+by the global norm, AdamW, dropping a non-finite update, learning-rate schedules -- is opt-in (`Trainer`'s arguments;
+w2v2_grad_accumulate / w2v2_grad_norm / w2v2_adamw_step) and leaves the default step as it is.
 """
 
 import ctypes as C
@@ -45,6 +47,50 @@ def stage2_learning_rate(epoch, lr1=1e-4, lr2=5e-5, transition_epochs=10):
     return lr1 if epoch <= transition_epochs else lr2
 
 
+def linear_schedule(peak_lr, warmup_steps, total_steps, final_lr=0.0):
+    """Iteration -> learning rate: linear from `peak_lr / warmup_steps` at iteration 0 to `peak_lr` at the last warm-up
+    iteration (`warmup_steps - 1`), then linear down to `final_lr` at `total_steps` and constant after it.  Pass it as
+    `Trainer(lr_schedule=...)`; a pure host function."""
+    warmup_steps, total_steps = int(warmup_steps), int(total_steps)
+    if not 0 <= warmup_steps <= total_steps or total_steps < 1:
+        raise ValueError("linear_schedule needs 0 <= warmup_steps <= total_steps and total_steps >= 1")
+
+    top = max(warmup_steps - 1, 0)          # the iteration that runs at peak_lr
+
+    def schedule(iteration):
+        if iteration < warmup_steps:
+            return peak_lr * (iteration + 1) / warmup_steps
+        if iteration >= total_steps:
+            return final_lr
+        return peak_lr + (final_lr - peak_lr) * (iteration - top) / (total_steps - top)
+    return schedule
+
+
+def tri_stage_schedule(peak_lr, total_steps, phase_ratio=(0.1, 0.4, 0.5), init_scale=0.01, final_scale=0.05):
+    """Iteration -> learning rate in the three stages of the wav2vec2 fine-tuning recipe: linear from `init_scale * peak_lr`
+    up to `peak_lr` over the first `phase_ratio[0]` of `total_steps`, held for `phase_ratio[1]`, then decayed exponentially
+    to `final_scale * peak_lr` at `total_steps` (constant after it).  Shape and defaults are that recipe's conventions, not
+    tuned here; a pure host function."""
+    if len(phase_ratio) != 3 or min(phase_ratio) < 0 or abs(sum(phase_ratio) - 1.0) > 1e-9:
+        raise ValueError("phase_ratio must be three non-negative fractions that sum to 1")
+    if total_steps < 1 or not 0 < final_scale:
+        raise ValueError("tri_stage_schedule needs total_steps >= 1 and final_scale > 0")
+    warm = int(total_steps * phase_ratio[0])
+    hold = int(total_steps * phase_ratio[1])
+    decay = total_steps - warm - hold
+    rate = -np.log(final_scale) / max(1, decay)
+
+    def schedule(iteration):
+        if iteration < warm:
+            return peak_lr * (init_scale + (1.0 - init_scale) * iteration / warm)
+        if iteration < warm + hold:
+            return peak_lr
+        if iteration >= total_steps:
+            return peak_lr * final_scale
+        return peak_lr * float(np.exp(-rate * (iteration - warm - hold)))
+    return schedule
+
+
 class Trainer:
     """One optimizer over one model.  Like `tf.keras.optimizers.Adam(...)` + `model.compile` in the reference, creating a
     Trainer starts a FRESH optimizer: iteration 0 and zero moments (src/main.py:213,240 build a new Adam for each of the
@@ -56,13 +102,39 @@ class Trainer:
     `allreduce_dtype`: "fp32" (default) or "bf16" -- the gradient payload of the data-parallel all-reduce.
 
     Speed perturbation (utterances played 0.9x / 1.1x) is not part of the step: apply `wav2vec2.audio.speed_perturb` to the
-    raw utterances before `batchify`."""
+    raw utterances before `batchify`.
+
+    What fine-tuning recipes add around the reference's bare step; with all of them at their defaults the step is
+    the reference's, call for call:
+      `max_grad_norm`       clip the gradient by its global norm (torch's `clip_grad_norm_` formula), taken after the
+                            all-reduce so every rank clips alike;
+      `weight_decay`        decoupled (AdamW): p *= 1 - lr * weight_decay, for every variable whose name ends in none of the
+                            `no_decay` suffixes;
+      `accumulation_steps`  k: `step` applies the SUM of k micro-batches' gradients on every k-th call (the loss is divided by
+                            the global batch, `CTCLoss.division_factor`, which therefore counts all k micro-batches);
+      `skip_nonfinite`      drop an update whose gradient holds an inf / NaN: variables and moments keep their bits.  The
+                            decision is taken and obeyed on the device, so the host does not know it: `iterations` and Adam's
+                            bias correction count a skipped step like any other;
+      `lr_schedule`         callable, iteration (0-based) -> learning rate, applied before every update
+                            (`linear_schedule`, `tri_stage_schedule`).
+    `last_grad_norm`, `last_clip_scale` and `skipped_steps` read the device record and synchronise only when read."""
 
     def __init__(self, model, loss, learning_rate=1e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-7, seed=0,
                  dropout=None, apply_spec_augment=None, overlap_all_reduce=True, reset_optimizer=True, allreduce_dtype="fp32",
-                 collective="torch"):
+                 collective="torch", max_grad_norm=None, weight_decay=0.0,
+                 no_decay=("bias", "gamma", "beta", "weight_g", "masked_spec_embed"), accumulation_steps=1, skip_nonfinite=False,
+                 lr_schedule=None):
         if not getattr(model, "_with_lm_head", False):
             raise ValueError("Trainer needs a Wav2Vec2ForCTC model")
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError("max_grad_norm must be positive (None: no clipping)")
+        if not weight_decay >= 0:
+            raise ValueError("weight_decay must be >= 0")
+        if int(accumulation_steps) != accumulation_steps or accumulation_steps < 1:
+            raise ValueError("accumulation_steps must be an integer >= 1")
+        if accumulation_steps > 1 and collective != "torch":
+            raise ValueError("gradient accumulation needs collective='torch': the native per-bucket collective waits only for the "
+                             "backward's bucket events and would race with the fold of the accumulated gradient")
         if allreduce_dtype not in ("fp32", "bf16"):
             raise ValueError("allreduce_dtype must be 'fp32' or 'bf16'")
         if collective not in ("torch", "native", "native-rs"):
@@ -88,14 +160,31 @@ class Trainer:
         self.overlap_all_reduce = bool(overlap_all_reduce)   # per-bucket all-reduces under the backward (all_reduce_gradients)
         self.allreduce_dtype = allreduce_dtype
         self._comm_stream = None
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.weight_decay = float(weight_decay)
+        self.no_decay = tuple(no_decay)
+        self.accumulation_steps = int(accumulation_steps)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.lr_schedule = lr_schedule
+        self._micro_step = 0                              # micro-batches accumulated since the last update
+        self._skipped_offset = 0                          # skipped steps of a loaded state, on top of the native count
+        # the optimizer path beyond the reference's: w2v2_grad_norm + w2v2_adamw_step instead of w2v2_adam_step
+        self._extended = (self.max_grad_norm is not None or self.weight_decay > 0 or self.accumulation_steps > 1
+                          or self.skip_nonfinite)
         if reset_optimizer:
             N.check(model._lib.w2v2_adam_reset(model._handle, N.current_stream()), "w2v2_adam_reset")
+        if self.weight_decay > 0:
+            names = model._native_inventory()
+            flags = (C.c_uint8 * len(names))(*[int(not n.endswith(self.no_decay)) for n in names])
+            N.check(model._lib.w2v2_set_decay_flags(model._handle, flags, len(names)), "w2v2_set_decay_flags")
 
     # -- pieces (also used by the parity tests) ----------------------------------------------------
     def forward(self, batch, attention_mask=None, spec_mask=None, sd_keep=None, step_seed=None):
         """Training-mode forward = `model(batch, attention_mask, training=True)` with this trainer's dropout rate, host RNG
         and step-derived seed (explicit `spec_mask` / `sd_keep` / `step_seed` override the draws)."""
-        seed = self.seed * 1000003 + self.iterations if step_seed is None else int(step_seed)
+        # (micro-batches of one accumulated update draw their own dropout masks; one micro-step per update: the seed as ever)
+        seed = (self.seed * 1000003 + self.iterations * self.accumulation_steps + self._micro_step
+                if step_seed is None else int(step_seed))
         logits, self.last = self.model._train_forward(batch, attention_mask, dropout=self.dropout,
                                                       apply_spec_augment=self.apply_spec_augment, spec_mask=spec_mask,
                                                       sd_keep=sd_keep, step_seed=seed, rng=self._rng)
@@ -161,7 +250,7 @@ class Trainer:
         self._ranges_cache = {trainable: ranges}          # (one entry: the trainable set changes between stages, not steps)
         return ranges
 
-    def all_reduce_gradients(self, force=False):
+    def all_reduce_gradients(self, force=False, overlap=None):
         """SUM over data-parallel ranks: the loss is pre-divided by the global batch (losses.py:45,
         main.py:198-200), so the sum is the global mean.
 
@@ -171,7 +260,8 @@ class Trainer:
         the calling stream then waits for all of them.  A layer of wav2vec2-base is a 28 MB bucket (large: 50 MB): big
         enough for the ring to run at link speed over xGMI, small enough that only the last one is exposed.  Only trainable
         slots travel (`reduce_ranges`); `allreduce_dtype="bf16"` halves the payload.
-        `overlap_all_reduce=False` (constructor) issues the same ranges after the whole backward on the calling stream."""
+        `overlap_all_reduce=False` (constructor; `overlap=False` for one call) issues the same ranges after the whole backward
+        on the calling stream."""
         if self.collective != "torch":
             return self._all_reduce_native(force)
         import torch
@@ -187,7 +277,7 @@ class Trainer:
         buf = self.grad_buffer()
         payload = torch.bfloat16 if self.allreduce_dtype == "bf16" else None
         ranges = self.reduce_ranges()
-        if not self.overlap_all_reduce:
+        if not (self.overlap_all_reduce if overlap is None else overlap):
             for runs in ranges:
                 for off, n in runs:
                     D.all_reduce_range(buf, off, n, payload)()
@@ -243,11 +333,47 @@ class Trainer:
         return out
 
     def apply_gradients(self):
+        """One optimizer update from the gradient buffer as it stands.  With every optimizer argument at its default: Keras
+        Adam (`w2v2_adam_step`).  Otherwise `w2v2_grad_norm` (global norm, clip factor, skip decision: left on the device)
+        followed by `w2v2_adamw_step`, which reads them there -- no synchronisation.  `iterations`, and with it the bias
+        correction, counts every call: a step the device skips (`skip_nonfinite`) is not known to the host."""
         m = self.model
+        if self.lr_schedule is not None:
+            self.learning_rate = float(self.lr_schedule(self.iterations))
         self.iterations += 1
-        N.check(m._lib.w2v2_adam_step(m._handle, float(self.learning_rate), float(self.beta_1), float(self.beta_2),
-                                      float(self.epsilon), self.iterations, N.current_stream()), "w2v2_adam_step")
-        m._dirty = False          # w2v2_adam_step re-derives the packed / normalised tensors itself
+        if self._extended:
+            s = N.current_stream()
+            N.check(m._lib.w2v2_grad_norm(m._handle, float(self.max_grad_norm or 0.0), int(self.skip_nonfinite), s), "w2v2_grad_norm")
+            N.check(m._lib.w2v2_adamw_step(m._handle, float(self.learning_rate), float(self.beta_1), float(self.beta_2),
+                                           float(self.epsilon), float(self.weight_decay), self.iterations, s), "w2v2_adamw_step")
+        else:
+            N.check(m._lib.w2v2_adam_step(m._handle, float(self.learning_rate), float(self.beta_1), float(self.beta_2),
+                                          float(self.epsilon), self.iterations, N.current_stream()), "w2v2_adam_step")
+        m._dirty = False          # w2v2_adam_step / w2v2_adamw_step re-derive the packed / normalised tensors themselves
+
+    def _optimizer_stats(self):
+        m = self.model
+        norm, scale, last, total = C.c_float(), C.c_float(), C.c_int32(), C.c_int64()
+        N.check(m._lib.w2v2_optimizer_stats(m._handle, C.byref(norm), C.byref(scale), C.byref(last), C.byref(total),
+                                            N.current_stream()), "w2v2_optimizer_stats")
+        return norm.value, scale.value, last.value, total.value
+
+    @property
+    def last_grad_norm(self):
+        """Global norm of the gradient of the last update (fp32; 0 before the first).  Synchronises."""
+        return self._optimizer_stats()[0]
+
+    @property
+    def last_clip_scale(self):
+        """Factor the last update multiplied its gradient by: min(1, max_grad_norm / (norm + 1e-6)).  Synchronises."""
+        return self._optimizer_stats()[1]
+
+    @property
+    def skipped_steps(self):
+        """Updates dropped for a non-finite gradient since this optimizer started (`skip_nonfinite`).  Synchronises."""
+        if not self.skip_nonfinite:
+            return self._skipped_offset          # (nothing is ever skipped: no native call, no synchronisation)
+        return self._optimizer_stats()[3] + self._skipped_offset
 
     # -- checkpoint / resume ----------------------------------------------------------------------------
     def _adam_views(self):
@@ -262,12 +388,18 @@ class Trainer:
     def state_dict(self):
         """Everything a resumed run needs besides the model's variables (`model.save_weights` / `save_pretrained`): the
         optimizer step count, Adam's moments, the hyper-parameters and the host RNG that draws spec-augment spans and
-        stochastic-depth decisions.  The reference's per-epoch ModelCheckpoint (training_utils.py:38-45) is the analogue."""
+        stochastic-depth decisions.  The reference's per-epoch ModelCheckpoint (training_utils.py:38-45) is the analogue.
+        Between the first and the last micro-step of an accumulation there is no such state to write (the partial sum is not
+        part of it): RuntimeError."""
+        if self._micro_step != 0:
+            raise RuntimeError(f"state_dict inside an accumulation ({self._micro_step} of {self.accumulation_steps} micro-steps "
+                               "done): checkpoint after the step that applies the gradients")
         am, av = self._adam_views()
         world, rank = _world_rank()
         return dict(iterations=int(self.iterations), learning_rate=float(self.learning_rate), beta_1=float(self.beta_1),
                     beta_2=float(self.beta_2), epsilon=float(self.epsilon), seed=int(self.seed), base_seed=int(self.base_seed),
-                    world_size=world, rank=rank, rng=self._rng.get_state(), adam_m=am.cpu().numpy(), adam_v=av.cpu().numpy())
+                    world_size=world, rank=rank, rng=self._rng.get_state(), adam_m=am.cpu().numpy(), adam_v=av.cpu().numpy(),
+                    skipped_steps=int(self.skipped_steps))
 
     def load_state_dict(self, state, batch_shape=None):
         """Inverse of `state_dict`.  A state without moments (e.g. one written before any step) zeroes them, so stale
@@ -283,6 +415,9 @@ class Trainer:
         else:
             N.check(self.model._lib.w2v2_adam_reset(self.model._handle, N.current_stream()), "w2v2_adam_reset")
         self.iterations = int(state["iterations"])
+        self._micro_step = 0
+        # (a state from before skipped steps existed has skipped none)
+        self._skipped_offset += int(state.get("skipped_steps", 0)) - int(self.skipped_steps)
         for k in ("learning_rate", "beta_1", "beta_2", "epsilon"):
             setattr(self, k, float(state[k]))
         # Randomness stays per REPLICA: the seed is re-derived for the rank that loads (a rank-0 checkpoint loaded on every
@@ -306,13 +441,28 @@ class Trainer:
     def step(self, batch, labels, attention_mask=None, all_reduce=True):
         """One fine-tune step.  `all_reduce=False` skips the data-parallel gradient collective (each replica then applies its
         own gradients): a MEASUREMENT switch -- bench.py times the step with and without it to report the exposed
-        communication time -- never the training semantics of the reference (main.py:156,192)."""
+        communication time -- never the training semantics of the reference (main.py:156,192).
+
+        With `accumulation_steps = k > 1` every call is one micro-batch and returns ITS loss total; the gradient is stored
+        (first micro-step) or added (later ones) into the accumulation buffer, and the k-th call folds the buffer back into
+        the gradient buffer, all-reduces, takes the norm and applies AdamW.  `iterations` advances on that call only.  The
+        all-reduce of an accumulated gradient is issued after the fold on the calling stream (the `overlap_all_reduce=False`
+        branch): the per-bucket events of the last backward say nothing about the fold."""
         logits = self.forward(batch, attention_mask)
         _, grad, total = self.loss.per_sample(labels, logits, with_grad=True, with_total=True)    # grad already / division_factor;
                                                                              # total = sum_b nll_b / division_factor, summed on the device
         self.backward(grad)
+        if self.accumulation_steps > 1:
+            m = self.model
+            last = self._micro_step == self.accumulation_steps - 1
+            mode = 2 if last else (0 if self._micro_step == 0 else 1)      # W2V2_ACCUM_FINISH / _STORE / _ADD
+            N.check(m._lib.w2v2_grad_accumulate(m._handle, mode, N.current_stream()), "w2v2_grad_accumulate")
+            if not last:
+                self._micro_step += 1
+                return total
+            self._micro_step = 0
         if all_reduce:
-            self.all_reduce_gradients()
+            self.all_reduce_gradients(overlap=False if self.accumulation_steps > 1 else None)
         self.apply_gradients()
         return total
 

@@ -628,6 +628,50 @@ int w2v2_get_grad(w2v2_model* m, const char* name, float* host_dst, int64_t nume
 int w2v2_train_storage(const w2v2_model* m, int32_t* mask, int64_t* workspace_bytes);
 int w2v2_adam_step(w2v2_model* m, float lr, float beta1, float beta2, float eps, int64_t step, void* stream);
 
+/* ---- gradient accumulation, clipping by the global norm, AdamW, non-finite step skip --------------------
+ * What the usual wav2vec2 CTC fine-tuning recipes put between the backward and the update, none of it in the reference's model.fit.
+ * Every decision stays in device memory: the norm, the clip factor and the skip flag are written into a small record by one call and
+ * read by the optimizer kernel of the next, so the step stays free of device-to-host synchronisation, capturable and bitwise
+ * reproducible (fixed summation orders, no float atomics).  All calls run over the trainable variables only, in 4096-element chunks;
+ * none of the buffers below exists until the first call that needs it, and w2v2_adam_step is untouched by all of this.
+ *   w2v2_grad_accumulate  micro-steps: mode W2V2_ACCUM_STORE copies the gradient buffer into a second flat buffer (allocated by the first
+ *                         such call), W2V2_ACCUM_ADD adds it, W2V2_ACCUM_FINISH adds the buffer INTO the gradient buffer -- a plain sum:
+ *                         the loss is divided by the global batch already, so micro-steps add exactly as data-parallel ranks do.
+ *                         With the native per-bucket collective (w2v2_allreduce_bucket) FINISH would race with the collectives, which
+ *                         wait for the backward's bucket events only: reduce after FINISH on the same stream instead.
+ *   w2v2_set_decay_flags  flags[i] != 0: variable i of the inventory takes the decoupled weight decay of w2v2_adamw_step; n must equal
+ *                         w2v2_num_params (the shape of w2v2_set_trainable_flags).  Default: none.
+ *   w2v2_grad_norm        the record of the current gradient (after any all-reduce, so every rank decides alike): sumsq in fp64 -- each
+ *                         thread adds its squares in index order, per-chunk and final sums fold in fixed trees --, norm = sqrt(sumsq),
+ *                         scale = min(1, max_norm / (norm + 1e-6)) evaluated in fp64 and rounded once (torch's clip_grad_norm_;
+ *                         max_norm <= 0: no clipping, scale = 1), nonfinite = an inf / NaN element was seen (exponent-field test),
+ *                         skip = skip_nonfinite && (nonfinite || norm not finite), skipped_total += skip.  With clipping on and
+ *                         skip_nonfinite off a non-finite gradient gives NaN parameters, as in torch.
+ *   w2v2_adamw_step       g' = g scale;  m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;  p = p (1 - lr wd) - lr_t m / (sqrt(v) + eps) with
+ *                         lr_t as in w2v2_adam_step (Keras' placement of eps) and wd = weight_decay for flagged variables, 0 otherwise;
+ *                         reads the record of the last w2v2_grad_norm (W2V2_ESTATE if none has run since the last backward); when skip is
+ *                         set, parameters and both moments keep their bits.  `step` is the caller's count of calls, skipped ones
+ *                         included: the host does not know the skip without a synchronisation, so a skipped step still advances the
+ *                         bias correction.  scale == 1, wd == 0, skip == 0: bit-identical to w2v2_adam_step.  Ends with w2v2_finalize.
+ *   w2v2_optimizer_stats  the one call that synchronises `stream`: norm, scale and skip of the last w2v2_grad_norm and the running count of
+ *                         skipped steps since the last w2v2_adam_reset (0, 1, 0, 0 before the first w2v2_grad_norm). */
+#define W2V2_ACCUM_STORE 0
+#define W2V2_ACCUM_ADD 1
+#define W2V2_ACCUM_FINISH 2
+typedef struct w2v2_opt_stats {
+    double sumsq;
+    float norm;
+    float scale;
+    int32_t nonfinite;
+    int32_t skip;
+    int64_t skipped_total;
+} w2v2_opt_stats;
+int w2v2_grad_accumulate(w2v2_model* m, int32_t mode, void* stream);
+int w2v2_set_decay_flags(w2v2_model* m, const uint8_t* flags, int32_t n);
+int w2v2_grad_norm(w2v2_model* m, float max_norm, int32_t skip_nonfinite, void* stream);
+int w2v2_adamw_step(w2v2_model* m, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream);
+int w2v2_optimizer_stats(w2v2_model* m, float* norm, float* scale, int32_t* skipped_last, int64_t* skipped_total, void* stream);
+
 /* ---- introspection (parity tests, profiling) -----------------------------
  * Stage activations of the LAST forward, by name: "conv0".."conv6",
  * "projection", "encoder_in", "layer0".."layerN-1", "encoder_out".  Copies
@@ -932,6 +976,11 @@ int w2v2_op_pos_conv_dw_bf16(const float* xz_dev, const float* dc_dev, float* dw
  * dweight_v = (g / n)(dW - <dW, v> v / n^2).  weight_v, dweight_v (K, cg, H); weight_g, dweight_g (K); dwg as above. */
 int w2v2_op_weight_norm_bwd(const float* weight_v_dev, const float* weight_g_dev, const float* dwg_dev, float* dweight_v_dev,
                             float* dweight_g_dev, int32_t K, int32_t cg, int32_t H, int32_t groups, void* stream);
+
+/* The two kernels of w2v2_grad_norm over a raw buffer g (n floats) cut into 4096-element chunks, the last one short: *stats_out_dev
+ * (device memory, zeroed first: skipped_total = skip) receives the record.  The per-chunk scratch is allocated and freed inside the
+ * call, so it synchronises the device: a test entry. */
+int w2v2_op_grad_norm(const float* g_dev, int64_t n, float max_norm, int32_t skip_nonfinite, w2v2_opt_stats* stats_out_dev, void* stream);
 
 #ifdef __cplusplus
 }
