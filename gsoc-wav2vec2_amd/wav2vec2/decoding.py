@@ -848,15 +848,9 @@ class ScoredTranscript(NamedTuple):
     word_confidence: list   # per word of ``words``: the summed posterior of the hypotheses that hold the word at its place
 
 
-def ctc_score(logits, labels, blank=0, frame_lengths=None, utterance=None):
-    """Exact CTC log-probability of each label sequence given its utterance's logits (``-ctc_loss`` in fp64; w2v2_ctc_score):
-    a float64 numpy array with one entry per pair.
-
-    ``logits``: what ``forced_align`` accepts, read in place.  ``labels``: one id sequence per pair, none of them the blank, at
-    most 8191 ids.  ``utterance[j]`` is the utterance pair j scores (default: j, which needs one label sequence per utterance);
-    several pairs may score the same utterance, whose logits are read where they lie.  Too few frames for the labels
-    (T < U + repeated neighbours) is no error: that pair's result is ``-inf``.  An utterance with a NaN or +inf logit gives NaN.
-    Raises ValueError, naming the pair, for a label outside the vocabulary, a blank label or more than 8191 labels."""
+def _score_pairs(logits, labels, blank, frame_lengths, utterance):
+    """The arguments ``ctc_score`` and ``ctc_score_grad`` share, checked: (base, V, row0, frames, utt, labels_dev, label0, nlabels,
+    blank) with the host arrays in the dtypes of the C ABI."""
     import torch
     from .alignment import _host, _logits_base
     base, row0, lens = _logits_base(logits, frame_lengths)
@@ -891,17 +885,76 @@ def ctc_score(logits, labels, blank=0, frame_lengths=None, utterance=None):
         if a.size > N.SCORE_MAX_LABELS:
             raise ValueError(f"pair {j}: {a.size} labels; at most {N.SCORE_MAX_LABELS} per pair")
         labs.append(a.astype(np.int32))
-    dev = base.device
     flat = np.concatenate(labs + [np.zeros(1, np.int32)])      # (one spare entry: never an empty buffer)
     label0 = np.cumsum([0] + [a.size for a in labs[:-1]]).astype(np.int64)
     nlab_h = np.asarray([a.size for a in labs], np.int32)
-    labels_dev = torch.from_numpy(flat).to(dev)
-    logp = torch.empty(m, dtype=torch.float64, device=dev)
-    row0_h = np.asarray(row0, np.int64)
-    frames_h = np.asarray(lens, np.int32)
-    N.check(N.load().w2v2_ctc_score(N.ptr(base), V, n, N.ptr(row0_h), N.ptr(frames_h), m, N.ptr(utt), N.ptr(labels_dev), N.ptr(label0),
-                                    N.ptr(nlab_h), blank, N.ptr(logp), N.current_stream()), "w2v2_ctc_score")
+    labels_dev = torch.from_numpy(flat).to(base.device)
+    return base, V, np.asarray(row0, np.int64), np.asarray(lens, np.int32), utt, labels_dev, label0, nlab_h, blank
+
+
+def ctc_score(logits, labels, blank=0, frame_lengths=None, utterance=None):
+    """Exact CTC log-probability of each label sequence given its utterance's logits (``-ctc_loss`` in fp64; w2v2_ctc_score):
+    a float64 numpy array with one entry per pair.
+
+    ``logits``: what ``forced_align`` accepts, read in place.  ``labels``: one id sequence per pair, none of them the blank, at
+    most 8191 ids.  ``utterance[j]`` is the utterance pair j scores (default: j, which needs one label sequence per utterance);
+    several pairs may score the same utterance, whose logits are read where they lie.  Too few frames for the labels
+    (T < U + repeated neighbours) is no error: that pair's result is ``-inf``.  An utterance with a NaN or +inf logit gives NaN.
+    Raises ValueError, naming the pair, for a label outside the vocabulary, a blank label or more than 8191 labels."""
+    import torch
+    base, V, row0_h, frames_h, utt, labels_dev, label0, nlab_h, blank = _score_pairs(logits, labels, blank, frame_lengths, utterance)
+    m = len(nlab_h)
+    logp = torch.empty(m, dtype=torch.float64, device=base.device)
+    N.check(N.load().w2v2_ctc_score(N.ptr(base), V, len(frames_h), N.ptr(row0_h), N.ptr(frames_h), m, N.ptr(utt), N.ptr(labels_dev),
+                                    N.ptr(label0), N.ptr(nlab_h), blank, N.ptr(logp), N.current_stream()), "w2v2_ctc_score")
     return logp.cpu().numpy()
+
+
+def ctc_score_grad(logits, labels, coef, blank=0, frame_lengths=None, utterance=None, max_workspace_bytes=8 << 30):
+    """The gradient of a weighted sum of exact CTC log-probabilities (w2v2_ctc_score_grad): ``(logp, grad)`` with
+    ``logp`` what ``ctc_score`` returns for the same pairs, bit for bit, and ``grad`` = d (sum_j coef_j logp_j) / d logits in fp32.
+
+    ``logits``, ``labels``, ``utterance`` and the ValueErrors are those of ``ctc_score``.  ``coef``: one float per pair, on the host
+    or as a device float64 tensor.  ``grad`` has the form of ``logits``: a padded (B, T, V) tensor with zero rows beyond each
+    length, or a list with one (T_i, V) tensor per utterance.  A pair whose ``logp`` is ``-inf`` or NaN contributes nothing; an
+    utterance none of whose pairs contributes gets zeros.  ``coef = -1`` on one pair per utterance is the CTC loss in fp64 log space
+    with its gradient, for any frame counts and up to 8191 labels.  The workspace holds ``T (2 U + 2)`` fp64 per pair; above
+    ``max_workspace_bytes`` the utterances run in groups that fit, with identical results, and MemoryError is raised, before
+    anything is allocated, when one utterance's pairs alone need more."""
+    import torch
+    base, V, row0_h, frames_h, utt, labels_dev, label0, nlab_h, blank = _score_pairs(logits, labels, blank, frame_lengths, utterance)
+    n, m = len(frames_h), len(nlab_h)
+    dev = base.device
+    if isinstance(coef, torch.Tensor):
+        coef_dev = coef.detach().to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+    else:
+        coef_dev = torch.from_numpy(np.asarray(list(coef), dtype=np.float64).reshape(-1)).to(dev)
+    if coef_dev.numel() != m:
+        raise ValueError(f"{m} label sequences with {coef_dev.numel()} coefficients")
+    cap = int(max_workspace_bytes)
+    if cap <= 0:
+        raise ValueError(f"max_workspace_bytes {cap} must be positive")
+    lib = N.load()
+    for i in range(n):                                           # one utterance's pairs must fit on their own
+        mine = np.flatnonzero(utt == i)
+        if not mine.size:
+            continue
+        one, zero, nl = frames_h[i:i + 1].copy(), np.zeros(mine.size, np.int32), np.ascontiguousarray(nlab_h[mine])     # (alive over the call)
+        need = int(lib.w2v2_ctc_score_grad_workspace(1, N.ptr(one), int(mine.size), N.ptr(zero), N.ptr(nl), V))
+        if need < 0:
+            N.check(need, "w2v2_ctc_score_grad_workspace")
+        if need > cap:
+            raise MemoryError(f"ctc_score_grad: utterance {i} ({int(frames_h[i])} frames, {mine.size} pairs) needs {need} bytes of "
+                              f"workspace; max_workspace_bytes is {cap}")
+    grad_base = torch.zeros((int(base.shape[0]), V), dtype=torch.float32, device=dev)     # (rows outside the utterances stay zero)
+    logp = torch.empty(m, dtype=torch.float64, device=dev)
+    N.check(lib.w2v2_ctc_score_grad(N.ptr(base), V, n, N.ptr(row0_h), N.ptr(frames_h), m, N.ptr(utt), N.ptr(labels_dev), N.ptr(label0),
+                                    N.ptr(nlab_h), blank, N.ptr(coef_dev), N.ptr(logp), N.ptr(grad_base), cap, N.current_stream()),
+            "w2v2_ctc_score_grad")
+    logp_h = logp.cpu().numpy()
+    if isinstance(logits, torch.Tensor):
+        return logp_h, grad_base.reshape(logits.shape)
+    return logp_h, [grad_base[int(r):int(r) + int(t)] for r, t in zip(row0_h, frames_h)]
 
 
 def rescore(logits, hypotheses, blank=0, frame_lengths=None):

@@ -331,6 +331,27 @@ int w2v2_ctc_score(const float* logits_dev, int32_t V, int32_t n, const int64_t*
                    const int32_t* utt_of_host, const int32_t* labels_dev, const int64_t* label0_host, const int32_t* nlabels_host,
                    int32_t blank, double* logp_dev, void* stream);
 
+/* The gradient of a weighted sum of exact CTC log-probabilities (exact definition in csrc/score_grad.hip): per
+ * utterance, grad = sum_j coef_j d logp_j / d logits over its pairs, with w2v2_ctc_score's addressing, argument checks and per-pair
+ * conventions; asynchronous on `stream`.  coef = -1 on one pair per utterance is the CTC loss in fp64 log space; coef_j = P_j (W_j - L)
+ * is an expected risk over an n-best list.
+ *   coef_dev     (m) fp64, in the caller's order
+ *   logp_dev     (m) fp64, out: the bits w2v2_ctc_score gives for the same pairs
+ *   grad_dev     fp32, rows addressed like logits_dev: every row of every utterance is written (zeros where no pair contributes);
+ *                rows outside the utterances are not touched
+ * A pair whose logp is -inf or NaN contributes nothing.  No float atomics: two runs give the same bits, and an utterance's rows do
+ * not depend on the other utterances, their pairs or their position.  The workspace holds frames_i (2 nlabels_j + 2) fp64 per pair;
+ * w2v2_ctc_score_grad_workspace returns the bytes of one pass over the call (host only; a negative W2V2_E* for bad shapes).  A call
+ * that needs more than max_workspace_bytes (0: 8 GiB) runs the utterances in consecutive groups that fit, stream-ordered, with
+ * identical results; if one utterance's pairs alone do not fit, W2V2_EINVAL before anything is allocated, the message naming the
+ * utterance and the bytes.  Nothing is launched or written on W2V2_EINVAL. */
+int w2v2_ctc_score_grad(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host,
+                        int32_t m, const int32_t* utt_of_host, const int32_t* labels_dev, const int64_t* label0_host,
+                        const int32_t* nlabels_host, int32_t blank, const double* coef_dev, double* logp_dev, float* grad_dev,
+                        int64_t max_workspace_bytes, void* stream);
+int64_t w2v2_ctc_score_grad_workspace(int32_t n, const int32_t* frames_host, int32_t m, const int32_t* utt_of_host,
+                                      const int32_t* nlabels_host, int32_t V);
+
 /* CTC phrase search (csrc/spot.hip): where in a recording a label string is spoken, for m (recording, phrase) pairs
  * in one call.  Model-free, with w2v2_ctc_score's addressing of recordings and pairs; asynchronous on `stream`.
  *   recording i: logits_dev rows [row0_host[i], row0_host[i] + frames_host[i]) of V fp32 (read in place; pairs share rows)
