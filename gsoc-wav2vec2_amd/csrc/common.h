@@ -401,7 +401,7 @@ int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int widt
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
 enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4, SCRATCH_BEAM = 5, SCRATCH_WINDOWS = 6,
                    SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8, SCRATCH_EDIT = 9, SCRATCH_ALIGN_LONG = 10, SCRATCH_SCORE = 11, SCRATCH_SPOT = 12, SCRATCH_SCORE_GRAD = 13,
-                   SCRATCH_SLOTS = 14 };
+                   SCRATCH_SCORE_STAR = 14, SCRATCH_SCORE_GRAD_STAR = 15, SCRATCH_SLOTS = 16 };
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out);
 int stream_scratch_release();       // frees the calling device's scratch buffers and staged-upload buffers
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }      // the parts of a workspace begin at multiples of 256 bytes
@@ -492,6 +492,16 @@ int launch_ctc_score_grad(const float* logits, int V, int n, const int64_t* row0
                           const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank, const double* coef,
                           double* logp, float* grad, int64_t max_workspace_bytes, hipStream_t s);
 int64_t ctc_score_grad_workspace(int n, const int32_t* frames, int m, const int32_t* utt_of, const int32_t* nlabels, int V);
+// ... both with the star, the wildcard label V (score_star.hip; w2v2_ctc_score_star, w2v2_ctc_score_grad_star; the definition in
+// score_star.hip): star_score <= 0; the gradient's workspace also holds the star's emission and the top token of every frame
+int launch_ctc_score_star(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int m, const int32_t* utt_of,
+                          const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank, float star_score,
+                          double* logp, hipStream_t s);
+int launch_ctc_score_grad_star(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int m,
+                               const int32_t* utt_of, const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank,
+                               float star_score, const double* coef, double* logp, float* grad, int64_t max_workspace_bytes,
+                               hipStream_t s);
+int64_t ctc_score_grad_star_workspace(int n, const int32_t* frames, int m, const int32_t* utt_of, const int32_t* nlabels, int V);
 // CTC phrase search (spot.hip; w2v2_ctc_spot): the same addressing and pairs; per pair max_hits slots of (score, begin, end), the
 // true count, and optionally z_t and c_t of every frame from trace0_j on (-1: none)
 int launch_ctc_spot(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int m, const int32_t* utt_of,

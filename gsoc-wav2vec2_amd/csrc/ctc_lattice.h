@@ -72,6 +72,30 @@ __device__ __forceinline__ int frame_lse_max(const float* logits, int V, int64_t
     return t;
 }
 
+// frame_lse_max that also yields the frame's top token (the star of the exact scorer and its gradient): lse[t] and m
+// by the same operations in the same order, then, in every lane, a = the lowest column index whose logit equals m (V when none
+// compares equal: a frame of NaN only, whose lse is not finite anyway).
+__device__ __forceinline__ int frame_lse_max_arg(const float* logits, int V, int64_t row0, int T, double* lse, float& m, int& a) {
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    m = -INFINITY;
+    a = V;
+    if (t >= T) return -1;
+    const int lane = threadIdx.x & 63;
+    const float* __restrict__ r = logits + (row0 + t) * V;
+    for (int v = lane; v < V; v += 64) m = fmaxf(m, r[v]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    double acc = 0.0;
+    for (int v = lane; v < V; v += 64) acc += exp((double)r[v] - (double)m);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane == 0) lse[t] = (double)m + log(acc);
+    for (int v = lane; v < V; v += 64) a = min(a, r[v] == m ? v : V);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a = min(a, __shfl_xor(a, off, 64));
+    return t;
+}
+
 // number of threads of the block for which pred holds (wave ballots, then the waves in order)
 __device__ __forceinline__ int block_count(bool pred, int* red) {
     const unsigned long long b = __ballot(pred);

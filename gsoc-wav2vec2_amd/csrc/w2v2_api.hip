@@ -580,6 +580,26 @@ int64_t w2v2_ctc_score_grad_workspace(int32_t n, const int32_t* frames, int32_t 
     return ctc_score_grad_workspace(n, frames, m, utt_of, nlabels, V);
 }
 
+int w2v2_ctc_score_star(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t m,
+                        const int32_t* utt_of, const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int32_t blank,
+                        float star_score, double* logp, void* stream) {
+    return launch_ctc_score_star(logits, V, n, row0, frames, m, utt_of, labels, label0, nlabels, blank, star_score, logp,
+                                 reinterpret_cast<hipStream_t>(stream));
+}
+
+int w2v2_ctc_score_grad_star(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t m,
+                             const int32_t* utt_of, const int32_t* labels, const int64_t* label0, const int32_t* nlabels,
+                             int32_t blank, float star_score, const double* coef, double* logp, float* grad,
+                             int64_t max_workspace_bytes, void* stream) {
+    return launch_ctc_score_grad_star(logits, V, n, row0, frames, m, utt_of, labels, label0, nlabels, blank, star_score, coef, logp,
+                                      grad, max_workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
+int64_t w2v2_ctc_score_grad_star_workspace(int32_t n, const int32_t* frames, int32_t m, const int32_t* utt_of,
+                                           const int32_t* nlabels, int32_t V) {
+    return ctc_score_grad_star_workspace(n, frames, m, utt_of, nlabels, V);
+}
+
 int w2v2_ctc_spot(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t m, const int32_t* utt_of,
                   const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int32_t blank, int32_t delim,
                   const double* min_score, int32_t max_hits, double* hit_score, int32_t* hit_begin, int32_t* hit_end, int32_t* count,

@@ -7,14 +7,14 @@ the Trainer's learning-rate schedules (wav2vec2.training: linear_schedule, tri_s
 from .audio import Resampler, resample, resampled_length, speed_perturb
 from .config import RobustWav2Vec2Config, Wav2Vec2Config
 from .longform import LongTranscript, ScoredLongTranscript, decode_long, window_plan
-from .losses import CTCLoss, MWERLoss, expected_risk
+from .losses import CTCLoss, MWERLoss, StarCTCLoss, expected_risk, star_labels
 from .metrics import (EditCounts, ErrorRate, Evaluation, cer, edit_distance, edit_distance_pairs, mbr_select, oracle_wer,
                       wer)
 from .modeling import Wav2Vec2ForCTC, Wav2Vec2Model
 from .processor import Wav2Vec2Processor
 from .training import Trainer, linear_schedule, tri_stage_schedule
 
-__all__ = ["Wav2Vec2Config", "RobustWav2Vec2Config", "CTCLoss", "MWERLoss", "expected_risk", "Wav2Vec2ForCTC", "Wav2Vec2Model",
+__all__ = ["Wav2Vec2Config", "RobustWav2Vec2Config", "CTCLoss", "MWERLoss", "StarCTCLoss", "expected_risk", "star_labels", "Wav2Vec2ForCTC", "Wav2Vec2Model",
            "Wav2Vec2Processor", "Trainer", "window_plan", "decode_long", "LongTranscript", "ScoredLongTranscript", "Resampler", "resample",
            "resampled_length", "speed_perturb", "EditCounts", "ErrorRate", "Evaluation", "wer", "cer", "oracle_wer", "mbr_select",
            "edit_distance", "edit_distance_pairs", "linear_schedule", "tri_stage_schedule"]

@@ -107,6 +107,9 @@ PROTOTYPES = {
     "w2v2_ctc_score": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _P, _P]),
     "w2v2_ctc_score_grad": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _I64, _P]),
     "w2v2_ctc_score_grad_workspace": (_I64, [_I32, _P, _I32, _P, _P, _I32]),
+    "w2v2_ctc_score_star": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, C.c_float, _P, _P]),
+    "w2v2_ctc_score_grad_star": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, C.c_float, _P, _P, _P, _I64, _P]),
+    "w2v2_ctc_score_grad_star_workspace": (_I64, [_I32, _P, _I32, _P, _P, _I32]),
     "w2v2_ctc_spot": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "w2v2_ctc_beam_search": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _I32, C.c_float, C.c_float, _I32, _P, _P, _P, _P, _P]),
     "w2v2_ctc_beam_search_words": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, C.POINTER(W2V2WordLM), _I32, C.c_float, C.c_float,

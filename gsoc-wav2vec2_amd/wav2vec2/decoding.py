@@ -848,11 +848,34 @@ class ScoredTranscript(NamedTuple):
     word_confidence: list   # per word of ``words``: the summed posterior of the hypotheses that hold the word at its place
 
 
-def _score_pairs(logits, labels, blank, frame_lengths, utterance):
+def _check_score_labels(labels, V, blank, star=False):
+    """The label sequences of ``ctc_score`` / ``ctc_score_grad`` as int32 arrays, checked (host code).  ``star``: the label V is
+    admitted (the star), two of them next to each other are not."""
+    from .alignment import _host
+    labs = []
+    for j, lab in enumerate(labels):
+        a = np.asarray(_host(lab) if hasattr(lab, "cpu") else list(lab), dtype=np.int64).reshape(-1)
+        if star:
+            if a.size and (a.min() < 0 or a.max() > V):
+                raise ValueError(f"pair {j}: labels must lie in [0, {V}] ({V} is the star), got [{a.min()}, {a.max()}]")
+            if a.size > 1 and ((a[1:] == V) & (a[:-1] == V)).any():
+                raise ValueError(f"pair {j}: two stars next to each other; collapse them into one")
+        elif a.size and (a.min() < 0 or a.max() >= V):
+            raise ValueError(f"pair {j}: labels must lie in [0, {V}), got [{a.min()}, {a.max()}]")
+        if a.size and (a == blank).any():
+            raise ValueError(f"pair {j}: label {blank} is the blank")
+        if a.size > N.SCORE_MAX_LABELS:
+            raise ValueError(f"pair {j}: {a.size} labels; at most {N.SCORE_MAX_LABELS} per pair")
+        labs.append(a.astype(np.int32))
+    return labs
+
+
+def _score_pairs(logits, labels, blank, frame_lengths, utterance, star=False):
     """The arguments ``ctc_score`` and ``ctc_score_grad`` share, checked: (base, V, row0, frames, utt, labels_dev, label0, nlabels,
-    blank) with the host arrays in the dtypes of the C ABI."""
+    blank) with the host arrays in the dtypes of the C ABI.  ``star``: the label V is admitted (the star), two of them next to each
+    other are not."""
     import torch
-    from .alignment import _host, _logits_base
+    from .alignment import _logits_base
     base, row0, lens = _logits_base(logits, frame_lengths)
     n, V = len(lens), int(base.shape[1])
     labels = list(labels)
@@ -875,16 +898,7 @@ def _score_pairs(logits, labels, blank, frame_lengths, utterance):
         raise ValueError(f"vocabulary {V}; the blank and at least one label")
     if not 0 <= blank < V:
         raise ValueError(f"blank {blank} outside the vocabulary [0, {V})")
-    labs = []
-    for j, lab in enumerate(labels):
-        a = np.asarray(_host(lab) if hasattr(lab, "cpu") else list(lab), dtype=np.int64).reshape(-1)
-        if a.size and (a.min() < 0 or a.max() >= V):
-            raise ValueError(f"pair {j}: labels must lie in [0, {V}), got [{a.min()}, {a.max()}]")
-        if a.size and (a == blank).any():
-            raise ValueError(f"pair {j}: label {blank} is the blank")
-        if a.size > N.SCORE_MAX_LABELS:
-            raise ValueError(f"pair {j}: {a.size} labels; at most {N.SCORE_MAX_LABELS} per pair")
-        labs.append(a.astype(np.int32))
+    labs = _check_score_labels(labels, V, blank, star)
     flat = np.concatenate(labs + [np.zeros(1, np.int32)])      # (one spare entry: never an empty buffer)
     label0 = np.cumsum([0] + [a.size for a in labs[:-1]]).astype(np.int64)
     nlab_h = np.asarray([a.size for a in labs], np.int32)
@@ -892,7 +906,7 @@ def _score_pairs(logits, labels, blank, frame_lengths, utterance):
     return base, V, np.asarray(row0, np.int64), np.asarray(lens, np.int32), utt, labels_dev, label0, nlab_h, blank
 
 
-def ctc_score(logits, labels, blank=0, frame_lengths=None, utterance=None):
+def ctc_score(logits, labels, blank=0, frame_lengths=None, utterance=None, star_score=None):
     """Exact CTC log-probability of each label sequence given its utterance's logits (``-ctc_loss`` in fp64; w2v2_ctc_score):
     a float64 numpy array with one entry per pair.
 
@@ -900,17 +914,33 @@ def ctc_score(logits, labels, blank=0, frame_lengths=None, utterance=None):
     most 8191 ids.  ``utterance[j]`` is the utterance pair j scores (default: j, which needs one label sequence per utterance);
     several pairs may score the same utterance, whose logits are read where they lie.  Too few frames for the labels
     (T < U + repeated neighbours) is no error: that pair's result is ``-inf``.  An utterance with a NaN or +inf logit gives NaN.
-    Raises ValueError, naming the pair, for a label outside the vocabulary, a blank label or more than 8191 labels."""
+    Raises ValueError, naming the pair, for a label outside the vocabulary, a blank label or more than 8191 labels.
+
+    ``star_score``: None is the call without a star: the label V is a ValueError.  A float <= 0 admits the star, label id V =
+    ``alignment.star_id(logits)`` (w2v2_ctc_score_star): it may stand anywhere, takes at least one frame, counts as
+    a label in the frame check and emits, per frame, max_v log_softmax(logits[t])[v] + star_score.  The result is then the score of
+    a set of paths, not a log-probability: it may exceed 0, and it is never below ``forced_align(..., star_score=...)``'s score.
+    Two stars next to each other and a star_score that is NaN or > 0 raise ValueError.  Pairs without a star get the bits of the
+    call without ``star_score``."""
     import torch
-    base, V, row0_h, frames_h, utt, labels_dev, label0, nlab_h, blank = _score_pairs(logits, labels, blank, frame_lengths, utterance)
+    star = star_score is not None
+    if star:
+        from .alignment import _check_star_score
+        star_score = _check_star_score(star_score)
+    base, V, row0_h, frames_h, utt, labels_dev, label0, nlab_h, blank = _score_pairs(logits, labels, blank, frame_lengths, utterance, star)
     m = len(nlab_h)
     logp = torch.empty(m, dtype=torch.float64, device=base.device)
+    if star:
+        N.check(N.load().w2v2_ctc_score_star(N.ptr(base), V, len(frames_h), N.ptr(row0_h), N.ptr(frames_h), m, N.ptr(utt),
+                                             N.ptr(labels_dev), N.ptr(label0), N.ptr(nlab_h), blank, star_score, N.ptr(logp),
+                                             N.current_stream()), "w2v2_ctc_score_star")
+        return logp.cpu().numpy()
     N.check(N.load().w2v2_ctc_score(N.ptr(base), V, len(frames_h), N.ptr(row0_h), N.ptr(frames_h), m, N.ptr(utt), N.ptr(labels_dev),
                                     N.ptr(label0), N.ptr(nlab_h), blank, N.ptr(logp), N.current_stream()), "w2v2_ctc_score")
     return logp.cpu().numpy()
 
 
-def ctc_score_grad(logits, labels, coef, blank=0, frame_lengths=None, utterance=None, max_workspace_bytes=8 << 30):
+def ctc_score_grad(logits, labels, coef, blank=0, frame_lengths=None, utterance=None, max_workspace_bytes=8 << 30, star_score=None):
     """The gradient of a weighted sum of exact CTC log-probabilities (w2v2_ctc_score_grad): ``(logp, grad)`` with
     ``logp`` what ``ctc_score`` returns for the same pairs, bit for bit, and ``grad`` = d (sum_j coef_j logp_j) / d logits in fp32.
 
@@ -920,9 +950,18 @@ def ctc_score_grad(logits, labels, coef, blank=0, frame_lengths=None, utterance=
     utterance none of whose pairs contributes gets zeros.  ``coef = -1`` on one pair per utterance is the CTC loss in fp64 log space
     with its gradient, for any frame counts and up to 8191 labels.  The workspace holds ``T (2 U + 2)`` fp64 per pair; above
     ``max_workspace_bytes`` the utterances run in groups that fit, with identical results, and MemoryError is raised, before
-    anything is allocated, when one utterance's pairs alone need more."""
+    anything is allocated, when one utterance's pairs alone need more.
+
+    ``star_score``: as ``ctc_score`` (w2v2_ctc_score_grad_star).  In the gradient a star state emits the frame's top token: its
+    occupancy goes to the lowest column that holds the frame's maximum, so on star frames a loss built on this sharpens the
+    model's own top token in proportion to the star's occupancy and does not supervise which token.  The workspace holds one more
+    fp64 and one int32 per frame."""
     import torch
-    base, V, row0_h, frames_h, utt, labels_dev, label0, nlab_h, blank = _score_pairs(logits, labels, blank, frame_lengths, utterance)
+    star = star_score is not None
+    if star:
+        from .alignment import _check_star_score
+        star_score = _check_star_score(star_score)
+    base, V, row0_h, frames_h, utt, labels_dev, label0, nlab_h, blank = _score_pairs(logits, labels, blank, frame_lengths, utterance, star)
     n, m = len(frames_h), len(nlab_h)
     dev = base.device
     if isinstance(coef, torch.Tensor):
@@ -940,17 +979,23 @@ def ctc_score_grad(logits, labels, coef, blank=0, frame_lengths=None, utterance=
         if not mine.size:
             continue
         one, zero, nl = frames_h[i:i + 1].copy(), np.zeros(mine.size, np.int32), np.ascontiguousarray(nlab_h[mine])     # (alive over the call)
-        need = int(lib.w2v2_ctc_score_grad_workspace(1, N.ptr(one), int(mine.size), N.ptr(zero), N.ptr(nl), V))
+        workspace = lib.w2v2_ctc_score_grad_star_workspace if star else lib.w2v2_ctc_score_grad_workspace
+        need = int(workspace(1, N.ptr(one), int(mine.size), N.ptr(zero), N.ptr(nl), V))
         if need < 0:
-            N.check(need, "w2v2_ctc_score_grad_workspace")
+            N.check(need, "w2v2_ctc_score_grad_star_workspace" if star else "w2v2_ctc_score_grad_workspace")
         if need > cap:
             raise MemoryError(f"ctc_score_grad: utterance {i} ({int(frames_h[i])} frames, {mine.size} pairs) needs {need} bytes of "
                               f"workspace; max_workspace_bytes is {cap}")
     grad_base = torch.zeros((int(base.shape[0]), V), dtype=torch.float32, device=dev)     # (rows outside the utterances stay zero)
     logp = torch.empty(m, dtype=torch.float64, device=dev)
-    N.check(lib.w2v2_ctc_score_grad(N.ptr(base), V, n, N.ptr(row0_h), N.ptr(frames_h), m, N.ptr(utt), N.ptr(labels_dev), N.ptr(label0),
-                                    N.ptr(nlab_h), blank, N.ptr(coef_dev), N.ptr(logp), N.ptr(grad_base), cap, N.current_stream()),
-            "w2v2_ctc_score_grad")
+    if star:
+        N.check(lib.w2v2_ctc_score_grad_star(N.ptr(base), V, n, N.ptr(row0_h), N.ptr(frames_h), m, N.ptr(utt), N.ptr(labels_dev),
+                                             N.ptr(label0), N.ptr(nlab_h), blank, star_score, N.ptr(coef_dev), N.ptr(logp),
+                                             N.ptr(grad_base), cap, N.current_stream()), "w2v2_ctc_score_grad_star")
+    else:
+        N.check(lib.w2v2_ctc_score_grad(N.ptr(base), V, n, N.ptr(row0_h), N.ptr(frames_h), m, N.ptr(utt), N.ptr(labels_dev),
+                                        N.ptr(label0), N.ptr(nlab_h), blank, N.ptr(coef_dev), N.ptr(logp), N.ptr(grad_base), cap,
+                                        N.current_stream()), "w2v2_ctc_score_grad")
     logp_h = logp.cpu().numpy()
     if isinstance(logits, torch.Tensor):
         return logp_h, grad_base.reshape(logits.shape)

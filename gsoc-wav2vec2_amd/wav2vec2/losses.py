@@ -11,6 +11,9 @@ The alpha/beta recursions run in the HIP library (w2v2_ctc_loss).
 
 ``expected_risk`` and ``MWERLoss`` are sequence-level losses over n-best lists: the expected number of errors under
 the list's renormalised exact CTC posteriors, with its gradient from w2v2_ctc_score_grad.  They have no counterpart in the reference.
+
+``StarCTCLoss`` and ``star_labels`` are the CTC loss for partial transcripts: label rows may hold the star, the
+wildcard label of ``alignment.forced_align``; the loss and its gradient come from w2v2_ctc_score_grad_star.
 """
 
 import math
@@ -328,6 +331,114 @@ class MWERLoss:
         self.last_total = total[0]
         if with_grad and float(self.division_factor) != 1.0:
             grad = grad / float(self.division_factor)
+        if with_total:
+            return (loss, grad, total[0]) if with_grad else (loss, total[0])
+        if with_grad:
+            return loss, grad
+        return loss
+
+    def __call__(self, labels, hidden_states):
+        return self.per_sample(labels, hidden_states, with_total=True)[1]
+
+    call = __call__
+
+
+def star_labels(texts, tokenizer, star="*", free_ends=False, vocab_size=None, pad_id=None):
+    """The label rows ``StarCTCLoss`` trains on, from partial transcripts: each text is encoded with ``tokenizer`` through
+    ``alignment.star_transcript`` -- a whitespace-separated word equal to ``star`` becomes the star label V and the word delimiter
+    next to it is dropped; ``free_ends`` puts a star before the first and after the last label; a sequence of ids is used as it is
+    and may hold V -- and the rows are padded to one length with ``pad_id``.  V is ``vocab_size`` (default: ``len(tokenizer
+    .get_vocab())``) and ``pad_id`` defaults to the tokenizer's "<pad>", the blank.  Returns an int32 numpy array (batch, max
+    length); a row with two stars next to each other raises ValueError."""
+    from .alignment import star_transcript
+    if isinstance(texts, str):
+        raise ValueError("`texts` is a list of transcripts, one per utterance")
+    vocab = tokenizer.get_vocab() if tokenizer is not None and hasattr(tokenizer, "get_vocab") else None
+    if vocab_size is None:
+        if vocab is None:
+            raise ValueError("without a tokenizer that has get_vocab(): pass vocab_size, the star's id")
+        vocab_size = len(vocab)
+    if pad_id is None:
+        if vocab is None or "<pad>" not in vocab:
+            raise ValueError("the tokenizer names no '<pad>': pass pad_id, the blank")
+        pad_id = vocab["<pad>"]
+    V, pad_id = int(vocab_size), int(pad_id)
+    rows = []
+    for i, tr in enumerate(texts):
+        ids = star_transcript(tr, V, tokenizer, star, free_ends)
+        if any(a == V and b == V for a, b in zip(ids, ids[1:])):
+            raise ValueError(f"transcript {i}: two stars next to each other; collapse them into one")
+        if any(v == pad_id for v in ids):
+            raise ValueError(f"transcript {i}: label {pad_id} is the padding (the blank)")
+        rows.append(ids)
+    width = max([len(r) for r in rows] + [1])
+    out = np.full((len(rows), width), pad_id, np.int32)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = r
+    return out
+
+
+class StarCTCLoss:
+    """The CTC loss for partial transcripts: ``nll_b = -logp_b`` with ``logp_b`` the exact star score of
+    ``decoding.ctc_score(..., star_score=star_score)``, in fp64 log space, for any frame counts and up to 8191 labels.
+
+    ``CTCLoss``'s constructor arguments and calling protocol -- ``per_sample(labels, logits, with_grad=False, with_total=False)``
+    and ``__call__`` --, so ``Trainer(model, StarCTCLoss(...))`` works as it stands.  Label rows are padded with ``pad_id`` (the
+    blank) and may hold the star's id V = ``logits.shape[-1]`` (``star_labels`` builds them from text).  Frame lengths follow
+    ``CTCLoss``'s convention (the full frame count from ``model_input_shape``) unless ``per_sample`` is given ``frame_lengths=``.
+    The gradient comes from ONE ``decoding.ctc_score_grad`` call with ``coef = -1 / division_factor``; the total is
+    ``sum_b nll_b / division_factor``.  A sample whose labels its frames cannot hold has ``nll = inf`` and no gradient.
+
+    What the loss does on star frames: in proportion to the star's occupancy it sharpens the model's own top token; it does not
+    supervise which token.  With a star ``nll`` may be negative: the star's column is not part of the softmax.
+    ``star_score = -0.5`` is the aligner's convention, not a value tuned here."""
+
+    def __init__(self, config, model_input_shape, division_factor=1, star_score=-0.5):
+        from .alignment import _check_star_score
+        self._ctc = CTCLoss(config, model_input_shape, division_factor)
+        self.pad_id = config.pad_id
+        self.division_factor = division_factor
+        self.model_input_shape = model_input_shape
+        if not float(division_factor) > 0:
+            raise ValueError(f"division_factor {division_factor} must be positive")
+        self.star_score = _check_star_score(star_score)
+
+    def per_sample(self, labels, logits, with_grad=False, with_total=False, frame_lengths=None):
+        """Per-sample loss (B,) [and d sum(loss) / d logits / division_factor] [and sum_b loss_b / division_factor]; torch CUDA
+        tensors, as ``CTCLoss.per_sample``."""
+        import torch
+        from . import decoding as D
+        if not torch.cuda.is_available():
+            raise RuntimeError("StarCTCLoss (MI355X build) needs a HIP device; there is no CPU fallback")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if not isinstance(logits, torch.Tensor):
+            logits = torch.as_tensor(np.asarray(logits, dtype=np.float32))
+        logits = logits.detach().as_subclass(torch.Tensor).to(device=dev, dtype=torch.float32).contiguous()
+        if logits.dim() != 3:
+            raise ValueError("logits must be (batch, frames, vocabulary)")
+        B, T, V = logits.shape
+        host = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels)
+        if host.ndim != 2 or host.shape[0] != B:
+            raise ValueError("labels must be (batch, max_label_len)")
+        if host.size and (host.min() < 0 or host.max() > V):
+            raise ValueError(f"labels must lie in [0, {V}] ({V} is the star): got [{host.min()}, {host.max()}]")
+        if frame_lengths is None:
+            logit_len = int(self._ctc._get_logit_length(int(self.model_input_shape[1])))
+            if logit_len > T:
+                raise ValueError(f"model_input_shape implies {logit_len} frames but logits have {T}")
+            frame_lengths = [logit_len] * B
+        frame_lengths = [int(v) for v in frame_lengths]
+        rows = [[int(v) for v in row if v != self.pad_id] for row in host]
+        div = float(self.division_factor)
+        if with_grad:
+            logp, grad = D.ctc_score_grad(logits, rows, [-1.0 / div] * B, blank=self.pad_id, frame_lengths=frame_lengths,
+                                          star_score=self.star_score)
+        else:
+            logp, grad = D.ctc_score(logits, rows, blank=self.pad_id, frame_lengths=frame_lengths, star_score=self.star_score), None
+        nll = -np.asarray(logp, np.float64)
+        loss = torch.from_numpy(nll.astype(np.float32)).to(dev)
+        total = torch.from_numpy(np.asarray(nll.sum() / div, np.float32).reshape(1)).to(dev)
+        self.last_total = total[0]
         if with_total:
             return (loss, grad, total[0]) if with_grad else (loss, total[0])
         if with_grad:

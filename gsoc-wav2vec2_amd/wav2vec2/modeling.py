@@ -788,25 +788,35 @@ class Wav2Vec2ForCTC(TFKerasModel):
             words = [word_spans(token_spans(a), delimiter_id, seconds_per_frame, vocab) for a in alignments]
         return words[0] if single else words
 
-    def score(self, waveforms, transcripts, tokenizer=None, sampling_rate=None, normalize=False):
+    def score(self, waveforms, transcripts, tokenizer=None, sampling_rate=None, normalize=False, star=None, free_ends=False,
+              star_score=-0.5):
         """Exact CTC log-probability of each transcript given its waveform, the sibling of `align`: `predict_packed(waveforms)`,
         then wav2vec2.decoding.ctc_score on the packed logits in place (blank = config.pad_id; the sum over ALL frame paths,
         -ctc_loss in fp64).  A transcript is text, encoded with `tokenizer`, or a sequence of ids.  Returns one
         (logp, logp / frames) per utterance; a transcript its frames cannot hold gives -inf.  `sampling_rate`, `normalize`: as
-        `predict_packed`."""
+        `predict_packed`.
+
+        Partial transcripts: `star`, `free_ends` and `star_score` are `align`'s.  A word equal to `star`, a star's
+        id (config.vocab_size) in an id transcript or `free_ends=True` switches the star on: ctc_score(..., star_score=star_score),
+        and the result is the score of a set of paths, never below `align`'s path score, no longer a log-probability.  Without
+        them nothing changes."""
         from .decoding import ctc_score
+        from .alignment import star_transcript
         if isinstance(transcripts, str) or len(transcripts) != len(waveforms):
             raise ValueError("one transcript per waveform")
+        use_star = star is not None or free_ends
+        V = self.config.vocab_size
         ids = []
         for i, tr in enumerate(transcripts):
             if isinstance(tr, str):
                 if tokenizer is None:
                     raise ValueError(f"transcript {i} is text: pass the tokenizer that encodes it")
-                ids.append(list(tokenizer(tr)))
+                ids.append(star_transcript(tr, V, tokenizer, star, free_ends) if use_star else list(tokenizer(tr)))
             else:
-                ids.append([int(x) for x in tr])
+                ids.append(star_transcript(tr, V, None, star, free_ends) if use_star else [int(x) for x in tr])
+        use_star = use_star or any(V in l for l in ids)          # (an id transcript that holds the star's id)
         logits = self.predict_packed(waveforms, sampling_rate, normalize)
-        logp = ctc_score(logits, ids, blank=self.config.pad_id)
+        logp = ctc_score(logits, ids, blank=self.config.pad_id, star_score=star_score if use_star else None)
         return [(float(v), float(v) / int(l.shape[0])) for v, l in zip(logp, logits)]
 
     def search(self, waveforms, phrases, tokenizer=None, sampling_rate=None, normalize=False, whole_words=True, **options):

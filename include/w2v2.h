@@ -352,6 +352,26 @@ int w2v2_ctc_score_grad(const float* logits_dev, int32_t V, int32_t n, const int
 int64_t w2v2_ctc_score_grad_workspace(int32_t n, const int32_t* frames_host, int32_t m, const int32_t* utt_of_host,
                                       const int32_t* nlabels_host, int32_t V);
 
+/* Exact CTC scoring and its gradient with the star, the wildcard label of w2v2_ctc_align_star (exact definition in
+ * csrc/score_star.hip): the arguments, checks and per-pair conventions of w2v2_ctc_score / w2v2_ctc_score_grad plus
+ *   labels_dev   may hold V, the star: a state like any other that takes at least one frame and counts as a label in the frame check
+ *   star_score   fp32, <= 0, nats per frame: a star frame emits (frame maximum + star_score) - lse.  NaN or > 0 is W2V2_EINVAL,
+ *                before anything is launched.
+ * With a star in the labels logp is the score of a set of paths, not a log-probability (it may exceed 0); it is never below the
+ * score w2v2_ctc_align_star gives for the same input.  In the gradient a star state emits the frame's top token: its occupancy is
+ * added to the lowest column that holds the frame's maximum.  A label < 0, > V or equal to the blank gives NaN.  Pairs without a
+ * star give the bits of w2v2_ctc_score / w2v2_ctc_score_grad, alone or mixed with star pairs.  The gradient's workspace holds two
+ * more arrays per frame (fp64 and int32) than w2v2_ctc_score_grad's; grouping under max_workspace_bytes changes no bit. */
+int w2v2_ctc_score_star(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host, int32_t m,
+                        const int32_t* utt_of_host, const int32_t* labels_dev, const int64_t* label0_host,
+                        const int32_t* nlabels_host, int32_t blank, float star_score, double* logp_dev, void* stream);
+int w2v2_ctc_score_grad_star(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host,
+                             int32_t m, const int32_t* utt_of_host, const int32_t* labels_dev, const int64_t* label0_host,
+                             const int32_t* nlabels_host, int32_t blank, float star_score, const double* coef_dev,
+                             double* logp_dev, float* grad_dev, int64_t max_workspace_bytes, void* stream);
+int64_t w2v2_ctc_score_grad_star_workspace(int32_t n, const int32_t* frames_host, int32_t m, const int32_t* utt_of_host,
+                                           const int32_t* nlabels_host, int32_t V);
+
 /* CTC phrase search (csrc/spot.hip): where in a recording a label string is spoken, for m (recording, phrase) pairs
  * in one call.  Model-free, with w2v2_ctc_score's addressing of recordings and pairs; asynchronous on `stream`.
  *   recording i: logits_dev rows [row0_host[i], row0_host[i] + frames_host[i]) of V fp32 (read in place; pairs share rows)
