@@ -100,6 +100,26 @@
 //    the step beside lmv / wch (one fp32 per candidate from delta[bst[j] V + c], at most 16 per thread) and used after the match; the
 //    new state is read once, by the lane that writes the entry into the next beam, where word_end is evaluated; a stay copies it.  No
 //    barrier and no atomic is added to a step; every store is a plain vector store.
+//
+// Resumable search (streaming; w2v2_ctc_beam_search_stream).  The definition above is a recursion over frames, so a
+// search may stop after any frame and go on later: the four <., ., true> instances run the SAME step body (the four <., ., false>
+// instances are the searches above, instruction for instruction) between a load and a store of the beam.
+//  * State slab, per stream, in global memory: the live BeamBuf / BeamBufWord, its half of bst, nb, a sticky `dead` flag, stable_len
+//    and stable_node.  A call with frames_done == 0 starts from the empty prefix as above; one with frames_done > 0 loads the slab
+//    into half 0 (buf[0], bst[0]) before the barrier that precedes the first step.  Step parity and the ring of log-probabilities are
+//    functions of the call-local t, so where a recording is cut changes which half an entry sits in and nothing else.  After the last
+//    step the live half goes back to the slab with plain vector stores; finalisation only reads the beam, so a call that returns
+//    hypotheses leaves the next call what a call without results would have left.
+//  * Nodes are numbered 1 + (frames_done + t) W + rank in a trie buffer the caller keeps for the stream (not in the call's scratch):
+//    same_prefix and the label walks cross into nodes of earlier calls, which stream order makes visible.
+//  * A call whose new frames hold a non-finite lse, or whose slab is dead, sets `dead`, advances nothing and reports no hypothesis, as
+//    does every later call of that stream.  A call of zero frames loads, stores and reports again.
+//  * stable_len: the length of the longest common prefix of the label strings of the nb entries after the call.  Every later entry
+//    extends a current one, so it never decreases and every hypothesis of a later call begins with those labels.  Wave 0 computes it
+//    after the state store: the entries walk their chains to the shortest entry's depth, then down in lockstep to the previous call's
+//    stable_len only, comparing LABELS across lanes (a prefix made twice has two nodes); once all chains stand on one node the rest
+//    is common.  stable_node is lane 0's node at that depth.  No atomic, no LDS, no barrier beyond those of the search above.
+//  * With a null labels array the call ends there: no -1 fill, no finalisation, no walk.
 #include "ctc_lattice.h"
 
 #include <algorithm>
@@ -123,7 +143,8 @@ struct BeamSeg {
     int64_t row0;      // first logits row
     int64_t lse0;      // first lse entry
     int64_t node0;     // first trie node
-    int32_t T, pad;
+    int32_t T;
+    int32_t done;      // frames of this stream that earlier calls searched (0 outside the resumable entry)
 };
 
 struct BeamArgs {
@@ -156,9 +177,18 @@ struct BeamBiasArgs : Base {
     int bstart;
 };
 
+// the state slabs and the stable-prefix output of the resumable instances behind the arguments of any of the four forms
+template <class Base>
+struct BeamStreamArgs : Base {
+    char* state;            // n slabs of BEAM_STATE_BYTES
+    int32_t* stable_len;    // (n)
+};
+
 template <bool WORD, bool BIAS>
-using BeamKernelArgs = std::conditional_t<BIAS, BeamBiasArgs<std::conditional_t<WORD, BeamWordArgs, BeamArgs>>,
-                                          std::conditional_t<WORD, BeamWordArgs, BeamArgs>>;
+using BeamFormArgs = std::conditional_t<BIAS, BeamBiasArgs<std::conditional_t<WORD, BeamWordArgs, BeamArgs>>,
+                                        std::conditional_t<WORD, BeamWordArgs, BeamArgs>>;
+template <bool WORD, bool BIAS, bool STREAM = false>
+using BeamKernelArgs = std::conditional_t<STREAM, BeamStreamArgs<BeamFormArgs<WORD, BIAS>>, BeamFormArgs<WORD, BIAS>>;
 
 struct BeamBuf {
     double pb[BEAM_W], pnb[BEAM_W], tot[BEAM_W], lm[BEAM_W];
@@ -172,6 +202,15 @@ struct BeamBufWord : BeamBuf {
     double dlm[BEAM_W];                         // lm and lmstate of this prefix + d (the c == d rule); dstate -1: dropped
     int wnode[BEAM_W], lmstate[BEAM_W], dstate[BEAM_W];
 };
+
+// A stream's state slab (w2v2_ctc_beam_search_stream): what a call leaves for the next one.  One size for all four forms.
+//   [0, 256)   int32 nb, dead, stable_len, stable_node
+//   [256, 512) the bias states of the entries (64 int32)
+//   [512, ..)  the live BeamBuf / BeamBufWord
+constexpr int BEAM_STATE_BST = 256, BEAM_STATE_BUF = 512;
+constexpr int BEAM_STATE_BYTES = BEAM_STATE_BUF + (int)sizeof(BeamBufWord);
+static_assert(BEAM_STATE_BYTES % 256 == 0 && sizeof(BeamBuf) % 8 == 0 && sizeof(BeamBufWord) % 8 == 0, "beam.hip: state slab layout");
+typedef u64 __attribute__((may_alias)) u64_alias;         // a beam buffer copied as 8-byte words
 
 __global__ __launch_bounds__(256) void beam_lse_kernel(BeamArgs a) {
     const BeamSeg sg = a.segs[blockIdx.y];
@@ -261,8 +300,10 @@ __device__ __forceinline__ void word_end(const BeamWordArgs& a, int wn, int st, 
 
 // WORD: the word n-gram model with a lexicon in place of the character table (the header's second part)
 // BIAS: a phrase bias on top of either (the header's third part)
-template <bool WORD, bool BIAS>
-__global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamKernelArgs<WORD, BIAS> a) {
+// STREAM: the resumable instance (the header's fourth part); what it does sits under `if constexpr (STREAM)`, and the few values it
+// shares with the common code (done, results, fresh) are compile-time constants when STREAM is false
+template <bool WORD, bool BIAS, bool STREAM>
+__global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamKernelArgs<WORD, BIAS, STREAM> a) {
     constexpr double NEG = -__builtin_inf();
     using Buf = std::conditional_t<WORD, BeamBufWord, BeamBuf>;
     __shared__ Buf buf[2];
@@ -288,12 +329,38 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamKernelArgs<WOR
     int32_t* __restrict__ out_lab = a.labels + (int64_t)blockIdx.x * nbest * a.max_len;
     const int64_t out0 = (int64_t)blockIdx.x * nbest;
 
+    // (STREAM) the slab, the frames behind this stream, the stable prefix the previous call left, and whether results are wanted
+    char* slab = nullptr;
+    int32_t* hdr = nullptr;
+    int done = 0, st_len = 0, st_node = 0;
+    bool results = true;
     bool bad = false;
+    if constexpr (STREAM) {
+        slab = a.state + (int64_t)blockIdx.x * BEAM_STATE_BYTES;
+        hdr = reinterpret_cast<int32_t*>(slab);
+        done = sg.done;
+        results = a.labels != nullptr;
+        if (done > 0) {
+            bad = hdr[1] != 0;                              // the sticky dead flag
+            st_len = hdr[2];
+            st_node = hdr[3];
+        }
+    }
     for (int t = tid; t < T; t += BEAM_NT) bad |= !(fabs(ls[t]) <= 1.7976931348623157e308);
     const int anybad = __syncthreads_or(bad);
-    for (int i = tid; i < nbest * a.max_len; i += BEAM_NT) out_lab[i] = -1;
+    if (results)
+        for (int i = tid; i < nbest * a.max_len; i += BEAM_NT) out_lab[i] = -1;
     if (anybad) {                                           // (block-uniform)
-        if (tid < nbest) {
+        if constexpr (STREAM) {                             // dead from here on: nothing advances, the stable prefix stays
+            if (tid == 0) {
+                if (done == 0) hdr[0] = 0;
+                hdr[1] = 1;
+                hdr[2] = st_len;
+                hdr[3] = st_node;
+                a.stable_len[blockIdx.x] = st_len;
+            }
+        }
+        if (results && tid < nbest) {
             a.length[out0 + tid] = -1;
             a.score[out0 + tid] = __builtin_nan("");
             a.total[out0 + tid] = __builtin_nan("");
@@ -318,7 +385,8 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamKernelArgs<WOR
 #pragma unroll
     for (int q = 0; q < 2; ++q)
         if (er[q] < BEAM_RING && er[q] < T) lpr[0][er[q]][ec[q]] = (double)lg[(int64_t)er[q] * V + ec[q]] - ls[er[q]];
-    if (tid == 0) {
+    const bool fresh = !STREAM || done == 0;
+    if (tid == 0 && fresh) {
         Buf& B = buf[0];
         B.pb[0] = 0.0;
         B.pnb[0] = NEG;
@@ -343,6 +411,16 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamKernelArgs<WOR
         if constexpr (BIAS) bst[0][0] = a.bstart;
     }
     int nb = 1;
+    if constexpr (STREAM) {
+        if (!fresh) {                                       // the beam as the previous call left it, into half 0
+            const u64_alias* src = reinterpret_cast<const u64_alias*>(slab + BEAM_STATE_BUF);
+            u64_alias* dst = reinterpret_cast<u64_alias*>(&buf[0]);
+            for (int i = tid; i < (int)(sizeof(Buf) / 8); i += BEAM_NT) dst[i] = src[i];
+            if constexpr (BIAS)
+                if (tid < BEAM_W) bst[0][tid] = reinterpret_cast<const int*>(slab + BEAM_STATE_BST)[tid];
+            nb = min(max(hdr[0], 0), BEAM_W);
+        }
+    }
     __syncthreads();
 
     for (int t = 0; t < T; ++t) {
@@ -618,7 +696,8 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamKernelArgs<WOR
                     }
                     if constexpr (BIAS) bst[(t & 1) ^ 1][cnt] = bst[t & 1][j];
                 } else {
-                    const int node = 1 + t * W + cnt;
+                    int node = 1 + t * W + cnt;
+                    if constexpr (STREAM) node = 1 + (done + t) * W + cnt;
                     nodes[node] = (u64)(uint32_t)B.node[j] << 32 | (u64)(uint32_t)c;
                     N.h[cnt] = hash_step(B.h[j], c);
                     N.hp[cnt] = B.h[j];
@@ -651,6 +730,56 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamKernelArgs<WOR
         __syncthreads();                                    // (also drains this step's node stores)
     }
 
+    if constexpr (STREAM) {
+        // the state for the next call (plain vector stores), then the stable prefix; the finalisation below only reads the beam
+        {
+            const u64_alias* src = reinterpret_cast<const u64_alias*>(&buf[T & 1]);
+            u64_alias* dst = reinterpret_cast<u64_alias*>(slab + BEAM_STATE_BUF);
+            for (int i = tid; i < (int)(sizeof(Buf) / 8); i += BEAM_NT) dst[i] = src[i];
+            if constexpr (BIAS)
+                if (tid < BEAM_W) reinterpret_cast<int*>(slab + BEAM_STATE_BST)[tid] = bst[T & 1][tid];
+        }
+        if (wave == 0) {
+            // the longest common prefix of the entries' label strings: every entry begins with the previous call's stable prefix
+            // (st_len labels), so the chains are compared from the shortest entry's depth back to depth st_len only.  Labels are
+            // compared, not nodes (a prefix made twice has two nodes); once all chains stand on ONE node the rest is common.
+            const Buf& B = buf[T & 1];
+            const bool on = lane < nb;
+            int n = on ? B.node[lane] : 0, d = on ? B.len[lane] : 0x7fffffff;
+            int minlen = d;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) minlen = min(minlen, __shfl_xor(minlen, off, 64));
+            int cand = st_len, sn = st_node;
+            if (nb > 0) {                                   // (wave-uniform)
+                while (d > minlen && n > 0) {
+                    n = (int)(node_load(nodes + n) >> 32);
+                    --d;
+                }
+                cand = minlen;
+                sn = __shfl(n, 0, 64);
+                for (int dd = minlen; dd > st_len; --dd) {
+                    const int n0 = __shfl(n, 0, 64);
+                    if (__ballot(on && n != n0) == 0) break;
+                    const u64 v = on && n > 0 ? node_load(nodes + n) : 0;
+                    const int lab = (int)(uint32_t)v, par = (int)(v >> 32);
+                    const int lab0 = __shfl(lab, 0, 64), par0 = __shfl(par, 0, 64);
+                    if (__ballot(on && lab != lab0) != 0) {
+                        cand = dd - 1;
+                        sn = par0;
+                    }
+                    n = par;
+                }
+            }
+            if (lane == 0) {
+                hdr[0] = nb;
+                hdr[1] = 0;
+                hdr[2] = cand;
+                hdr[3] = sn;
+                a.stable_len[blockIdx.x] = cand;
+            }
+        }
+        if (!results) return;
+    }
     if constexpr (WORD || BIAS) {
         // finalisation (wave 0: W <= 64): the open word ended, eos, the bias' end-of-utterance term, then the entries in descending
         // total, equal totals by beam rank
@@ -721,12 +850,34 @@ __global__ __launch_bounds__(BEAM_NT) void beam_search_kernel(BeamKernelArgs<WOR
     }
 }
 
+// what the resumable entry adds to a call: per stream the frames already searched, the state slab and the trie's place and room
+struct BeamStreamCall {
+    const int64_t* frames_done;
+    void* state;
+    u64* nodes;
+    const int64_t* node0;
+    const int64_t* node_cap;
+    int32_t* stable_len;
+};
+
+template <bool WORD, bool BIAS, class Args>
+void beam_launch_stream(const Args& form, const BeamStreamCall& sc, int n, hipStream_t s) {
+    BeamStreamArgs<Args> b{};
+    static_cast<Args&>(b) = form;
+    b.state = static_cast<char*>(sc.state);
+    b.stable_len = sc.stable_len;
+    W2V2_LAUNCH((beam_search_kernel<WORD, BIAS, true>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, b);
+}
+
 // the checks, the workspace and the launches the entries share; `a` arrives with its language model fields set; `bias` (checked by
-// the caller) or null
+// the caller) or null; `sc`: the resumable entry's arguments, null for the entries that search whole utterances
 int beam_run(BeamWordArgs& a, bool word, const w2v2_ctc_bias* bias, const float* logits, int V, int n, const int64_t* row0,
              const int32_t* frames, int blank, int beam_width, int nbest, float lm_alpha, float lm_beta, int max_len,
-             int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s) {
-    W2V2_REQUIRE(logits && row0 && frames && labels_out && length && score && total, "ctc_beam_search: null argument");
+             int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s, const BeamStreamCall* sc = nullptr) {
+    W2V2_REQUIRE(logits && row0 && frames && (labels_out || sc) && ((length && score && total) || (sc && !labels_out)),
+                 "ctc_beam_search: null argument");
+    W2V2_REQUIRE(!sc || (sc->frames_done && sc->state && sc->nodes && sc->node0 && sc->node_cap && sc->stable_len),
+                 "ctc_beam_search_stream: null argument");
     W2V2_REQUIRE(n >= 1, "ctc_beam_search: %d utterances (need at least one)", n);
     W2V2_REQUIRE(V >= 1 && V <= W2V2_BEAM_MAX_VOCAB, "ctc_beam_search: vocabulary of %d entries; 1 to %d", V, W2V2_BEAM_MAX_VOCAB);
     W2V2_REQUIRE(blank >= 0 && blank < V, "ctc_beam_search: blank index %d outside vocabulary %d", blank, V);
@@ -734,32 +885,49 @@ int beam_run(BeamWordArgs& a, bool word, const w2v2_ctc_bias* bias, const float*
                  W2V2_BEAM_MAX_WIDTH);
     W2V2_REQUIRE(nbest >= 1 && nbest <= beam_width, "ctc_beam_search: nbest %d outside [1, beam width %d]", nbest, beam_width);
     W2V2_REQUIRE(std::isfinite(lm_alpha) && std::isfinite(lm_beta), "ctc_beam_search: language model weights must be finite");
-    int Tmax = 0;
+    int Tmax = 0;           // the longest utterance of the call
+    int64_t Lmax = 0;       // the most frames a hypothesis can span: with `sc`, the earlier calls' frames included
     for (int i = 0; i < n; ++i) {
-        W2V2_REQUIRE(frames[i] >= 1, "ctc_beam_search: utterance %d has %d frames (need at least one)", i, frames[i]);
         W2V2_REQUIRE(row0[i] >= 0, "ctc_beam_search: utterance %d has a negative offset", i);
-        W2V2_REQUIRE((int64_t)frames[i] * beam_width < ((int64_t)1 << 31) - 1, "ctc_beam_search: utterance %d has too many frames (%d)",
-                     i, frames[i]);
+        if (sc) {
+            const int64_t done = sc->frames_done[i];
+            W2V2_REQUIRE(frames[i] >= 0, "ctc_beam_search_stream: stream %d is given %d frames", i, frames[i]);
+            W2V2_REQUIRE(done >= 0, "ctc_beam_search_stream: stream %d has %lld frames done", i, (long long)done);
+            W2V2_REQUIRE(done < ((int64_t)1 << 31) && (done + frames[i]) * beam_width < ((int64_t)1 << 31) - 1,
+                         "ctc_beam_search_stream: stream %d has too many frames (%lld done and %d new)", i, (long long)done, frames[i]);
+            W2V2_REQUIRE(sc->node0[i] >= 0, "ctc_beam_search_stream: stream %d has a negative node offset", i);
+            W2V2_REQUIRE((done + frames[i]) * beam_width + 1 <= sc->node_cap[i],
+                         "ctc_beam_search_stream: stream %d needs %lld trie nodes after this call, its buffer holds %lld", i,
+                         (long long)((done + frames[i]) * beam_width + 1), (long long)sc->node_cap[i]);
+            Lmax = std::max(Lmax, done + frames[i]);
+        } else {
+            W2V2_REQUIRE(frames[i] >= 1, "ctc_beam_search: utterance %d has %d frames (need at least one)", i, frames[i]);
+            W2V2_REQUIRE((int64_t)frames[i] * beam_width < ((int64_t)1 << 31) - 1, "ctc_beam_search: utterance %d has too many frames (%d)",
+                         i, frames[i]);
+            Lmax = std::max(Lmax, (int64_t)frames[i]);
+        }
         Tmax = std::max(Tmax, (int)frames[i]);
     }
-    W2V2_REQUIRE(max_len >= Tmax, "ctc_beam_search: max_len %d below the longest utterance's %d frames", max_len, Tmax);
-    W2V2_REQUIRE((int64_t)nbest * max_len < ((int64_t)1 << 31), "ctc_beam_search: nbest * max_len = %d * %d does not fit 31 bits", nbest,
-                 max_len);
+    if (labels_out) {
+        W2V2_REQUIRE(max_len >= Lmax, "ctc_beam_search: max_len %d below the longest utterance's %lld frames", max_len, (long long)Lmax);
+        W2V2_REQUIRE((int64_t)nbest * max_len < ((int64_t)1 << 31), "ctc_beam_search: nbest * max_len = %d * %d does not fit 31 bits", nbest,
+                     max_len);
+    }
     std::vector<BeamSeg> segs((size_t)n);
     int64_t out = 0, nn = 0;
     for (int i = 0; i < n; ++i) {
-        segs[i] = BeamSeg{row0[i], out, nn, frames[i], 0};
+        segs[i] = BeamSeg{row0[i], out, sc ? sc->node0[i] : nn, frames[i], sc ? (int32_t)sc->frames_done[i] : 0};
         out += frames[i];
-        nn += (int64_t)frames[i] * beam_width + 1;
+        if (!sc) nn += (int64_t)frames[i] * beam_width + 1;
     }
-    // workspace: the table | lse (fp64, sum T_i) | trie nodes (sum T_i W + 1)
+    // workspace: the table | lse (fp64, sum T_i) | trie nodes (sum T_i W + 1; with `sc` the caller's buffers hold them)
     const size_t tab_bytes = up256((size_t)n * sizeof(BeamSeg)), lse_bytes = up256((size_t)out * sizeof(double));
     void* raw = nullptr;
     if (int e = stream_scratch(SCRATCH_BEAM, s, tab_bytes + lse_bytes + (size_t)nn * sizeof(u64), &raw)) return e;
     a.logits = logits;
     a.segs = static_cast<const BeamSeg*>(raw);
     a.lse = reinterpret_cast<double*>(static_cast<char*>(raw) + tab_bytes);
-    a.nodes = reinterpret_cast<u64*>(static_cast<char*>(raw) + tab_bytes + lse_bytes);
+    a.nodes = sc ? sc->nodes : reinterpret_cast<u64*>(static_cast<char*>(raw) + tab_bytes + lse_bytes);
     a.labels = labels_out;
     a.length = length;
     a.score = score;
@@ -774,21 +942,25 @@ int beam_run(BeamWordArgs& a, bool word, const w2v2_ctc_bias* bias, const float*
     if (int e = staged_upload(SCRATCH_BEAM, s, raw, {{segs.data(), (size_t)n * sizeof(BeamSeg), 0}}, (size_t)16 << 10)) return e;
     // (work for the profile: about 4 fp64 operations per candidate and step; the logits read once by the lse pass)
     ProfScope ps(nullptr, FAM_CTC, 4.0 * (double)out * beam_width * V, 4.0 * (double)out * V, s);
-    W2V2_LAUNCH(beam_lse_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);
+    if (Tmax > 0) W2V2_LAUNCH(beam_lse_kernel, dim3((unsigned)((Tmax + 3) / 4), (unsigned)n), dim3(256), 0, s, a);     // (a stream call may bring no frame)
     if (bias && word) {
         BeamBiasArgs<BeamWordArgs> b{};
         static_cast<BeamWordArgs&>(b) = a;
         b.bnext = bias->next_dev, b.bdelta = bias->delta_dev, b.bfinal = bias->final_dev, b.bstart = bias->start_state;
-        W2V2_LAUNCH((beam_search_kernel<true, true>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, b);
+        if (sc) beam_launch_stream<true, true>(b, *sc, n, s);
+        else W2V2_LAUNCH((beam_search_kernel<true, true, false>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, b);
     } else if (bias) {
         BeamBiasArgs<BeamArgs> b{};
         static_cast<BeamArgs&>(b) = a;
         b.bnext = bias->next_dev, b.bdelta = bias->delta_dev, b.bfinal = bias->final_dev, b.bstart = bias->start_state;
-        W2V2_LAUNCH((beam_search_kernel<false, true>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, b);
+        if (sc) beam_launch_stream<false, true>(b, *sc, n, s);
+        else W2V2_LAUNCH((beam_search_kernel<false, true, false>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, b);
     } else if (word) {
-        W2V2_LAUNCH((beam_search_kernel<true, false>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, a);
+        if (sc) beam_launch_stream<true, false>(a, *sc, n, s);
+        else W2V2_LAUNCH((beam_search_kernel<true, false, false>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, a);
     } else {
-        W2V2_LAUNCH((beam_search_kernel<false, false>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, static_cast<const BeamArgs&>(a));
+        if (sc) beam_launch_stream<false, false>(static_cast<const BeamArgs&>(a), *sc, n, s);
+        else W2V2_LAUNCH((beam_search_kernel<false, false, false>), dim3((unsigned)n), dim3(BEAM_NT), 0, s, static_cast<const BeamArgs&>(a));
     }
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
@@ -871,6 +1043,30 @@ int launch_ctc_beam_search_biased(const float* logits, int V, int n, const int64
     if (int e = word_lm ? word_args(a, V, blank, word_lm, delim, unk_penalty, score_eos) : char_args(a, V, lm_table, lm_order)) return e;
     return beam_run(a, word_lm != nullptr, bias, logits, V, n, row0, frames, blank, beam_width, nbest, lm_alpha, lm_beta, max_len,
                     labels_out, length, score, total, s);
+}
+
+int64_t ctc_beam_stream_state_bytes() { return BEAM_STATE_BYTES; }
+
+int launch_ctc_beam_search_stream(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int64_t* frames_done,
+                                  int blank, int beam_width, int nbest, const float* lm_table, int lm_order, const w2v2_word_lm* word_lm,
+                                  int delim, float lm_alpha, float lm_beta, float unk_penalty, int score_eos, const w2v2_ctc_bias* bias,
+                                  void* state, uint64_t* nodes, const int64_t* node0, const int64_t* node_cap, int max_len,
+                                  int32_t* labels_out, int32_t* length, double* score, double* total, int32_t* stable_len, hipStream_t s) {
+    if (bias) {
+        W2V2_REQUIRE(bias->next_dev && bias->delta_dev && bias->final_dev, "ctc_beam_search_stream: null bias array");
+        W2V2_REQUIRE(bias->n_states >= 1 && bias->n_states <= W2V2_BIAS_MAX_STATES, "ctc_beam_search_stream: %d bias states; 1 to %d",
+                     bias->n_states, W2V2_BIAS_MAX_STATES);
+        W2V2_REQUIRE(bias->start_state >= 0 && bias->start_state < bias->n_states, "ctc_beam_search_stream: bias start state %d outside [0, %d)",
+                     bias->start_state, bias->n_states);
+        W2V2_REQUIRE(V < 1 || (int64_t)bias->n_states * V < ((int64_t)1 << 31),
+                     "ctc_beam_search_stream: bias of %d states times %d labels does not fit 31 bits", bias->n_states, V);
+    }
+    W2V2_REQUIRE(!(word_lm && lm_table), "ctc_beam_search_stream: both a word model and a character table given");
+    BeamWordArgs a{};
+    if (int e = word_lm ? word_args(a, V, blank, word_lm, delim, unk_penalty, score_eos) : char_args(a, V, lm_table, lm_order)) return e;
+    const BeamStreamCall sc{frames_done, state, reinterpret_cast<u64*>(nodes), node0, node_cap, stable_len};
+    return beam_run(a, word_lm != nullptr, bias, logits, V, n, row0, frames, blank, beam_width, nbest, lm_alpha, lm_beta, max_len,
+                    labels_out, length, score, total, s, &sc);
 }
 
 }  // namespace w2v2

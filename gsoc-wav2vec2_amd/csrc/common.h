@@ -538,6 +538,14 @@ int launch_ctc_beam_search_biased(const float* logits, int V, int n, const int64
                                   int beam_width, int nbest, const float* lm_table, int lm_order, const w2v2_word_lm* word_lm, int delim,
                                   float lm_alpha, float lm_beta, float unk_penalty, int score_eos, const w2v2_ctc_bias* bias, int max_len,
                                   int32_t* labels_out, int32_t* length, double* score, double* total, hipStream_t s);
+// any of the four forms, resumable (w2v2_ctc_beam_search_stream): stream i goes on behind its frames_done_i frames from its state slab,
+// its trie in nodes[node0_i, node0_i + node_cap_i); labels_out may be null (the call then only advances the state)
+int64_t ctc_beam_stream_state_bytes();
+int launch_ctc_beam_search_stream(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, const int64_t* frames_done,
+                                  int blank, int beam_width, int nbest, const float* lm_table, int lm_order, const w2v2_word_lm* word_lm,
+                                  int delim, float lm_alpha, float lm_beta, float unk_penalty, int score_eos, const w2v2_ctc_bias* bias,
+                                  void* state, uint64_t* nodes, const int64_t* node0, const int64_t* node_cap, int max_len,
+                                  int32_t* labels_out, int32_t* length, double* score, double* total, int32_t* stable_len, hipStream_t s);
 
 // ---- device helpers ---------------------------------------------------------
 #ifdef __HIPCC__

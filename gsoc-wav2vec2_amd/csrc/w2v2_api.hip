@@ -633,6 +633,19 @@ int w2v2_ctc_beam_search_biased(const float* logits, int32_t V, int32_t n, const
                                          reinterpret_cast<hipStream_t>(stream));
 }
 
+int64_t w2v2_ctc_beam_stream_state_bytes(void) { return ctc_beam_stream_state_bytes(); }
+
+int w2v2_ctc_beam_search_stream(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames,
+                                const int64_t* frames_done, int32_t blank, int32_t beam_width, int32_t nbest, const float* lm_table,
+                                int32_t lm_order, const w2v2_word_lm* word_lm, int32_t delim, float lm_alpha, float lm_beta,
+                                float unk_penalty, int32_t score_eos, const w2v2_ctc_bias* bias, void* state, uint64_t* nodes,
+                                const int64_t* node0, const int64_t* node_cap, int32_t max_len, int32_t* labels_out, int32_t* length,
+                                double* score, double* total, int32_t* stable_len, void* stream) {
+    return launch_ctc_beam_search_stream(logits, V, n, row0, frames, frames_done, blank, beam_width, nbest, lm_table, lm_order, word_lm,
+                                         delim, lm_alpha, lm_beta, unk_penalty, score_eos, bias, state, nodes, node0, node_cap, max_len,
+                                         labels_out, length, score, total, stable_len, reinterpret_cast<hipStream_t>(stream));
+}
+
 int w2v2_ctc_pause_cuts(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t blank,
                         int32_t delim, float margin, int32_t min_pause, int32_t max_cuts, int32_t* cut, int32_t* pause, int32_t* count,
                         void* stream) {

@@ -116,7 +116,10 @@ PROTOTYPES = {
                                              C.c_float, _I32, _I32, _P, _P, _P, _P, _P]),
     "w2v2_ctc_beam_search_biased": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _I32, C.POINTER(W2V2WordLM), _I32, C.c_float,
                                               C.c_float, C.c_float, _I32, C.POINTER(W2V2CtcBias), _I32, _P, _P, _P, _P, _P]),
-    "w2v2_ctc_pause_cuts": (C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, C.c_float, _I32, _I32, _P, _P, _P, _P]),
+    "w2v2_ctc_beam_stream_state_bytes": (_I64, []),
+    "w2v2_ctc_beam_search_stream": (C.c_int, [_P, _I32, _I32, _P, _P, _P, _I32, _I32, _I32, _P, _I32, C.POINTER(W2V2WordLM), _I32, C.c_float,
+                                              C.c_float, C.c_float, _I32, C.POINTER(W2V2CtcBias), _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "w2v2_ctc_pause_cuts":(C.c_int, [_P, _I32, _I32, _P, _P, _I32, _I32, C.c_float, _I32, _I32, _P, _P, _P, _P]),
     "w2v2_edit_distance": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     "w2v2_resample_design": (C.c_int, [_I32, _I32, _I32, C.c_double, C.c_double, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32),
                                        C.POINTER(_I32), _P, _I64]),

@@ -11,6 +11,10 @@ with a lexicon that spells its words in the model's labels (w2v2_ctc_beam_search
 ``ContextBias`` is a list of phrases the search should prefer (contextual biasing, "hotwords"), compiled into an automaton that
 the kernel walks beside either language model or none (w2v2_ctc_beam_search_biased).
 
+``BeamStream`` is ``beam_search`` over logits that arrive in pieces: the beams stay on the device between calls, any chunking gives
+the bits of one call, and every call reports how much of the transcript can no longer change (w2v2_ctc_beam_search_stream;
+DESIGN.md §25).
+
 ``ctc_score`` is the exact CTC log-probability of label sequences given logits (the sum over all frame paths, a HIP kernel);
 ``rescore`` replaces the beam's lower bounds in n-best lists by it; ``hypothesis_posteriors`` and ``word_confidence`` turn the
 rescored lists into probabilities of the hypotheses and of the best hypothesis' words (host code over a few numbers).
@@ -829,6 +833,141 @@ def _hypotheses(n, nbest, labels, length, score, total):
     score_h, total_h = score.cpu().numpy(), total.cpu().numpy()
     return [[Hypothesis(tuple(int(v) for v in labels_h[i, k, :length_h[i, k]]), float(score_h[i, k]), float(total_h[i, k]))
              for k in range(nbest) if length_h[i, k] >= 0] for i in range(n)]
+
+
+class StreamStep(NamedTuple):
+    hypotheses: object  # the stream's n best Hypothesis so far, best first (None when the call asked for no results)
+    stable_len: int     # leading labels that every entry of the beam shares: no later call can change them
+    frames_done: int    # frames of the stream searched so far
+
+
+class BeamStream:
+    """The beam search of ``beam_search`` over logits that arrive in pieces (w2v2_ctc_beam_search_stream): ``n``
+    independent streams, each with its beam kept on the device between calls.  Feeding a stream's frames in any chunking -- empty
+    chunks included -- gives, bit for bit, what one ``beam_search`` call over all of them gives.
+
+    ``lm``, ``bias``, ``beam_width``, ``nbest``, ``blank`` and ``vocab_size`` are fixed for the object's life (the kernel trusts
+    that they do not change within a stream).  The object owns per stream a state slab, a trie buffer and the count of frames
+    done.  A trie buffer starts with room for ``initial_frames`` frames and doubles, by allocate-and-copy on the current torch
+    stream, when the next call would not fit; should the buffers of all streams then exceed ``max_workspace_bytes`` (None: 8 GiB)
+    the call raises MemoryError before anything is allocated.  A stream that meets a NaN or +inf logit is dead: it returns no
+    hypothesis from then on, until ``reset``."""
+
+    DEFAULT_MAX_WORKSPACE = 8 << 30
+
+    def __init__(self, n, vocab_size, beam_width=16, nbest=1, blank=0, lm=None, bias=None, max_workspace_bytes=None, initial_frames=256):
+        import torch
+        n, V = int(n), int(vocab_size)
+        beam_width, nbest, blank, initial_frames = int(beam_width), int(nbest), int(blank), int(initial_frames)
+        if n < 1:
+            raise ValueError(f"{n} streams; at least one")
+        _check_args(V, beam_width, nbest, blank, lm, bias)
+        if initial_frames < 1:
+            raise ValueError(f"initial_frames {initial_frames}: at least one")
+        cap = self.DEFAULT_MAX_WORKSPACE if max_workspace_bytes is None else int(max_workspace_bytes)
+        if cap < 1:
+            raise ValueError(f"max_workspace_bytes {cap} must be positive")
+        self.n, self.vocab_size, self.beam_width, self.nbest, self.blank, self.lm, self.bias = n, V, beam_width, nbest, blank, lm, bias
+        self.max_workspace_bytes = cap
+        self._cap_frames = [initial_frames] * n
+        if 8 * sum(self._entries(c) for c in self._cap_frames) > cap:
+            raise MemoryError(f"BeamStream: {n} streams of {initial_frames} frames at width {beam_width} need "
+                              f"{8 * sum(self._entries(c) for c in self._cap_frames)} bytes of trie; max_workspace_bytes is {cap}")
+        self._lib = N.load()
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self._state = torch.zeros((n, int(self._lib.w2v2_ctc_beam_stream_state_bytes())), dtype=torch.uint8, device=self.device)
+        self._nodes = [torch.zeros(self._entries(c), dtype=torch.int64, device=self.device) for c in self._cap_frames]
+        self._stable = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self._empty = torch.zeros((1, V), dtype=torch.float32, device=self.device)
+        self.frames_done = np.zeros(n, np.int64)
+
+    def _entries(self, frames):
+        return int(frames) * self.beam_width + 1
+
+    def reset(self, i):
+        """Start stream ``i`` again from the empty prefix (its buffers are kept)."""
+        if not 0 <= int(i) < self.n:
+            raise ValueError(f"stream {i} outside [0, {self.n})")
+        self.frames_done[int(i)] = 0
+
+    def _grow(self, need_frames):
+        """trie room for ``need_frames[i]`` frames of stream i: doubled until it fits, the nodes written so far copied"""
+        import torch
+        new = list(self._cap_frames)
+        for i, f in enumerate(need_frames):
+            while new[i] < f:
+                new[i] *= 2
+        if new == self._cap_frames:
+            return
+        total = 8 * sum(self._entries(c) for c in new)
+        if total > self.max_workspace_bytes:
+            grown = ", ".join(f"stream {i}: {f} frames" for i, f in enumerate(need_frames) if new[i] != self._cap_frames[i])
+            raise MemoryError(f"BeamStream: {grown} at width {self.beam_width} need {total} bytes of trie in all; "
+                              f"max_workspace_bytes is {self.max_workspace_bytes}")
+        for i, c in enumerate(new):
+            if c != self._cap_frames[i]:
+                buf = torch.zeros(self._entries(c), dtype=torch.int64, device=self.device)
+                used = self._entries(min(int(self.frames_done[i]), self._cap_frames[i]))
+                buf[:used].copy_(self._nodes[i][:used])
+                self._nodes[i], self._cap_frames[i] = buf, c
+
+    def advance(self, logits, results=True):
+        """Search the next frames of every stream: ``logits`` holds one (T_i, V) tensor or None (no new frame) per stream, read in
+        place where ``beam_search`` would read them in place.  Returns one ``StreamStep(hypotheses, stable_len, frames_done)`` per
+        stream; the hypotheses are those of everything searched so far, as ``beam_search`` would return them had the utterance
+        ended here (an empty list for a dead stream or one without a hypothesis).  ``results=False`` only advances the beams
+        (``hypotheses`` is None): the call skips the walk that writes the transcripts."""
+        import ctypes
+        import torch
+        from .alignment import _logits_base
+        if isinstance(logits, torch.Tensor) and logits.dim() == 2 and self.n == 1:
+            logits = [logits]
+        logits = list(logits)
+        if len(logits) != self.n:
+            raise ValueError(f"{len(logits)} entries for {self.n} streams")
+        n, V = self.n, self.vocab_size
+        for i, l in enumerate(logits):
+            if l is not None and (not isinstance(l, torch.Tensor) or l.dim() != 2 or int(l.shape[1]) != V):
+                raise ValueError(f"stream {i}: logits must be a (T_i, {V}) tensor or None")
+        have = [i for i, l in enumerate(logits) if l is not None and int(l.shape[0]) > 0]
+        row0_h, frames_h = np.zeros(n, np.int64), np.zeros(n, np.int32)
+        base = self._empty
+        if have:
+            base, row0, lens = _logits_base([logits[i] for i in have], None)
+            if base.device != self.device:
+                raise ValueError(f"the logits live on {base.device}, the streams on {self.device}")
+            row0_h[have], frames_h[have] = row0, lens
+        after = self.frames_done + frames_h
+        if int((after * self.beam_width).max()) >= 2 ** 31 - 1:
+            raise ValueError(f"a stream would reach {int(after.max())} frames: frames * beam_width must stay below 2^31 - 1")
+        self._grow(after.tolist())
+        lo = min(t.data_ptr() for t in self._nodes)
+        node0_h = np.asarray([(t.data_ptr() - lo) // 8 for t in self._nodes], np.int64)
+        cap_h = np.asarray([t.numel() for t in self._nodes], np.int64)
+        done_h = np.ascontiguousarray(self.frames_done)
+        lm, bias = self.lm, self.bias
+        word = isinstance(lm, WordNgramLM)
+        bst, _keep_bias = bias.device_arrays(self.device) if bias is not None else (None, None)
+        st, _keep = lm.device_arrays(self.device) if word else (None, None)
+        table = lm.device_table(self.device) if lm is not None and not word else None
+        labels = length = score = total = None
+        max_len = max(1, int(after.max()))
+        if results:
+            labels = torch.empty((n, self.nbest, max_len), dtype=torch.int32, device=self.device)
+            length = torch.empty((n, self.nbest), dtype=torch.int32, device=self.device)
+            score = torch.empty((n, self.nbest), dtype=torch.float64, device=self.device)
+            total = torch.empty((n, self.nbest), dtype=torch.float64, device=self.device)
+        N.check(self._lib.w2v2_ctc_beam_search_stream(
+            N.ptr(base), V, n, N.ptr(row0_h), N.ptr(frames_h), N.ptr(done_h), self.blank, self.beam_width, self.nbest, N.ptr(table),
+            1 if lm is None or word else lm.order, ctypes.byref(st) if word else None, lm.delimiter if word else 0,
+            lm.alpha if lm is not None else 0.0, lm.beta if lm is not None else 0.0, lm.unk_penalty if word else 0.0,
+            int(lm.score_eos) if word else 0, ctypes.byref(bst) if bias is not None else None, N.ptr(self._state), ctypes.c_void_p(lo),
+            N.ptr(node0_h), N.ptr(cap_h), max_len, N.ptr(labels), N.ptr(length), N.ptr(score), N.ptr(total), N.ptr(self._stable),
+            N.current_stream()), "w2v2_ctc_beam_search_stream")
+        self.frames_done = after
+        stable = self._stable.cpu().numpy()
+        hyps = _hypotheses(n, self.nbest, labels, length, score, total) if results else [None] * n
+        return [StreamStep(hyps[i], int(stable[i]), int(after[i])) for i in range(n)]
 
 
 class Transcript(NamedTuple):

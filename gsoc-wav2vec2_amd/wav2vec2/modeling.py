@@ -956,3 +956,28 @@ class Wav2Vec2ForCTC(TFKerasModel):
         return decode_long(logits, tokenizer, beam_width=beam_width, nbest=nbest, lm=lm, blank=self.config.pad_id, timestamps=timestamps,
                            seconds_per_frame=seconds_per_frame, rescore=rescore, confidence=confidence, posterior_scale=posterior_scale,
                            bias=bias, **cut_options)
+
+    def stream(self, tokenizer, n_streams=1, window_s=8.0, margin_s=2.0, beam_width=16, nbest=1, lm=None, bias=None, normalize=True,
+               keep_logits=False, sampling_rate=None):
+        """Transcribe audio while it arrives: a wav2vec2.streaming.StreamingSession over `n_streams` independent recordings.
+        `session.feed(chunks)` takes one 1-D chunk of 16 kHz samples (or None) per stream, runs every window of `predict_long`'s
+        plan that is complete, of all streams, in one windowed forward and one resumed beam search
+        (wav2vec2.decoding.BeamStream), and returns per stream Partial(text, stable_text, ids, stable_len, frames, seconds):
+        `text` the best hypothesis of everything decoded so far, `stable_text` the part of it no later audio can change (the
+        prefix every entry of the beam shares; it only ever grows).  `session.finish(timestamps=False)` decodes what was held
+        back and returns one wav2vec2.decoding.Transcript per stream: text and ids are, bit for bit, those of `beam_search` on
+        `predict_long(recording, window_s, margin_s, normalize)` -- the chunking changes nothing.  `timestamps=True` needs
+        `keep_logits=True` (the session then keeps its logits; `session.logits(i)` returns them).
+        `window_s` / `margin_s`: as `predict_long`.  The defaults (8 s, 2 s) are a convention, not tuned values: nobody has
+        measured their effect on the word error rate.  They set the latency: with H = window_s - 2 margin_s, the frames of
+        seconds [k H + margin_s, (k + 1) H + margin_s) are decoded once more than k H + window_s seconds are in, so a word waits
+        at most H + margin_s seconds (6 s at the defaults) plus one chunk before it shows in `text`; how soon it shows in
+        `stable_text` depends on the beam.
+        `lm`, `bias`, `beam_width`, `nbest`: as `transcribe`, fixed for the session; a language model sees the whole recording as
+        one utterance.  16 kHz input only (`sampling_rate` other than None / 16000: ValueError; a resampler that carries its
+        filter state across chunks does not exist here).  Precision modes as `predict_long` ("bf16" raises).  No pause
+        segmentation, rescoring or confidence in a session."""
+        from .streaming import StreamingSession
+        return StreamingSession(self, tokenizer, n_streams=n_streams, window_s=window_s, margin_s=margin_s, beam_width=beam_width,
+                                nbest=nbest, lm=lm, bias=bias, normalize=normalize, keep_logits=keep_logits,
+                                sampling_rate=sampling_rate)

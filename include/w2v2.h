@@ -496,6 +496,40 @@ int w2v2_ctc_beam_search_biased(const float* logits_dev, int32_t V, int32_t n, c
                                 int32_t score_eos, const w2v2_ctc_bias* bias, int32_t max_len, int32_t* labels_out_dev,
                                 int32_t* length_dev, double* score_dev, double* total_dev, void* stream);
 
+/* The same search, RESUMABLE (streaming; DESIGN.md §25, exact definition in csrc/beam.hip): any of the four forms above -- no model or
+ * a character table (lm_table_dev, lm_order), or a word model (word_lm; lm_table_dev then NULL), each with or without a phrase bias
+ * (`bias` may be NULL) -- over frames that arrive in pieces.  Stream i has searched frames_done_host[i] frames in earlier calls; this
+ * call searches the frames_host[i] >= 0 rows from row0_host[i] on as the frames behind them and leaves the stream ready for the next
+ * call.  Cutting T frames into calls in any way -- calls of zero frames included -- gives the bits of one call of T frames, and one call
+ * from frames_done = 0 gives the bits of the entry of that form above.
+ *   state_dev     n slabs of w2v2_ctc_beam_stream_state_bytes() bytes, slab i stream i's: the beam between two calls, written by every
+ *                 call, read when frames_done_i > 0 (a call with frames_done_i == 0 starts the stream and needs no initialised slab)
+ *   nodes_dev     the prefix tries: stream i owns entries [node0_host[i], node0_host[i] + node_cap_host[i]) and needs
+ *                 (frames_done_i + frames_i) * beam_width + 1 of them after this call; the entries written by earlier calls must still be
+ *                 there (a caller that moves a stream to a larger buffer copies them)
+ *   labels_out_dev (n, nbest, max_len) or NULL.  Given: the hypotheses of everything searched so far, as the entries above would return
+ *                 them had the utterance ended here (open word ended, eos, end-of-utterance bias term), with length_dev, score_dev and
+ *                 total_dev; returning them does not disturb the state.  NULL: the call only advances the state (length_dev, score_dev
+ *                 and total_dev are not written and may be NULL).
+ *   stable_len_dev (n) int32, always written: the number of leading labels that all entries of stream i's beam share after this call.
+ *                 Every hypothesis any later call returns for the stream begins with those labels, and the number never decreases.
+ * A stream that meets a frame with a non-finite log-sum-exp (a NaN or +inf logit, a frame of -inf only) is DEAD from that call on:
+ * the call and every later one advance nothing and report no hypothesis (length -1, score = total = NaN), stable_len keeps its value;
+ * the other streams of the call are unaffected.  Starting again with frames_done_i == 0 revives it.
+ * W2V2_EINVAL with a message, before anything is launched: every check of the entry of the chosen form (frames_i == 0 is legal here),
+ * frames_i < 0, frames_done_i < 0, node0_i < 0, (frames_done_i + frames_i) * beam_width + 1 > node_cap_i,
+ * (frames_done_i + frames_i) * beam_width >= 2^31 - 1, and, with labels_out_dev, max_len < frames_done_i + frames_i.  The CONTENTS of
+ * the slabs, and that V, blank, beam_width, the model and the bias are the same in all calls of a stream, are trusted
+ * (wav2vec2.decoding.BeamStream guards them).  Enqueued on `stream` like the entries above; calls of one stream must be ordered. */
+int64_t w2v2_ctc_beam_stream_state_bytes(void);   /* per stream, one size for all four forms, a multiple of 256 */
+int w2v2_ctc_beam_search_stream(const float* logits_dev, int32_t V, int32_t n, const int64_t* row0_host, const int32_t* frames_host,
+                                const int64_t* frames_done_host, int32_t blank, int32_t beam_width, int32_t nbest,
+                                const float* lm_table_dev, int32_t lm_order, const w2v2_word_lm* word_lm, int32_t delim,
+                                float lm_alpha, float lm_beta, float unk_penalty, int32_t score_eos, const w2v2_ctc_bias* bias /* may be NULL */,
+                                void* state_dev /* n slabs */, uint64_t* nodes_dev, const int64_t* node0_host, const int64_t* node_cap_host,
+                                int32_t max_len, int32_t* labels_out_dev /* may be NULL */, int32_t* length_dev, double* score_dev,
+                                double* total_dev, int32_t* stable_len_dev, void* stream);
+
 /* Pause cuts (exact definition in csrc/segment.hip and, in numpy, tests/longform_reference.py): where the logits
  * of a long recording can be cut into utterance-sized pieces for w2v2_ctc_beam_search and w2v2_ctc_align.  Model-free, with their
  * addressing:  utterance i: logits_dev rows [row0_host[i], row0_host[i] + frames_host[i]) of V fp32.
