@@ -481,27 +481,20 @@ int launch_ctc_align_long(const float* logits, int V, int n, const int64_t* row0
                           hipStream_t s, bool star = false, float star_score = 0.f);
 int64_t ctc_align_long_workspace(int n, const int32_t* frames, const int32_t* nlabels, int strip_pairs, int panel_frames,
                                  bool star = false);
-// exact CTC scoring (score.hip; w2v2_ctc_score): the same addressing of the logits; pair j = utterance utt_of[j] against labels
-// [label0_j, label0_j + nlabels_j); one fp64 log-probability per pair, in the caller's order
+// exact CTC scoring (score.hip, with the definitions; w2v2_ctc_score, w2v2_ctc_score_star): the same addressing of the logits; pair
+// j = utterance utt_of[j] against labels [label0_j, label0_j + nlabels_j); one fp64 log-probability per pair, in the caller's
+// order.  star: label V is the wildcard, star_score <= 0 its penalty per frame
 int launch_ctc_score(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int m, const int32_t* utt_of,
-                     const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank, double* logp, hipStream_t s);
-// its gradient (score_grad.hip; w2v2_ctc_score_grad): grad rows, addressed like the logits, = sum_j coef_j d logp_j / d logits over
-// each utterance's pairs; utterances in groups whose workspace fits max_workspace_bytes (0: 8 GiB).  ctc_score_grad_workspace: the
-// bytes of one pass over the whole call (host only; a negative W2V2_E* for bad shapes)
+                     const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank, bool star, float star_score,
+                     double* logp, hipStream_t s);
+// its gradient (w2v2_ctc_score_grad, w2v2_ctc_score_grad_star): grad rows, addressed like the logits, = sum_j coef_j d logp_j /
+// d logits over each utterance's pairs; utterances in groups whose workspace fits max_workspace_bytes (0: 8 GiB).
+// ctc_score_grad_workspace: the bytes of one pass over the whole call (host only; a negative W2V2_E* for bad shapes); with the star
+// it also holds the star's emission and the top token of every frame
 int launch_ctc_score_grad(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int m, const int32_t* utt_of,
-                          const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank, const double* coef,
-                          double* logp, float* grad, int64_t max_workspace_bytes, hipStream_t s);
-int64_t ctc_score_grad_workspace(int n, const int32_t* frames, int m, const int32_t* utt_of, const int32_t* nlabels, int V);
-// ... both with the star, the wildcard label V (score_star.hip; w2v2_ctc_score_star, w2v2_ctc_score_grad_star; the definition in
-// score_star.hip): star_score <= 0; the gradient's workspace also holds the star's emission and the top token of every frame
-int launch_ctc_score_star(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int m, const int32_t* utt_of,
-                          const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank, float star_score,
-                          double* logp, hipStream_t s);
-int launch_ctc_score_grad_star(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int m,
-                               const int32_t* utt_of, const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank,
-                               float star_score, const double* coef, double* logp, float* grad, int64_t max_workspace_bytes,
-                               hipStream_t s);
-int64_t ctc_score_grad_star_workspace(int n, const int32_t* frames, int m, const int32_t* utt_of, const int32_t* nlabels, int V);
+                          const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int blank, bool star, float star_score,
+                          const double* coef, double* logp, float* grad, int64_t max_workspace_bytes, hipStream_t s);
+int64_t ctc_score_grad_workspace(int n, const int32_t* frames, int m, const int32_t* utt_of, const int32_t* nlabels, int V, bool star);
 // CTC phrase search (spot.hip; w2v2_ctc_spot): the same addressing and pairs; per pair max_hits slots of (score, begin, end), the
 // true count, and optionally z_t and c_t of every frame from trace0_j on (-1: none)
 int launch_ctc_spot(const float* logits, int V, int n, const int64_t* row0, const int32_t* frames, int m, const int32_t* utt_of,

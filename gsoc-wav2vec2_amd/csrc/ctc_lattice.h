@@ -35,47 +35,12 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 
 // The frame log-sum-exp, the body of every *_lse_kernel: blocks of 256 threads, one wave per frame, grid.x covers the frames.
 // lse[t] of frame t < T of the utterance whose logits begin at row0: the fp32 max over lane-strided columns and a butterfly, then
-// lane-strided fp64 sums of exp(x - max) and a butterfly, then max + log(sum).  One order of operations, so one set of bits.
-__device__ __forceinline__ void frame_lse(const float* logits, int V, int64_t row0, int T, double* lse) {
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= T) return;
-    const int lane = threadIdx.x & 63;
-    const float* __restrict__ r = logits + (row0 + t) * V;
-    float m = -INFINITY;
-    for (int v = lane; v < V; v += 64) m = fmaxf(m, r[v]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    double acc = 0.0;
-    for (int v = lane; v < V; v += 64) acc += exp((double)r[v] - (double)m);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (lane == 0) lse[t] = (double)m + log(acc);
-}
-
-// frame_lse that also yields the frame's maximum (the star emission of the aligners): the same operations in the
-// same order, so lse[t] has frame_lse's bits.  Returns the wave's frame t (-1: none) and, in every lane, m = the fp32 maximum of
-// the frame's V logits (fmaxf: a NaN logit is ignored; -inf when all are NaN).
-__device__ __forceinline__ int frame_lse_max(const float* logits, int V, int64_t row0, int T, double* lse, float& m) {
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    m = -INFINITY;
-    if (t >= T) return -1;
-    const int lane = threadIdx.x & 63;
-    const float* __restrict__ r = logits + (row0 + t) * V;
-    for (int v = lane; v < V; v += 64) m = fmaxf(m, r[v]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    double acc = 0.0;
-    for (int v = lane; v < V; v += 64) acc += exp((double)r[v] - (double)m);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (lane == 0) lse[t] = (double)m + log(acc);
-    return t;
-}
-
-// frame_lse_max that also yields the frame's top token (the star of the exact scorer and its gradient): lse[t] and m
-// by the same operations in the same order, then, in every lane, a = the lowest column index whose logit equals m (V when none
-// compares equal: a frame of NaN only, whose lse is not finite anyway).
-__device__ __forceinline__ int frame_lse_max_arg(const float* logits, int V, int64_t row0, int T, double* lse, float& m, int& a) {
+// lane-strided fp64 sums of exp(x - max) and a butterfly, then max + log(sum).  One order of operations, so one set of bits,
+// whatever else a caller asks for.  Returns the wave's frame t (-1: none) and, in every lane, m = the fp32 maximum of the frame's
+// V logits (fmaxf: a NaN logit is ignored; -inf when all are NaN) and, with ARG, a = the lowest column index whose logit equals m
+// (V when none compares equal: a frame of NaN only, whose lse is not finite anyway).
+template <bool ARG>
+__device__ __forceinline__ int frame_lse_body(const float* logits, int V, int64_t row0, int T, double* lse, float& m, int& a) {
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     m = -INFINITY;
     a = V;
@@ -90,10 +55,27 @@ __device__ __forceinline__ int frame_lse_max_arg(const float* logits, int V, int
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
     if (lane == 0) lse[t] = (double)m + log(acc);
-    for (int v = lane; v < V; v += 64) a = min(a, r[v] == m ? v : V);
+    if constexpr (ARG) {
+        for (int v = lane; v < V; v += 64) a = min(a, r[v] == m ? v : V);
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a = min(a, __shfl_xor(a, off, 64));
+        for (int off = 32; off > 0; off >>= 1) a = min(a, __shfl_xor(a, off, 64));
+    }
     return t;
+}
+// lse[t] alone (the aligners without a star, the scorer, the beam search, the phrase search)
+__device__ __forceinline__ void frame_lse(const float* logits, int V, int64_t row0, int T, double* lse) {
+    float m;
+    int a;
+    frame_lse_body<false>(logits, V, row0, T, lse, m, a);
+}
+// ... and the frame's maximum (the star emission of the aligners)
+__device__ __forceinline__ int frame_lse_max(const float* logits, int V, int64_t row0, int T, double* lse, float& m) {
+    int a;
+    return frame_lse_body<false>(logits, V, row0, T, lse, m, a);
+}
+// ... and the frame's top token (the star of the exact scorer and its gradient)
+__device__ __forceinline__ int frame_lse_max_arg(const float* logits, int V, int64_t row0, int T, double* lse, float& m, int& a) {
+    return frame_lse_body<true>(logits, V, row0, T, lse, m, a);
 }
 
 // number of threads of the block for which pred holds (wave ballots, then the waves in order)

@@ -564,40 +564,40 @@ int64_t w2v2_ctc_align_long_star_workspace(int32_t n, const int32_t* frames, con
 
 int w2v2_ctc_score(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t m, const int32_t* utt_of,
                    const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int32_t blank, double* logp, void* stream) {
-    return launch_ctc_score(logits, V, n, row0, frames, m, utt_of, labels, label0, nlabels, blank, logp,
+    return launch_ctc_score(logits, V, n, row0, frames, m, utt_of, labels, label0, nlabels, blank, false, 0.f, logp,
                             reinterpret_cast<hipStream_t>(stream));
 }
 
 int w2v2_ctc_score_grad(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t m,
                         const int32_t* utt_of, const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int32_t blank,
                         const double* coef, double* logp, float* grad, int64_t max_workspace_bytes, void* stream) {
-    return launch_ctc_score_grad(logits, V, n, row0, frames, m, utt_of, labels, label0, nlabels, blank, coef, logp, grad,
+    return launch_ctc_score_grad(logits, V, n, row0, frames, m, utt_of, labels, label0, nlabels, blank, false, 0.f, coef, logp, grad,
                                  max_workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
 int64_t w2v2_ctc_score_grad_workspace(int32_t n, const int32_t* frames, int32_t m, const int32_t* utt_of, const int32_t* nlabels,
                                       int32_t V) {
-    return ctc_score_grad_workspace(n, frames, m, utt_of, nlabels, V);
+    return ctc_score_grad_workspace(n, frames, m, utt_of, nlabels, V, false);
 }
 
 int w2v2_ctc_score_star(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t m,
                         const int32_t* utt_of, const int32_t* labels, const int64_t* label0, const int32_t* nlabels, int32_t blank,
                         float star_score, double* logp, void* stream) {
-    return launch_ctc_score_star(logits, V, n, row0, frames, m, utt_of, labels, label0, nlabels, blank, star_score, logp,
-                                 reinterpret_cast<hipStream_t>(stream));
+    return launch_ctc_score(logits, V, n, row0, frames, m, utt_of, labels, label0, nlabels, blank, true, star_score, logp,
+                            reinterpret_cast<hipStream_t>(stream));
 }
 
 int w2v2_ctc_score_grad_star(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t m,
                              const int32_t* utt_of, const int32_t* labels, const int64_t* label0, const int32_t* nlabels,
                              int32_t blank, float star_score, const double* coef, double* logp, float* grad,
                              int64_t max_workspace_bytes, void* stream) {
-    return launch_ctc_score_grad_star(logits, V, n, row0, frames, m, utt_of, labels, label0, nlabels, blank, star_score, coef, logp,
-                                      grad, max_workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+    return launch_ctc_score_grad(logits, V, n, row0, frames, m, utt_of, labels, label0, nlabels, blank, true, star_score, coef, logp,
+                                 grad, max_workspace_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
 int64_t w2v2_ctc_score_grad_star_workspace(int32_t n, const int32_t* frames, int32_t m, const int32_t* utt_of,
                                            const int32_t* nlabels, int32_t V) {
-    return ctc_score_grad_star_workspace(n, frames, m, utt_of, nlabels, V);
+    return ctc_score_grad_workspace(n, frames, m, utt_of, nlabels, V, true);
 }
 
 int w2v2_ctc_spot(const float* logits, int32_t V, int32_t n, const int64_t* row0, const int32_t* frames, int32_t m, const int32_t* utt_of,

@@ -1,5 +1,5 @@
 """CTC prefix beam search and exact CTC scoring on the GPU (w2v2_ctc_beam_search, csrc/beam.hip, DESIGN.md §12;
-w2v2_ctc_score, csrc/score.hip).
+w2v2_ctc_score and its gradient, both also with a star, csrc/score.hip).
 
 ``beam_search`` returns, per utterance, the n most probable transcripts with their log-probabilities; ``CharNgramLM`` is an
 optional character n-gram language model, a dense table of log-probabilities that the kernel reads on the device.  The search

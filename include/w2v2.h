@@ -331,7 +331,7 @@ int w2v2_ctc_score(const float* logits_dev, int32_t V, int32_t n, const int64_t*
                    const int32_t* utt_of_host, const int32_t* labels_dev, const int64_t* label0_host, const int32_t* nlabels_host,
                    int32_t blank, double* logp_dev, void* stream);
 
-/* The gradient of a weighted sum of exact CTC log-probabilities (exact definition in csrc/score_grad.hip): per
+/* The gradient of a weighted sum of exact CTC log-probabilities (exact definition in csrc/score.hip): per
  * utterance, grad = sum_j coef_j d logp_j / d logits over its pairs, with w2v2_ctc_score's addressing, argument checks and per-pair
  * conventions; asynchronous on `stream`.  coef = -1 on one pair per utterance is the CTC loss in fp64 log space; coef_j = P_j (W_j - L)
  * is an expected risk over an n-best list.
@@ -353,7 +353,7 @@ int64_t w2v2_ctc_score_grad_workspace(int32_t n, const int32_t* frames_host, int
                                       const int32_t* nlabels_host, int32_t V);
 
 /* Exact CTC scoring and its gradient with the star, the wildcard label of w2v2_ctc_align_star (exact definition in
- * csrc/score_star.hip): the arguments, checks and per-pair conventions of w2v2_ctc_score / w2v2_ctc_score_grad plus
+ * csrc/score.hip): the arguments, checks and per-pair conventions of w2v2_ctc_score / w2v2_ctc_score_grad plus
  *   labels_dev   may hold V, the star: a state like any other that takes at least one frame and counts as a label in the frame check
  *   star_score   fp32, <= 0, nats per frame: a star frame emits (frame maximum + star_score) - lse.  NaN or > 0 is W2V2_EINVAL,
  *                before anything is launched.

@@ -1,5 +1,5 @@
 """fp64 numpy reference of the gradient of a weighted sum of exact CTC log-probabilities, step for step the definition in
-csrc/score_grad.hip (w2v2_ctc_score_grad; test infrastructure only; the package never imports it).
+csrc/score.hip (w2v2_ctc_score_grad; test infrastructure only; the package never imports it).
 
 lp, ext, S = 2U + 1, the skip rule, alpha and logp are those of tests/score_reference.py.  The backward variable excludes the
 frame's own emission, so no lp is ever subtracted:

@@ -1,5 +1,5 @@
 """fp64 numpy reference of the exact CTC score with a star and of its gradient, step for step the definition in
-csrc/score_star.hip (w2v2_ctc_score_star, w2v2_ctc_score_grad_star; test infrastructure only; the package never
+csrc/score.hip (w2v2_ctc_score_star, w2v2_ctc_score_grad_star; test infrastructure only; the package never
 imports it).
 
 Everything is tests/score_reference.py (alpha, logp) and tests/score_grad_reference.py (beta, gamma, Gamma, G) except:
