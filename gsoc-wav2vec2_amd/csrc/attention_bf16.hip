@@ -54,6 +54,7 @@ struct Attn16Args {
     uint16_t* ctx16;            // optional bf16 shadow of ctx (the out-projection GEMM's A operand)
     int B, T, H, heads;
     int nqb, nwork;             // row blocks per (sample, head); blocks in the grid
+    const SegTile* tiles;       // SEG: the packed stream's table, one entry per 128-query block of an utterance (B = 1, T = stream frames)
 };
 
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
@@ -180,20 +181,40 @@ __device__ __forceinline__ void load_col_frags(u32x4 (&f)[4], const uint16_t* p)
 // The row sum uses the un-dropped p; 1 / (1 - p) is applied once, with the final normalisation.  What the forward saves for the backward
 // kernels below is  lse2 = -(m C2 + log2 l)  -- minus the log-sum-exp in the exponent's own units, so that P = exp2(S C2 + lse2) is one
 // fused multiply-add and one v_exp_f32 there.
-template <bool TRAIN, bool DROP>
+// SEG (the packed forward, inference only): the work items are (utterance, head, 128-query block) in that order, so that one XCD
+// still walks the query blocks of one (utterance, head).  Table entry work / heads is a block of the item's utterance (an utterance
+// with n blocks owns n heads consecutive items, from a multiple of heads on), and that entry's t0 says which of the utterance's
+// entries it is.  From there on the block is the dense kernel at B = 1, T = the utterance's frames: `T` below is that count, every
+// row clamp stops at the utterance's own last frame, and no block reads a row of a neighbour or past the stream.
+template <bool TRAIN, bool DROP, bool SEG = false>
 __global__ __launch_bounds__(NW * 64, 3) void attention_bf16_pipe_kernel(Attn16Args a, AttnTrain tr) {
     constexpr int STAGE = 2 * IMG;           // K image, V image
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_a16[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
     const int work = xcd_work(blockIdx.x, a.nwork);
-    const int bh = work / a.nqb, qb = work - bh * a.nqb;
-    const int b = bh / a.heads, head = bh - b * a.heads;
+    int bh = work / a.nqb, qb = work - bh * a.nqb;
+    int b = bh / a.heads, head = bh - b * a.heads;
+    int T_ = a.T;                             // frames of the sequence this block attends within
+    int64_t seq0 = (int64_t)b * a.T;          // its first row in qkv / ctx
+    if constexpr (SEG) {
+        const int e = work / a.heads;
+        const SegTile st = a.tiles[e];
+        const int nqb_u = (st.nf + NW * 32 - 1) / (NW * 32);
+        const int local = work - a.heads * (e - st.t0 / (NW * 32));      // 0 .. heads nqb_u - 1 inside the utterance
+        head = local / nqb_u;
+        qb = local - head * nqb_u;
+        b = 0;
+        bh = head;
+        T_ = st.nf;
+        seq0 = st.f0;
+    }
+    const int T = T_;
     const int q0 = (qb * NW + wave) * 32;
     const int ld = 3 * a.H;
-    const uint16_t* __restrict__ base = a.qkv16 + (int64_t)b * a.T * ld + head * DH;
-    const int flen = a.frame_len ? a.frame_len[b] : a.T;
-    const int ntiles = (a.T + KT - 1) / KT;
+    const uint16_t* __restrict__ base = a.qkv16 + seq0 * ld + head * DH;
+    const int flen = (!SEG && a.frame_len) ? a.frame_len[b] : T;
+    const int ntiles = (T + KT - 1) / KT;
 
     TrOff tro;
     tro.init(lane);
@@ -202,8 +223,8 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_bf16_pipe_kernel(Attn16A
     auto issue = [&](int tile, int slot) {          // (tile clamped: past the end the last tile is fetched again, never used)
         unsigned char* S = smem_a16 + slot * STAGE + (2 * wave) * 1024;
         const int row0 = min(tile, ntiles - 1) * KT;
-        const int a0 = min(row0 + dma_r0, a.T - 1) * ld + 8 * (dma_l7 ^ swz(dma_r0));
-        const int a1 = min(row0 + dma_r0 + 8, a.T - 1) * ld + 8 * (dma_l7 ^ swz(dma_r0 + 8));
+        const int a0 = min(row0 + dma_r0, T - 1) * ld + 8 * (dma_l7 ^ swz(dma_r0));
+        const int a1 = min(row0 + dma_r0 + 8, T - 1) * ld + 8 * (dma_l7 ^ swz(dma_r0 + 8));
 #pragma unroll
         for (int kv = 0; kv < 2; ++kv) {
             const uint16_t* src = base + (1 + kv) * a.H;
@@ -217,7 +238,7 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_bf16_pipe_kernel(Attn16A
     issue(1, 1);
 
     u32x4 qf[4];
-    load_col_frags(qf, base + min(q0 + li, a.T - 1) * ld + 8 * lh);
+    load_col_frags(qf, base + min(q0 + li, T - 1) * ld + 8 * lh);
 
     f32x16 o[2];
 #pragma unroll
@@ -227,11 +248,11 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_bf16_pipe_kernel(Attn16A
     float m_run = -INFINITY, l_run = 0.f;
     const uint32_t drop_key = DROP ? dropout_key(tr.seed, tr.stream) : 0u, drop_thr = DROP ? dropout_threshold(tr.p) : 0u;
     const uint32_t thr1s_pk = dropout_thr1s_pk(drop_thr);
-    const uint32_t drop_row = (uint32_t)(((uint64_t)bh * a.T + (uint64_t)min(q0 + li, a.T - 1)) * attention_drop_stride(a.T));
+    const uint32_t drop_row = (uint32_t)(((uint64_t)bh * T + (uint64_t)min(q0 + li, T - 1)) * attention_drop_stride(T));
     constexpr bool drop = DROP;            // (a template parameter: as a run-time branch inside the loop the two PV paths kept O in
                                            //  different registers and the loop paid 16 v_mov_b64 + an MFMA drain per sub-tile to merge them)
     const int xr = swz(li);
-    const int kend = min(flen, a.T);
+    const int kend = min(flen, T);
     const uint32_t keep_lane = (uint32_t)(lh * a.nqb * NW * 32 + q0 + li);
 
     // S^T of one 32-key sub-tile: four MFMAs over d
@@ -249,7 +270,7 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_bf16_pipe_kernel(Attn16A
             const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
             float v = s[r];
             v = key >= flen ? v + MASK_BIAS : v;
-            s[r] = key >= a.T ? -INFINITY : v;
+            s[r] = key >= T ? -INFINITY : v;
         }
     };
     // online softmax of one sub-tile: s -> un-normalised probabilities relative to the new running maximum; returns the factor the
@@ -351,10 +372,10 @@ __global__ __launch_bounds__(NW * 64, 3) void attention_bf16_pipe_kernel(Attn16A
     }
 
     const int q = q0 + li;
-    if (TRAIN && q < a.T && lh == 0) tr.lse[(int64_t)bh * a.T + q] = -fmaf(m_run, C2, __builtin_amdgcn_logf(l_run));      // lse2 (v_log_f32 = log2)
-    if (q < a.T) {
+    if (TRAIN && q < T && lh == 0) tr.lse[(int64_t)bh * T + q] = -fmaf(m_run, C2, __builtin_amdgcn_logf(l_run));      // lse2 (v_log_f32 = log2)
+    if (q < T) {
         const float inv = (drop ? 1.0f / (1.0f - tr.p) : 1.0f) / l_run;
-        const int64_t o0 = ((int64_t)b * a.T + q) * a.H + head * DH + 4 * lh;
+        const int64_t o0 = (seq0 + q) * a.H + head * DH + 4 * lh;
         if (a.ctx) {
             float* op = a.ctx + o0;
 #pragma unroll
@@ -743,6 +764,31 @@ int shadow_or_scratch(const float* x, const uint16_t* x16, int64_t n, int slot, 
 }  // namespace
 
 bool attention_bf16_supported(int head_size) { return head_size == DH; }
+
+int attention_bf16_packed_rows() { return NW * 32; }
+
+// The packed forward in precision mode 1 (inference): `tiles` holds, utterance by utterance, one entry per
+// attention_bf16_packed_rows() queries (t0 = 0, 128, ...); each utterance's ctx / ctx16 are the bits launch_attention_fwd_bf16
+// gives it alone (B = 1, T = its frames, no frame_len).  qkv / ctx: (frames, 3H) / (frames, H) stream buffers; qkv16: the bf16
+// shadow of qkv (null: made here from the fp32 tensor).  ctx or ctx16 may be null (not both).
+int launch_attention_bf16_packed(Profiler* prof, const float* qkv, const uint16_t* qkv16, float* ctx, uint16_t* ctx16, const SegTile* tiles,
+                                 int ntiles, int64_t frames, double sum_nf2, int H, int heads, hipStream_t s) {
+    W2V2_REQUIRE(tiles && ntiles > 0 && frames > 0 && frames < INT32_MAX && heads > 0, "attention_bf16_packed: bad argument");
+    W2V2_REQUIRE(H % heads == 0 && H / heads == DH, "attention_bf16_packed: head size %d unsupported (64)", H / heads);
+    W2V2_REQUIRE(ctx || ctx16, "attention_bf16_packed: no output");
+    // (row offsets inside an utterance are 32-bit; no utterance has more than sqrt(sum_nf2) frames)
+    W2V2_REQUIRE((sqrt(sum_nf2) + 1.0) * 3.0 * H < 2147483648.0 && (int64_t)ntiles * heads < INT32_MAX,
+                 "attention_bf16_packed: an utterance too long for 32-bit row offsets");
+    ProfScope ps(prof, FAM_ATTENTION, 4.0 * heads * sum_nf2 * DH, 4.0 * (double)frames * 4.0 * H, s);
+    const uint16_t* q16 = nullptr;
+    if (int e = shadow_or_scratch(qkv, qkv16, frames * 3 * H, SCRATCH_QKV16, s, &q16)) return e;
+    W2V2_REQUIRE(((reinterpret_cast<uintptr_t>(q16) | reinterpret_cast<uintptr_t>(ctx)) & 15) == 0 && (reinterpret_cast<uintptr_t>(ctx16) & 7) == 0,
+                 "attention_bf16_packed: unaligned operand");
+    Attn16Args a{q16, nullptr, ctx, ctx16, 1, (int)frames, H, heads, 1, ntiles * heads, tiles};
+    W2V2_LAUNCH((attention_bf16_pipe_kernel<false, false, true>), dim3(a.nwork), dim3(NW * 64), 3 * 2 * IMG, s, a, AttnTrain{0.f, 0, 0, nullptr});
+    W2V2_HIP_CHECK(hipGetLastError());
+    return W2V2_OK;
+}
 
 int attention_colpart_rows(int B, int T) { return B * ((T + NW * 32 - 1) / (NW * 32)); }
 

@@ -331,7 +331,8 @@ int launch_conv0_packed(Profiler* prof, const float* wave, const float* kernel, 
                         float eps, int act, const PackSeg* segs, int nseg, hipStream_t s,
                         const PlaneOut* planes = nullptr /* optional planes of out (K = 10, stride 5, C % 4 == 0; out may then be null) */,
                         double* gram_ws = nullptr /* conv0_gram_ws_doubles(): statistics in the dense pass's form, as each utterance alone */,
-                        int max_seg_frames = 0 /* with gram_ws: conv0 rows of the longest utterance */);
+                        int max_seg_frames = 0 /* with gram_ws: conv0 rows of the longest utterance */,
+                        uint16_t* out16 = nullptr /* optional bf16 shadow of out, as launch_conv0_x writes it (out may then be null) */);
 int64_t conv0_gram_ws_doubles(int64_t L, int stride, int nseg);
 int launch_conv0(Profiler* prof, const float* wave, const float* kernel, const float* bias,
                  const float* gamma, const float* beta, float* out, float* ws, int B, int64_t L,
@@ -387,6 +388,14 @@ int launch_pos_conv_packed(Profiler* prof, const float* x, const float* wg, cons
 int attention_packed_rows(int head_size);
 int launch_attention_packed(Profiler* prof, const float* qkv, float* ctx, const SegTile* tiles, int ntiles, int64_t frames,
                             double sum_nf2, int H, int heads, hipStream_t s);
+// packed forward, precision mode 1 (posconv.hip, attention_bf16.hip): segment forms of launch_pos_conv_bf16 (pad_left = K / 2,
+// residual on; rows of y no utterance owns are zeroed) and of launch_attention_fwd_bf16 over a table of
+// attention_bf16_packed_rows()-query tiles; each utterance's output is bit for bit what the dense launcher gives it alone
+int launch_pos_conv_bf16_packed(Profiler* prof, const float* x, const uint16_t* w16, const float* bias, float* y, const PackSeg* segs,
+                                int nseg, int64_t frames, int H, int K, int groups, int act, hipStream_t s);
+int attention_bf16_packed_rows();
+int launch_attention_bf16_packed(Profiler* prof, const float* qkv, const uint16_t* qkv16, float* ctx, uint16_t* ctx16, const SegTile* tiles,
+                                 int ntiles, int64_t frames, double sum_nf2, int H, int heads, hipStream_t s);
 // packed.hip: caller's samples (from src0 on, per utterance) -> aligned stream (gaps zeroed); stream rows -> caller's rows.
 // stats: null (a copy), or launch_pack_stats' (nseg, 2) fp64 (mean, sqrt(var + eps)): (x - mean) / that, formed in fp64
 int launch_pack_scatter(const float* src, float* stream, int64_t L, const PackSeg* segs, int nseg, hipStream_t s,
@@ -395,13 +404,15 @@ int launch_pack_stats(const float* src, const PackSeg* segs, int nseg, double ep
 int launch_pack_gather(const float* stream_rows, float* out, int64_t out_rows, int width, const PackSeg* segs, int nseg,
                        hipStream_t s);
 // zero the stream rows no utterance owns -- [f0 + nf, next f0) behind each, [f0 + nf, frames) behind the last -- of an fp32
-// (frames, width) buffer (x, may be null) and of its planes (pl, may be null): what the segment kernels never write stays defined
-int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int width, const PackSeg* segs, int nseg, hipStream_t s);
+// (frames, width) buffer (x, may be null), of its planes (pl, may be null) and of its bf16 shadow (x16, may be null): what the
+// segment kernels never write stays defined
+int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int width, const PackSeg* segs, int nseg, hipStream_t s,
+                          uint16_t* x16 = nullptr);
 
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
 enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4, SCRATCH_BEAM = 5, SCRATCH_WINDOWS = 6,
                    SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8, SCRATCH_EDIT = 9, SCRATCH_ALIGN_LONG = 10, SCRATCH_SCORE = 11, SCRATCH_SPOT = 12, SCRATCH_SCORE_GRAD = 13,
-                   SCRATCH_SCORE_STAR = 14, SCRATCH_SCORE_GRAD_STAR = 15, SCRATCH_SLOTS = 16 };
+                   SCRATCH_SCORE_STAR = 14, SCRATCH_SCORE_GRAD_STAR = 15, SCRATCH_POS_PACKED = 16, SCRATCH_SLOTS = 17 };
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out);
 int stream_scratch_release();       // frees the calling device's scratch buffers and staged-upload buffers
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }      // the parts of a workspace begin at multiples of 256 bytes

@@ -599,6 +599,8 @@ int conv0_chunk_frames() { return TC; }
 // Packed stream: pass 1 is the per-chunk conv recompute (conv0_kernel<0>), each chunk counting only the rows of the utterance
 // whose span holds it; the finalize combines each utterance's chunks; the apply pass reads the utterance's scale / shift.
 // (The Gram-form statistics of the dense path take 2048-frame blocks, which would straddle utterances.)
+// out16 (precision mode 1): the bf16 shadow of the output, written by the apply pass as launch_conv0_x's writes it (the
+// nearest-even rounding of the value `out` receives), whichever statistics form fed the scale / shift table.
 // gram_ws (w2v2_forward_windows; conv0_gram_ws_doubles): the statistics in the dense pass's Gram form instead, per utterance in
 // blocks counted from its own start -- bit for bit what launch_conv0_x gives the utterance alone; max_seg_frames: the longest
 // utterance's conv0 rows.
@@ -607,9 +609,9 @@ int64_t conv0_gram_ws_doubles(int64_t L, int stride, int nseg) { return (L / str
 int launch_conv0_packed(Profiler* prof, const float* wave, const float* kernel, const float* bias, const float* gamma,
                         const float* beta, float* out, float* ws, float* scale_shift, int64_t L, int K, int stride, int C,
                         float eps, int act, const PackSeg* segs, int nseg, hipStream_t s, const PlaneOut* planes, double* gram_ws,
-                        int max_seg_frames) {
+                        int max_seg_frames, uint16_t* out16) {
     const PlaneOut pl = planes ? *planes : PlaneOut{};
-    W2V2_REQUIRE(wave && kernel && gamma && beta && (out || pl.p) && ws && scale_shift && segs && nseg > 0, "conv0_packed: null operand");
+    W2V2_REQUIRE(wave && kernel && gamma && beta && (out || out16 || pl.p) && ws && scale_shift && segs && nseg > 0, "conv0_packed: null operand");
     W2V2_REQUIRE(C > 0 && K > 0 && K <= 32 && stride > 0 && L >= K, "conv0_packed: unsupported C=%d K=%d stride=%d L=%lld", C, K,
                  stride, (long long)L);
     // (as in launch_conv0_x: only the 16-byte-store apply kernel writes planes, so its geometry and alignment are required up front)
@@ -619,7 +621,7 @@ int launch_conv0_packed(Profiler* prof, const float* wave, const float* kernel, 
                              reinterpret_cast<uintptr_t>(scale_shift)) & 15) == 0),
                  "conv0_packed: plane output needs the K = 10 / stride 5 geometry, C %% 4 == 0 and 16-byte aligned operands");
     Conv0Args a{};
-    a.wave = wave; a.kernel = kernel; a.bias = bias; a.gamma = gamma; a.beta = beta; a.out = out; a.planes = pl;
+    a.wave = wave; a.kernel = kernel; a.bias = bias; a.gamma = gamma; a.beta = beta; a.out = out; a.out16 = out16; a.planes = pl;
     a.L = L; a.K = K; a.stride = stride; a.C = C; a.eps = eps; a.norm_mode = 0; a.act = act;
     a.T0 = (int)(1 + (L - K) / stride);
     a.nchunks = conv0_nchunks(L, K, stride);
@@ -642,7 +644,7 @@ int launch_conv0_packed(Profiler* prof, const float* wave, const float* kernel, 
         }
     }
     {
-        const double out_bytes = ((out ? 4.0 : 0.0) + (pl.p ? 2.0 * plane_count(pl.fmt) : 0.0)) * (double)a.T0 * C;
+        const double out_bytes = ((out ? 4.0 : 0.0) + (out16 ? 2.0 : 0.0) + (pl.p ? 2.0 * plane_count(pl.fmt) : 0.0)) * (double)a.T0 * C;
         ProfScope ps(prof, FAM_CONV0_APPLY, flops, 4.0 * (double)L + out_bytes, s);
         launch_mode<1>(a, 1, s);
     }

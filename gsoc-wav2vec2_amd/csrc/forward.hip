@@ -201,7 +201,8 @@ bool w2v2_pos_conv_bf16_ok(const w2v2_model* m) {
     return m->precision == 1 && cg % 8 == 0 && cg <= 64 && (m->cfg.num_conv_pos_embeddings * cg) % 64 == 0;
 }
 
-int w2v2_ensure_pos16(w2v2_model* m, int B, int T, hipStream_t s) {
+// the bf16 shadow of the regrouped positional-conv kernel (both the dense and the packed bf16 positional conv read it)
+static int ensure_pos_w16(w2v2_model* m, hipStream_t s) {
     const w2v2_config& c = m->cfg;
     const int H = c.hidden_size, K = c.num_conv_pos_embeddings, G = c.num_conv_pos_embedding_groups, cg = H / G;
     if (!m->pos_w16) W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->pos_w16), (size_t)K * cg * H * sizeof(uint16_t)));
@@ -209,6 +210,13 @@ int w2v2_ensure_pos16(w2v2_model* m, int B, int T, hipStream_t s) {
         if (int e = launch_pos_conv_weight_shadow(m->pos_wg, m->pos_w16, K, cg, G, s)) return e;
         m->pos16_valid = true;
     }
+    return W2V2_OK;
+}
+
+int w2v2_ensure_pos16(w2v2_model* m, int B, int T, hipStream_t s) {
+    const w2v2_config& c = m->cfg;
+    const int H = c.hidden_size, K = c.num_conv_pos_embeddings;
+    if (int e = ensure_pos_w16(m, s)) return e;
     if (!m->pos_pack16) {
         float* p = nullptr;
         if (int e = w2v2_ws_alloc(m, &p, (pos_conv_bf16_pack_elems(B, T, H, K) + 1) / 2 + 4)) return e;
@@ -251,7 +259,9 @@ ForwardPlan w2v2_plan_forward(const w2v2_model* m, int B, int64_t L, bool planes
     p.act = c.is_gelu_approx ? 2 : 1;
     // element-wise kernels in precision mode 1 evaluate exact GELU through the 5-term erf the bf16 GEMM epilogue uses (act 3)
     p.act_ew = (p.act == 1 && m->precision == 1) ? 3 : p.act;
-    p.pos16 = !packed && w2v2_pos_conv_bf16_ok(m);
+    // (dense and packed alike: the packed forward runs in mode 1 only under W2V2_OPT_BF16_PACKED, and then with the segment form)
+    (void)packed;
+    p.pos16 = w2v2_pos_conv_bf16_ok(m);
     const bool sh = p.sh, pm = p.pm, keep = p.keep;
 
     // ---- plane-fed call sites ----
@@ -307,7 +317,7 @@ ForwardPlan w2v2_plan_forward(const w2v2_model* m, int B, int64_t L, bool planes
     p.attn_in = p.prenorm ? forms(!((p.p_qkv && !keep) || ln16_only), sh, p.p_qkv) : forms(true, sh, p.p_qkv);
     // the bf16 attention kernels read q | k | v only as bf16: the projection then writes just that shadow
     p.qkv = p.attn16 ? (unsigned)B16 : (unsigned)F32;
-    // (the packed modes never have attn16, so this one line serves the dense and the packed forward)
+    // (the packed forward in mode 1 runs the segment form of the same kernel, so this one line serves the dense and the packed forward)
     p.ctx = forms(!(p.ctx16_only || (p.ctx_fused && !keep)), p.attn16, p.p_out);
     p.attn_kernel = p.ctx_fused ? p.ctx : (p.ctx & ~(unsigned)PLANES);
     // the FFN input t2: postnorm it is also the FFN's residual, so fp32 stays
@@ -422,7 +432,7 @@ int w2v2_forward_frontend(w2v2_model* m, const ForwardPlan& plan, const float* w
             if (int e = launch_conv0_packed(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr, fe(0, "/layer_norm/gamma"),
                                             fe(0, "/layer_norm/beta"), ForwardPlan::f32(k, m->conv[0]), m->conv0_ws, m->pk_scale, L, c.kernal_sizes[0],
                                             c.strides[0], c.filter_sizes[0], 1e-5f, plan.act_ew, pk->segs, pk->nseg, s, po, pk->gram_ws,
-                                            pk->max_conv0_rows))
+                                            pk->max_conv0_rows, ForwardPlan::b16(k, m->conv16, 0)))
                 return e;
         } else if (int e = launch_conv0_x(pf, wave, fe(0, "/conv/kernel"), c.conv_bias ? fe(0, "/conv/bias") : nullptr,
                                           fe(0, "/layer_norm/gamma"), fe(0, "/layer_norm/beta"), ForwardPlan::f32(k, m->conv[0]),
@@ -467,7 +477,7 @@ int w2v2_forward_frontend(w2v2_model* m, const ForwardPlan& plan, const float* w
 }
 
 // The inference forward over (B, L).  pk null: the batched forward (w2v2_forward).  pk set: one stream of packed utterances
-// (B = 1; precision modes fp32, bf16x3, f16x2); the three stages that mix frames -- conv0's GroupNorm statistics, the positional
+// (B = 1; precision modes fp32, bf16x3, f16x2, and bf16 under W2V2_OPT_BF16_PACKED); the three stages that mix frames -- conv0's GroupNorm statistics, the positional
 // conv and attention -- take their segment-aware forms, everything else runs unchanged over the stream.  The stream rows no
 // utterance owns (1-2 behind each) are zeroed in the two buffers only segment kernels write, posout and ctx, so that every
 // row a plane producer reads is defined by the call's own inputs.
@@ -482,8 +492,9 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
     W2V2_REQUIRE(m->ws_B == B && m->ws_L >= L, "forward: workspace (%d, %lld) does not hold (%d, %lld)", m->ws_B, (long long)m->ws_L,
                  B, (long long)L);
     const ForwardPlan plan = w2v2_plan_forward(m, B, L, true, pk != nullptr);
+    // (packed: the shadows are sized once per workspace, so for its capacity -- a later, longer stream that fits reuses them)
     if (plan.sh)
-        if (int e = w2v2_ensure_shadows(m, B, plan.T, s)) return e;
+        if (int e = w2v2_ensure_shadows(m, B, pk ? m->conv_T.back() : plan.T, s)) return e;
     // (packed: sized for the workspace's capacity, so that a later packed call whose stream fits reuses them as it reuses the workspace)
     if (plan.any_planes)
         if (int e = w2v2_ensure_planes(m, B, pk ? m->ws_L : L, plan.fmt)) return e;
@@ -501,7 +512,12 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
         if (int e = launch_frame_lengths(pf, mask, m->frame_len, B, L, c.kernal_sizes, c.strides, c.num_conv_layers, s)) return e;
         flen = m->frame_len;
     }
-    if (pk) {                            // each utterance zero-padded at its own edges (the fp32 kernel in every mode, as the dense split modes)
+    if (pk && plan.pos16) {              // packed, precision mode 1: the dense mode's batched GEMM over a padded stream (posconv.hip);
+        if (int e = ensure_pos_w16(m, s)) return e;      // it zeroes the rows of posout that no utterance owns itself
+        if (int e = launch_pos_conv_bf16_packed(pf, m->proj, m->pos_w16, m->P("encoder/pos_conv_embed/conv/bias"), m->posout, pk->segs, pk->nseg, T, H,
+                                                c.num_conv_pos_embeddings, c.num_conv_pos_embedding_groups, act, s))
+            return e;
+    } else if (pk) {                     // each utterance zero-padded at its own edges (the fp32 kernel, as the dense forward outside mode 1's shapes)
         if (int e = launch_pos_conv_packed(pf, m->proj, m->pos_wg, m->P("encoder/pos_conv_embed/conv/bias"), m->posout, pk->pos_tiles, pk->npos,
                                            T, H, c.num_conv_pos_embeddings, c.num_conv_pos_embedding_groups, act, s))
             return e;
@@ -527,8 +543,13 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
         attn_pl.o.range_flag = m->range_flag;
         attn_pl.on = true;
     }
-    if (pk)                              // (the attention kernels write only the utterances' rows of ctx and of its planes, in every layer)
+    // packed, precision mode 1 with head size 64: the segment form of the bf16 kernel, as launch_attention_x picks the dense one
+    const bool pk_attn16 = pk && m->precision == W2V2_PRECISION_BF16 && attention_bf16_supported(H / c.num_heads);
+    if (pk_attn16) {                     // (the forms of ctx that kernel writes in this plan: with ctx16_only just the shadow)
+        if (int e = launch_pack_zero_gaps(ForwardPlan::f32(plan.ctx, m->ctx), nullptr, T, H, pk->segs, pk->nseg, s, ForwardPlan::b16(plan.ctx, m->ctx16))) return e;
+    } else if (pk) {                     // (the attention kernels write only the utterances' rows of ctx and of its planes, in every layer)
         if (int e = launch_pack_zero_gaps(m->ctx, po_ctx, T, H, pk->segs, pk->nseg, s)) return e;
+    }
     // the tensors of a layer as GEMM operands.  Postnorm: the attention input is hs[i], written by the previous LayerNorm; prenorm: t0.
     const Tens qkv{plan.qkv, m->qkv, m->qkv16, nullptr}, ctx{plan.ctx, m->ctx, m->ctx16, &m->ctx48}, t1{plan.hidden, m->t1, nullptr, nullptr},
                ffn_in{plan.ffn_in, m->t2, m->t2_16, &m->ffn_in48}, ffn{plan.ffn, m->ffn, m->ffn16, &m->ffn48};
@@ -547,7 +568,11 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
                 return e;
         if (int e = gemm(m, plan, s, plan.p_qkv, attn_in, H, 0, m->qkv_w[i], 3 * H, qkv, 3 * H, 0, m->qkv_b[i], nullptr, (int)BT, 3 * H, H, 1, 0))
             return e;
-        if (pk && plan.split_attn) {     // packed, precision modes 2 / 3: queries and keys of one utterance per block
+        if (pk_attn16) {
+            if (int e = launch_attention_bf16_packed(pf, ForwardPlan::f32(plan.qkv, m->qkv), ForwardPlan::b16(plan.qkv, m->qkv16), ForwardPlan::f32(plan.ctx, m->ctx),
+                                                     ForwardPlan::b16(plan.ctx, m->ctx16), pk->attn_tiles, pk->nattn, T, pk->sum_nf2, H, c.num_heads, s))
+                return e;
+        } else if (pk && plan.split_attn) {     // packed, precision modes 2 / 3: queries and keys of one utterance per block
             if (int e = launch_attention_split_packed(pf, m->qkv, ForwardPlan::f32(plan.ctx, m->ctx), pk->attn_tiles, pk->nattn, T, pk->sum_nf2, H,
                                                       c.num_heads, s, attn_pl, plan.fmt, attn_pl.on ? attn_pl.o.range_flag : nullptr))
                 return e;
@@ -621,8 +646,9 @@ static int stream_forward_ready(w2v2_model* m, const char* who) {
         return W2V2_ESTATE;
     }
     static const char* modes[] = {"fp32", "bf16", "bf16x3", "f16x2"};
-    W2V2_REQUIRE(m->precision == W2V2_PRECISION_FP32 || m->precision == W2V2_PRECISION_BF16X3 || m->precision == W2V2_PRECISION_F16X2,
-                 "%s: precision mode %s is not supported (fp32, bf16x3, f16x2)", who,
+    W2V2_REQUIRE(m->precision == W2V2_PRECISION_FP32 || m->precision == W2V2_PRECISION_BF16X3 || m->precision == W2V2_PRECISION_F16X2 ||
+                     (m->precision == W2V2_PRECISION_BF16 && m->opt_bf16_packed),
+                 "%s: precision mode %s is not supported (fp32, bf16x3, f16x2; bf16 with the option W2V2_OPT_BF16_PACKED)", who,
                  (m->precision >= 0 && m->precision <= 3) ? modes[m->precision] : "?");
     return W2V2_OK;
 }
@@ -659,7 +685,9 @@ static int forward_stream(w2v2_model* m, const char* who, const float* wave, con
     const int64_t T = w2v2_num_frames(m, L);
     W2V2_REQUIRE(T < (1 << 24) && (int64_t)segs.back().f0 + segs.back().nf <= T, "%s: stream of %lld samples out of range", who,
                  (long long)L);
-    const int H = c.hidden_size, PR = pos_conv_packed_rows(), AR = attention_packed_rows(H / c.num_heads);
+    // (attention tiles of the height of the kernel that will run: 128 queries for mode 1's bf16 kernel, 256 for the others)
+    const int H = c.hidden_size, PR = pos_conv_packed_rows(), AR32 = attention_packed_rows(H / c.num_heads), AR16 = attention_bf16_packed_rows();
+    const int AR = (m->precision == W2V2_PRECISION_BF16 && attention_bf16_supported(H / c.num_heads)) ? AR16 : AR32;
     std::vector<SegTile> tiles;
     for (const int rows_per_tile : {PR, AR})
         for (const PackSeg& sg : segs)
@@ -674,7 +702,7 @@ static int forward_stream(w2v2_model* m, const char* who, const float* wave, con
     if (m->pk_L != m->ws_L) {
         const int64_t Tcap = w2v2_num_frames(m, m->ws_L);
         m->pk_seg_cap = (int)(m->ws_L / U);
-        m->pk_tile_cap = (int)(2 * (int64_t)m->pk_seg_cap + Tcap / PR + Tcap / AR);
+        m->pk_tile_cap = (int)(2 * (int64_t)m->pk_seg_cap + Tcap / PR + Tcap / std::min(AR32, AR16));
         if (int e = w2v2_ws_alloc(m, &m->pk_wave, m->ws_L)) return e;
         if (int e = w2v2_ws_alloc(m, &m->pk_scale, (int64_t)m->pk_seg_cap * 2 * c.filter_sizes[0])) return e;
         if (int e = w2v2_ws_alloc(m, &m->pk_out, c.with_lm_head ? Tcap * c.vocab_size : 0)) return e;

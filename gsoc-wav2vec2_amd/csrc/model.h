@@ -79,6 +79,7 @@ struct w2v2_model {
     bool opt_planes = true;                                  // W2V2_OPT_SPLIT_PLANES
     bool opt_wgrad_stream = false;                           // W2V2_OPT_WGRAD_STREAM
     bool opt_defer_folds = true;                             // W2V2_OPT_DEFER_FOLDS
+    bool opt_bf16_packed = false;                            // W2V2_OPT_BF16_PACKED
     int pl_fmt = -1, pl_B = 0;
     int64_t pl_L = 0;
     std::vector<void*> pl_allocs;

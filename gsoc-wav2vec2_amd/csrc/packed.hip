@@ -75,14 +75,15 @@ __global__ __launch_bounds__(256) void pack_gather_kernel(const float* __restric
     for (int c = threadIdx.x; c < width; c += 256) dst[c] = src[c];
 }
 
-// one block per utterance: the rows behind it that no utterance owns, in fp32 and in every plane
+// one block per utterance: the rows behind it that no utterance owns, in fp32, in every plane and in the bf16 shadow
 __global__ __launch_bounds__(256) void pack_zero_gaps_kernel(float* __restrict__ x, PlaneOut pl, int np, int64_t frames, int width,
-                                                             const PackSeg* __restrict__ segs, int nseg) {
+                                                             const PackSeg* __restrict__ segs, int nseg, uint16_t* __restrict__ x16) {
     const int i = blockIdx.x;
     const int64_t r0 = (int64_t)segs[i].f0 + segs[i].nf, r1 = min(i + 1 < nseg ? (int64_t)segs[i + 1].f0 : frames, frames);
     const int64_t n = (r1 > r0 ? r1 - r0 : 0) * width, e0 = r0 * width;
     for (int64_t e = threadIdx.x; e < n; e += 256) {
         if (x) x[e0 + e] = 0.f;
+        if (x16) x16[e0 + e] = 0;
         for (int p = 0; p < np; ++p) pl.p[p * pl.plane + e0 + e] = 0;
     }
 }
@@ -114,11 +115,12 @@ int launch_pack_gather(const float* stream_rows, float* out, int64_t out_rows, i
     return W2V2_OK;
 }
 
-int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int width, const PackSeg* segs, int nseg, hipStream_t s) {
+int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int width, const PackSeg* segs, int nseg, hipStream_t s,
+                          uint16_t* x16) {
     const PlaneOut p = pl ? *pl : PlaneOut{};
-    W2V2_REQUIRE((x || p.p) && segs && nseg > 0 && frames > 0 && width > 0 && (!p.p || p.plane >= frames * width),
+    W2V2_REQUIRE((x || p.p || x16) && segs && nseg > 0 && frames > 0 && width > 0 && (!p.p || p.plane >= frames * width),
                  "pack_zero_gaps: bad argument");
-    W2V2_LAUNCH(pack_zero_gaps_kernel, dim3((unsigned)nseg), dim3(256), 0, s, x, p, p.p ? plane_count(p.fmt) : 0, frames, width, segs, nseg);
+    W2V2_LAUNCH(pack_zero_gaps_kernel, dim3((unsigned)nseg), dim3(256), 0, s, x, p, p.p ? plane_count(p.fmt) : 0, frames, width, segs, nseg, x16);
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }

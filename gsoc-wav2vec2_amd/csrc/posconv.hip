@@ -617,6 +617,113 @@ int launch_pos_conv_bf16(Profiler* prof, const float* x, const uint16_t* w16, co
                               gx, s);
 }
 
+// ---- the packed forward in precision mode 1: the same GEMM over a padded stream ----
+// The stream's rows, with `gap` = max(pad, K - 1 - pad) more zero rows in front of every utterance but the first: utterance i
+// (stream rows f0 .. f0 + nf) sits at padded rows pad + f0 + i gap .. of a (groups, Rp, cg) image, Rp = pad + frames + (n - 1) gap +
+// K - 1 - pad.  Every utterance then has at least `pad` zero rows in front and K - 1 - pad behind it (neighbours share them; the 1-2
+// stream rows no utterance owns are zero rows too), so GEMM row f0 + i gap + t over the image reads exactly what row t of the
+// utterance alone reads from its own image, and the one batched GEMM of launch_pos_conv_bf16 (M = Rp - K + 1 rows, nbatch = groups)
+// computes every utterance plus `gap` junk rows between neighbours.  Its rows are independent and its bits do not depend on the
+// tile a row falls in (gemm_bf16.hip), so after the finish pass -- act + residual as the dense GEMM's epilogue applies them --
+// each utterance carries the bits launch_pos_conv_bf16 gives it alone.
+namespace {
+
+// index of the utterance whose padded region holds image row r (regions start at f0 + i gap, the first at 0)
+__device__ __forceinline__ int pos_seg_of_row(const PackSeg* __restrict__ segs, int n, int64_t r, int gap) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((int64_t)segs[mid].f0 + (int64_t)mid * gap <= r) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// one block per image row r: its utterance's frame r - pad - (f0 + i gap) rounded to bf16 if the utterance has it, else zeros
+__global__ __launch_bounds__(256) void pos_pack_seg_kernel(const float* __restrict__ x, uint16_t* __restrict__ P, const PackSeg* __restrict__ segs,
+                                                           int nseg, int H, int cg, int64_t Rp, int pad, int gap) {
+    const int64_t r = blockIdx.x;
+    const int i = pos_seg_of_row(segs, nseg, r, gap);
+    const int f0 = segs[i].f0, nf = segs[i].nf;
+    const int64_t t = r - pad - ((int64_t)f0 + (int64_t)i * gap);
+    const bool inside = t >= 0 && t < nf;
+    const float* __restrict__ xr = x + (f0 + (inside ? t : 0)) * (int64_t)H;
+    for (int c = 4 * threadIdx.x; c < H; c += 4 * 256) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (inside) v = *reinterpret_cast<const float4*>(xr + c);
+        const int g = c / cg;
+        *reinterpret_cast<uint2*>(P + ((int64_t)g * Rp + r) * cg + (c - g * cg)) = make_uint2(pack_bf16_rne(v.x, v.y), pack_bf16_rne(v.z, v.w));
+    }
+}
+
+// one block per stream row: y = act(pre) + x on an utterance's row (pre: the GEMM's row f0 + i gap + t, bias included), zeros on a
+// row no utterance owns.  The activation and the add are the GEMM epilogue's own (gemm_epilogue.h, FAST_GELU).
+__global__ __launch_bounds__(256) void pos_finish_seg_kernel(const float* __restrict__ pre, const float* __restrict__ x, float* __restrict__ y,
+                                                             const PackSeg* __restrict__ segs, int nseg, int H, int act, int gap) {
+    const int64_t r = blockIdx.x;
+    int lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (segs[mid].f0 <= r) lo = mid; else hi = mid - 1;
+    }
+    const int64_t t = r - segs[lo].f0;
+    const bool inside = t >= 0 && t < segs[lo].nf;
+    const float* __restrict__ pr = pre + (inside ? r + (int64_t)lo * gap : 0) * H;
+    for (int c = 4 * threadIdx.x; c < H; c += 4 * 256) {
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (inside) {
+            const float4 p = *reinterpret_cast<const float4*>(pr + c), q = *reinterpret_cast<const float4*>(x + r * H + c);
+            if (act == 1) {
+                const f32x2_t a = gelu_erf_fast2(f32x2_t{p.x, p.y}), b = gelu_erf_fast2(f32x2_t{p.z, p.w});
+                o = make_float4(a[0], a[1], b[0], b[1]);
+            } else if (act == 2) {
+                o = make_float4(gelu_tanh(p.x), gelu_tanh(p.y), gelu_tanh(p.z), gelu_tanh(p.w));
+            } else {
+                o = p;
+            }
+            o = make_float4(o.x + q.x, o.y + q.y, o.z + q.z, o.w + q.w);
+        }
+        *reinterpret_cast<float4*>(y + r * H + c) = o;
+    }
+}
+
+}  // namespace
+
+// x, y: (frames, H) stream buffers; segs: the stream's utterances (device; f0 and nf are read), nseg of them, the last ending at
+// or before `frames`.  Rows of y no utterance owns are zeroed.  Scratch (the image and the GEMM's fp32 rows) is sized from this
+// call's frames and utterances.
+int launch_pos_conv_bf16_packed(Profiler* prof, const float* x, const uint16_t* w16, const float* bias, float* y, const PackSeg* segs,
+                                int nseg, int64_t frames, int H, int K, int groups, int act, hipStream_t s) {
+    W2V2_REQUIRE(x && w16 && y && segs, "pos_conv_bf16_packed: null operand");
+    W2V2_REQUIRE(nseg > 0 && frames > 0 && frames < (1 << 24) && K > 0 && groups > 0 && H % groups == 0, "pos_conv_bf16_packed: bad sizes");
+    const int cg = H / groups, pad = K / 2, gap = pad > K - 1 - pad ? pad : K - 1 - pad;
+    W2V2_REQUIRE(cg % 8 == 0 && cg <= 64 && (K * cg) % 64 == 0, "pos_conv_bf16_packed: channels per group %d / taps %d unsupported", cg, K);
+    W2V2_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0, "pos_conv_bf16_packed: unaligned operand");
+    const int64_t M = frames + (int64_t)(nseg - 1) * gap, Rp = M + K - 1;
+    W2V2_REQUIRE(Rp < INT32_MAX / 64, "pos_conv_bf16_packed: %lld padded rows are too many", (long long)Rp);
+    const size_t pack_bytes = up256((size_t)Rp * H * sizeof(uint16_t)), pre_bytes = (size_t)M * H * sizeof(float);
+    void* ws = nullptr;
+    // (grow-only; whole 8 MiB so that calls of slightly different sizes do not each reallocate)
+    if (int e = stream_scratch(SCRATCH_POS_PACKED, s, (pack_bytes + pre_bytes + ((size_t)8 << 20) - 1) & ~(((size_t)8 << 20) - 1), &ws)) return e;
+    uint16_t* pack16 = static_cast<uint16_t*>(ws);
+    float* pre = reinterpret_cast<float*>(static_cast<char*>(ws) + pack_bytes);
+    ProfScope ps(prof, FAM_POSCONV, 2.0 * (double)M * H * cg * K, (2.0 * Rp + 8.0 * M + 12.0 * frames) * H + 2.0 * K * cg * H, s);
+    W2V2_LAUNCH(pos_pack_seg_kernel, dim3((unsigned)Rp), dim3(256), 0, s, x, pack16, segs, nseg, H, cg, Rp, pad, gap);
+    GemmShadows gx;
+    gx.A16 = pack16;
+    gx.B16 = w16;
+    gx.ldb16 = (int64_t)K * cg;
+    gx.zmod = groups;
+    gx.strideB16 = (int64_t)cg * K * cg;
+    gx.strideC2 = M * H;
+    gx.strideBias = cg;
+    // A: row r of group g starts at pack16 + (g Rp + r) cg  -> lda = cg, batch stride Rp cg
+    if (int e = launch_gemm_bf16_x(nullptr, nullptr, cg, Rp * cg, nullptr, cg, 0, pre, H, cg, bias, nullptr, (int)M, cg, K * cg, groups, 0, gx, s))
+        return e;
+    W2V2_LAUNCH(pos_finish_seg_kernel, dim3((unsigned)frames), dim3(256), 0, s, pre, x, y, segs, nseg, H, act, gap);
+    W2V2_HIP_CHECK(hipGetLastError());
+    return W2V2_OK;
+}
+
 // The slab count S of launch_pos_conv_dw_bf16 (see there): 1, 2 or 4, a divisor of B, the one whose tiles x groups x S blocks waste the
 // least of whole rounds of the 512 block slots (the smallest on a tie).
 int pos_conv_dw_bf16_slabs(int B, int H, int K, int groups) {

@@ -479,6 +479,7 @@ int w2v2_set_option(w2v2_model* m, int32_t option, int32_t value) {
         case W2V2_OPT_SPLIT_PLANES: m->opt_planes = value != 0; return W2V2_OK;
         case W2V2_OPT_WGRAD_STREAM: m->opt_wgrad_stream = value != 0; return W2V2_OK;
         case W2V2_OPT_DEFER_FOLDS: m->opt_defer_folds = value != 0; return W2V2_OK;
+        case W2V2_OPT_BF16_PACKED: m->opt_bf16_packed = value != 0; return W2V2_OK;
         default: set_error("set_option: unknown option %d", option); return W2V2_EINVAL;
     }
 }
@@ -490,6 +491,7 @@ int w2v2_get_option(const w2v2_model* m, int32_t option) {
         case W2V2_OPT_SPLIT_PLANES: return m->opt_planes ? 1 : 0;
         case W2V2_OPT_WGRAD_STREAM: return m->opt_wgrad_stream ? 1 : 0;
         case W2V2_OPT_DEFER_FOLDS: return m->opt_defer_folds ? 1 : 0;
+        case W2V2_OPT_BF16_PACKED: return m->opt_bf16_packed ? 1 : 0;
         default: return W2V2_EINVAL;
     }
 }
@@ -950,6 +952,56 @@ int w2v2_op_attention_packed(const float* qkv, int32_t n, const int32_t* cu_fram
     }
     (void)hipStreamSynchronize(s);
     (void)hipFree(dt);
+    return e;
+}
+int w2v2_op_attention_packed_bf16(const float* qkv, const uint16_t* qkv16, int32_t n, const int32_t* cu_frames, float* ctx, uint16_t* ctx16,
+                                  int32_t H, int32_t heads, void* stream) {
+    W2V2_REQUIRE((qkv || qkv16) && cu_frames && (ctx || ctx16), "op_attention_packed_bf16: null operand");
+    W2V2_REQUIRE(n >= 1 && cu_frames[0] == 0, "op_attention_packed_bf16: need n >= 1 utterances and cu_frames[0] == 0");
+    W2V2_REQUIRE(heads > 0 && H % heads == 0 && attention_bf16_supported(H / heads), "op_attention_packed_bf16: bad sizes H=%d heads=%d (head size 64)", H,
+                 heads);
+    // the tile table of the packed forward in precision mode 1, utterances back to back
+    const int AR = attention_bf16_packed_rows();
+    std::vector<SegTile> tiles;
+    double sum_nf2 = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const int nf = cu_frames[i + 1] - cu_frames[i];
+        W2V2_REQUIRE(nf >= 1, "op_attention_packed_bf16: utterance %d has %d frames (need at least one)", i, nf);
+        for (int t0 = 0; t0 < nf; t0 += AR) tiles.push_back(SegTile{cu_frames[i], nf, t0, 0});
+        sum_nf2 += (double)nf * (double)nf;
+    }
+    const int64_t frames = cu_frames[n];
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    SegTile* dt = nullptr;
+    W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dt), tiles.size() * sizeof(SegTile)));
+    int e = hipMemcpyAsync(dt, tiles.data(), tiles.size() * sizeof(SegTile), hipMemcpyHostToDevice, s) == hipSuccess &&
+                    hipStreamSynchronize(s) == hipSuccess ? W2V2_OK : W2V2_EHIP;
+    if (e) set_error("op_attention_packed_bf16: staging the tile table failed");
+    if (!e) e = launch_attention_bf16_packed(nullptr, qkv, qkv16, ctx, ctx16, dt, (int)tiles.size(), frames, sum_nf2, H, heads, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(dt);
+    return e;
+}
+int w2v2_op_pos_conv_packed_bf16(const float* x, const uint16_t* w16, const float* bias, int32_t n, const int32_t* cu_frames, float* y, int32_t H,
+                                 int32_t K, int32_t groups, int32_t act, void* stream) {
+    W2V2_REQUIRE(x && w16 && cu_frames && y, "op_pos_conv_packed_bf16: null operand");
+    W2V2_REQUIRE(n >= 1 && cu_frames[0] == 0, "op_pos_conv_packed_bf16: need n >= 1 utterances and cu_frames[0] == 0");
+    W2V2_REQUIRE(act >= 0 && act <= 2, "op_pos_conv_packed_bf16: bad activation %d", act);
+    std::vector<PackSeg> segs((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int nf = cu_frames[i + 1] - cu_frames[i];
+        W2V2_REQUIRE(nf >= 1, "op_pos_conv_packed_bf16: utterance %d has %d frames (need at least one)", i, nf);
+        segs[i] = PackSeg{0, 0, 0, cu_frames[i], nf, cu_frames[i], 0};
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PackSeg* ds = nullptr;
+    W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ds), segs.size() * sizeof(PackSeg)));
+    int e = hipMemcpyAsync(ds, segs.data(), segs.size() * sizeof(PackSeg), hipMemcpyHostToDevice, s) == hipSuccess &&
+                    hipStreamSynchronize(s) == hipSuccess ? W2V2_OK : W2V2_EHIP;
+    if (e) set_error("op_pos_conv_packed_bf16: staging the utterance table failed");
+    if (!e) e = launch_pos_conv_bf16_packed(nullptr, x, w16, bias, y, ds, n, cu_frames[n], H, K, groups, act, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(ds);
     return e;
 }
 int w2v2_op_frame_lengths(const int32_t* mask, int32_t* frame_len, int32_t B, int64_t L,

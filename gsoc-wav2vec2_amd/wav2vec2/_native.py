@@ -206,6 +206,8 @@ PROTOTYPES = {
     "w2v2_op_pos_conv": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "w2v2_op_attention": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "w2v2_op_attention_packed": (C.c_int, [_P, _I32, _P, _P, _P, _I64, _P, _I32, _I32, _P]),
+    "w2v2_op_attention_packed_bf16": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _I32, _P]),
+    "w2v2_op_pos_conv_packed_bf16": (C.c_int, [_P, _P, _P, _I32, _P, _P, _I32, _I32, _I32, _I32, _P]),
     "w2v2_op_frame_lengths": (C.c_int, [_P, _P, _I32, _I64, C.POINTER(_I32), C.POINTER(_I32), _I32, _P]),
     "w2v2_op_normalize_windows": (C.c_int, [_P, _I32, _P, _P, _P, _P]),
 }

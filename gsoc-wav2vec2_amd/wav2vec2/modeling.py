@@ -314,12 +314,16 @@ class TFKerasModel(Layer):
         CONTRACT of "f16x2": activations must stay below 4094 in magnitude.  A forward that meets a larger one saturates it, sets a
         sticky device flag and STILL RETURNS logits -- they are then not fp32-grade.  `model(x)` does not read the flag (that would
         synchronise every forward); a caller that cannot bound its activations must poll `range_overflow()` after the forwards
-        it cares about and rerun those in "bf16x3" / "fp32".  Training in "f16x2" is refused (w2v2_train_forward)."""
+        it cares about and rerun those in "bf16x3" / "fp32".  Training in "f16x2" is refused (w2v2_train_forward).
+
+        The packed and windowed entry points (`predict_packed`, `predict_long`, `stream`, ...) take "fp32", "bf16x3" and "f16x2";
+        they take "bf16" once `set_option("bf16_packed", True)` is set."""
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(set(self.PRECISIONS))}, got {precision!r}")
         N.check(self._lib.w2v2_set_precision(self._handle, self.PRECISIONS[precision]), "w2v2_set_precision")
 
-    OPTIONS = {"bf16_shadows": 0, "keep_activations": 1, "split_planes": 2, "wgrad_stream": 3, "defer_folds": 4}      # W2V2_OPT_* of include/w2v2.h
+    OPTIONS = {"bf16_shadows": 0, "keep_activations": 1, "split_planes": 2, "wgrad_stream": 3, "defer_folds": 4,
+               "bf16_packed": 5}      # W2V2_OPT_* of include/w2v2.h
 
     def set_option(self, name, value):
         """Per-model switches of the bf16 precision mode (include/w2v2.h: w2v2_set_option): "bf16_shadows" (default on; off =
@@ -329,7 +333,10 @@ class TFKerasModel(Layer):
         of the model, same bits); "split_planes" (default on; off = the "bf16x3" / "f16x2" forward GEMMs split fp32 rows
         in registers instead of streaming planes written by their producers: the round-4 path, for A/B measurements);
         "defer_folds" (default on; training backward: the nine small reductions that finish an encoder layer's gradients run as one
-        launch in front of the layer's bucket event; off = one launch behind each producer, same bits)."""
+        launch in front of the layer's bucket event; off = one launch behind each producer, same bits);
+        "bf16_packed" (default off; on = `predict_packed`, `predict_long`, `stream` and everything built on them also run in
+        precision "bf16", each utterance with the bf16-grade logits `model(x)` gives it alone in that mode -- good for
+        decoding, too coarse for exact scores; off = those entry points refuse "bf16", as before the option existed)."""
         if name not in self.OPTIONS:
             raise KeyError(f"unknown option {name!r}; one of {sorted(self.OPTIONS)}")
         N.check(self._lib.w2v2_set_option(self._handle, self.OPTIONS[name], int(bool(value))), "w2v2_set_option")
@@ -542,7 +549,9 @@ class TFKerasModel(Layer):
     def predict_packed(self, waveforms, sampling_rate=None, normalize=False):
         """Inference on utterances of different lengths in one call, each computed exactly as `self(wave[None])` computes it
         alone: no padding enters any statistic and no frame attends across utterances (w2v2_forward_packed).  Precision modes
-        "fp32", "bf16x3" and "f16x2" (set_precision); "bf16" raises.  In "f16x2" the contract of set_precision holds: poll
+        "fp32", "bf16x3" and "f16x2" (set_precision); "bf16" raises unless `set_option("bf16_packed", True)` is set, and then
+        gives each utterance the bf16-grade logits of `self(wave[None])` in that mode (for decoding, not for exact scores).
+        In "f16x2" the contract of set_precision holds: poll
         `range_overflow()` after the calls whose activations are not known to stay in range.
         `waveforms`: a list of 1-D numpy arrays or torch tensors, each already normalised.  Returns a list of
         (T_i, vocab | hidden) tensors, T_i = num_frames(len_i): views of one packed output.
@@ -975,7 +984,7 @@ class Wav2Vec2ForCTC(TFKerasModel):
         `stable_text` depends on the beam.
         `lm`, `bias`, `beam_width`, `nbest`: as `transcribe`, fixed for the session; a language model sees the whole recording as
         one utterance.  16 kHz input only (`sampling_rate` other than None / 16000: ValueError; a resampler that carries its
-        filter state across chunks does not exist here).  Precision modes as `predict_long` ("bf16" raises).  No pause
+        filter state across chunks does not exist here).  Precision modes as `predict_long` ("bf16" raises unless the option "bf16_packed" is on).  No pause
         segmentation, rescoring or confidence in a session."""
         from .streaming import StreamingSession
         return StreamingSession(self, tokenizer, n_streams=n_streams, window_s=window_s, margin_s=margin_s, beam_width=beam_width,

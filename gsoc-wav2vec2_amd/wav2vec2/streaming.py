@@ -61,9 +61,9 @@ class StreamingSession:
                              "that carries its state across them first")
         if not model._with_lm_head:
             raise ValueError("a streaming session needs a model with the CTC head")
-        if model.precision == "bf16":
+        if model.precision == "bf16" and not model.get_option("bf16_packed"):
             raise RuntimeError('a streaming session runs the windowed forward, which takes the precision modes "fp32", "bf16x3" and '
-                               '"f16x2"; the model is in "bf16"')
+                               '"f16x2"; the model is in "bf16" (set_option("bf16_packed", True) lets it through)')
         cfg = model.config
         w_s, m_s = seconds_to_samples(window_s, margin_s, cfg)
         self.window = w_s if window is None else int(window)

@@ -163,12 +163,19 @@ int w2v2_get_precision(const w2v2_model* m);
  *                                          attention column-sum folds: nine launches per layer) run as ONE launch in front of the
  *                                          layer's bucket event.  Same summation order, same bits; 0 = one launch behind each
  *                                          producer (the round-4 behaviour, kept for the bit-identity test and A/B timing).
+ *   W2V2_OPT_BF16_PACKED (default 0)       1 = w2v2_forward_packed, w2v2_forward_windows and everything built on them accept
+ *                                          W2V2_PRECISION_BF16: attention and the positional conv take segment forms of the bf16
+ *                                          kernels, each utterance as w2v2_forward computes it alone in that mode.  bf16-grade
+ *                                          logits (what torch.autocast(bfloat16) costs the model): for decoding, not for exact
+ *                                          scores.  0 = the mode is refused there, as before the option existed.  No effect on
+ *                                          the other precision modes.
  * w2v2_get_option returns the value, or W2V2_EINVAL for an unknown option. */
 #define W2V2_OPT_BF16_SHADOWS 0
 #define W2V2_OPT_KEEP_ACTIVATIONS 1
 #define W2V2_OPT_SPLIT_PLANES 2
 #define W2V2_OPT_WGRAD_STREAM 3
 #define W2V2_OPT_DEFER_FOLDS 4
+#define W2V2_OPT_BF16_PACKED 5
 int w2v2_set_option(w2v2_model* m, int32_t option, int32_t value);
 int w2v2_get_option(const w2v2_model* m, int32_t option);
 /* W2V2_PRECISION_F16X2: *flag = 1 if a forward since the last call met an activation outside fp16's range after scaling
@@ -193,7 +200,8 @@ int w2v2_forward(w2v2_model* m, const float* wave_dev, int32_t B, int64_t L,
  *   wave_dev         (sum len_i) fp32, the utterances back to back, each already normalised
  *   cu_samples_host  (n + 1) int64 prefix offsets, cu_samples_host[0] = 0
  *   out_dev          (sum T_i, vocab | hidden), T_i = w2v2_num_frames(len_i); utterance i at row sum_{j<i} T_j
- * Precision modes W2V2_PRECISION_FP32, _BF16X3 and _F16X2; W2V2_PRECISION_BF16 gives W2V2_EINVAL naming the mode.  In
+ * Precision modes W2V2_PRECISION_FP32, _BF16X3 and _F16X2, and W2V2_PRECISION_BF16 once W2V2_OPT_BF16_PACKED is set (without the
+ * option it gives W2V2_EINVAL naming the mode; with it, each utterance carries w2v2_forward's bf16-grade logits).  In
  * f16x2 the same range contract as w2v2_forward holds: poll w2v2_range_overflow.  Every len_i must give T_i >= 1.
  * The utterances run as one stream with each start aligned to the conv stack's total stride; only conv0's GroupNorm
  * statistics, the positional conv and attention see utterance boundaries.  The 1-2 stream rows behind each utterance
@@ -218,7 +226,8 @@ int w2v2_forward_packed(w2v2_model* m, const float* wave_dev, int32_t n, const i
  *                  0: the samples are used as they are
  *   out_dev        (sum keepn_i, vocab | hidden); window i's kept rows at row sum_{j<i} keepn_j
  * W2V2_EINVAL with a message naming the window: a window outside [0, wave_samples), shorter than the receptive field, keepn_i == 0,
- * a kept range outside the window's frames; also precision W2V2_PRECISION_BF16 (naming the mode) and normalize outside {0, 1}. */
+ * a kept range outside the window's frames; also precision W2V2_PRECISION_BF16 without W2V2_OPT_BF16_PACKED (naming the mode) and
+ * normalize outside {0, 1}.  In W2V2_PRECISION_BF16 with the option a window's rows carry the bits w2v2_forward gives it alone in that mode. */
 int w2v2_forward_windows(w2v2_model* m, const float* wave_dev, int64_t wave_samples, int32_t n, const int64_t* sample0_host,
                          const int64_t* samples_host, const int32_t* keep0_host, const int32_t* keepn_host, int32_t normalize,
                          float* out_dev, void* stream);
@@ -960,12 +969,20 @@ int w2v2_op_attention(const float* qkv_dev, const int32_t* frame_len_dev, float*
  * [cu_frames_host[i], cu_frames_host[i + 1]) of qkv (rows, 3H) and ctx (rows, H), back to back, and attends only
  * within them, unmasked -- each as w2v2_op_attention computes it alone (B = 1, T = its frames, no frame_len).
  * Dispatches on w2v2_op_set_precision: fp32 kernel in mode 0; the split kernel in modes 2 / 3 (head size 64, else the
- * fp32 kernel and a split of its output); mode 1 (bf16) gives W2V2_EINVAL.  planes_dev (optional, modes 2 / 3):
+ * fp32 kernel and a split of its output); mode 1 (bf16) gives W2V2_EINVAL (w2v2_op_attention_packed_bf16 is that mode's
+ * entry).  planes_dev (optional, modes 2 / 3):
  * the planes of ctx, plane_stride elements apart (W2V2_PLANES_* of the mode); ctx_dev may then be null on the split
  * kernel.  range_flag_dev (optional): f16x2 sticky saturation flag.  Stages its tile table synchronously. */
 int w2v2_op_attention_packed(const float* qkv_dev, int32_t n, const int32_t* cu_frames_host, float* ctx_dev,
                              uint16_t* planes_dev, int64_t plane_stride, int32_t* range_flag_dev,
                              int32_t H, int32_t heads, void* stream);
+
+/* The same packed layout on the bf16 matrix pipe (head size 64): the segment form of precision mode 1's attention kernel, whatever
+ * w2v2_op_set_precision says.  Each utterance's ctx (fp32) and ctx16 (its nearest-even bf16 shadow) are the bits w2v2_op_attention
+ * gives it alone in mode 1.  qkv16_dev: the bf16 shadow of qkv, or NULL (qkv_dev is then rounded into scratch first); qkv_dev may be
+ * NULL when the shadow is given.  ctx_dev or ctx16_dev may be NULL, not both.  Stages its tile table synchronously. */
+int w2v2_op_attention_packed_bf16(const float* qkv_dev, const uint16_t* qkv16_dev, int32_t n, const int32_t* cu_frames_host,
+                                  float* ctx_dev, uint16_t* ctx16_dev, int32_t H, int32_t heads, void* stream);
 
 /* frame_len[b] = conv-stack length arithmetic applied to sum(mask[b, :])
  * (modeling.py:201-204). */
@@ -1031,6 +1048,14 @@ int w2v2_op_pos_conv_weight_shadow(const float* wg_dev, uint16_t* w16_dev, int32
 int w2v2_op_pos_conv_bf16(const float* x_dev, const uint16_t* w16_dev, const float* bias_dev, const int32_t* frame_len_dev, float* y_dev,
                           float* pre_act_dev, uint16_t* pack16_dev, float* xz_ws_dev, int32_t B, int32_t T, int32_t H, int32_t K,
                           int32_t groups, int32_t act, int32_t pad_left, int32_t add_residual, void* stream);
+
+/* The forward positional conv (pad_left = K / 2, residual on) of n packed utterances on the bf16 matrix pipe: utterance i owns rows
+ * [cu_frames_host[i], cu_frames_host[i + 1]) of x and y (rows, H), back to back, and is zero-padded at its own edges -- each as
+ * w2v2_op_pos_conv_bf16 computes it alone (B = 1, T = its frames, no frame_len), bit for bit.  Scratch is the library's own.
+ * Stages its utterance table synchronously. */
+int w2v2_op_pos_conv_packed_bf16(const float* x_dev, const uint16_t* w16_dev, const float* bias_dev, int32_t n,
+                                 const int32_t* cu_frames_host, float* y_dev, int32_t H, int32_t K, int32_t groups, int32_t act,
+                                 void* stream);
 
 /* wg_t[g][K-1-k][co][ci] = wg[g][k][ci][co]: the kernel of the data-gradient pass. */
 int w2v2_op_pos_conv_flip_regroup(const float* wg_dev, float* wg_t_dev, int32_t K, int32_t cg, int32_t groups, void* stream);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Throughput of three ways to run one set of differently sized utterances through the base Wav2Vec2ForCTC (seeded weights), in
-one precision mode (--precision fp32 | bf16x3 | f16x2, default fp32; the mode holds for all three forms):
+one precision mode (--precision fp32 | bf16 | bf16x3 | f16x2, default fp32; the mode holds for all three forms; "bf16" sets the
+option "bf16_packed", which the packed form needs in that mode -- b1 and padded run the dense bf16 forward either way):
 
   packed  one predict_packed call (w2v2_forward_packed): each utterance exact, no padded frame computed;
   b1      a B = 1 loop: exact, one forward per utterance (a new length re-sizes the workspace, as for any caller);
@@ -9,8 +10,9 @@ one precision mode (--precision fp32 | bf16x3 | f16x2, default fp32; the mode ho
 
 The lengths are drawn once from a seed, uniform in [--min-s, --max-s] seconds (default 64 utterances of 1.5-35 s, roughly
 LibriSpeech test-clean's range).  Prints one JSON line: audio-s/s per form, ms per pass, and the padded batch's padding fraction.
+--families adds one more packed pass under the model's profiler and its time per kernel family ("packed_families_ms").
 
-    python tools/packed_bench.py [--n 64] [--steps 3] [--warmup 1] [--forms packed,b1,padded] [--precision fp32]
+    python tools/packed_bench.py [--n 64] [--steps 3] [--warmup 1] [--forms packed,b1,padded] [--precision fp32] [--families]
 """
 import argparse
 import json
@@ -35,7 +37,8 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--forms", default="packed,b1,padded")
-    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "f16x2"])
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16x3", "f16x2"])
+    ap.add_argument("--families", action="store_true")
     args = ap.parse_args()
 
     import torch
@@ -46,6 +49,8 @@ def main():
     m = wav2vec2.Wav2Vec2ForCTC(cfg, input_shape=(1, 2048))
     m.set_weights(V.seeded_weights(cfg, seed=1))
     m.set_precision(args.precision)
+    if args.precision == "bf16":
+        m.set_option("bf16_packed", True)
     rng = np.random.default_rng(args.seed)
     lens = rng.integers(int(args.min_s * SR), int(args.max_s * SR) + 1, size=args.n)
     waves = [torch.randn(int(n), device="cuda") for n in lens]
@@ -88,6 +93,13 @@ def main():
         if name == "padded":
             padded = None
             torch.cuda.empty_cache()
+    if args.families and "packed" in res:
+        m.profile(True)
+        m.profile_reset()
+        run_packed()
+        torch.cuda.synchronize()
+        res["packed_families_ms"] = {k: round(v["ms"], 3) for k, v in m.profile_read().items() if v["launches"]}
+        m.profile(False)
     if "packed" in res and "padded" in res:
         res["packed_over_padded"] = round(res["packed"]["audio_s_per_s"] / res["padded"]["audio_s_per_s"], 3)
     if "packed" in res and "b1" in res:
