@@ -177,9 +177,8 @@ int launch_gemm(Profiler* prof, const float* A, int64_t lda, int64_t strideA, co
                 const float* residual, int M, int N, int K, int nbatch, int act, hipStream_t s);
 
 // fp32 GEMM on the LDS-ring kernels (gemm_f32_sw.hip): tile 0 = 256 x 128, 1 = 128 x 128, 2 = 64 x 64; persist: at most two blocks per CU,
-// each looping over its tiles.  launch_gemm routes to them; gemm_f32_ring_ok says whether a shape fits.
-void gemm_f32_force_ring(int route);      // this thread's next launch_gemm calls: 0 | 1 | 2 as gemm_f32.hip's RING_DEFAULT, -1 = by shape
-bool gemm_f32_ring_form_ok(const float* bias, const float* residual, int act);      // the ring kernels have an instance for this epilogue
+// each looping over its tiles.  launch_gemm routes to them (gemm_f32_route.h); gemm_f32_ring_ok says whether a shape fits.
+void gemm_f32_force_ring(int route);      // this thread's next launch_gemm calls: 0 double buffer | 1 ring | 2 persistent ring, -1 = by shape
 void gemm_f32_ring_launches(int64_t* counts /* [4]: 256 x 128, 128 x 128, 64 x 64, 64 x 64 quarters */);      // launches so far, this process
 bool gemm_f32_ring_ok(int tile, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb, int64_t strideB,
                       int M, int N, int K);

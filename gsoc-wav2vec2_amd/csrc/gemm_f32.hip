@@ -20,11 +20,9 @@
 // is free as long as A and B agree, so each lane fetches its A fragment as ONE
 // 16-byte LDS read (4 consecutive k) and the k-steps are taken as
 // {k, k+4}, {k+1, k+5}, ... within an 8-wide k block.
-#include <stdlib.h>
-
-
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_f32_route.h"
 
 namespace w2v2 {
 
@@ -56,8 +54,9 @@ __device__ __forceinline__ float ld_b(const float* B, const GemmArgs& g, int k, 
 }
 
 
-template <int BM, int BN, int WM, int WN>
-struct Cfg {
+// the register-staged kernel's one instance: 128 x 128 x 32, 2 x 2 waves of 64 x 64, two blocks per CU
+struct Staged {
+    static constexpr int BM = 128, BN = 128, WM = 2, WN = 2, MINW = 2;
     static constexpr int NT = WM * WN * 64;             // threads
     static constexpr int WTM = BM / WM, WTN = BN / WN;  // wave tile
     static constexpr int MT = WTM / 32, NTL = WTN / 32; // 32x32 accumulators per wave
@@ -67,9 +66,11 @@ struct Cfg {
     static constexpr size_t LDS = 2 * STAGE * sizeof(float);
 };
 
-template <bool FAST, int BM, int BN, int WM, int WN, int MINW>
-__global__ __launch_bounds__(WM* WN * 64, MINW) void gemm_f32_kernel(GemmArgs g) {
-    using C_ = Cfg<BM, BN, WM, WN>;
+// Register-staged variant for the shapes without 16-byte global accesses (K % 32, N % 4, a leading dimension or a pointer off
+// alignment): guarded scalar loads, zero-filled past M, N and K.  Every other shape takes the LDS-DMA kernels below.
+__global__ __launch_bounds__(Staged::NT, Staged::MINW) void gemm_f32_kernel(GemmArgs g) {
+    using C_ = Staged;
+    constexpr int BM = C_::BM, BN = C_::BN, WN = C_::WN;
     constexpr int NT = C_::NT, MT = C_::MT, NTL = C_::NTL, NA = C_::NA, NB = C_::NB, STAGE = C_::STAGE;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
@@ -95,48 +96,31 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void gemm_f32_kernel(GemmArgs g)
 
     // ---- global -> register staging of one K tile (float4 per thread) ---------
     f32x4 ra[NA], rb[NB];
-    int64_t a_off[NA], b_off[NB];
     int a_lds[NA], b_lds[NB];
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
         const int idx = tid + i * NT;
-        const int r = idx / (BK / 4), c = (idx % (BK / 4)) * 4;
-        int row = m0 + r;
-        row = row < g.M ? row : g.M - 1;               // clamp: loads stay in bounds, stores are guarded
-        a_off[i] = (int64_t)row * g.lda + c;
-        a_lds[i] = r * LDA_S + c;
+        a_lds[i] = (idx / (BK / 4)) * LDA_S + (idx % (BK / 4)) * 4;
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
         const int idx = tid + i * NT;
-        const int r = idx / (BN / 4), c = (idx % (BN / 4)) * 4;
-        int col = n0 + c;
-        col = col < g.N ? col : (g.N >= 4 ? g.N - 4 : 0);   // clamped columns feed accumulators never stored
-        b_off[i] = (int64_t)r * g.ldb + col;
-        b_lds[i] = BM * LDA_S + r * BN + c;
+        b_lds[i] = BM * LDA_S + (idx / (BN / 4)) * BN + (idx % (BN / 4)) * 4;
     }
 
     auto load_tile = [&](int kt) {
         const int k0 = kt * BK;
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
-            if constexpr (FAST) {
-                ra[i] = *reinterpret_cast<const f32x4*>(A + a_off[i] + k0);
-            } else {
-                const int idx = tid + i * NT;
-                const int row = m0 + idx / (BK / 4), k = k0 + (idx % (BK / 4)) * 4;
-                ra[i] = f32x4{ld_a(A, g, row, k), ld_a(A, g, row, k + 1), ld_a(A, g, row, k + 2), ld_a(A, g, row, k + 3)};
-            }
+            const int idx = tid + i * NT;
+            const int row = m0 + idx / (BK / 4), k = k0 + (idx % (BK / 4)) * 4;
+            ra[i] = f32x4{ld_a(A, g, row, k), ld_a(A, g, row, k + 1), ld_a(A, g, row, k + 2), ld_a(A, g, row, k + 3)};
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
-            if constexpr (FAST) {
-                rb[i] = *reinterpret_cast<const f32x4*>(Bm + b_off[i] + (int64_t)k0 * g.ldb);
-            } else {
-                const int idx = tid + i * NT;
-                const int k = k0 + idx / (BN / 4), col = n0 + (idx % (BN / 4)) * 4;
-                rb[i] = f32x4{ld_b(Bm, g, k, col), ld_b(Bm, g, k, col + 1), ld_b(Bm, g, k, col + 2), ld_b(Bm, g, k, col + 3)};
-            }
+            const int idx = tid + i * NT;
+            const int k = k0 + idx / (BN / 4), col = n0 + (idx % (BN / 4)) * 4;
+            rb[i] = f32x4{ld_b(Bm, g, k, col), ld_b(Bm, g, k, col + 1), ld_b(Bm, g, k, col + 2), ld_b(Bm, g, k, col + 3)};
         }
     };
     auto store_tile = [&](int buf) {
@@ -210,8 +194,8 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void gemm_f32_kernel(GemmArgs g)
     }
 }
 
-// ---- LDS-DMA variant (FAST shapes only) ---------------------------------------
-// Same 128x128x32 tile and MFMA loop, but the K tiles go HBM/L2 -> LDS directly with
+// ---- LDS-DMA variant (shapes with 16-byte global accesses) ----------------------
+// Same tile and MFMA loop, but the K tiles go HBM/L2 -> LDS directly with
 // global_load_lds_dwordx4 (no VGPR staging, no ds_write pass, 32 fewer VGPRs).  The DMA writes
 // LDS lane-linearly (wave-uniform base + lane * 16 B), so the A image cannot be row-padded; the
 // bank-conflict fix is an XOR swizzle applied on the per-lane GLOBAL source address and again on
@@ -364,30 +348,18 @@ int launch_dma(GemmArgs& g, int nbatch, hipStream_t s) {
     return W2V2_OK;
 }
 
-template <int BM, int BN, int WM, int WN, int MINW>
-int launch_cfg(GemmArgs& g, bool fast, int nbatch, hipStream_t s) {
-    using C_ = Cfg<BM, BN, WM, WN>;
-    g.tiles_m = (g.M + BM - 1) / BM;
-    g.tiles_n = (g.N + BN - 1) / BN;
+int launch_staged(GemmArgs& g, int nbatch, hipStream_t s) {
+    g.tiles_m = (g.M + Staged::BM - 1) / Staged::BM;
+    g.tiles_n = (g.N + Staged::BN - 1) / Staged::BN;
     static std::atomic<bool> attr_set{false};   // (idempotent call; atomic so concurrent host threads agree on the flag)
     if (!attr_set) {   // > 64 KiB of dynamic LDS needs the opt-in
-        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_kernel<true, BM, BN, WM, WN, MINW>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)C_::LDS));
-        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_kernel<false, BM, BN, WM, WN, MINW>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)C_::LDS));
+        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)Staged::LDS));
         attr_set = true;
     }
-    dim3 grid(g.tiles_m * g.tiles_n, 1, nbatch), block(C_::NT);
-    if (fast)
-        W2V2_LAUNCH((gemm_f32_kernel<true, BM, BN, WM, WN, MINW>), grid, block, C_::LDS, s, g);
-    else
-        W2V2_LAUNCH((gemm_f32_kernel<false, BM, BN, WM, WN, MINW>), grid, block, C_::LDS, s, g);
+    W2V2_LAUNCH(gemm_f32_kernel, dim3(g.tiles_m * g.tiles_n, 1, nbatch), dim3(Staged::NT), Staged::LDS, s, g);
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
-}
-
-int forced_cfg() {
-    return tune_int("W2V2_GEMM_CFG", -1);
 }
 
 // ---- split-K for small problems (serving: B = 1) ------------------------------------------------------------------
@@ -416,12 +388,22 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 
 thread_local int tl_precision = 0;
-thread_local int tl_ring = -1;      // w2v2_op_gemm_variant: forces the ring route below for one call (-1: by shape)
+thread_local int tl_ring = -1;      // w2v2_op_gemm_variant: GemmF32Problem::ring of this thread's calls (-1: by shape)
 
-// The LDS-ring kernels (gemm_f32_sw.hip) for the shapes that took gemm_f32_dma_kernel's 256 x 128 x 16, 128 x 128 x 32 and
-// 64 x 64 x 32 instances (the split-K slabs keep the last): 0 = those instances, 1 = the ring kernels with one tile per block, 2 = the ring kernels with a persistent grid.
-constexpr int RING_DEFAULT = 2;
-int ring_route_any() { return tl_ring >= 0 ? tl_ring : tune_int("W2V2_GEMM_RING", RING_DEFAULT); }
+// one launch of a route: `g` over nbatch batches on kernel k (GemmF32Kernel)
+int launch_kernel(int k, bool persist, GemmArgs& g, int nbatch, hipStream_t s) {
+    switch (k) {
+        case GK_RING_256x128: case GK_RING_128x128: case GK_RING_64x64:
+            return launch_gemm_f32_ring(k - GK_RING_256x128, persist, g.A, g.lda, g.strideA, g.B, g.ldb, g.strideB, g.C, g.ldc, g.strideC, g.bias,
+                                        g.residual, g.M, g.N, g.K, nbatch, g.act, s);
+        case GK_DB_256x128x16: return launch_dma<4, 2, 2, 16, 256, 128>(g, nbatch, s);      // 8 waves of 64 x 64, 48 KiB: two blocks per CU
+        case GK_DB_128x128x32: return launch_dma<2, 4, 2>(g, nbatch, s);                     // 8 waves of 64 x 32, two blocks per CU
+        case GK_DB_64x64x32: return launch_dma<2, 2, 2, 32, 64, 64>(g, nbatch, s);           // 4 waves of 32 x 32
+        case GK_STAGED_128x128: return launch_staged(g, nbatch, s);
+    }
+    W2V2_REQUIRE(false, "gemm: the route names no kernel (%d)", k);
+    return W2V2_OK;
+}
 
 }  // namespace
 
@@ -435,7 +417,8 @@ int launch_gemm(Profiler* prof, const float* A, int64_t lda, int64_t strideA, co
     return launch_gemm_ex(prof, A, lda, strideA, B, ldb, 0, C, ldc, strideC, bias, residual, M, N, K, nbatch, act, s);
 }
 
-// strideB != 0: every batch has its own B (split-K weight gradients: A, B advance along K, C is a slab)
+// strideB != 0: every batch has its own B (split-K weight gradients: A, B advance along K, C is a slab).
+// gemm_f32_route (gemm_f32_route.h) decides which kernels run; this function runs them.
 int launch_gemm_ex(Profiler* prof, const float* A, int64_t lda, int64_t strideA, const float* B,
                    int64_t ldb, int64_t strideB, float* C, int64_t ldc, int64_t strideC, const float* bias,
                    const float* residual, int M, int N, int K, int nbatch, int act, hipStream_t s) {
@@ -445,159 +428,44 @@ int launch_gemm_ex(Profiler* prof, const float* A, int64_t lda, int64_t strideA,
     W2V2_REQUIRE(M > 0 && N > 0 && K > 0 && nbatch > 0, "gemm: bad sizes M=%d N=%d K=%d batch=%d", M, N, K, nbatch);
     W2V2_REQUIRE(lda >= 1 && ldb >= N && ldc >= N && ldc < (1 << 23), "gemm: bad leading dimensions");
     W2V2_REQUIRE(act >= 0 && act <= 2, "gemm: bad activation %d", act);
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.bias = bias; g.residual = residual;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.strideA = strideA; g.strideB = strideB; g.strideC = strideC;
-    g.M = M; g.N = N; g.K = K; g.act = act;
-    const bool fast = (K % BK == 0) && (N % 4 == 0) && (lda % 4 == 0) && (ldb % 4 == 0) &&
-                      (strideA % 4 == 0) && (strideB % 4 == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0) &&
-                      ((reinterpret_cast<uintptr_t>(B) & 15) == 0);
+    auto aligned16 = [](const void* a, const void* b, const void* c = nullptr) {
+        return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+    };
+    const GemmF32Problem p{M, N, K, nbatch, lda, ldb, ldc, strideA, strideB, act, bias != nullptr, residual != nullptr,
+                           aligned16(A, B), aligned16(C, bias, residual), tl_ring};
+    const GemmF32Route route = gemm_f32_route(p);
+    GemmArgs g{A, B, C, bias, residual, lda, ldb, ldc, strideA, strideB, strideC, M, N, K, act};
     ProfScope ps(prof, FAM_GEMM, 2.0 * M * (double)N * K * nbatch,
                  4.0 * nbatch * ((double)M * K + (double)M * N) + 4.0 * (double)K * N, s);
-    // (the ring kernels hold one instance per epilogue form the models use; the other forms, tanh GELU among them, keep the double buffer)
-    auto ring_route = [&]() { return gemm_f32_ring_form_ok(bias, residual, act) ? ring_route_any() : 0; };
-    int cfg = forced_cfg();
-    const bool by_shape = cfg < 0;      // (a forced W2V2_GEMM_CFG names a gemm_f32_dma_kernel / gemm_f32_kernel instance)
-    // default: the LDS-DMA 128x128 kernel with 8 waves (2x4, each wave 64x32), 2 blocks per CU = 4 waves
-    // per SIMD, whenever the shape allows 16-byte global accesses (every GEMM of the model does).
-    // Measured on MI355X, B=32 base shapes (profiles/r01_gemm_tile_study.md): this 118-129 TF; the same
-    // with 4 waves 112-123; register-staged 128x128 107-120; 128x256 / 256x128 at 1 wave per SIMD 75-100;
-    // 256x256 8-wave 67-115; BK=16 variants with 3-4 blocks per CU 114-125.
-    // (cfg 14 = 128x96 tiles with 6 waves, meant to turn the 2.25 "rounds" of the N = 768 GEMMs into 3.0 exact ones:
-    // measured 100 TF against 114-121 -- blocks are not scheduled in lock-step rounds, so the quantisation it removes
-    // does not exist, and the 6-wave block is simply less efficient.)
-    if (cfg < 0 && fast && nbatch == 1 && strideB == 0 && K >= 1024 && (ldc % 4) == 0 &&
-        ((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(residual) | reinterpret_cast<uintptr_t>(bias)) & 15) == 0) {
-        const int64_t tiles64 = (int64_t)((M + 63) / 64) * ((N + 63) / 64);
-        int S = 1;
-        for (int cand = 8; cand >= 2; cand >>= 1)
-            if (K % (cand * BK) == 0 && K / cand >= 256 && tiles64 * cand <= 512) { S = cand; break; }
-        if (S > 1 && tiles64 <= 256) {
-            const size_t need = (size_t)S * M * N;
-            float* ws = nullptr;
-            void* raw = nullptr;
-            if (int e = stream_scratch(SCRATCH_SPLITK, s, need * sizeof(float), &raw)) return e;
-            ws = reinterpret_cast<float*>(raw);
+    switch (route.kind) {
+        case GR_ONE: return launch_kernel(route.kernel[0], route.persist, g, nbatch, s);
+        case GR_SPLIT_K: {      // S slabs of K / S as batches (A advances along its columns, B along its rows), then the fold with the epilogue
+            void* ws = nullptr;
+            if (int e = stream_scratch(SCRATCH_SPLITK, s, (size_t)route.S * M * N * sizeof(float), &ws)) return e;
             GemmArgs h = g;
-            h.C = ws; h.bias = nullptr; h.residual = nullptr; h.act = 0;
-            h.K = K / S; h.strideA = K / S; h.strideB = (int64_t)(K / S) * ldb; h.ldc = N; h.strideC = (int64_t)M * N;
-            if (int e = launch_dma<2, 2, 2, 32, 64, 64>(h, S, s)) return e;
-            const int64_t n4 = (int64_t)M * N / 4;
-            int64_t blocks = (n4 + 255) / 256;
-            blocks = blocks > 2048 ? 2048 : blocks;
-            W2V2_LAUNCH(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ws, C, bias, residual, M, N, ldc, S, act);
+            h.C = reinterpret_cast<float*>(ws); h.bias = nullptr; h.residual = nullptr; h.act = 0;
+            h.K = K / route.S; h.strideA = K / route.S; h.strideB = (int64_t)(K / route.S) * ldb; h.ldc = N; h.strideC = (int64_t)M * N;
+            if (int e = launch_kernel(route.kernel[0], false, h, route.S, s)) return e;
+            const int64_t n4 = (int64_t)M * N / 4, blocks = (n4 + 255) / 256;
+            W2V2_LAUNCH(splitk_reduce_kernel, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, s, h.C, C, bias, residual, M, N, ldc, route.S, act);
             W2V2_HIP_CHECK(hipGetLastError());
             return W2V2_OK;
         }
-    }
-    if (cfg < 0) {
-        cfg = 7;
-        // small problems (batch 1-4 of the transformer GEMMs: M = 768 rows is 6 row tiles): 128x128 tiles leave most
-        // of the 256 CUs idle and serialise a long K loop per tile, so switch to 64x64 tiles (4x the blocks, 4 waves)
-        const int64_t tiles128 = (int64_t)((M + 127) / 128) * ((N + 127) / 128) * nbatch;
-        if (fast && tiles128 < 384) cfg = 16;
-        // Tail fill.  512 blocks of the 128x128 kernel are resident (2 per CU); T tiles whose last, partial round fills at
-        // most a quarter of those slots (N = 768 at B = 32: 1152 = 2 x 512 + 128) leave most CUs idle for one whole tile time.
-        // (A half-full last round is better left alone: large-robust at B = 16 has 768 = 512 + 256 tiles for N = 1024,
-        // a third of the work would move to the slower 64x64 kernel, 82.3 vs 80.5 ms per forward.)
-        // The rows of that partial round are computed with 64x64 tiles instead (4x the blocks, a quarter of the time each).
-        // Whole tile rows leave the small tiles a partial round of their own (N = 768 at B = 32: 22 tile rows = 528 tiles of 64x64 for
-        // 512 places at two 4-wave blocks per CU; sixteen CUs run three and set the time: 142 us where 512 tiles take 102), so the
-        // ring kernels split the tile order instead of the rows where they can (below).
-        // Every output element still sums its K products in the same order, so results do not depend on the tiling
-        // (a row's value is independent of its position in the batch: test_linearity_of_lm_head_at_full_size).
-        const int tail_knob = tune_int("W2V2_GEMM_TAIL", 1);
-        const int64_t tn = (N + 127) / 128, S = 512, r = tiles128 % S;
-        if (tail_knob && fast && cfg == 7 && nbatch == 1 && tiles128 > S && r != 0 && tune_int("W2V2_GEMM_TAIL_DIV", 4) * r <= S) {
-            const int64_t main_rows = ((tiles128 - r) / tn) * 128;
-            // No partial tile (M, N multiples of 128): the ring kernels split the tile order itself, its first tiles128 - r tiles at
-            // 128 x 128 (whole rounds) and the r others as 4 r <= 512 tiles of 64 x 64 (launch_gemm_f32_ring_split, gemm_f32_sw.hip).
-            // Other shapes, and the double buffer, split at a tile row:
-            const int ring_flat = by_shape && tune_int("W2V2_GEMM_TAIL_FLAT", 1) ? ring_route() : 0;
-            if (ring_flat && strideB == 0 && M % 128 == 0 && N % 128 == 0 && gemm_f32_ring_ok(1, A, lda, 0, B, ldb, 0, M, N, K) &&
-                gemm_f32_ring_ok(2, A, lda, 0, B, ldb, 0, M, N, K))
-                return launch_gemm_f32_ring_split(ring_flat == 2, tiles128 - r, A, lda, B, ldb, C, ldc, bias, residual, M, N, K, act, s);
-            if (main_rows > 0 && main_rows < M) {
-                GemmArgs h = g;
-                h.M = (int)main_rows;
-                const int ring = by_shape ? ring_route() : 0;
-                if (ring && strideB == 0 && gemm_f32_ring_ok(1, A, lda, strideA, B, ldb, strideB, h.M, N, K)) {
-                    if (int e = launch_gemm_f32_ring(1, ring == 2, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, bias, residual,
-                                                     h.M, N, K, 1, act, s))
-                        return e;
-                } else if (int e = launch_dma<2, 4, 2>(h, 1, s)) {
-                    return e;
-                }
-                GemmArgs t = g;
-                t.A = g.A + main_rows * lda;
-                t.C = g.C + main_rows * ldc;
-                t.residual = g.residual ? g.residual + main_rows * ldc : nullptr;
-                t.M = M - (int)main_rows;
-                // (Round 4 measured the alternative the round-3 review asked for -- the leftover rows of the K = 3072 members on the 128 x 128
-                //  kernel, K split four ways into slabs folded by splitk_reduce_kernel: 512 blocks at full occupancy, 24 k-steps each.
-                //  Forward 62.38 / 62.44 ms against 62.32 / 62.47 with the 64 x 64 tiles, arms interleaved on one box, two-way split
-                //  62.8-62.9 (profiles/r04_ab_gemm_tail_splitk.txt): a quarter-length K loop pays prologue + epilogue + the fold of 25 MB
-                //  of slabs, which is what the small tiles lose to their single accumulator per wave.  Not kept: it also gave up the
-                //  bit-for-bit independence of a row from its position in the batch.)
-                if (ring && strideB == 0 && gemm_f32_ring_ok(2, t.A, lda, strideA, B, ldb, strideB, t.M, N, K))
-                    return launch_gemm_f32_ring(2, ring == 2, t.A, lda, strideA, B, ldb, strideB, t.C, ldc, strideC, bias,
-                                                t.residual, t.M, N, K, 1, act, s);
-                return launch_dma<2, 2, 2, 32, 64, 64>(t, 1, s);
-            }
+        case GR_ORDER_SPLIT:
+            return launch_gemm_f32_ring_split(route.persist, route.main_tiles, A, lda, B, ldb, C, ldc, bias, residual, M, N, K, act, s);
+        case GR_ROW_SPLIT: {    // every output element still sums its K products in the same order: a row's value does not depend on the cut
+            GemmArgs h = g, t = g;
+            h.M = route.main_rows;
+            t.A = A + (int64_t)route.main_rows * lda;
+            t.C = C + (int64_t)route.main_rows * ldc;
+            t.residual = residual ? residual + (int64_t)route.main_rows * ldc : nullptr;
+            t.M = M - route.main_rows;
+            if (int e = launch_kernel(route.kernel[0], route.persist, h, 1, s)) return e;
+            return launch_kernel(route.kernel[1], route.persist, t, 1, s);
         }
     }
-    if (cfg == 16 && fast && by_shape) {      // the small problems, batched ones included (conv rows of a short input)
-        const int ring = ring_route();
-        if (ring && strideB == 0 && gemm_f32_ring_ok(2, A, lda, strideA, B, ldb, strideB, M, N, K))
-            return launch_gemm_f32_ring(2, ring == 2, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, bias, residual, M, N, K,
-                                        nbatch, act, s);
-    }
-    // Wide tiles for the well-filled shapes (round 4, profiles/r04_gemm_f32_tile_study.txt): 256 x 128 x 16, 8 waves of 64 x 64 (4 x 2), still
-    // two blocks per CU (48 KiB of LDS each, 118 VGPRs) -- 25 % less LDS-DMA per flop and a third fewer fragment reads per MFMA than
-    // 128 x 128 x 32, the same flops per barrier.  Measured per shape against the default: conv1 132.6 vs 130.4 TF, conv2 131.1 vs 130.5,
-    // q|k|v 129.3 vs 127.4, FFN up 126.5 vs 125.3; it LOSES where its tile count quantises (N = 768: 99-104 vs 115-121; conv3-6 with their
-    // 4-8 % row padding), so it takes only GEMMs with >= 3 full rounds of tiles and <= 2.5 % padded rows.  Every output element still sums
-    // its K products in ascending order two at a time: the same bits as the 128 x 128 kernel.
-    const int wide_min = tune_int("W2V2_GEMM_WIDE", 1536);      // fewest 256 x 128 tiles that take the wide kernel (0: never)
-    if (cfg == 7 && fast && wide_min > 0 && N % 128 == 0) {
-        const int64_t tm256 = (M + 255) / 256, tiles256 = tm256 * (N / 128) * nbatch;
-        if (tiles256 >= wide_min && (tm256 * 256 - M) * 40 <= M) {
-            const int ring = by_shape ? ring_route() : 0;
-            if (ring && strideB == 0 && gemm_f32_ring_ok(0, A, lda, strideA, B, ldb, strideB, M, N, K))
-                return launch_gemm_f32_ring(0, ring == 2, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, bias, residual, M, N, K,
-                                            nbatch, act, s);
-            return launch_dma<4, 2, 2, 16, 256, 128>(g, nbatch, s);
-        }
-    }
-    if (cfg == 7 && fast) {
-        const int ring = by_shape ? ring_route() : 0;
-        if (ring && strideB == 0 && gemm_f32_ring_ok(1, A, lda, strideA, B, ldb, strideB, M, N, K))
-            return launch_gemm_f32_ring(1, ring == 2, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, bias, residual, M, N, K,
-                                        nbatch, act, s);
-    }
-    switch (cfg) {
-        case 16: if (fast) return launch_dma<2, 2, 2, 32, 64, 64>(g, nbatch, s); return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);
-        case 14: if (fast) return launch_dma<2, 3, 2, 32, 128, 96>(g, nbatch, s); return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);
-        case 1: return launch_cfg<128, 256, 2, 2, 1>(g, fast, nbatch, s);
-        case 2: return launch_cfg<256, 128, 2, 2, 1>(g, fast, nbatch, s);
-        case 3: return launch_cfg<256, 256, 4, 2, 2>(g, fast, nbatch, s);
-        case 4: if (fast) return launch_dma<2, 2, 2>(g, nbatch, s); return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);
-        case 6: if (fast) return launch_dma<4, 2, 2>(g, nbatch, s); return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);
-        case 7: if (fast) return launch_dma<2, 4, 2>(g, nbatch, s); return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);
-        case 9: if (fast) return launch_dma<2, 4, 3, 16>(g, nbatch, s); return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);
-        case 10: if (fast) return launch_dma<2, 4, 4, 16>(g, nbatch, s); return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);
-        case 11: if (fast) return launch_dma<2, 2, 4, 16>(g, nbatch, s); return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);
-        case 12: if (fast && g.N >= 256) return launch_dma<4, 4, 1, 32, 256, 256>(g, nbatch, s); return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);
-        case 13: if (fast && g.N >= 128) return launch_dma<4, 2, 1, 32, 256, 128>(g, nbatch, s); return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);
-        case 8: if (fast) return launch_dma<4, 4, 1>(g, nbatch, s); return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);
-#ifdef W2V2_TUNING
-        // round-4 tile study (tools-only build): wider tiles at BK = 16, two blocks per CU -- 25 % less LDS-DMA per flop than 128 x 128 x 32
-        case 17: if (fast && g.N >= 256) return launch_dma<2, 4, 2, 16, 128, 256>(g, nbatch, s); return launch_dma<2, 4, 2>(g, nbatch, s);
-        case 18: if (fast && g.N >= 128) return launch_dma<4, 2, 2, 16, 256, 128>(g, nbatch, s); return launch_dma<2, 4, 2>(g, nbatch, s);
-        case 19: if (fast && g.N >= 256) return launch_dma<2, 4, 2, 32, 128, 256>(g, nbatch, s); return launch_dma<2, 4, 2>(g, nbatch, s);
-#endif
-        default: return launch_cfg<128, 128, 2, 2, 2>(g, fast, nbatch, s);
-    }
+    W2V2_REQUIRE(false, "gemm: unknown route kind %d", route.kind);
+    return W2V2_OK;
 }
 
 }  // namespace w2v2

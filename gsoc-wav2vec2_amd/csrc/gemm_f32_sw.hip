@@ -16,6 +16,7 @@
 // any other combination, tanh GELU included, stays on gemm_f32_dma_kernel, whose epilogue takes its switches at run time.
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_f32_route.h"
 #include "gemm_sw_common.h"
 
 namespace w2v2 {
@@ -262,17 +263,10 @@ int launch_ring_form(GemmRingArgs& g, bool persist, hipStream_t s, int64_t first
     return W2V2_OK;
 }
 
-// the epilogue forms with an instance: plain, bias, bias + exact GELU, bias + residual, residual, exact GELU (the bias-free conv layers);
-// -1: none, the caller keeps gemm_f32_dma_kernel
-int ring_form(const float* bias, const float* residual, int act) {
-    if (act == 1) return residual ? -1 : bias ? 2 : 5;
-    if (act != 0) return -1;
-    return residual ? (bias ? 3 : 4) : (bias ? 1 : 0);
-}
-
+// one instance per epilogue form (gemm_f32_route.h: gemm_f32_ring_form); the router keeps every other form on gemm_f32_dma_kernel
 template <int WM, int WN, int BKT, int BM, int BN, int NS, bool QUAD = false>
 int launch_ring(GemmRingArgs& g, int act, bool persist, hipStream_t s, int64_t first = -1, int gm = 0) {
-    switch (ring_form(g.bias, g.residual, act)) {
+    switch (gemm_f32_ring_form(g.bias != nullptr, g.residual != nullptr, act)) {
         case 0: return launch_ring_form<WM, WN, BKT, BM, BN, NS, QUAD, false, false, false>(g, persist, s, first, gm);
         case 1: return launch_ring_form<WM, WN, BKT, BM, BN, NS, QUAD, true, false, false>(g, persist, s, first, gm);
         case 2: return launch_ring_form<WM, WN, BKT, BM, BN, NS, QUAD, true, true, false>(g, persist, s, first, gm);
@@ -286,19 +280,14 @@ int launch_ring(GemmRingArgs& g, int act, bool persist, hipStream_t s, int64_t f
 
 }  // namespace
 
-bool gemm_f32_ring_form_ok(const float* bias, const float* residual, int act) { return ring_form(bias, residual, act) >= 0; }
 void gemm_f32_ring_launches(int64_t* counts) {
     for (int i = 0; i < 4; ++i) counts[i] = g_ring_launches[i].load(std::memory_order_relaxed);
 }
 
 bool gemm_f32_ring_ok(int tile, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb, int64_t strideB,
                       int M, int N, int K) {
-    const int BM = tile == 0 ? 256 : tile == 1 ? 128 : 64, BKT = tile == 2 ? 32 : 16;
-    const bool align = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 && lda % 4 == 0 &&
-                       ldb % 4 == 0 && strideA % 4 == 0 && strideB % 4 == 0;
-    // per-lane DMA offsets are 32-bit byte offsets from the tile's row / column base
-    return align && K % BKT == 0 && N % 4 == 0 && N >= 4 && (int64_t)BM * lda * 4 < (1ll << 31) &&
-           (int64_t)BKT * ldb * 4 < (1ll << 31) && M > 0;
+    const bool ab_aligned = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0;
+    return gemm_f32_ring_shape_ok(tile, ab_aligned, lda, strideA, ldb, strideB, M, N, K);
 }
 
 int launch_gemm_f32_ring(int tile, bool persist, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb,

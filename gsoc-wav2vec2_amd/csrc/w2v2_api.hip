@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gemm_f32_route.h"
 #include "model.h"
 #include "train.h"
 
@@ -807,6 +808,15 @@ int w2v2_op_gelu_reference(const float* x, float* y, int64_t n, void* stream) {
 int w2v2_op_gemm_ring_launches(int64_t* counts) {
     W2V2_REQUIRE(counts, "op_gemm_ring_launches: null argument");
     gemm_f32_ring_launches(counts);
+    return W2V2_OK;
+}
+int w2v2_op_gemm_f32_route(int32_t M, int32_t N, int32_t K, int32_t nbatch, int64_t lda, int64_t ldb, int64_t ldc, int64_t strideA, int64_t strideB,
+                           int32_t act, int32_t has_bias, int32_t has_residual, int32_t ab_aligned, int32_t c_aligned, int32_t variant, int32_t* out) {
+    W2V2_REQUIRE(out && M > 0 && N > 0 && K > 0 && nbatch > 0 && variant >= -1 && variant <= 2, "op_gemm_f32_route: bad argument");
+    const GemmF32Route r = gemm_f32_route(GemmF32Problem{M, N, K, nbatch, lda, ldb, ldc, strideA, strideB, act, has_bias != 0, has_residual != 0,
+                                                         ab_aligned != 0, c_aligned != 0, variant});
+    const int32_t v[8] = {r.kind, r.kernel[0], r.kernel[1], r.S, (int32_t)r.main_tiles, r.main_rows, r.persist, r.kind == GR_ONE ? 1 : 2};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
     return W2V2_OK;
 }
 int w2v2_op_split_planes(const float* x, uint16_t* planes, int64_t plane_stride, int64_t n, int32_t fmt, int32_t* range_flag, void* stream) {

@@ -890,6 +890,17 @@ int w2v2_op_gelu_reference(const float* x_dev, float* y_dev, int64_t n, void* st
  * [3] 64 x 64 quarters of a split launch.  Diagnostic only (one relaxed atomic add per launch): tests read it before and after a call
  * to see which instances the call reached. */
 int w2v2_op_gemm_ring_launches(int64_t* counts);
+/* Which kernels w2v2_op_gemm (variant -1) / w2v2_op_gemm_variant would launch for this problem (csrc/gemm_f32_route.h).  Host only:
+ * touches no device and launches nothing.  ab_aligned: A and B are 16-byte aligned; c_aligned: C, bias and residual are.
+ *   out[0] kind: 0 one launch, 1 split-K (out[3] slabs on out[1], then the fold), 2 split of the 128 x 128 tile order at out[4] tiles
+ *          (out[1], then out[2] as quarters), 3 split at row out[5] (out[1], then out[2]);
+ *   out[1], out[2] kernels (out[2] = 0: none): 1 ring 256 x 128, 2 ring 128 x 128, 3 ring 64 x 64, 4 ring 64 x 64 quarters (the four
+ *          counters of w2v2_op_gemm_ring_launches, in order), 5 double buffer 256 x 128 x 16, 6 double buffer 128 x 128 x 32,
+ *          7 double buffer 64 x 64 x 32, 8 register-staged 128 x 128 (shapes without 16-byte accesses);
+ *   out[6] the ring kernels run a persistent grid; out[7] kernel launches in all. */
+int w2v2_op_gemm_f32_route(int32_t M, int32_t N, int32_t K, int32_t nbatch, int64_t lda, int64_t ldb, int64_t ldc, int64_t strideA,
+                           int64_t strideB, int32_t act, int32_t has_bias, int32_t has_residual, int32_t ab_aligned, int32_t c_aligned,
+                           int32_t variant, int32_t* out);
 
 /* The weight-gradient form of the same GEMM: C_z (M, N) = A_z^T B_z with A given TRANSPOSED, (K, M) fp32 row-major with
  * row stride lda (>= M), and per-batch strides on A, B and C (split-K: batch z covers rows [z K, (z+1) K) of both
