@@ -12,6 +12,7 @@
 #include <string>
 
 #include "../../include/w2v2.h"
+#include "gemm_bf16_route.h"
 
 namespace w2v2 {
 
@@ -264,15 +265,14 @@ struct GemmShadows {
     bool b_zero_row = false;
     int force_kernel = 0;        // forward form with both shadows: 0 = by shape, 1 = the 128 x 128 kernel, 2 = the 128 x 256 software-pipelined one
 };
-// 128 x 256 software-pipelined form, two 4-wave blocks per CU (gemm_bf16_sw.hip): same arithmetic, identical bits
-bool gemm_bf16_sw_ok(int M, int N, int K, int64_t lda, int64_t ldb16, int64_t strideA);
+// 128 x 256 software-pipelined form, two 4-wave blocks per CU (gemm_bf16_sw.hip): same arithmetic, identical bits.  Which shapes they
+// take (gemm_bf16_sw_ok, gemm_bf16_swtr_ok) and which stream A's shadow (gemm_bf16_streams_a16): gemm_bf16_route.h
 int launch_gemm_bf16_sw(const uint16_t* A16, int64_t lda, int64_t strideA, const uint16_t* B16, int64_t ldb16, float* C, uint16_t* C16,
                         int64_t ldc, int64_t strideC, const float* bias, const float* residual, int M, int N, int K, int nbatch, int act,
                         hipStream_t s);
-bool gemm_bf16_swtr_ok(int M, int N, int K, int64_t lda, int64_t ldb, int64_t strideA, int64_t strideB);
 int launch_gemm_bf16_swtr(const uint16_t* A16, int64_t lda, int64_t strideA, const uint16_t* B16, int64_t ldb, int64_t strideB, float* C,
                           int64_t ldc, int64_t strideC, int M, int N, int K, int nbatch, hipStream_t s, int kextra = 0, int krag = 0);
-bool gemm_bf16_streams_a16(int K, int64_t lda, int64_t strideA);     // launch_gemm_bf16_x streams A's shadow for this shape (gemm_bf16.hip)
+void gemm_bf16_launches(int64_t* counts /* [GB_KERNELS], by GemmBf16Kernel */);      // launch_gemm_bf16_x's launches so far, this process
 int launch_gemm_bf16_x(Profiler* prof, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb,
                        int64_t strideB, float* C, int64_t ldc, int64_t strideC, const float* bias,
                        const float* residual, int M, int N, int K, int nbatch, int act, const GemmShadows& x,

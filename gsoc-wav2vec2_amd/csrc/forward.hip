@@ -290,7 +290,7 @@ ForwardPlan w2v2_plan_forward(const w2v2_model* m, int B, int64_t L, bool planes
     p.ctx_fused = p.p_out && split_ok;
 
     // ---- mode bf16: tensors whose one reader is a GEMM certain to stream the bf16 shadow are written only as bf16 ----
-    // One predicate, gemm_bf16_streams_a16 (gemm_bf16.hip), for all of them.  The weight side needs no test: w2v2_ensure_shadows, which
+    // One predicate, gemm_bf16_streams_a16 (gemm_bf16_route.h), for all of them.  The weight side needs no test: w2v2_ensure_shadows, which
     // every forward with `sh` runs first, creates the (N, K) shadow of every GEMM weight, and no entry of m->w16 is ever erased.
     // K = lda = H (or F), strideA = 0: the predicate comes to H % 64 == 0 (F % 64 == 0).
     const bool h_streams = gemm_bf16_streams_a16(H, H, 0), f_streams = gemm_bf16_streams_a16(F, F, 0);

@@ -6,20 +6,31 @@
 //
 // Same contract as gemm_f32.hip (overlapping-row A for the strided convs, per-batch strides for the
 // split-K weight gradients), so the whole model -- forward and backward -- switches precision by
-// routing launch_gemm here (gemm_set_precision).
+// routing launch_gemm here (gemm_set_precision).  Operands that exist as bf16 shadows (GemmShadows) are read from those.
 //
-// Tile: BM x 128 x 64, (BM/64) x 2 waves, each wave a 64x64 sub-tile = 2x2 accumulators of
-// 32x32.  One K tile is 16 MFMAs per wave (512 matrix-pipe cycles) against 16 ds_read_b128.
+// This file holds two kernels, their launchers, and launch_gemm_bf16_x, which validates a call, asks gemm_bf16_route
+// (gemm_bf16_route.h) which kernel it reaches, and launches that one (the 128 x 256 software-pipelined kernels of
+// gemm_bf16_sw.hip included).
+//
+// gemm_bf16_kernel<SRC, BM, BN, WM, WN, MINB>: tile BM x BN x 64 on WM x WN waves, double-buffered LDS, one K tile of
+// prefetch.  Six sources (SRC below) in eight instances: the four register-staged forward sources and the transposed-fp32
+// weight-gradient source at 128 x 128 on 2 x 2 waves (each wave a 64 x 64 sub-tile = 2 x 2 accumulators of 32 x 32: 16 MFMAs
+// against 16 ds_read_b128 per K tile), the LDS-DMA source at 128 x 128 on 2 x 4 waves (64 x 32 each, hand-counted waits), and
+// the LDS-DMA and transposed-fp32 sources at 128 x 64 for narrow outputs.
 // LDS image: rows of 64 bf16 = 128 B (A rows = m, B rows = n, both k-contiguous so a fragment is ONE
 // 16-byte read of 8 consecutive k); the 16-B slot index is XOR-swizzled per row (swz) so that the
-// fragment reads, the A stores and the transposing B stores are all bank-conflict free.  B arrives
+// fragment reads, the A stores and the transposing B stores are all bank-conflict free.  fp32 B arrives
 // n-contiguous from HBM ([K, N] TF kernel layout); the transpose to k-contiguous happens in registers:
 // a thread owns an 8(k) x 4(n) patch, loads it as eight float4 and writes four 16-byte rows.
+//
+// gemm_bf16_tr_kernel<2, 4, 2>: the weight gradient dW = X^T dY from both bf16 shadows, 128 x 128 tiles on 8 waves, LDS-DMA
+// of the operands as they lie in memory and transposing LDS reads (described above the kernel).
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_bf16_route.h"
 #include "gemm_epilogue.h"
 
 namespace w2v2 {
@@ -87,17 +98,18 @@ template <> struct FVec<4> { using type = f32x4; };
 template <> struct FVec<2> { using type = f32x2; };
 
 // SRC: where the operands come from.  0 = fp32 with scalar guards (any shape), 1 = fp32, 16-byte loads,
-// 2 = A from its bf16 shadow, 3 = B from its bf16 [N][K] shadow, 4 = both shadows (no conversion at all: the tile
-// step streams 32 KiB instead of 64), 5 = both shadows copied HBM/L2 -> LDS by global_load_lds_dwordx4 (the swizzle
-// then goes on the per-lane SOURCE address, as in gemm_f32.hip), 7 = fp32 with A TRANSPOSED in memory ((K, M), the
-// activation itself in a weight-gradient GEMM  dW = X^T dY): A takes B's register-transposing path, no transposed copy.  Shadows hold exactly the values the fp32 path would round to, so all five
-// produce bit-identical results.
+// 2 = A from its bf16 shadow, 3 = B from its bf16 [N][K] shadow, 5 = both shadows copied HBM/L2 -> LDS by
+// global_load_lds_dwordx4 (no conversion, no registers: the tile step streams 32 KiB instead of 64; the swizzle goes on the
+// per-lane SOURCE address, as in gemm_f32.hip), 7 = fp32 with A TRANSPOSED in memory ((K, M), the activation itself in a
+// weight-gradient GEMM  dW = X^T dY): A takes B's register-transposing path, no transposed copy.  (4 and 6 were both shadows
+// through registers and through a 4-stage LDS-DMA ring: no longer built)  Shadows hold exactly the
+// values the fp32 path would round to, so all six produce bit-identical results.
 template <int SRC, int BM, int BN, int WM, int WN, int MINB>
 __global__ __launch_bounds__(WM* WN * 64, MINB) void gemm_bf16_kernel(Gemm16Args g) {
-    constexpr bool FAST = SRC >= 1, A16 = SRC == 2 || (SRC >= 4 && SRC <= 6), B16 = SRC == 3 || (SRC >= 4 && SRC <= 6);
-    constexpr bool DMA = SRC == 5 || SRC == 6;      // both shadows, LDS-DMA staging (no registers, no ds_write)
+    static_assert(SRC == 0 || SRC == 1 || SRC == 2 || SRC == 3 || SRC == 5 || SRC == 7, "no such operand source");
+    constexpr bool FAST = SRC >= 1, A16 = SRC == 2 || SRC == 5, B16 = SRC == 3 || SRC == 5;
+    constexpr bool DMA = SRC == 5;                  // both shadows, LDS-DMA staging (no registers, no ds_write)
     constexpr bool AT = SRC == 7;                   // A given TRANSPOSED ((K, M) fp32, m-contiguous): staged like B
-    constexpr int NS = SRC == 6 ? 4 : 2;   // LDS stages; SRC 6 = 4-stage ring, three tiles in flight across raw barriers
     constexpr int NT = WM * WN * 64;
     constexpr int NA16 = BM * 8 / NT, NB16 = BN * 8 / NT;   // 16-byte (8 x bf16) chunks per thread when a shadow is the source
     constexpr int WTM = BM / WM, WTN = BN / WN, MT = WTM / 32, NTL = WTN / 32;   // wave tile, 32x32 accumulators
@@ -459,42 +471,20 @@ __global__ __launch_bounds__(WM* WN * 64, MINB) void gemm_bf16_kernel(Gemm16Args
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ub + db[i]),
                                                  (__attribute__((address_space(3))) void*)(S + BM * ROWB + (wave * PPB + i) * 1024), 16, 0, 0);
         };
-        if constexpr (NS == 2) {
-            issue(0, 0);
-            __syncthreads();                    // carries the vmcnt(0) that retires the DMA
+        issue(0, 0);
+        __syncthreads();                    // carries the vmcnt(0) that retires the DMA
+        W2V2_TRC();
+        for (int kt = 0; kt + 1 < nk; ++kt) {
+            const int cur = kt & 1;
+            if (!(abl & 1)) issue(kt + 1, cur ^ 1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (!(abl & 2)) compute(cur);
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
             W2V2_TRC();
-            for (int kt = 0; kt + 1 < nk; ++kt) {
-                const int cur = kt & 1;
-                if (!(abl & 1)) issue(kt + 1, cur ^ 1);
-                __builtin_amdgcn_sched_barrier(0);
-                if (!(abl & 2)) compute(cur);
-                __builtin_amdgcn_sched_barrier(0);
-                __syncthreads();
-                W2V2_TRC();
-            }
-            compute((nk - 1) & 1);
-            W2V2_TRC();
-        } else {
-            // Ring of NS stages, NS - 1 tiles in flight.  One MFMA block per tile step is only 512 cycles while an
-            // L2 / HBM round trip under load is several thousand, so a single tile of prefetch leaves the loop
-            // latency-bound.  __syncthreads() would drain every DMA (vmcnt(0)); a counted wait + raw barrier keeps the
-            // younger tiles in flight:  this wave's share of tile kt has landed when at most (NS - 2) tiles' worth of
-            // its own DMA instructions are outstanding, and the barrier extends that to every wave's share.
-            constexpr int PER_TILE = PPA + PPB;
-            static_assert(PER_TILE * (NS - 2) < 64, "vmcnt is a 6-bit counter");
-#pragma unroll
-            for (int t = 0; t < NS - 1; ++t) issue(t < nk ? t : nk - 1, t);      // (re-reads the last tile when K is short)
-            for (int kt = 0; kt < nk; ++kt) {
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_TILE * (NS - 2)) : "memory");
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                const int nxt = kt + NS - 1;
-                issue(nxt < nk ? nxt : nk - 1, nxt % NS);      // into the stage whose MFMAs finished before the barrier
-                __builtin_amdgcn_sched_barrier(0);
-                compute(kt % NS);
-                __builtin_amdgcn_sched_barrier(0);
-            }
         }
+        compute((nk - 1) & 1);
+        W2V2_TRC();
     } else {
         load_tile(0);
         store_tile(0);
@@ -740,7 +730,7 @@ int launch_tr16(Gemm16Args& g, int nbatch, hipStream_t s) {
 
 template <int SRC, int BM, int BN, int WM, int WN, int MINB>
 int launch_src16(Gemm16Args& g, int nbatch, hipStream_t s) {
-    constexpr size_t LDS = (SRC == 6 ? 4 : 2) * (BM + BN) * ROWB;
+    constexpr size_t LDS = 2 * (BM + BN) * ROWB;
     g.tiles_m = (g.M + BM - 1) / BM;
     g.tiles_n = (g.N + BN - 1) / BN;
     static std::atomic<bool> attr_set{false};   // (idempotent call; atomic so concurrent host threads agree on the flag)
@@ -755,46 +745,17 @@ int launch_src16(Gemm16Args& g, int nbatch, hipStream_t s) {
     return W2V2_OK;
 }
 
-template <int BM, int BN, int WM, int WN, int MINB>
-int launch_cfg16(Gemm16Args& g, int src, int nbatch, hipStream_t s) {
-    switch (src) {
-        case 1: return launch_src16<1, BM, BN, WM, WN, MINB>(g, nbatch, s);
-        case 2: return launch_src16<2, BM, BN, WM, WN, MINB>(g, nbatch, s);
-        case 3: return launch_src16<3, BM, BN, WM, WN, MINB>(g, nbatch, s);
-        case 4: return launch_src16<4, BM, BN, WM, WN, MINB>(g, nbatch, s);
-        case 5: return launch_src16<5, BM, BN, WM, WN, MINB>(g, nbatch, s);
-        case 6: return launch_src16<6, BM, BN, WM, WN, 1>(g, nbatch, s);
-        case 7: return launch_src16<7, BM, BN, WM, WN, MINB>(g, nbatch, s);
-        default: return launch_src16<0, BM, BN, WM, WN, MINB>(g, nbatch, s);
-    }
-}
+std::atomic<int64_t> g_launches[GB_KERNELS];      // launch_gemm_bf16_x's launches per GemmBf16Kernel (gemm_bf16_launches)
+
+}  // namespace
 
 #ifdef W2V2_TUNING
-}  // namespace
 unsigned long long* g_tune_trace = nullptr;      // set by w2v2_tune_set_trace (tuning_entry.hip)
-namespace {
 #endif
 
-// Which shadow-fed shapes take the 128 x 256 software-pipelined kernel (measured at B = 32, profiles/r03_gemm_bf16_study.md: it wins
-// 8-25 % on every model shape with N K >= 768 x 1024 and on the batched conv layers, and loses 5-10 % on the two smaller Dense
-// shapes): whole 256-column tiles, at least 256 of them (half of the chip's 512 block slots), a weight of >= 576 Ki elements (round 3: 768 Ki) or a batch.  GemmShadows::force_kernel overrides
-// (1 = never, 2 = whenever the operands allow it: the op-level parity tests compare the two kernels bit for bit).
-bool use_sw_kernel(const GemmShadows& x, int M, int N, int K, int64_t lda, int64_t ldb16, int64_t strideA, int nbatch) {
-    if (x.zmod != 0 || x.force_kernel == 1 || !gemm_bf16_sw_ok(M, N, K, lda, ldb16, strideA)) return false;
-    if (x.force_kernel == 2) return true;
-    if (tune_int("W2V2_GEMM16_SW", 1) == 0) return false;
-    const int64_t tiles = (int64_t)((M + 127) / 128) * (N / 256) * nbatch;
-    // (round 5: the threshold moved from N K >= 768 x 1024 to 768 x 768 -- with the leaner fp32 epilogue of this round the out-projection and
-    //  its data gradient, 25 launches per step on the 128 x 128 kernel at MFMA busy 0.23, are faster here too: fine-tune step 32.95 -> 32.32 ms,
-    //  forward 11.30 -> 11.24 ms same-box, profiles/r05_ab_sw_768x768.txt; W2V2_SW_MIN_K in the tools-only build)
-    return tiles >= 256 && ((int64_t)N * K >= (int64_t)768 * tune_int("W2V2_SW_MIN_K", 768) || nbatch > 1);      // 
+void gemm_bf16_launches(int64_t* counts) {
+    for (int i = 0; i < GB_KERNELS; ++i) counts[i] = g_launches[i].load(std::memory_order_relaxed);
 }
-
-int forced_cfg16() {
-    return tune_int("W2V2_GEMM16_CFG", -1);
-}
-
-}  // namespace
 
 int launch_gemm_bf16(Profiler* prof, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb,
                      int64_t strideB, float* C, int64_t ldc, int64_t strideC, const float* bias,
@@ -803,11 +764,7 @@ int launch_gemm_bf16(Profiler* prof, const float* A, int64_t lda, int64_t stride
                               GemmShadows{}, s);
 }
 
-// The shape part of "this GEMM streams the bf16 shadow of A": whole 64-wide K tiles, and rows / batch strides that keep every
-// 16-byte piece aligned.  The launcher below adds the run-time part (a shadow was passed, its pointer is 16-byte aligned); the forward
-// plan asks this before the launch to decide which tensors need no fp32 copy.
-bool gemm_bf16_streams_a16(int K, int64_t lda, int64_t strideA) { return K % BK == 0 && lda % 8 == 0 && strideA % 8 == 0; }
-
+// Validate the call, ask gemm_bf16_route which kernel it reaches, launch that one.
 int launch_gemm_bf16_x(Profiler* prof, const float* A, int64_t lda, int64_t strideA, const float* B, int64_t ldb,
                        int64_t strideB, float* C, int64_t ldc, int64_t strideC, const float* bias,
                        const float* residual, int M, int N, int K, int nbatch, int act, const GemmShadows& x,
@@ -836,65 +793,42 @@ int launch_gemm_bf16_x(Profiler* prof, const float* A, int64_t lda, int64_t stri
     g.trace = g_tune_trace;
 #endif
     W2V2_REQUIRE(x.zmod >= 0 && (x.zmod == 0 || nbatch % x.zmod == 0), "gemm_bf16: batch %d is not a multiple of the inner batch %d", nbatch, x.zmod);
-    const bool kfast = K % BK == 0;
-    const bool a32 = A && (lda % 4 == 0) && (strideA % 4 == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);
-    const bool b32 = B && (N % 4 == 0) && (ldb % 4 == 0) && (strideB % 4 == 0) && ((reinterpret_cast<uintptr_t>(B) & 15) == 0);
-    const bool a16 = x.A16 && gemm_bf16_streams_a16(K, lda, strideA) && ((reinterpret_cast<uintptr_t>(x.A16) & 15) == 0);
-    const bool b16 = x.B16 && kfast && strideB == 0 && (g.ldb16 % 8 == 0) && ((reinterpret_cast<uintptr_t>(x.B16) & 15) == 0);
-    int src;
-    // tuning knob: 0 = register-staged shadows (595 TF on the forward mix), 1 = LDS-DMA, 2 stages, 2 blocks/CU (617, default),
-    // 2 = LDS-DMA 4-stage ring with three tiles in flight, 1 block/CU (513: deeper prefetch does not pay for half the waves)
-    const int dma = tune_int("W2V2_GEMM16_DMA", 1);
-    if (x.transA) {
-        // both bf16 shadows, whole 128 x 128 tiles, 16-byte aligned rows: LDS-DMA + transposing LDS reads (the fp32 operands are
-        // not touched and may be null)
-        const int tr = tune_int("W2V2_GEMM16_TR", 1);
-        if (tr && kfast && C && x.A16 && x.B16p && !x.colsum && !x.overlapA && M % 128 == 0 && N % 128 == 0 && lda % 8 == 0 && ldb % 8 == 0 &&
-            strideA % 8 == 0 && strideB % 8 == 0 && ((reinterpret_cast<uintptr_t>(x.A16) | reinterpret_cast<uintptr_t>(x.B16p)) & 15) == 0) {
-            const double krows = (double)K * nbatch + 64.0 * x.kextra;          // rows of the K dimension over all slabs
-            ProfScope ps(prof, FAM_GEMM_BF16, 2.0 * M * (double)N * krows, 2.0 * krows * ((double)M + N) + nbatch * 4.0 * (double)M * N, s);
-            // every row exists and the columns fill 256-wide tiles: the 128 x 256 software-pipelined kernel in its transposed form
-            // (gemm_bf16_sw.hip); identical bits.  Ragged row counts (validK) stay on the kernel below, which reads rows past the end as zero.
-            const int64_t krows_all = (int64_t)K * nbatch + 64 * x.kextra;
-            const bool whole = x.validK == 0 || x.validK == krows_all;
-            // (rows missing only from the last K tile, and a zero row promised behind B: the same kernel, ragged form)
-            const int krag = (!whole && x.b_zero_row && x.validK > krows_all - 64 && x.validK < krows_all) ? (int)(x.validK - (krows_all - 64)) : 0;
-            if (x.force_kernel != 1 && (whole || krag > 0) && gemm_bf16_swtr_ok(M, N, K, lda, ldb, strideA, strideB) &&
-                (x.force_kernel == 2 || tune_int("W2V2_GEMM16_SW", 1) != 0))
-                return launch_gemm_bf16_swtr(x.A16, lda, strideA, x.B16p, ldb, strideB, C, ldc, strideC, M, N, K, nbatch, s, x.kextra, krag);
-            W2V2_REQUIRE(x.kextra == 0, "gemm_bf16: uneven slabs (kextra) are a feature of the 128 x 256 transposed kernel");
-            return launch_tr16(g, nbatch, s);
-        }
-        W2V2_REQUIRE(x.validK == 0, "gemm_bf16: validK needs the LDS-DMA weight-gradient form (both shadows, whole 128 x 128 tiles)");
-        // (the generic transposed-A path below contracts exactly K * nbatch rows: an operand set that asks for more would be cut short silently)
-        W2V2_REQUIRE(x.kextra == 0 && !x.b_zero_row, "gemm_bf16: uneven slabs (kextra) / the zero row behind B need the LDS-DMA weight-gradient form");
-        W2V2_REQUIRE(A && kfast && b32 && (M % 4 == 0) && (lda % 4 == 0) && (strideA % 4 == 0) &&
-                         ((reinterpret_cast<uintptr_t>(A) & 15) == 0) && (lda >= M || x.overlapA),
-                     "gemm_bf16: transposed A needs fp32 A and B, K %% 64 == 0, M %% 4 == 0 and 16-byte alignment");
-        src = 7;
-    } else if (a16 && b16) src = dma == 2 ? 6 : (dma ? 5 : 4);
-    else if (a16 && b32) src = 2;
-    else if (b16 && a32) src = 3;
-    else if (kfast && a32 && b32) src = 1;
-    else src = 0;
-    W2V2_REQUIRE(src != 0 || (A && B), "gemm_bf16: a shadow-only operand needs K %% 64 == 0 and 16-byte alignment");
-    const double abytes = (src == 2 || (src >= 4 && src <= 6)) ? 2.0 : 4.0, bbytes = (src >= 3 && src <= 6) ? 2.0 : 4.0;
-    ProfScope ps(prof, FAM_GEMM_BF16, 2.0 * M * (double)N * K * nbatch,
-                 nbatch * (abytes * (double)M * K + (C ? 4.0 : 0.0) * (double)M * N + (x.C16 ? 2.0 : 0.0) * (double)M * N) +
-                     bbytes * (double)K * N, s);
-    int cfg = forced_cfg16();
-    // both operands from shadows, enough tiles to fill the chip: 128 x 256 tiles, 4-wave software-pipelined blocks, two per CU
-    // (gemm_bf16_sw.hip).  Same bits as the kernels below.
-    if (src == 5 && use_sw_kernel(x, M, N, K, lda, g.ldb16, strideA, nbatch))
-        return launch_gemm_bf16_sw(x.A16, lda, strideA, x.B16, g.ldb16, C, x.C16, ldc, strideC, bias, residual, M, N, K, nbatch, act, s);
-    if (cfg == 2 && src == 1) return launch_src16<1, 256, 256, 2, 4, 1>(g, nbatch, s);   // tile study: 8 waves of 128x64
-    if (N <= 64 && src == 5) return launch_src16<5, 128, 64, 2, 2, 2>(g, nbatch, s);     // narrow outputs (grouped conv: 48 | 64 columns)
-    if (N <= 64 && src == 7) return launch_src16<7, 128, 64, 2, 2, 2>(g, nbatch, s);
-    // both operands from shadows by LDS-DMA: 8 waves of 64x32 per 128x128 tile (2 x 4 per SIMD pair, 2 blocks / CU) measured
-    // 670 TF on the forward mix against 642 for 4 waves of 64x64 (more waves issuing DMA pieces and fragment reads); the
-    // register-staged sources keep 4 waves (their patch ownership is tied to 256 threads)
-    if (src == 5 && cfg != 0) return launch_src16<5, 128, 128, 2, 4, 2>(g, nbatch, s);
-    return launch_cfg16<128, 128, 2, 2, 2>(g, src, nbatch, s);
+
+    auto operand = [](const void* p) { return !p ? GO_ABSENT : (reinterpret_cast<uintptr_t>(p) & 15) == 0 ? GO_ALIGNED : GO_PRESENT; };
+    GemmBf16Problem p;
+    p.M = M; p.N = N; p.K = K; p.nbatch = nbatch;
+    p.lda = lda; p.ldb = ldb; p.strideA = strideA; p.strideB = strideB; p.ldb16 = g.ldb16;
+    p.A = operand(A); p.B = operand(B); p.A16 = operand(x.A16); p.B16 = operand(x.B16); p.B16p = operand(x.B16p);
+    p.C = C != nullptr; p.C16 = x.C16 != nullptr;
+    p.transA = x.transA; p.zmod = x.zmod; p.colsum = x.colsum != nullptr; p.overlapA = x.overlapA;
+    p.validK = x.validK; p.kextra = x.kextra; p.b_zero_row = x.b_zero_row; p.force_kernel = x.force_kernel;
+    const GemmBf16Route route = gemm_bf16_route(p);
+    W2V2_REQUIRE(route.refusal == GBR_NONE, "%s", gemm_bf16_refusal_text(route.refusal));
+
+    // what the profiler is charged: the weight-gradient shadow forms read krows rows of both operands and write one fp32 slab per
+    // batch; every other form reads A per batch, B once, and writes the outputs asked for
+    const bool wgrad = route.kernel == GB_TR_128x128 || route.kernel == GB_SWTR_128x256;
+    const double krows = (double)route.krows, mn = (double)M * N;
+    ProfScope ps(prof, FAM_GEMM_BF16, 2.0 * mn * krows,
+                 wgrad ? krows * (route.a_bytes * (double)M + route.b_bytes * (double)N) + nbatch * 4.0 * mn
+                       : nbatch * (route.a_bytes * (double)M * K + (C ? 4.0 : 0.0) * mn + (x.C16 ? 2.0 : 0.0) * mn) + route.b_bytes * (double)K * N, s);
+    g_launches[route.kernel].fetch_add(1, std::memory_order_relaxed);
+    switch (route.kernel) {
+        case GB_F32_GUARDED: return launch_src16<0, 128, 128, 2, 2, 2>(g, nbatch, s);
+        case GB_F32_VEC: return launch_src16<1, 128, 128, 2, 2, 2>(g, nbatch, s);
+        case GB_A_SHADOW: return launch_src16<2, 128, 128, 2, 2, 2>(g, nbatch, s);
+        case GB_B_SHADOW: return launch_src16<3, 128, 128, 2, 2, 2>(g, nbatch, s);
+        case GB_DMA_128x128: return launch_src16<5, 128, 128, 2, 4, 2>(g, nbatch, s);
+        case GB_DMA_128x64: return launch_src16<5, 128, 64, 2, 2, 2>(g, nbatch, s);
+        case GB_AT_F32_128x128: return launch_src16<7, 128, 128, 2, 2, 2>(g, nbatch, s);
+        case GB_AT_F32_128x64: return launch_src16<7, 128, 64, 2, 2, 2>(g, nbatch, s);
+        case GB_TR_128x128: return launch_tr16(g, nbatch, s);
+        case GB_SW_128x256:
+            return launch_gemm_bf16_sw(x.A16, lda, strideA, x.B16, g.ldb16, C, x.C16, ldc, strideC, bias, residual, M, N, K, nbatch, act, s);
+        case GB_SWTR_128x256:
+            return launch_gemm_bf16_swtr(x.A16, lda, strideA, x.B16p, ldb, strideB, C, ldc, strideC, M, N, K, nbatch, s, x.kextra, route.krag);
+    }
+    W2V2_REQUIRE(false, "gemm_bf16: route without a kernel");
 }
 
 }  // namespace w2v2

@@ -403,19 +403,8 @@ int launch_sw(GemmSWArgs& g, dim3 grid, hipStream_t s) {
 extern unsigned long long* g_tune_trace;
 #endif
 
-// Shapes: both operands as aligned bf16 shadows, whole 256-column tiles (B's per-lane offsets are shared by its four items),
-// K a multiple of 64 with at least 3 K tiles, any M.
-bool gemm_bf16_sw_ok(int M, int N, int K, int64_t lda, int64_t ldb16, int64_t strideA) {
-    return M >= 1 && N >= 256 && N % 256 == 0 && K % 64 == 0 && K >= 192 && lda % 8 == 0 && ldb16 % 8 == 0 && strideA % 8 == 0 &&
-           128 * lda < (1 << 29) && 256 * ldb16 < (1 << 29);
-}
-
+// The shapes these launchers take: gemm_bf16_sw_ok and gemm_bf16_swtr_ok (gemm_bf16_route.h).
 // Weight-gradient form: C_z (M, N) = A16_z^T B16_z with A16 (K, M) rows lda apart and B16 (K, N) rows ldb apart, K rows per batch.
-bool gemm_bf16_swtr_ok(int M, int N, int K, int64_t lda, int64_t ldb, int64_t strideA, int64_t strideB) {
-    return M >= 128 && M % 128 == 0 && N >= 256 && N % 256 == 0 && K % 64 == 0 && K >= 192 && lda % 8 == 0 && ldb % 8 == 0 && strideA % 8 == 0 &&
-           strideB % 8 == 0 && 64 * lda < (1 << 29) && 64 * ldb < (1 << 29);
-}
-
 int launch_gemm_bf16_swtr(const uint16_t* A16, int64_t lda, int64_t strideA, const uint16_t* B16, int64_t ldb, int64_t strideB, float* C,
                           int64_t ldc, int64_t strideC, int M, int N, int K, int nbatch, hipStream_t s, int kextra, int krag) {
     W2V2_REQUIRE(A16 && B16 && C && gemm_bf16_swtr_ok(M, N, K, lda, ldb, strideA, strideB), "gemm_bf16_swtr: unsupported operands");

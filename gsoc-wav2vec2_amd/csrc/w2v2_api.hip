@@ -819,6 +819,25 @@ int w2v2_op_gemm_f32_route(int32_t M, int32_t N, int32_t K, int32_t nbatch, int6
     for (int i = 0; i < 8; ++i) out[i] = v[i];
     return W2V2_OK;
 }
+int w2v2_op_gemm_bf16_route(const int64_t* q, int32_t* out) {
+    W2V2_REQUIRE(q && out && q[0] > 0 && q[1] > 0 && q[2] > 0 && q[3] > 0, "op_gemm_bf16_route: bad argument");
+    GemmBf16Problem p;
+    p.M = (int)q[0]; p.N = (int)q[1]; p.K = (int)q[2]; p.nbatch = (int)q[3];
+    p.lda = q[4]; p.ldb = q[5]; p.strideA = q[6]; p.strideB = q[7]; p.ldb16 = q[8] ? q[8] : q[2];
+    p.A = (int)q[9]; p.B = (int)q[10]; p.A16 = (int)q[11]; p.B16 = (int)q[12]; p.B16p = (int)q[13];
+    p.C = q[14] != 0; p.C16 = q[15] != 0;
+    p.transA = q[16] != 0; p.zmod = (int)q[17]; p.colsum = q[18] != 0; p.overlapA = q[19] != 0;
+    p.validK = q[20]; p.kextra = (int)q[21]; p.b_zero_row = q[22] != 0; p.force_kernel = (int)q[23];
+    const GemmBf16Route r = gemm_bf16_route(p);
+    const int32_t v[5] = {r.kernel, r.krag, r.refusal, r.a_bytes, r.b_bytes};
+    for (int i = 0; i < 5; ++i) out[i] = v[i];
+    return W2V2_OK;
+}
+int w2v2_op_gemm_bf16_launches(int64_t* counts) {
+    W2V2_REQUIRE(counts, "op_gemm_bf16_launches: null argument");
+    gemm_bf16_launches(counts);
+    return W2V2_OK;
+}
 int w2v2_op_split_planes(const float* x, uint16_t* planes, int64_t plane_stride, int64_t n, int32_t fmt, int32_t* range_flag, void* stream) {
     W2V2_REQUIRE(fmt == PF_BF16X3 || fmt == PF_F16X2, "op_split_planes: unknown plane format %d", fmt);
     return launch_split_planes(x, planes, plane_stride, n, fmt, range_flag, reinterpret_cast<hipStream_t>(stream));

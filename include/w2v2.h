@@ -901,6 +901,20 @@ int w2v2_op_gemm_ring_launches(int64_t* counts);
 int w2v2_op_gemm_f32_route(int32_t M, int32_t N, int32_t K, int32_t nbatch, int64_t lda, int64_t ldb, int64_t ldc, int64_t strideA,
                            int64_t strideB, int32_t act, int32_t has_bias, int32_t has_residual, int32_t ab_aligned, int32_t c_aligned,
                            int32_t variant, int32_t* out);
+/* Which kernel a bf16 GEMM call (w2v2_op_gemm_bf16, _shadows, _at, w2v2_op_weight_grad_bf16, and every bf16 GEMM of the models) would
+ * launch (csrc/gemm_bf16_route.h).  Host only: touches no device and launches nothing.  problem[24], in order: M, N, K, nbatch, lda,
+ * ldb, strideA, strideB, ldb16 (0 = K); the operands fp32 A, fp32 B, A16, B16, B16p (0 absent, 1 present, 2 present and 16-byte
+ * aligned); C, C16 asked for (0 / 1); then of GemmShadows transA, zmod, colsum given, overlapA, validK, kextra, b_zero_row,
+ * force_kernel.
+ *   out[0] kernel (0 when refused): 1 fp32 guarded loads, 2 fp32 16-byte loads, 3 A from its shadow, 4 B from its shadow, 5 LDS-DMA
+ *          128 x 128, 6 LDS-DMA 128 x 64, 7 transposed fp32 128 x 128, 8 transposed fp32 128 x 64, 9 transposing-read 128 x 128,
+ *          10 software-pipelined 128 x 256, 11 its weight-gradient form;
+ *   out[1] rows in the ragged last K tile of kernel 11 (0 = whole); out[2] != 0: the call is refused (the reason, by
+ *          GemmBf16Refusal); out[3], out[4] bytes per element read of A and B. */
+int w2v2_op_gemm_bf16_route(const int64_t* problem, int32_t* out);
+/* Launches by this process so far per kernel of that list (host memory): counts[12], counts[k] for kernel k, counts[0] unused.
+ * Diagnostic only (one relaxed atomic add per launch), the twin of w2v2_op_gemm_ring_launches. */
+int w2v2_op_gemm_bf16_launches(int64_t* counts);
 
 /* The weight-gradient form of the same GEMM: C_z (M, N) = A_z^T B_z with A given TRANSPOSED, (K, M) fp32 row-major with
  * row stride lda (>= M), and per-batch strides on A, B and C (split-K: batch z covers rows [z K, (z+1) K) of both
