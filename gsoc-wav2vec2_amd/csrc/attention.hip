@@ -17,7 +17,7 @@
 // key assignment.  No LDS round trip, no transposes, no cross-lane traffic
 // beyond the one max/sum exchange.
 //
-// Block = NW waves x 32 queries of one (batch, head) (NW in {4, 6, 8, 12}, picked per launch to fill
+// Block = NW waves x 32 queries of one (batch, head) (NW in {4, 8, 12}, picked by attention_route to fill
 // the 256 CUs in whole rounds); K and V tiles of 64 keys reach LDS by LDS-DMA, double-buffered, one
 // barrier per tile, and are shared by the waves.
 #include <limits.h>
@@ -264,12 +264,7 @@ __global__ __launch_bounds__(NW * 64) void attention_kernel(AttnArgs a, AttnTrai
 template <int DH, int NW>
 int launch_attn_nw(const AttnArgs& a, hipStream_t s) {
     const size_t lds = (size_t)2 * 2 * KT * DH * sizeof(float);
-    static std::atomic<bool> attr_set{false};   // (idempotent call; atomic so concurrent host threads agree on the flag)
-    if (!attr_set) {
-        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<DH, NW>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
+    if (int e = set_dynamic_lds<attention_kernel<DH, NW>>(lds)) return e;
     const int qb = NW * 32;
     dim3 grid((a.T + qb - 1) / qb, a.heads, a.B), block(NW * 64);
     W2V2_LAUNCH((attention_kernel<DH, NW>), grid, block, lds, s, a, AttnTrain{0.f, 0, 0, nullptr});
@@ -279,51 +274,16 @@ int launch_attn_nw(const AttnArgs& a, hipStream_t s) {
 
 // packed forward: a fixed 8 waves (256 queries) per tile -- the tile table is built by the host before the launch
 constexpr int SEG_NW = 8;
+static_assert(SEG_NW == ATTN_F32_PACKED_WAVES, "attention_route.h names this file's packed block shape");
 
 template <int DH>
 int launch_attn_seg(const AttnArgs& a, int ntiles, hipStream_t s) {
     const size_t lds = (size_t)2 * 2 * KT * DH * sizeof(float);
-    static std::atomic<bool> attr_set{false};
-    if (!attr_set) {
-        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<DH, SEG_NW, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
+    if (int e = set_dynamic_lds<attention_kernel<DH, SEG_NW, false, true>>(lds)) return e;
     dim3 grid(ntiles, a.heads, 1), block(SEG_NW * 64);
     W2V2_LAUNCH((attention_kernel<DH, SEG_NW, false, true>), grid, block, lds, s, a, AttnTrain{0.f, 0, 0, nullptr});
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
-}
-
-// Pick the queries-per-block that fills 256 CUs in the fewest rounds.  Waves per block stay a multiple
-// of 4 (one per SIMD; 6 waves measured 77 TF vs 95-105: two SIMDs carry double load).  Measured at
-// T=768, B=32, 12 heads: 4 waves (2 blocks/CU) 95 TF, 8 waves 93, 12 waves (3 per SIMD) 105.
-template <int DH>
-int launch_attn(const AttnArgs& a, hipStream_t s) {
-    const int forced = tune_int("W2V2_ATTN_NW", -1);
-    const int cand[3] = {12, 8, 4};
-    int best = 4;
-    int64_t best_cost = INT64_MAX;
-    for (int i = 0; i < 3; ++i) {
-        const int nw = cand[i];
-        if (DH == 128 && nw == 12) continue;                  // 241 VGPRs: 3 waves per SIMD would spill
-        const int bpc = (DH != 128 && nw == 4) ? 2 : 1;       // blocks per CU the VGPR / LDS budget admits
-        const int64_t nblk = (int64_t)((a.T + nw * 32 - 1) / (nw * 32)) * a.heads * a.B;
-        const int64_t rounds = (nblk + 256 * bpc - 1) / (256 * bpc);
-        const int64_t cost = rounds * nw * bpc * (nw == 12 ? 9 : 10);   // 3 waves per SIMD run ~10 % better
-        if (cost < best_cost) { best_cost = cost; best = nw; }
-    }
-    if (forced > 0) best = forced;
-    if constexpr (DH == 128) {
-        return best == 8 ? launch_attn_nw<DH, 8>(a, s) : launch_attn_nw<DH, 4>(a, s);
-    } else {
-        switch (best) {
-            case 6: return launch_attn_nw<DH, 6>(a, s);
-            case 8: return launch_attn_nw<DH, 8>(a, s);
-            case 12: return launch_attn_nw<DH, 12>(a, s);
-            default: return launch_attn_nw<DH, 4>(a, s);
-        }
-    }
 }
 
 
@@ -632,39 +592,24 @@ __global__ __launch_bounds__(256) void attention_bwd_dkv_kernel(AttnBwdArgs a, A
 }
 
 template <int DH, int NW>
-int launch_attn_train_impl(const AttnArgs& a, const AttnTrain& tr, hipStream_t s) {
+int launch_attn_train(const AttnArgs& a, const AttnTrain& tr, hipStream_t s) {
     const size_t lds = (size_t)2 * 2 * KT * DH * sizeof(float);
-    static std::atomic<bool> attr_set{false};   // (idempotent call; atomic so concurrent host threads agree on the flag)
-    if (!attr_set) {
-        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<DH, NW, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
+    if (int e = set_dynamic_lds<attention_kernel<DH, NW, true>>(lds)) return e;
     dim3 grid((a.T + NW * 32 - 1) / (NW * 32), a.heads, a.B), block(NW * 64);
     W2V2_LAUNCH((attention_kernel<DH, NW, true>), grid, block, lds, s, a, tr);
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }
 
-// 12 waves per block (3 per SIMD) when the sequence is long enough to fill whole blocks, as the inference launcher picks
-template <int DH>
-int launch_attn_train(const AttnArgs& a, const AttnTrain& tr, hipStream_t s) {
-    if constexpr (DH == 64) {
-        if (a.T >= 384) return launch_attn_train_impl<DH, 12>(a, tr, s);
-    }
-    return launch_attn_train_impl<DH, 4>(a, tr, s);
-}
-
 template <int DH>
 int launch_attn_bwd(const AttnBwdArgs& a, const AttnTrain& tr, const float* ctx, float* dvec, hipStream_t s) {
+    static_assert(ATTN_F32_BWD_WAVES == 4, "attention_route.h names the backward kernels' block shape");
     W2V2_LAUNCH(attn_dvec_kernel<DH>, dim3((unsigned)((int64_t)a.B * a.T)), dim3(256), 0, s, ctx, a.d_o, dvec,
                        a.B, a.T, a.H, a.heads);
     const size_t lds_q = (size_t)2 * 2 * KT * DH * sizeof(float);
     const size_t lds_kv = (size_t)2 * (2 * KT * DH + 2 * KT) * sizeof(float);
-    W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_dq_kernel<DH>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
-    W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_dkv_kernel<DH>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv));
+    if (int e = set_dynamic_lds<attention_bwd_dq_kernel<DH>>(lds_q)) return e;
+    if (int e = set_dynamic_lds<attention_bwd_dkv_kernel<DH>>(lds_kv)) return e;
     dim3 grid((a.T + 127) / 128, a.heads, a.B), block(256);
     W2V2_LAUNCH(attention_bwd_dq_kernel<DH>, grid, block, lds_q, s, a, tr);
     W2V2_LAUNCH(attention_bwd_dkv_kernel<DH>, grid, block, lds_kv, s, a, tr);
@@ -672,27 +617,116 @@ int launch_attn_bwd(const AttnBwdArgs& a, const AttnTrain& tr, const float* ctx,
     return W2V2_OK;
 }
 
+std::atomic<int64_t> g_launches[AK_KERNELS];      // the routed launchers' launches per AttnKernel (attention_launches)
+
+// a route that names no kernel: its message; otherwise count the launch
+int refused_or_count(const AttnRoute& r) {
+    if (r.refusal) {
+        set_error(attention_refusal_text(r), r.dh);
+        return W2V2_EINVAL;
+    }
+    g_launches[r.kernel].fetch_add(1, std::memory_order_relaxed);
+    return W2V2_OK;
+}
+bool aligned16(const void* a, const void* b) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0; }
+
 }  // namespace
 
-int attention_packed_rows(int) { return SEG_NW * 32; }
+void attention_launches(int64_t* counts) {
+    for (int i = 0; i < AK_KERNELS; ++i) counts[i] = g_launches[i].load(std::memory_order_relaxed);
+}
 
-int launch_attention_packed(Profiler* prof, const float* qkv, float* ctx, const SegTile* tiles, int ntiles, int64_t frames,
-                            double sum_nf2, int H, int heads, hipStream_t s) {
-    W2V2_REQUIRE(qkv && ctx && tiles, "attention_packed: null operand");
-    W2V2_REQUIRE(ntiles > 0 && frames > 0 && frames < INT32_MAX && heads > 0 && H % heads == 0, "attention_packed: bad sizes");
-    const int dh = H / heads;
-    ProfScope ps(prof, FAM_ATTENTION, 4.0 * heads * sum_nf2 * dh, 4.0 * (double)frames * 4.0 * H, s);
-    AttnArgs a{qkv, nullptr, ctx, 1, (int)frames, H, heads, 1.0f / sqrtf((float)dh), tiles};
-    switch (dh) {
-        case 32: return launch_attn_seg<32>(a, ntiles, s);
-        case 64: return launch_attn_seg<64>(a, ntiles, s);
-        case 128: return launch_attn_seg<128>(a, ntiles, s);
-        default:
-            set_error("attention_packed: head size %d unsupported (32, 64, 128)", dh);
-            return W2V2_EINVAL;
+bool attention_split_allowed() { return tune_int("W2V2_SPLIT_ATTN", 1) != 0; }
+
+// Inference forward, dense (io.frame_len) or packed (io.tiles): validates, charges the profiler, launches route.kernel.
+int launch_attention_routed(Profiler* prof, const AttnRoute& r, const AttnIO& io, hipStream_t s) {
+    const AttnProblem& p = r.p;
+    const bool packed = p.packed;
+    W2V2_REQUIRE(p.pass == AP_INFER, "attention: a route of pass %d given to the inference launcher", p.pass);
+    W2V2_REQUIRE(p.B > 0 && p.T > 0 && p.heads > 0 && p.H % p.heads == 0, "attention: bad sizes");
+    W2V2_REQUIRE(!packed || (io.tiles && io.ntiles > 0 && io.frames > 0 && io.frames < INT32_MAX), "attention_packed: bad sizes");
+    const int B = p.B, T = packed ? (int)io.frames : p.T, H = p.H, heads = p.heads;
+    const bool planes = io.planes && io.planes->p;
+    ProfScope ps(prof, FAM_ATTENTION, packed ? 4.0 * heads * io.sum_nf2 * r.dh : 4.0 * B * (double)heads * T * (double)T * r.dh,
+                 4.0 * (packed ? 1 : B) * (double)T * 4.0 * H, s);
+    W2V2_REQUIRE(r.family == AF_BF16 || (io.qkv && (io.ctx || planes)), "attention: null operand");
+    // (the io must be the one the problem described: a form the family cannot write is refused by the route, not dropped here)
+    W2V2_REQUIRE(r.refusal || ((r.family == AF_BF16 || !io.ctx16) && (r.family == AF_SPLIT || !planes)), "attention: the route was made for other outputs");
+    if (int e = refused_or_count(r)) return e;
+    const PlaneOut* pl = io.planes;
+    const AttnArgs a{io.qkv, io.frame_len, io.ctx, packed ? 1 : B, T, H, heads, 1.0f / sqrtf((float)r.dh), io.tiles};
+    switch (r.kernel) {
+        case AK_F32_D32_W4: return launch_attn_nw<32, 4>(a, s);
+        case AK_F32_D32_W8: return launch_attn_nw<32, 8>(a, s);
+        case AK_F32_D32_W12: return launch_attn_nw<32, 12>(a, s);
+        case AK_F32_D64_W4: return launch_attn_nw<64, 4>(a, s);
+        case AK_F32_D64_W8: return launch_attn_nw<64, 8>(a, s);
+        case AK_F32_D64_W12: return launch_attn_nw<64, 12>(a, s);
+        case AK_F32_D128_W4: return launch_attn_nw<128, 4>(a, s);
+        case AK_F32_D128_W8: return launch_attn_nw<128, 8>(a, s);
+        case AK_F32_PACKED_D32: return launch_attn_seg<32>(a, io.ntiles, s);
+        case AK_F32_PACKED_D64: return launch_attn_seg<64>(a, io.ntiles, s);
+        case AK_F32_PACKED_D128: return launch_attn_seg<128>(a, io.ntiles, s);
+        case AK_SPLIT_BF16X3:
+        case AK_SPLIT_F16X2:      // fp32-level results, bf16 / fp16 matrix cores
+            return launch_attention_split(io.qkv, io.frame_len, io.ctx, B, T, H, heads, s, pl, r.fmt, pl ? pl->range_flag : nullptr);
+        case AK_SPLIT_PACKED_BF16X3:
+        case AK_SPLIT_PACKED_F16X2:
+            return launch_attention_split_packed(io.qkv, io.ctx, io.tiles, io.ntiles, io.frames, H, heads, s, pl, r.fmt, pl ? pl->range_flag : nullptr);
+        case AK_BF16: return launch_attention_fwd_bf16(io.qkv, io.qkv16, io.frame_len, io.ctx, io.ctx16, B, T, H, heads, nullptr, s);
+        case AK_BF16_PACKED:
+            return launch_attention_bf16_packed(io.qkv, io.qkv16, io.ctx, io.ctx16, io.tiles, io.ntiles, io.frames, io.sum_nf2, H, heads, s);
+        default: set_error("attention: route kernel %d is not an inference kernel", r.kernel); return W2V2_EINVAL;
     }
 }
 
+int launch_attention_train_routed(Profiler* prof, const AttnRoute& r, const AttnIO& io, hipStream_t s) {
+    const AttnProblem& p = r.p;
+    W2V2_REQUIRE(p.pass == AP_TRAIN && io.train, "attention_train: a route of pass %d, or no training arguments", p.pass);
+    const AttnTrain& tr = *io.train;
+    const int B = p.B, T = p.T, H = p.H, heads = p.heads;
+    W2V2_REQUIRE((io.qkv || io.qkv16) && (io.ctx || io.ctx16) && tr.lse, "attention_train: null operand");
+    W2V2_REQUIRE(B > 0 && T > 0 && heads > 0 && H % heads == 0 && tr.p >= 0.f && tr.p < 1.f, "attention_train: bad sizes");
+    ProfScope ps(prof, FAM_ATTENTION, 4.0 * B * (double)heads * T * (double)T * r.dh, 4.0 * B * (double)T * 4.0 * H, s);
+    W2V2_REQUIRE(r.family == AF_BF16 || (io.qkv && io.ctx), "attention_train: the fp32 kernels need the fp32 qkv and write the fp32 ctx");
+    W2V2_REQUIRE(r.refusal || r.family == AF_BF16 || !io.ctx16, "attention_train: the route was made for other outputs");
+    if (int e = refused_or_count(r)) return e;
+    const AttnArgs a{io.qkv, io.frame_len, io.ctx, B, T, H, heads, 1.0f / sqrtf((float)r.dh)};
+    switch (r.kernel) {
+        case AK_F32_TRAIN_D32_W4: return launch_attn_train<32, 4>(a, tr, s);
+        case AK_F32_TRAIN_D64_W4: return launch_attn_train<64, 4>(a, tr, s);
+        case AK_F32_TRAIN_D64_W12: return launch_attn_train<64, 12>(a, tr, s);
+        case AK_BF16_TRAIN: return launch_attention_fwd_bf16(io.qkv, io.qkv16, io.frame_len, io.ctx, io.ctx16, B, T, H, heads, &tr, s);
+        default: set_error("attention_train: route kernel %d is not a training kernel", r.kernel); return W2V2_EINVAL;
+    }
+}
+
+int launch_attention_bwd_routed(Profiler* prof, const AttnRoute& r, const AttnIO& io, hipStream_t s) {
+    const AttnProblem& p = r.p;
+    W2V2_REQUIRE(p.pass == AP_BWD && io.train, "attention_bwd: a route of pass %d, or no training arguments", p.pass);
+    const AttnTrain& tr = *io.train;
+    const int B = p.B, T = p.T, H = p.H, heads = p.heads;
+    W2V2_REQUIRE((io.qkv || io.qkv16) && (io.ctx || io.ctx16) && (io.dctx || io.dctx16) && (io.dqkv || io.dqkv16) && io.dvec_ws && tr.lse,
+                 "attention_bwd: null operand");
+    W2V2_REQUIRE(B > 0 && T > 0 && heads > 0 && H % heads == 0, "attention_bwd: bad sizes");
+    ProfScope ps(prof, FAM_ATTENTION, 10.0 * B * (double)heads * T * (double)T * r.dh, 4.0 * B * (double)T * 8.0 * H, s);
+    W2V2_REQUIRE(r.family == AF_BF16 || (io.qkv && io.dqkv && io.ctx && io.dctx && !io.colpart),
+                 "attention_bwd: the fp32 kernels need the fp32 qkv / ctx / dctx / dqkv and leave no column sums");
+    W2V2_REQUIRE(r.refusal || r.family == AF_BF16 || !io.dqkv16, "attention_bwd: the route was made for other outputs");
+    if (int e = refused_or_count(r)) return e;
+    const AttnBwdArgs a{io.qkv, io.frame_len, io.dctx, io.dvec_ws, io.dqkv, B, T, H, heads, 1.0f / sqrtf((float)r.dh)};
+    switch (r.kernel) {
+        case AK_F32_BWD_D32: return launch_attn_bwd<32>(a, tr, io.ctx, io.dvec_ws, s);
+        case AK_F32_BWD_D64: return launch_attn_bwd<64>(a, tr, io.ctx, io.dvec_ws, s);
+        case AK_BF16_BWD:
+            // (D = rowsum(dO o O) is computed by the dQ kernel from the bf16 values of dO and O, whichever form they arrive in)
+            return launch_attention_bwd_bf16(io.qkv, io.qkv16, io.frame_len, io.dctx, io.dctx16, io.dvec_ws, io.dqkv, io.dqkv16, B, T, H, heads, tr, s,
+                                             io.colpart, io.ctx, io.ctx16);
+        default: set_error("attention_bwd: route kernel %d is not a backward kernel", r.kernel); return W2V2_EINVAL;
+    }
+}
+
+// ---- the op-level forms: the calling thread's precision and the pointers pose the problem ----
 int launch_attention(Profiler* prof, const float* qkv, const int32_t* frame_len, float* ctx, int B,
                      int T, int H, int heads, hipStream_t s) {
     return launch_attention_x(prof, qkv, nullptr, frame_len, ctx, B, T, H, heads, nullptr, s);
@@ -700,33 +734,11 @@ int launch_attention(Profiler* prof, const float* qkv, const int32_t* frame_len,
 
 int launch_attention_x(Profiler* prof, const float* qkv, const uint16_t* qkv16, const int32_t* frame_len, float* ctx, int B, int T, int H,
                        int heads, uint16_t* ctx16, hipStream_t s, const PlaneOut* planes) {
-    W2V2_REQUIRE(B > 0 && T > 0 && heads > 0 && H % heads == 0, "attention: bad sizes");
-    const int dh = H / heads;
-    ProfScope ps(prof, FAM_ATTENTION, 4.0 * B * (double)heads * T * (double)T * dh,
-                 4.0 * B * (double)T * 4.0 * H, s);
-    if (gemm_get_precision() == 1 && attention_bf16_supported(dh))
-        return launch_attention_fwd_bf16(qkv, qkv16, frame_len, ctx, ctx16, B, T, H, heads, nullptr, s);
-    W2V2_REQUIRE(qkv && (ctx || (planes && planes->p)), "attention: null operand");
-    W2V2_REQUIRE(!ctx16, "attention: a bf16 shadow output needs the bf16 kernel (precision 1, head size 64)");
-    if (gemm_get_precision() >= 2 && tune_int("W2V2_SPLIT_ATTN", 1) != 0 && attention_split_supported(dh) && H % 4 == 0 &&
-        ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(ctx)) & 15) == 0)
-        return launch_attention_split(qkv, frame_len, ctx, B, T, H, heads, s, planes, gemm_get_precision() == W2V2_PRECISION_F16X2 ? PF_F16X2 : PF_BF16X3,
-                                      planes ? planes->range_flag : nullptr);     // fp32-level results, bf16 / fp16 matrix cores
-    W2V2_REQUIRE(ctx && !(planes && planes->p), "attention: a plane output needs the split kernel (precision modes 2 / 3, head size 64)");
-    AttnArgs a{qkv, frame_len, ctx, B, T, H, heads, 1.0f / sqrtf((float)dh)};
-    switch (dh) {
-        case 32: return launch_attn<32>(a, s);
-        case 64: return launch_attn<64>(a, s);
-        case 128: return launch_attn<128>(a, s);
-        default:
-            set_error("attention: head size %d unsupported (32, 64, 128)", dh);
-            return W2V2_EINVAL;
-    }
+    AttnIO io;
+    io.qkv = qkv; io.qkv16 = qkv16; io.frame_len = frame_len; io.ctx = ctx; io.ctx16 = ctx16; io.planes = planes;
+    return launch_attention_routed(prof, attention_route(attention_problem(AP_INFER, gemm_get_precision(), B, T, H, heads, false, ctx != nullptr,
+                                                                           ctx16 != nullptr, planes && planes->p, aligned16(qkv, ctx))), io, s);
 }
-
-}  // namespace w2v2
-
-namespace w2v2 {
 
 int launch_attention_train(Profiler* prof, const float* qkv, const int32_t* frame_len, float* ctx, int B, int T,
                            int H, int heads, const AttnTrain& tr, hipStream_t s) {
@@ -735,46 +747,22 @@ int launch_attention_train(Profiler* prof, const float* qkv, const int32_t* fram
 
 int launch_attention_train_x(Profiler* prof, const float* qkv, const uint16_t* qkv16, const int32_t* frame_len, float* ctx, uint16_t* ctx16,
                              int B, int T, int H, int heads, const AttnTrain& tr, hipStream_t s) {
-    W2V2_REQUIRE((qkv || qkv16) && (ctx || ctx16) && tr.lse, "attention_train: null operand");
-    W2V2_REQUIRE(B > 0 && T > 0 && heads > 0 && H % heads == 0 && tr.p >= 0.f && tr.p < 1.f, "attention_train: bad sizes");
-    const int dh = H / heads;
-    ProfScope ps(prof, FAM_ATTENTION, 4.0 * B * (double)heads * T * (double)T * dh, 4.0 * B * (double)T * 4.0 * H, s);
-    if (gemm_get_precision() == 1 && attention_bf16_supported(dh))
-        return launch_attention_fwd_bf16(qkv, qkv16, frame_len, ctx, ctx16, B, T, H, heads, &tr, s);
-    W2V2_REQUIRE(qkv && ctx, "attention_train: the fp32 kernels need the fp32 qkv and write the fp32 ctx");
-    AttnArgs a{qkv, frame_len, ctx, B, T, H, heads, 1.0f / sqrtf((float)dh)};
-    W2V2_REQUIRE(!ctx16, "attention_train: a bf16 shadow output needs the bf16 kernel (precision 1, head size 64)");
-    switch (dh) {
-        case 32: return launch_attn_train<32>(a, tr, s);
-        case 64: return launch_attn_train<64>(a, tr, s);
-        default:
-            set_error("attention_train: head size %d unsupported (32, 64)", dh);
-            return W2V2_EINVAL;
-    }
+    AttnIO io;
+    io.qkv = qkv; io.qkv16 = qkv16; io.frame_len = frame_len; io.ctx = ctx; io.ctx16 = ctx16; io.train = &tr;
+    return launch_attention_train_routed(prof, attention_route(attention_problem(AP_TRAIN, gemm_get_precision(), B, T, H, heads, false, ctx != nullptr,
+                                                                                 ctx16 != nullptr)), io, s);
 }
 
 int launch_attention_bwd(Profiler* prof, const float* qkv, const int32_t* frame_len, const float* ctx,
                          const float* dctx, float* dqkv, float* dvec_ws, int B, int T, int H, int heads,
                          const AttnTrain& tr, hipStream_t s, uint16_t* dqkv16, const uint16_t* qkv16, const uint16_t* dctx16, float* colpart,
                          const uint16_t* ctx16) {
-    W2V2_REQUIRE((qkv || qkv16) && (ctx || ctx16) && (dctx || dctx16) && (dqkv || dqkv16) && dvec_ws && tr.lse, "attention_bwd: null operand");
-    W2V2_REQUIRE(B > 0 && T > 0 && heads > 0 && H % heads == 0, "attention_bwd: bad sizes");
-    const int dh = H / heads;
-    ProfScope ps(prof, FAM_ATTENTION, 10.0 * B * (double)heads * T * (double)T * dh, 4.0 * B * (double)T * 8.0 * H, s);
-    if (gemm_get_precision() == 1 && attention_bf16_supported(dh)) {
-        // (D = rowsum(dO o O) is computed by the dQ kernel from the bf16 values of dO and O, whichever form they arrive in)
-        return launch_attention_bwd_bf16(qkv, qkv16, frame_len, dctx, dctx16, dvec_ws, dqkv, dqkv16, B, T, H, heads, tr, s, colpart, ctx, ctx16);
-    }
-    W2V2_REQUIRE(qkv && dqkv && ctx && dctx && !colpart, "attention_bwd: the fp32 kernels need the fp32 qkv / ctx / dctx / dqkv and leave no column sums");
-    AttnBwdArgs a{qkv, frame_len, dctx, dvec_ws, dqkv, B, T, H, heads, 1.0f / sqrtf((float)dh)};
-    W2V2_REQUIRE(!dqkv16, "attention_bwd: a bf16 shadow of dqkv is only written by the bf16 kernels (head size 64, precision mode 1)");
-    switch (dh) {
-        case 32: return launch_attn_bwd<32>(a, tr, ctx, dvec_ws, s);
-        case 64: return launch_attn_bwd<64>(a, tr, ctx, dvec_ws, s);
-        default:
-            set_error("attention_bwd: head size %d unsupported (32, 64)", dh);
-            return W2V2_EINVAL;
-    }
+    AttnIO io;
+    io.qkv = qkv; io.qkv16 = qkv16; io.frame_len = frame_len; io.train = &tr;
+    io.ctx = const_cast<float*>(ctx); io.ctx16 = const_cast<uint16_t*>(ctx16);      // (read only in this pass)
+    io.dctx = dctx; io.dctx16 = dctx16; io.dqkv = dqkv; io.dqkv16 = dqkv16; io.dvec_ws = dvec_ws; io.colpart = colpart;
+    return launch_attention_bwd_routed(prof, attention_route(attention_problem(AP_BWD, gemm_get_precision(), B, T, H, heads, false, dqkv != nullptr,
+                                                                               dqkv16 != nullptr)), io, s);
 }
 
 }  // namespace w2v2

@@ -763,23 +763,20 @@ int shadow_or_scratch(const float* x, const uint16_t* x16, int64_t n, int slot, 
 
 }  // namespace
 
-bool attention_bf16_supported(int head_size) { return head_size == DH; }
-
-int attention_bf16_packed_rows() { return NW * 32; }
+static_assert(NW == ATTN_BF16_WAVES && DH == ATTN_BF16_DH, "attention_route.h names this file's block shape and head size");
 
 // The packed forward in precision mode 1 (inference): `tiles` holds, utterance by utterance, one entry per
-// attention_bf16_packed_rows() queries (t0 = 0, 128, ...); each utterance's ctx / ctx16 are the bits launch_attention_fwd_bf16
+// NW * 32 queries (t0 = 0, 128, ...); each utterance's ctx / ctx16 are the bits launch_attention_fwd_bf16
 // gives it alone (B = 1, T = its frames, no frame_len).  qkv / ctx: (frames, 3H) / (frames, H) stream buffers; qkv16: the bf16
 // shadow of qkv (null: made here from the fp32 tensor).  ctx or ctx16 may be null (not both).
-int launch_attention_bf16_packed(Profiler* prof, const float* qkv, const uint16_t* qkv16, float* ctx, uint16_t* ctx16, const SegTile* tiles,
-                                 int ntiles, int64_t frames, double sum_nf2, int H, int heads, hipStream_t s) {
+int launch_attention_bf16_packed(const float* qkv, const uint16_t* qkv16, float* ctx, uint16_t* ctx16, const SegTile* tiles, int ntiles,
+                                 int64_t frames, double sum_nf2, int H, int heads, hipStream_t s) {
     W2V2_REQUIRE(tiles && ntiles > 0 && frames > 0 && frames < INT32_MAX && heads > 0, "attention_bf16_packed: bad argument");
     W2V2_REQUIRE(H % heads == 0 && H / heads == DH, "attention_bf16_packed: head size %d unsupported (64)", H / heads);
     W2V2_REQUIRE(ctx || ctx16, "attention_bf16_packed: no output");
     // (row offsets inside an utterance are 32-bit; no utterance has more than sqrt(sum_nf2) frames)
     W2V2_REQUIRE((sqrt(sum_nf2) + 1.0) * 3.0 * H < 2147483648.0 && (int64_t)ntiles * heads < INT32_MAX,
                  "attention_bf16_packed: an utterance too long for 32-bit row offsets");
-    ProfScope ps(prof, FAM_ATTENTION, 4.0 * heads * sum_nf2 * DH, 4.0 * (double)frames * 4.0 * H, s);
     const uint16_t* q16 = nullptr;
     if (int e = shadow_or_scratch(qkv, qkv16, frames * 3 * H, SCRATCH_QKV16, s, &q16)) return e;
     W2V2_REQUIRE(((reinterpret_cast<uintptr_t>(q16) | reinterpret_cast<uintptr_t>(ctx)) & 15) == 0 && (reinterpret_cast<uintptr_t>(ctx16) & 7) == 0,

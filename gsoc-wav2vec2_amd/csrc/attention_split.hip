@@ -343,27 +343,7 @@ __global__ __launch_bounds__(NT, 2) void attention_split_kernel(AttnSplitArgs a)
     report_overflow(a.planes.range_flag, ovf);
 }
 
-}  // namespace
-
-bool attention_split_supported(int head_dim) { return head_dim == DH; }
-
-namespace {
-
-// the four instances share one LDS budget per format: two stages of K and V^T planes
-int set_split_attrs() {
-    static std::atomic<bool> attr_set{false};   // (idempotent call; atomic so concurrent host threads agree on the flag)
-    if (attr_set) return W2V2_OK;
-    W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_split_kernel<PF_BF16X3>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage_bytes(PF_BF16X3)));
-    W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_split_kernel<PF_F16X2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage_bytes(PF_F16X2)));
-    W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_split_kernel<PF_BF16X3, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage_bytes(PF_BF16X3)));
-    W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attention_split_kernel<PF_F16X2, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 2 * stage_bytes(PF_F16X2)));
-    attr_set = true;
-    return W2V2_OK;
-}
+static_assert(NW == ATTN_SPLIT_WAVES && DH == ATTN_SPLIT_DH, "attention_route.h names this file's block shape and head size");
 
 int check_split_args(const float* qkv, const float* ctx, const PlaneOut& pl, int H, int heads, int fmt) {
     W2V2_REQUIRE(!pl.p || (pl.plane % 4 == 0 && (reinterpret_cast<uintptr_t>(pl.p) & 7) == 0), "attention_split: unaligned planes");
@@ -382,30 +362,33 @@ int launch_attention_split(const float* qkv, const int32_t* frame_len, float* ct
     W2V2_REQUIRE(qkv && (ctx || pl.p) && B > 0 && T > 0 && heads > 0, "attention_split: bad argument");
     if (int e = check_split_args(qkv, ctx, pl, H, heads, fmt)) return e;
     AttnSplitArgs a{qkv, frame_len, ctx, B, T, H, heads, 1.0f / sqrtf((float)DH), pl, range_flag, nullptr};
-    if (int e = set_split_attrs()) return e;
     dim3 grid((T + NW * 32 - 1) / (NW * 32), heads, B), block(NT);
-    if (fmt == PF_F16X2)
+    if (fmt == PF_F16X2) {
+        if (int e = set_dynamic_lds<attention_split_kernel<PF_F16X2>>(2 * stage_bytes(PF_F16X2))) return e;
         W2V2_LAUNCH(attention_split_kernel<PF_F16X2>, grid, block, 2 * stage_bytes(PF_F16X2), s, a);
-    else
+    } else {
+        if (int e = set_dynamic_lds<attention_split_kernel<PF_BF16X3>>(2 * stage_bytes(PF_BF16X3))) return e;
         W2V2_LAUNCH(attention_split_kernel<PF_BF16X3>, grid, block, 2 * stage_bytes(PF_BF16X3), s, a);
+    }
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }
 
-int launch_attention_split_packed(Profiler* prof, const float* qkv, float* ctx, const SegTile* tiles, int ntiles, int64_t frames,
-                                  double sum_nf2, int H, int heads, hipStream_t s, const PlaneOut* planes, int fmt, int* range_flag) {
+int launch_attention_split_packed(const float* qkv, float* ctx, const SegTile* tiles, int ntiles, int64_t frames, int H, int heads, hipStream_t s,
+                                  const PlaneOut* planes, int fmt, int* range_flag) {
     const PlaneOut pl = planes ? *planes : PlaneOut{};
     W2V2_REQUIRE(qkv && (ctx || pl.p) && tiles, "attention_split_packed: null operand");
     W2V2_REQUIRE(ntiles > 0 && frames > 0 && frames < INT32_MAX && heads > 0, "attention_split_packed: bad sizes");
     if (int e = check_split_args(qkv, ctx, pl, H, heads, fmt)) return e;
-    ProfScope ps(prof, FAM_ATTENTION, 4.0 * heads * sum_nf2 * DH, 4.0 * (double)frames * 4.0 * H, s);
     AttnSplitArgs a{qkv, nullptr, ctx, 1, (int)frames, H, heads, 1.0f / sqrtf((float)DH), pl, range_flag, tiles};
-    if (int e = set_split_attrs()) return e;
     dim3 grid(ntiles, heads, 1), block(NT);
-    if (fmt == PF_F16X2)
+    if (fmt == PF_F16X2) {
+        if (int e = set_dynamic_lds<attention_split_kernel<PF_F16X2, true>>(2 * stage_bytes(PF_F16X2))) return e;
         W2V2_LAUNCH((attention_split_kernel<PF_F16X2, true>), grid, block, 2 * stage_bytes(PF_F16X2), s, a);
-    else
+    } else {
+        if (int e = set_dynamic_lds<attention_split_kernel<PF_BF16X3, true>>(2 * stage_bytes(PF_BF16X3))) return e;
         W2V2_LAUNCH((attention_split_kernel<PF_BF16X3, true>), grid, block, 2 * stage_bytes(PF_BF16X3), s, a);
+    }
     W2V2_HIP_CHECK(hipGetLastError());
     return W2V2_OK;
 }

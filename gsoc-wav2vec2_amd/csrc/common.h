@@ -13,6 +13,7 @@
 
 #include "../../include/w2v2.h"
 #include "gemm_bf16_route.h"
+#include "attention_route.h"
 
 namespace w2v2 {
 
@@ -36,6 +37,18 @@ void set_error(const char* fmt, ...);
             return W2V2_EINVAL;                \
         }                                      \
     } while (0)
+
+// A kernel's dynamic LDS limit, raised once per kernel (the call is idempotent; the flag is atomic so that concurrent host threads
+// agree on it).  `bytes` is a constant of the kernel.
+template <auto Kernel>
+int set_dynamic_lds(size_t bytes) {
+    static std::atomic<bool> done{false};
+    if (!done) {
+        W2V2_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        done = true;
+    }
+    return W2V2_OK;
+}
 
 // ---- tuning knobs -----------------------------------------------------------
 // The shipping library has NO environment reads: every knob is its measured default, folded at compile time.  The tools-only
@@ -375,26 +388,19 @@ void pos_conv_dw_bf16_ws_floats(int B, int T, int H, int K, int groups, int64_t 
 int launch_pos_conv_dw_bf16(Profiler* prof, const float* xz, const float* dc, float* dwg, float* pack32, float* slabs, float* red_ws,
                             int B, int T, int H, int K, int groups, hipStream_t s, float* dc_pad = nullptr /* (B, 64 ceil(T/64), H): T % 64 != 0 */);
 
-int launch_attention(Profiler* prof, const float* qkv, const int32_t* frame_len, float* ctx, int B,
-                     int T, int H, int heads, hipStream_t s);
-
 // packed forward, fp32: the positional conv over tiles of 128 frames (pos_conv_packed_rows()), each utterance zero-padded at its
-// own edges; attention over tiles of attention_packed_rows() queries, keys restricted to the tile's utterance.  x / y and
-// qkv / ctx are (frames, H) / (frames, 3H) stream buffers; frames and sum_nf2 (sum of squared utterance frames) size the profile.
+// own edges; attention over tiles of AttnRoute::rows queries, keys restricted to the tile's utterance.  x / y and
+// qkv / ctx are (frames, H) / (frames, 3H) stream buffers.
 int pos_conv_packed_rows();
 int launch_pos_conv_packed(Profiler* prof, const float* x, const float* wg, const float* bias, float* y, const SegTile* tiles,
                            int ntiles, int64_t frames, int H, int K, int groups, int act, hipStream_t s);
-int attention_packed_rows(int head_size);
-int launch_attention_packed(Profiler* prof, const float* qkv, float* ctx, const SegTile* tiles, int ntiles, int64_t frames,
-                            double sum_nf2, int H, int heads, hipStream_t s);
 // packed forward, precision mode 1 (posconv.hip, attention_bf16.hip): segment forms of launch_pos_conv_bf16 (pad_left = K / 2,
 // residual on; rows of y no utterance owns are zeroed) and of launch_attention_fwd_bf16 over a table of
-// attention_bf16_packed_rows()-query tiles; each utterance's output is bit for bit what the dense launcher gives it alone
+// 128-query tiles; each utterance's output is bit for bit what the dense launcher gives it alone
 int launch_pos_conv_bf16_packed(Profiler* prof, const float* x, const uint16_t* w16, const float* bias, float* y, const PackSeg* segs,
                                 int nseg, int64_t frames, int H, int K, int groups, int act, hipStream_t s);
-int attention_bf16_packed_rows();
-int launch_attention_bf16_packed(Profiler* prof, const float* qkv, const uint16_t* qkv16, float* ctx, uint16_t* ctx16, const SegTile* tiles,
-                                 int ntiles, int64_t frames, double sum_nf2, int H, int heads, hipStream_t s);
+int launch_attention_bf16_packed(const float* qkv, const uint16_t* qkv16, float* ctx, uint16_t* ctx16, const SegTile* tiles, int ntiles,
+                                 int64_t frames, double sum_nf2, int H, int heads, hipStream_t s);
 // packed.hip: caller's samples (from src0 on, per utterance) -> aligned stream (gaps zeroed); stream rows -> caller's rows.
 // stats: null (a copy), or launch_pack_stats' (nseg, 2) fp64 (mean, sqrt(var + eps)): (x - mean) / that, formed in fp64
 int launch_pack_scatter(const float* src, float* stream, int64_t L, const PackSeg* segs, int nseg, hipStream_t s,
@@ -445,21 +451,57 @@ int staged_upload(int slot, hipStream_t s, void* dst, std::initializer_list<Stag
 int launch_qkv_pack(float* packed_w, float* packed_b, const float* const w[3], const float* const b[3], int H, hipStream_t s);
 int launch_qkv_pack_layers(float* const* packed_w, float* const* packed_b, const float* const* w, const float* const* b, int layers, int H, hipStream_t s);
 int launch_qkv_unpack(const float* packed_w, const float* packed_b, float* const w[3], float* const b[3], int H, hipStream_t s);
-bool attention_bf16_supported(int head_size);   // attention_bf16.hip: head size 64
-bool attention_split_supported(int head_size);  // attention_split.hip (precision mode 2): head size 64
-int launch_attention_split(const float* qkv, const int32_t* frame_len, float* ctx, int B, int T, int H, int heads, hipStream_t s,
-                           const PlaneOut* planes = nullptr /* optional planes of ctx; ctx itself may then be null */,
-                           int fmt = PF_BF16X3 /* PF_F16X2: two fp16 terms / three products per contraction (precision mode 3) */,
-                           int* range_flag = nullptr /* f16x2: sticky flag for q / k / v beyond fp16's scaled range */);
-// packed forward, precision modes 2 / 3: the split kernel over the same 256-query tile table as launch_attention_packed, keys and
-// values restricted to the tile's utterance; each utterance's ctx (and planes) bit-identical to launch_attention_split on it alone
-int launch_attention_split_packed(Profiler* prof, const float* qkv, float* ctx, const SegTile* tiles, int ntiles, int64_t frames,
-                                  double sum_nf2, int H, int heads, hipStream_t s, const PlaneOut* planes, int fmt, int* range_flag);
+// ---- attention: attention_route (attention_route.h) decides, these execute ----
+static_assert(PF_BF16X3 == 0 && PF_F16X2 == 1, "AttnRoute::fmt is a PlaneFmt");
+bool attention_split_allowed();      // W2V2_SPLIT_ATTN (tools/nll_drift_probe.py separates the attention from the GEMMs): its one reader
+// the problem of a caller that has no pointers yet (a plan) or whose buffers are 16-byte aligned by construction
+inline AttnProblem attention_problem(int pass, int precision, int B, int T, int H, int heads, bool packed, bool want_f32 = true, bool want_b16 = false,
+                                     bool want_planes = false, bool io_aligned = true) {
+    return AttnProblem{pass, precision, B, T, H, heads, packed, attention_split_allowed(), io_aligned, want_f32, want_b16, want_planes};
+}
+struct AttnTrain;
+// What a routed launch reads and writes.  A form the route's family does not use may be null; qkv16 is optional everywhere (the bf16
+// kernels round qkv into scratch without it), and with ctx16 the fp32 ctx may be null.
+struct AttnIO {
+    const float* qkv = nullptr;
+    const uint16_t* qkv16 = nullptr;
+    const int32_t* frame_len = nullptr;      // dense: (B) valid frames, or null
+    const SegTile* tiles = nullptr;          // packed: one entry per AttnRoute::rows queries of an utterance, utterance by utterance
+    int ntiles = 0;
+    int64_t frames = 0;                      // ... the stream's frames and the sum of squared utterance frames (sizes the profile)
+    double sum_nf2 = 0.0;
+    float* ctx = nullptr;                    // (backward: the forward's output, read)
+    uint16_t* ctx16 = nullptr;
+    const PlaneOut* planes = nullptr;        // split family: planes of ctx and / or the f16x2 range flag
+    const AttnTrain* train = nullptr;        // training forward and backward
+    // backward: dctx (B, T, H) in, dqkv (B, T, 3H) out, each as fp32 and / or bf16; dvec_ws (B, heads, T) scratch; colpart: see launch_attention_bwd_bf16
+    const float* dctx = nullptr;
+    const uint16_t* dctx16 = nullptr;
+    float* dqkv = nullptr;
+    uint16_t* dqkv16 = nullptr;
+    float *dvec_ws = nullptr, *colpart = nullptr;
+};
+int launch_attention_routed(Profiler* prof, const AttnRoute& route, const AttnIO& io, hipStream_t s);            // AP_INFER, dense or packed
+int launch_attention_train_routed(Profiler* prof, const AttnRoute& route, const AttnIO& io, hipStream_t s);      // AP_TRAIN
+int launch_attention_bwd_routed(Profiler* prof, const AttnRoute& route, const AttnIO& io, hipStream_t s);        // AP_BWD
+void attention_launches(int64_t* counts);      // AK_KERNELS launch counts of the three launchers above
+// The op-level forms: the problem comes from the calling thread's precision (gemm_get_precision) and the pointers' alignment.
+int launch_attention(Profiler* prof, const float* qkv, const int32_t* frame_len, float* ctx, int B,
+                     int T, int H, int heads, hipStream_t s);
 // qkv16: optional bf16 shadow of qkv (precision mode 1 with head size 64 reads ONLY it; qkv may then be null.  Without it that
 // kernel rounds qkv into scratch first).  ctx may be null when ctx16 is given.
 int launch_attention_x(Profiler* prof, const float* qkv, const uint16_t* qkv16, const int32_t* frame_len, float* ctx, int B, int T, int H,
                        int heads, uint16_t* ctx16 /* optional bf16 shadow of ctx (bf16 kernel only) */, hipStream_t s,
                        const PlaneOut* planes = nullptr /* optional planes of ctx (split kernel only: precision modes 2 / 3, head size 64) */);
+// The kernels' own launchers (their files keep the kernels in anonymous namespaces): they check their operands and launch.
+int launch_attention_split(const float* qkv, const int32_t* frame_len, float* ctx, int B, int T, int H, int heads, hipStream_t s,
+                           const PlaneOut* planes = nullptr /* optional planes of ctx; ctx itself may then be null */,
+                           int fmt = PF_BF16X3 /* PF_F16X2: two fp16 terms / three products per contraction (precision mode 3) */,
+                           int* range_flag = nullptr /* f16x2: sticky flag for q / k / v beyond fp16's scaled range */);
+// packed forward, precision modes 2 / 3: the split kernel over the same 256-query tile table as the fp32 segment kernel, keys and
+// values restricted to the tile's utterance; each utterance's ctx (and planes) bit-identical to launch_attention_split on it alone
+int launch_attention_split_packed(const float* qkv, float* ctx, const SegTile* tiles, int ntiles, int64_t frames, int H, int heads, hipStream_t s,
+                                  const PlaneOut* planes, int fmt, int* range_flag);
 
 int launch_frame_lengths(Profiler* prof, const int32_t* mask, int32_t* frame_len, int B, int64_t L,
                          const int32_t* ks, const int32_t* ss, int nl, hipStream_t s);

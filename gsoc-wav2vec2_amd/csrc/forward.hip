@@ -250,7 +250,10 @@ ForwardPlan w2v2_plan_forward(const w2v2_model* m, int B, int64_t L, bool planes
     const int64_t BT = p.BT = (int64_t)B * p.T;
     const int H = c.hidden_size, F = c.intermediate_size;
     p.sh = m->precision == 1 && m->opt_shadows;
-    p.attn16 = p.sh && attention_bf16_supported(H / c.num_heads);
+    // the attention kernel: one route for every layer, dense or over the packed stream's tiles (B = 1).  The bf16 family runs in
+    // mode 1 with or without shadows; with them q | k | v and ctx are also kept as bf16
+    p.attn = attention_route(attention_problem(AP_INFER, m->precision, packed ? 1 : B, p.T, H, c.num_heads, packed));
+    p.attn16 = p.sh && p.attn.family == AF_BF16;
     p.pm = planes && m->precision >= W2V2_PRECISION_BF16X3 && m->opt_planes;
     p.fmt = m->precision == W2V2_PRECISION_F16X2 ? PF_F16X2 : PF_BF16X3;
     p.keep = m->opt_keep_acts;
@@ -260,7 +263,6 @@ ForwardPlan w2v2_plan_forward(const w2v2_model* m, int B, int64_t L, bool planes
     // element-wise kernels in precision mode 1 evaluate exact GELU through the 5-term erf the bf16 GEMM epilogue uses (act 3)
     p.act_ew = (p.act == 1 && m->precision == 1) ? 3 : p.act;
     // (dense and packed alike: the packed forward runs in mode 1 only under W2V2_OPT_BF16_PACKED, and then with the segment form)
-    (void)packed;
     p.pos16 = w2v2_pos_conv_bf16_ok(m);
     const bool sh = p.sh, pm = p.pm, keep = p.keep;
 
@@ -285,9 +287,8 @@ ForwardPlan w2v2_plan_forward(const w2v2_model* m, int B, int64_t L, bool planes
     p.fused = NC > 1 && p.cp[1] && c.kernal_sizes[0] == 10 && c.strides[0] == 5 && 256 % (c.filter_sizes[0] / 4) == 0 && c.filter_sizes[0] / 4 <= 256;
     // the split attention kernel (precision modes 2 / 3, planes or not) -- and, where the out-projection is plane-fed, it writes ctx's
     // planes itself; any other attention kernel leaves fp32 to be split.  (p_out implies modes 2 / 3: ctx_fused implies split_attn.)
-    const bool split_ok = attention_split_supported(H / c.num_heads) && H % 4 == 0 && tune_int("W2V2_SPLIT_ATTN", 1) != 0;
-    p.split_attn = m->precision >= W2V2_PRECISION_BF16X3 && split_ok;
-    p.ctx_fused = p.p_out && split_ok;
+    p.split_attn = p.attn.family == AF_SPLIT;
+    p.ctx_fused = p.p_out && p.split_attn;
 
     // ---- mode bf16: tensors whose one reader is a GEMM certain to stream the bf16 shadow are written only as bf16 ----
     // One predicate, gemm_bf16_streams_a16 (gemm_bf16_route.h), for all of them.  The weight side needs no test: w2v2_ensure_shadows, which
@@ -543,8 +544,8 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
         attn_pl.o.range_flag = m->range_flag;
         attn_pl.on = true;
     }
-    // packed, precision mode 1 with head size 64: the segment form of the bf16 kernel, as launch_attention_x picks the dense one
-    const bool pk_attn16 = pk && m->precision == W2V2_PRECISION_BF16 && attention_bf16_supported(H / c.num_heads);
+    // packed with the bf16 family: ctx exists in the forms that kernel writes
+    const bool pk_attn16 = pk && plan.attn.family == AF_BF16;
     if (pk_attn16) {                     // (the forms of ctx that kernel writes in this plan: with ctx16_only just the shadow)
         if (int e = launch_pack_zero_gaps(ForwardPlan::f32(plan.ctx, m->ctx), nullptr, T, H, pk->segs, pk->nseg, s, ForwardPlan::b16(plan.ctx, m->ctx16))) return e;
     } else if (pk) {                     // (the attention kernels write only the utterances' rows of ctx and of its planes, in every layer)
@@ -554,6 +555,18 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
     const Tens qkv{plan.qkv, m->qkv, m->qkv16, nullptr}, ctx{plan.ctx, m->ctx, m->ctx16, &m->ctx48}, t1{plan.hidden, m->t1, nullptr, nullptr},
                ffn_in{plan.ffn_in, m->t2, m->t2_16, &m->ffn_in48}, ffn{plan.ffn, m->ffn, m->ffn16, &m->ffn48};
     auto hs = [&](int i, unsigned forms) { return Tens{forms, m->hs[i], ForwardPlan::b16(forms, m->hs16, i), &m->attn_in48}; };
+    // what the attention kernel of every layer reads and writes: the forms of q | k | v and ctx this plan has (the packed fp32 family reads the fp32 q | k | v)
+    AttnIO attn_io;
+    attn_io.qkv = ForwardPlan::f32(plan.qkv, m->qkv);
+    attn_io.qkv16 = ForwardPlan::b16(plan.qkv, m->qkv16);
+    attn_io.ctx = ForwardPlan::f32(plan.ctx, m->ctx);
+    attn_io.ctx16 = ForwardPlan::b16(plan.ctx, m->ctx16);
+    attn_io.planes = plan.attn.family == AF_SPLIT ? (const PlaneOut*)attn_pl : nullptr;
+    if (pk) {
+        attn_io.tiles = pk->attn_tiles; attn_io.ntiles = pk->nattn; attn_io.frames = T; attn_io.sum_nf2 = pk->sum_nf2;
+    } else {
+        attn_io.frame_len = flen;
+    }
     if (!prenorm)
         if (int e = launch_layer_norm_x(pf, m->posout, m->hs[0], m->P("encoder/layer_norm/gamma"), m->P("encoder/layer_norm/beta"), BT, H, eps, 0,
                                         ForwardPlan::b16(plan.attn_in, m->hs16, 0), s, po_attn))
@@ -568,20 +581,7 @@ static int forward_impl(w2v2_model* m, const float* wave, int32_t B, int64_t L, 
                 return e;
         if (int e = gemm(m, plan, s, plan.p_qkv, attn_in, H, 0, m->qkv_w[i], 3 * H, qkv, 3 * H, 0, m->qkv_b[i], nullptr, (int)BT, 3 * H, H, 1, 0))
             return e;
-        if (pk_attn16) {
-            if (int e = launch_attention_bf16_packed(pf, ForwardPlan::f32(plan.qkv, m->qkv), ForwardPlan::b16(plan.qkv, m->qkv16), ForwardPlan::f32(plan.ctx, m->ctx),
-                                                     ForwardPlan::b16(plan.ctx, m->ctx16), pk->attn_tiles, pk->nattn, T, pk->sum_nf2, H, c.num_heads, s))
-                return e;
-        } else if (pk && plan.split_attn) {     // packed, precision modes 2 / 3: queries and keys of one utterance per block
-            if (int e = launch_attention_split_packed(pf, m->qkv, ForwardPlan::f32(plan.ctx, m->ctx), pk->attn_tiles, pk->nattn, T, pk->sum_nf2, H,
-                                                      c.num_heads, s, attn_pl, plan.fmt, attn_pl.on ? attn_pl.o.range_flag : nullptr))
-                return e;
-        } else if (pk) {
-            if (int e = launch_attention_packed(pf, m->qkv, ForwardPlan::f32(plan.ctx, m->ctx), pk->attn_tiles, pk->nattn, T, pk->sum_nf2, H, c.num_heads, s)) return e;
-        } else if (int e = launch_attention_x(pf, ForwardPlan::f32(plan.qkv, m->qkv), ForwardPlan::b16(plan.qkv, m->qkv16), flen, ForwardPlan::f32(plan.ctx, m->ctx), B, T, H,
-                                              c.num_heads, ForwardPlan::b16(plan.ctx, m->ctx16), s, attn_pl)) {
-            return e;
-        }
+        if (int e = launch_attention_routed(pf, plan.attn, attn_io, s)) return e;
         if ((plan.ctx & PLANES) && !(plan.attn_kernel & PLANES)) {
             W2V2_REQUIRE(plan.ctx & F32, "forward: ctx's planes are to be split off an fp32 ctx this forward does not write");
             if (int e = launch_split_planes(m->ctx, m->ctx48.p, m->ctx48.plane, BT * H, plan.fmt, m->range_flag, s)) return e;
@@ -686,8 +686,10 @@ static int forward_stream(w2v2_model* m, const char* who, const float* wave, con
     W2V2_REQUIRE(T < (1 << 24) && (int64_t)segs.back().f0 + segs.back().nf <= T, "%s: stream of %lld samples out of range", who,
                  (long long)L);
     // (attention tiles of the height of the kernel that will run: 128 queries for mode 1's bf16 kernel, 256 for the others)
-    const int H = c.hidden_size, PR = pos_conv_packed_rows(), AR32 = attention_packed_rows(H / c.num_heads), AR16 = attention_bf16_packed_rows();
-    const int AR = (m->precision == W2V2_PRECISION_BF16 && attention_bf16_supported(H / c.num_heads)) ? AR16 : AR32;
+    const int H = c.hidden_size, PR = pos_conv_packed_rows();
+    const AttnRoute attn = attention_route(attention_problem(AP_INFER, m->precision, 1, (int)T, H, c.num_heads, true));
+    W2V2_REQUIRE(!attn.refusal, attention_refusal_text(attn), attn.dh);
+    const int AR = attn.rows;
     std::vector<SegTile> tiles;
     for (const int rows_per_tile : {PR, AR})
         for (const PackSeg& sg : segs)
@@ -702,7 +704,7 @@ static int forward_stream(w2v2_model* m, const char* who, const float* wave, con
     if (m->pk_L != m->ws_L) {
         const int64_t Tcap = w2v2_num_frames(m, m->ws_L);
         m->pk_seg_cap = (int)(m->ws_L / U);
-        m->pk_tile_cap = (int)(2 * (int64_t)m->pk_seg_cap + Tcap / PR + Tcap / std::min(AR32, AR16));
+        m->pk_tile_cap = (int)(2 * (int64_t)m->pk_seg_cap + Tcap / PR + Tcap / ATTN_MIN_PACKED_ROWS);
         if (int e = w2v2_ws_alloc(m, &m->pk_wave, m->ws_L)) return e;
         if (int e = w2v2_ws_alloc(m, &m->pk_scale, (int64_t)m->pk_seg_cap * 2 * c.filter_sizes[0])) return e;
         if (int e = w2v2_ws_alloc(m, &m->pk_out, c.with_lm_head ? Tcap * c.vocab_size : 0)) return e;

@@ -123,7 +123,8 @@ struct ForwardPlan {
     bool layer_mode = false, prenorm = false;
     int act = 1, act_ew = 1;                 // GELU form of the GEMM epilogues / of the element-wise kernels
     bool fused = false;                      // conv0's kernel writes the planes of its output itself
-    bool split_attn = false;                 // the split attention kernel runs (the packed forward picks its launcher by this)
+    w2v2::AttnRoute attn;                    // the attention kernel of this forward (attention_route.h), dense or packed
+    bool split_attn = false;                 // ... is the split kernel
     bool ctx_fused = false;                  // ... and writes ctx's planes itself
     bool ctx16_only = false, ffn_sh_only = false;      // mode bf16: ctx / the FFN hidden exist only as bf16 (both ignore `keep`)
     bool pos16 = false;                      // the bf16 positional conv (needs w2v2_ensure_pos16)
@@ -168,6 +169,7 @@ struct TrainPlan {
     int act = 1, act_ew = 1;                 // GELU form of the GEMM epilogues / of the element-wise kernels
     int u_round = 0;                         // the element-wise kernels round an fp32 u to bf16 on the way in (mode bf16)
     bool lse_log2 = false;                   // the attention forward saved lse2 = -(m C2 + log2 l) (bf16 kernels), not the natural lse
+    w2v2::AttnRoute attn, attn_bwd;          // the attention kernels of the step (attention_route.h): attn16 and lse_log2 are read off them
 };
 
 // implemented in w2v2_api.hip

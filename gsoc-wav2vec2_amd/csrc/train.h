@@ -268,8 +268,7 @@ struct AttnTrain {
     uint32_t* keep_bits = nullptr;
 };
 int64_t attention_keep_bits_words(int B, int T, int heads);
-// bf16 matrix-pipe attention (attention_bf16.hip); taken by launch_attention* while the thread's precision is 1
-bool attention_bf16_supported(int head_size);
+// bf16 matrix-pipe attention (attention_bf16.hip): the AF_BF16 family of attention_route
 // (the kernels read bf16 shadows of qkv / dctx; a null shadow is made from the fp32 tensor in per-stream scratch)
 int launch_attention_fwd_bf16(const float* qkv, const uint16_t* qkv16, const int32_t* frame_len, float* ctx, uint16_t* ctx16, int B,
                               int T, int H, int heads, const AttnTrain* tr, hipStream_t s);

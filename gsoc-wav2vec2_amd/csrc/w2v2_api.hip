@@ -838,6 +838,19 @@ int w2v2_op_gemm_bf16_launches(int64_t* counts) {
     gemm_bf16_launches(counts);
     return W2V2_OK;
 }
+int w2v2_op_attention_route(const int32_t* q, int32_t* out) {
+    W2V2_REQUIRE(q && out && q[0] >= AP_INFER && q[0] <= AP_BWD && q[2] > 0 && q[3] > 0 && q[4] > 0 && q[5] > 0 && q[4] % q[5] == 0,
+                 "op_attention_route: bad argument");
+    const AttnRoute r = attention_route(AttnProblem{q[0], q[1], q[2], q[3], q[4], q[5], q[6] != 0, q[7] != 0, q[8] != 0, q[9] != 0, q[10] != 0, q[11] != 0});
+    const int32_t v[10] = {r.kernel, r.refusal, r.family, r.fmt, r.dh, r.waves, r.rows, r.lse_log2, r.writes_b16, r.writes_planes};
+    for (int i = 0; i < 10; ++i) out[i] = v[i];
+    return W2V2_OK;
+}
+int w2v2_op_attention_launches(int64_t* counts) {
+    W2V2_REQUIRE(counts, "op_attention_launches: null argument");
+    attention_launches(counts);
+    return W2V2_OK;
+}
 int w2v2_op_split_planes(const float* x, uint16_t* planes, int64_t plane_stride, int64_t n, int32_t fmt, int32_t* range_flag, void* stream) {
     W2V2_REQUIRE(fmt == PF_BF16X3 || fmt == PF_F16X2, "op_split_planes: unknown plane format %d", fmt);
     return launch_split_planes(x, planes, plane_stride, n, fmt, range_flag, reinterpret_cast<hipStream_t>(stream));
@@ -943,6 +956,34 @@ int w2v2_op_attention(const float* qkv, const int32_t* frame_len, float* ctx, in
                       int32_t H, int32_t num_heads, void* stream) {
     return launch_attention(nullptr, qkv, frame_len, ctx, B, T, H, num_heads, reinterpret_cast<hipStream_t>(stream));
 }
+}  // extern "C"
+namespace {
+// The tile table of a packed attention op -- one entry per `rows` queries of an utterance, utterances back to back as cu_frames
+// cuts them -- staged on the device, handed to `launch` with an AttnIO that carries it, and freed.
+template <class F>
+int with_attention_tiles(const char* who, int32_t n, const int32_t* cu_frames, int rows, hipStream_t s, F&& launch) {
+    W2V2_REQUIRE(n >= 1 && cu_frames[0] == 0, "%s: need n >= 1 utterances and cu_frames[0] == 0", who);
+    std::vector<SegTile> tiles;
+    AttnIO io;
+    for (int i = 0; i < n; ++i) {
+        const int nf = cu_frames[i + 1] - cu_frames[i];
+        W2V2_REQUIRE(nf >= 1, "%s: utterance %d has %d frames (need at least one)", who, i, nf);
+        for (int t0 = 0; t0 < nf; t0 += rows) tiles.push_back(SegTile{cu_frames[i], nf, t0, 0});
+        io.sum_nf2 += (double)nf * (double)nf;
+    }
+    SegTile* dt = nullptr;
+    W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dt), tiles.size() * sizeof(SegTile)));
+    int e = hipMemcpyAsync(dt, tiles.data(), tiles.size() * sizeof(SegTile), hipMemcpyHostToDevice, s) == hipSuccess &&
+                    hipStreamSynchronize(s) == hipSuccess ? W2V2_OK : W2V2_EHIP;
+    if (e) set_error("%s: staging the tile table failed", who);
+    io.tiles = dt; io.ntiles = (int)tiles.size(); io.frames = cu_frames[n];
+    if (!e) e = launch(io);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(dt);
+    return e;
+}
+}  // namespace
+extern "C" {
 int w2v2_op_attention_packed(const float* qkv, int32_t n, const int32_t* cu_frames, float* ctx, uint16_t* planes, int64_t plane_stride,
                              int32_t* range_flag, int32_t H, int32_t heads, void* stream) {
     W2V2_REQUIRE(qkv && cu_frames && (ctx || planes), "op_attention_packed: null operand");
@@ -950,66 +991,38 @@ int w2v2_op_attention_packed(const float* qkv, int32_t n, const int32_t* cu_fram
     W2V2_REQUIRE(heads > 0 && H % heads == 0, "op_attention_packed: bad sizes H=%d heads=%d", H, heads);
     const int mode = gemm_get_precision();
     W2V2_REQUIRE(mode != W2V2_PRECISION_BF16, "op_attention_packed: precision mode bf16 is not supported (fp32, bf16x3, f16x2)");
-    const int dh = H / heads, fmt = mode == W2V2_PRECISION_F16X2 ? PF_F16X2 : PF_BF16X3;
-    const bool split = mode >= W2V2_PRECISION_BF16X3 && attention_split_supported(dh) && H % 4 == 0 && tune_int("W2V2_SPLIT_ATTN", 1) != 0;
-    W2V2_REQUIRE(split || ctx, "op_attention_packed: this mode and head size run the fp32 kernel, which needs ctx");
     W2V2_REQUIRE(!planes || mode >= W2V2_PRECISION_BF16X3, "op_attention_packed: planes are written in precision modes bf16x3 / f16x2 only");
-    // the tile table of the packed forward, utterances back to back
-    const int AR = attention_packed_rows(dh);
-    std::vector<SegTile> tiles;
-    double sum_nf2 = 0.0;
-    for (int i = 0; i < n; ++i) {
-        const int nf = cu_frames[i + 1] - cu_frames[i];
-        W2V2_REQUIRE(nf >= 1, "op_attention_packed: utterance %d has %d frames (need at least one)", i, nf);
-        for (int t0 = 0; t0 < nf; t0 += AR) tiles.push_back(SegTile{cu_frames[i], nf, t0, 0});
-        sum_nf2 += (double)nf * (double)nf;
-    }
-    const int64_t frames = cu_frames[n];
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    SegTile* dt = nullptr;
-    W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dt), tiles.size() * sizeof(SegTile)));
-    int e = hipMemcpyAsync(dt, tiles.data(), tiles.size() * sizeof(SegTile), hipMemcpyHostToDevice, s) == hipSuccess &&
-                    hipStreamSynchronize(s) == hipSuccess ? W2V2_OK : W2V2_EHIP;
-    if (e) set_error("op_attention_packed: staging the tile table failed");
+    // the split kernel writes the planes itself; the fp32 segment kernel needs ctx, and (modes 2 / 3) the planes are split off its
+    // output, as the packed forward does
+    const AttnRoute r = attention_route(attention_problem(AP_INFER, mode, 1, cu_frames[n], H, heads, true, ctx != nullptr, false, false,
+                                                          ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(ctx)) & 15) == 0));
+    W2V2_REQUIRE(r.family == AF_SPLIT || ctx, "op_attention_packed: this mode and head size run the fp32 kernel, which needs ctx");
+    W2V2_REQUIRE(!r.refusal, attention_refusal_text(r), r.dh);
+    const int fmt = mode == W2V2_PRECISION_F16X2 ? PF_F16X2 : PF_BF16X3;
     PlaneOut pl;
     pl.p = planes; pl.plane = plane_stride; pl.fmt = fmt; pl.range_flag = range_flag;
-    if (!e && split) {
-        e = launch_attention_split_packed(nullptr, qkv, ctx, dt, (int)tiles.size(), frames, sum_nf2, H, heads, s, planes ? &pl : nullptr, fmt, range_flag);
-    } else if (!e) {      // the fp32 segment kernel, then (modes 2 / 3) the planes of its output, as the packed forward does
-        e = launch_attention_packed(nullptr, qkv, ctx, dt, (int)tiles.size(), frames, sum_nf2, H, heads, s);
-        if (!e && planes) e = launch_split_planes(ctx, planes, plane_stride, frames * H, fmt, range_flag, s);
-    }
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(dt);
-    return e;
+    return with_attention_tiles("op_attention_packed", n, cu_frames, r.rows, s, [&](AttnIO& io) {
+        io.qkv = qkv; io.ctx = ctx;
+        if (r.family == AF_SPLIT) io.planes = &pl;
+        int e = launch_attention_routed(nullptr, r, io, s);
+        if (!e && r.family != AF_SPLIT && planes) e = launch_split_planes(ctx, planes, plane_stride, io.frames * H, fmt, range_flag, s);
+        return e;
+    });
 }
 int w2v2_op_attention_packed_bf16(const float* qkv, const uint16_t* qkv16, int32_t n, const int32_t* cu_frames, float* ctx, uint16_t* ctx16,
                                   int32_t H, int32_t heads, void* stream) {
     W2V2_REQUIRE((qkv || qkv16) && cu_frames && (ctx || ctx16), "op_attention_packed_bf16: null operand");
     W2V2_REQUIRE(n >= 1 && cu_frames[0] == 0, "op_attention_packed_bf16: need n >= 1 utterances and cu_frames[0] == 0");
-    W2V2_REQUIRE(heads > 0 && H % heads == 0 && attention_bf16_supported(H / heads), "op_attention_packed_bf16: bad sizes H=%d heads=%d (head size 64)", H,
-                 heads);
-    // the tile table of the packed forward in precision mode 1, utterances back to back
-    const int AR = attention_bf16_packed_rows();
-    std::vector<SegTile> tiles;
-    double sum_nf2 = 0.0;
-    for (int i = 0; i < n; ++i) {
-        const int nf = cu_frames[i + 1] - cu_frames[i];
-        W2V2_REQUIRE(nf >= 1, "op_attention_packed_bf16: utterance %d has %d frames (need at least one)", i, nf);
-        for (int t0 = 0; t0 < nf; t0 += AR) tiles.push_back(SegTile{cu_frames[i], nf, t0, 0});
-        sum_nf2 += (double)nf * (double)nf;
-    }
-    const int64_t frames = cu_frames[n];
+    W2V2_REQUIRE(heads > 0 && H % heads == 0, "op_attention_packed_bf16: bad sizes H=%d heads=%d (head size 64)", H, heads);
+    // (whatever w2v2_op_set_precision says: this op is mode 1's route)
+    const AttnRoute r = attention_route(attention_problem(AP_INFER, W2V2_PRECISION_BF16, 1, cu_frames[n], H, heads, true, ctx != nullptr, ctx16 != nullptr));
+    W2V2_REQUIRE(r.family == AF_BF16, "op_attention_packed_bf16: bad sizes H=%d heads=%d (head size 64)", H, heads);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    SegTile* dt = nullptr;
-    W2V2_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dt), tiles.size() * sizeof(SegTile)));
-    int e = hipMemcpyAsync(dt, tiles.data(), tiles.size() * sizeof(SegTile), hipMemcpyHostToDevice, s) == hipSuccess &&
-                    hipStreamSynchronize(s) == hipSuccess ? W2V2_OK : W2V2_EHIP;
-    if (e) set_error("op_attention_packed_bf16: staging the tile table failed");
-    if (!e) e = launch_attention_bf16_packed(nullptr, qkv, qkv16, ctx, ctx16, dt, (int)tiles.size(), frames, sum_nf2, H, heads, s);
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(dt);
-    return e;
+    return with_attention_tiles("op_attention_packed_bf16", n, cu_frames, r.rows, s, [&](AttnIO& io) {
+        io.qkv = qkv; io.qkv16 = qkv16; io.ctx = ctx; io.ctx16 = ctx16;
+        return launch_attention_routed(nullptr, r, io, s);
+    });
 }
 int w2v2_op_pos_conv_packed_bf16(const float* x, const uint16_t* w16, const float* bias, int32_t n, const int32_t* cu_frames, float* y, int32_t H,
                                  int32_t K, int32_t groups, int32_t act, void* stream) {

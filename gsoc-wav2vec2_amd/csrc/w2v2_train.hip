@@ -287,10 +287,13 @@ static TrainPlan plan_train(const w2v2_model* m, int B, int64_t L) {
     // epilogues, LayerNorm, dropout, attention -- also writes the nearest-even bf16 copy, so the forward GEMMs stream 2-byte operands
     // by LDS-DMA instead of converting fp32 in registers; results are bit-identical either way.
     p.sh = m->precision == 1 && m->opt_shadows;
+    // the attention kernels of the step (attention_route.h): the forward and the backward run from these two routes
+    p.attn = attention_route(attention_problem(AP_TRAIN, m->precision, B, p.T, H, c.num_heads, false));
+    p.attn_bwd = attention_route(attention_problem(AP_BWD, m->precision, B, p.T, H, c.num_heads, false));
     // the bf16 attention kernels (forward and backward) read q | k | v only as bf16: the projection then writes just that shadow
-    p.attn16 = p.sh && attention_bf16_supported(H / c.num_heads);
-    // ... and they save lse2 = -(m C2 + log2 l) where the fp32 kernels save the natural lse (launch_attention_train_x picks by the mode)
-    p.lse_log2 = m->precision == 1 && attention_bf16_supported(H / c.num_heads);
+    p.attn16 = p.sh && p.attn.family == AF_BF16;
+    // ... and they save lse2 = -(m C2 + log2 l) where the fp32 kernels save the natural lse
+    p.lse_log2 = p.attn.lse_log2;
     // FFN hidden activation dropout(GELU(u)) as bf16 only: needs the shadow paths on both sides (forward GEMM by LDS-DMA, weight gradient
     // in the transposing-read form, whole 128-tiles) and the plain bf16 copies of the FFN kernels for the data gradients
     p.ffn16_only = p.sh && m->w16_valid && F % 128 == 0 && H % 128 == 0 && (p.BT * F) % 4 == 0 && !m->w16p.empty();
@@ -366,8 +369,10 @@ static int ensure_train_ws(w2v2_model* m, const TrainPlan& plan, int64_t L) {
             l.t2_16 = l.ctx16 + up8(BT * H);
             l.gd16 = l.t2_16 + up8(BT * H);
             l.qkv16 = l.gd16 + up8(BT * F);          // q | k | v as the bf16 attention kernels read it
+            // (the keep bits and, below, the column partials of the bf16 kernels: allocated wherever those kernels exist for the head size,
+            // in every mode -- a step in another mode on the same shapes reuses this workspace)
             float* kb = nullptr;
-            if (attention_bf16_supported((int)(H / c.num_heads))) {
+            if (plan.attn.dh == ATTN_BF16_DH) {
                 if (int e = t_alloc(t, &kb, attention_keep_bits_words(B, T, c.num_heads))) return e;
             }
             l.keep_bits = reinterpret_cast<uint32_t*>(kb);
@@ -388,7 +393,7 @@ static int ensure_train_ws(w2v2_model* m, const TrainPlan& plan, int64_t L) {
     t->red_ws_floats = rw + 16;
     if (int e = t_alloc(t, &t->dvec, (int64_t)B * c.num_heads * T)) return e;
     t->attn_colpart = nullptr;
-    if (attention_bf16_supported((int)(H / c.num_heads)))
+    if (plan.attn.dh == ATTN_BF16_DH)
         if (int e = t_alloc(t, &t->attn_colpart, (int64_t)attention_colpart_rows(B, T) * 3 * H)) return e;
     {
         // (BT + 1, H) + (BT + 1, F) + (BT + 1, 3H) + (BT, H) bf16, each 16-byte aligned.  Row BT of the first three is never written
@@ -766,9 +771,10 @@ int w2v2_train_forward(w2v2_model* m, const float* wave, int32_t B, int64_t L, c
                          nullptr, (int)BT, 3 * H, H, 1, 0))
             return e;
         AttnTrain tr{p, seed, layer_stream(i, 0), l.lse, attn16 ? l.keep_bits : nullptr};
-        if (int e = launch_attention_train_x(pf, attn16 ? nullptr : l.qkv, attn16 ? l.qkv16 : nullptr, flen, ctx16_only ? nullptr : l.ctx, attn16 ? l.ctx16 : nullptr, B, T,
-                                             H, c.num_heads, tr, s))
-            return e;
+        AttnIO aio;
+        aio.qkv = attn16 ? nullptr : l.qkv; aio.qkv16 = attn16 ? l.qkv16 : nullptr; aio.frame_len = flen;
+        aio.ctx = ctx16_only ? nullptr : l.ctx; aio.ctx16 = attn16 ? l.ctx16 : nullptr; aio.train = &tr;
+        if (int e = launch_attention_train_routed(pf, plan.attn, aio, s)) return e;
         // o = ctx Wo + bo;  t1 = dropout(o) + x   (encoder.py:116-119)
         // (dropout + residual as their own pass: folded into this GEMM's epilogue they were measured slower, study section 12 / r03)
         if (int e = gemm(ctx16_only ? nullptr : l.ctx, attn16 ? l.ctx16 : nullptr, H, 0, m->P(b + "/attention/out_proj/kernel"), H, m->t0, nullptr, H, 0,
@@ -1110,10 +1116,12 @@ int BwdCtx::attn_branch_bwd(int i, LayerSave& l, const std::string& b, const flo
     if (side_on)
         if (int e = side(2, out_weight_grad)) return e;
     if (int e = side_wait(3)) return e;                  // (dqkv / its shadow / the column partials: the layer above's q|k|v weight gradient)
-    if (int e = launch_attention_bwd(m->prof, plan.attn16 ? nullptr : l.qkv, flen, c16 ? nullptr : l.ctx, c16 ? nullptr : dctx, q16 ? nullptr : t->g3h, t->dvec,
-                                     B, T, H, m->cfg.num_heads, tr, s, s16q, plan.attn16 ? l.qkv16 : nullptr, dctx16, q16 ? t->attn_colpart : nullptr,
-                                     c16 ? l.ctx16 : nullptr))
-        return e;
+    AttnIO aio;
+    aio.qkv = plan.attn16 ? nullptr : l.qkv; aio.qkv16 = plan.attn16 ? l.qkv16 : nullptr; aio.frame_len = flen; aio.train = &tr;
+    aio.ctx = c16 ? nullptr : l.ctx; aio.ctx16 = c16 ? l.ctx16 : nullptr;
+    aio.dctx = c16 ? nullptr : dctx; aio.dctx16 = dctx16;
+    aio.dqkv = q16 ? nullptr : t->g3h; aio.dqkv16 = s16q; aio.dvec_ws = t->dvec; aio.colpart = q16 ? t->attn_colpart : nullptr;
+    if (int e = launch_attention_bwd_routed(m->prof, plan.attn_bwd, aio, s)) return e;
     // (one stream: the out-projection's weight gradient runs here, not before its data gradient: the attention backward has just read O, so
     //  the GEMM finds it in the Infinity Cache instead of streaming it from HBM cold; d_o / its shadow are untouched until below)
     if (!side_on)
@@ -1380,7 +1388,7 @@ int w2v2_train_backward(w2v2_model* m, const float* dlogits, void* stream) {
     const int H = c.hidden_size, F = c.intermediate_size;
     const int64_t BT = plan.BT;
     BwdCtx x{m, t, plan, s, plan.B, plan.T, H, F, BT, c.layer_norm_eps, t->p, t->seed, t->have_mask ? m->frame_len : nullptr, shb,
-             shb ? t->dy16_h : nullptr, shb ? t->dy16_f : nullptr, (shb && attention_bf16_supported(H / c.num_heads)) ? t->dy16_3h : nullptr,
+             shb ? t->dy16_h : nullptr, shb ? t->dy16_f : nullptr, (shb && plan.attn_bwd.family == AF_BF16) ? t->dy16_3h : nullptr,
              t->gh[0], t->gh[1], t->gh[2], t->gh[3]};
     if (shb && BT % 64 != 0) {
         // Ragged row count: the weight-gradient GEMMs read the missing rows of their last K tile from the zero row behind each dY

@@ -915,6 +915,23 @@ int w2v2_op_gemm_bf16_route(const int64_t* problem, int32_t* out);
 /* Launches by this process so far per kernel of that list (host memory): counts[12], counts[k] for kernel k, counts[0] unused.
  * Diagnostic only (one relaxed atomic add per launch), the twin of w2v2_op_gemm_ring_launches. */
 int w2v2_op_gemm_bf16_launches(int64_t* counts);
+/* Which kernel an attention call (w2v2_op_attention, _packed, _packed_bf16, _train, _bwd, and the attention of every model forward
+ * and training step) would launch (csrc/attention_route.h).  Host only: touches no device and launches nothing.  problem[12], in
+ * order: pass (0 inference forward, 1 training forward, 2 backward), precision (W2V2_PRECISION_*), B, T, H, heads, packed,
+ * split_allowed (1 outside the tools-only build), io_aligned (q | k | v and ctx on 16-byte boundaries), then the output forms wanted:
+ * fp32, bf16 shadow, planes.
+ *   out[0] kernel (0 when refused): 1-3 fp32 head size 32 with 4 / 8 / 12 waves, 4-6 head size 64, 7-8 head size 128 with 4 / 8,
+ *          9-11 fp32 packed head size 32 / 64 / 128, 12 fp32 training head size 32, 13-14 head size 64 with 4 / 12 waves, 15-16 fp32
+ *          backward head size 32 / 64, 17-18 split bf16x3 / f16x2, 19-20 their packed forms, 21 bf16, 22 bf16 packed, 23 bf16
+ *          training, 24 bf16 backward;
+ *   out[1] != 0: the call is refused (1 head size, 2 a bf16 shadow wanted outside the bf16 family, 3 planes wanted outside the split
+ *          family); out[2] family (1 fp32, 2 split, 3 bf16); out[3] plane format of the split family (0 bf16x3, 1 f16x2, else -1);
+ *   out[4] head size; out[5] waves per block; out[6] queries per block (the height of a packed tile); out[7] the training forward
+ *          saves the base-2 lse; out[8], out[9] the family can write a bf16 shadow / planes. */
+int w2v2_op_attention_route(const int32_t* problem, int32_t* out);
+/* Launches by this process so far per kernel of that list (host memory): counts[25], counts[k] for kernel k, counts[0] unused.  One
+ * count per call of a pass (the backward's three kernels count once).  Diagnostic only, as w2v2_op_gemm_bf16_launches. */
+int w2v2_op_attention_launches(int64_t* counts);
 
 /* The weight-gradient form of the same GEMM: C_z (M, N) = A_z^T B_z with A given TRANSPOSED, (K, M) fp32 row-major with
  * row stride lda (>= M), and per-batch strides on A, B and C (split-K: batch z covers rows [z K, (z+1) K) of both
