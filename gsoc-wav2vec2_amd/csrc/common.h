@@ -417,7 +417,7 @@ int launch_pack_zero_gaps(float* x, const PlaneOut* pl, int64_t frames, int widt
 // grow-only device scratch per (purpose, stream), owned by the library (shadow.hip)
 enum ScratchSlot { SCRATCH_SPLITK = 0, SCRATCH_CTC = 1, SCRATCH_QKV16 = 2, SCRATCH_DCTX16 = 3, SCRATCH_ALIGN = 4, SCRATCH_BEAM = 5, SCRATCH_WINDOWS = 6,
                    SCRATCH_CUTS = 7, SCRATCH_RESAMPLE = 8, SCRATCH_EDIT = 9, SCRATCH_ALIGN_LONG = 10, SCRATCH_SCORE = 11, SCRATCH_SPOT = 12, SCRATCH_SCORE_GRAD = 13,
-                   SCRATCH_SCORE_STAR = 14, SCRATCH_SCORE_GRAD_STAR = 15, SCRATCH_POS_PACKED = 16, SCRATCH_SLOTS = 17 };
+                   SCRATCH_SCORE_STAR = 14, SCRATCH_SCORE_GRAD_STAR = 15, SCRATCH_POS_PACKED = 16, SCRATCH_AUGMENT = 17, SCRATCH_SLOTS = 18 };
 int stream_scratch(int slot, hipStream_t s, size_t bytes, void** out);
 int stream_scratch_release();       // frees the calling device's scratch buffers and staged-upload buffers
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }      // the parts of a workspace begin at multiples of 256 bytes
@@ -569,6 +569,13 @@ int launch_resample(const float* in, int n, const int64_t* in0, const int64_t* i
 int resample_design(int rate_in, int rate_out, int zeros, double rolloff, double beta, int32_t* L, int32_t* M, int32_t* K, int32_t* lead,
                     float* table, int64_t table_capacity);
 int64_t resample_length(int64_t len, int L, int M);
+// waveform augmentation (augment.hip; w2v2_fir, w2v2_mix): segment i = in[in0_i, in0_i + len_i) convolved with its own taps, or with a
+// wrapped stretch of noise added at a gain from the two powers, to out[out0_i, + len_i); gain (n floats) may be null
+int launch_fir(const float* in, int n, const int64_t* in0, const int64_t* len, const float* taps, const int64_t* taps0, const int32_t* ntaps,
+               const int32_t* delay, float* out, const int64_t* out0, int match_power, float* gain, hipStream_t s);
+int launch_mix(const float* in, int n, const int64_t* in0, const int64_t* len, const float* noise, const int64_t* noise0,
+               const int64_t* noise_len, const int64_t* offset, const double* scale, float* out, const int64_t* out0, float* gain,
+               hipStream_t s);
 // edit distance and its breakdown (edit.hip; w2v2_edit_distance): pair p = tokens[hyp0_p, + hyp_len_p) against tokens[ref0_p, + ref_len_p);
 // out (n_pairs, 4) = distance, substitutions, deletions, insertions
 int launch_edit_distance(const int32_t* tokens, int64_t n_tokens, int n_pairs, const int64_t* hyp0, const int32_t* hyp_len,

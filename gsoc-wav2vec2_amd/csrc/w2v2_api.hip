@@ -673,6 +673,16 @@ int w2v2_resample(const float* in, int32_t n, const int64_t* in0, const int64_t*
     return launch_resample(in, n, in0, in_len, filter_of, filters, n_filters, out, out0, reinterpret_cast<hipStream_t>(stream));
 }
 
+int w2v2_fir(const float* in, int32_t n, const int64_t* in0, const int64_t* len, const float* taps, const int64_t* taps0, const int32_t* ntaps,
+             const int32_t* delay, float* out, const int64_t* out0, int32_t match_power, float* gain, void* stream) {
+    return launch_fir(in, n, in0, len, taps, taps0, ntaps, delay, out, out0, match_power, gain, reinterpret_cast<hipStream_t>(stream));
+}
+
+int w2v2_mix(const float* in, int32_t n, const int64_t* in0, const int64_t* len, const float* noise, const int64_t* noise0,
+             const int64_t* noise_len, const int64_t* offset, const double* scale, float* out, const int64_t* out0, float* gain, void* stream) {
+    return launch_mix(in, n, in0, len, noise, noise0, noise_len, offset, scale, out, out0, gain, reinterpret_cast<hipStream_t>(stream));
+}
+
 int w2v2_activation_info(const w2v2_model* m, const char* name, int64_t shape[3]) {
     W2V2_REQUIRE(m && name && shape, "activation_info: null argument");
     auto it = m->acts.find(name);

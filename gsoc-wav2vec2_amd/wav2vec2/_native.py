@@ -24,6 +24,9 @@ CUTS_MAX_FRAMES = 1 << 24        # W2V2_CUTS_MAX_FRAMES
 RESAMPLE_TILE = 2048             # W2V2_RESAMPLE_TILE: outputs per block of w2v2_resample
 RESAMPLE_MAX_L = 4096            # W2V2_RESAMPLE_MAX_L, W2V2_RESAMPLE_MAX_TABLE: limits of a filter of w2v2_resample
 RESAMPLE_MAX_TABLE = 1 << 22
+FIR_MAX_TAPS = 65536             # W2V2_FIR_MAX_TAPS: taps per filter of w2v2_fir
+FIR_TILE = 8192                  # W2V2_FIR_TILE, W2V2_FIR_CHUNK: outputs per block of w2v2_fir, and the taps it walks between two stagings
+FIR_CHUNK = 2048
 EDIT_MAX_LEN = 65535             # W2V2_EDIT_MAX_LEN: tokens per sequence of w2v2_edit_distance
 WORDLM_MAX_ORDER = 5             # W2V2_WORDLM_MAX_ORDER: order of the word n-gram model of w2v2_ctc_beam_search_words
 BIAS_MAX_STATES = 1 << 20        # W2V2_BIAS_MAX_STATES: states of the phrase bias of w2v2_ctc_beam_search_biased
@@ -125,6 +128,8 @@ PROTOTYPES = {
                                        C.POINTER(_I32), _P, _I64]),
     "w2v2_resample_length": (_I64, [_I64, _I32, _I32]),
     "w2v2_resample": (C.c_int, [_P, _I32, _P, _P, _P, C.POINTER(W2V2ResampleFilter), _I32, _P, _P, _P]),
+    "w2v2_fir": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P]),
+    "w2v2_mix": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "w2v2_set_trainable": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "w2v2_set_trainable_flags": (C.c_int, [_P, _P, _I32]),
     "w2v2_set_option": (C.c_int, [_P, _I32, _I32]),

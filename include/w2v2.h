@@ -561,7 +561,7 @@ int w2v2_ctc_pause_cuts(const float* logits_dev, int32_t V, int32_t n, const int
                         int32_t blank, int32_t delim, float margin, int32_t min_pause, int32_t max_cuts, int32_t* cut_dev,
                         int32_t* pause_dev, int32_t* count_dev, void* stream);
 
-/* Edit distance with its breakdown (DESIGN.md §16, exact definition in csrc/edit.hip and, in plain Python,
+/* Edit distance with its breakdown (DESIGN.md §27, exact definition in csrc/edit.hip and, in plain Python,
  * tests/edit_reference.py): what a word or character error rate is made of.  Model-free: many pairs per call, addressed by host
  * tables into ONE token buffer, each pair computed as if it were alone.
  *   pair p: the hypothesis tokens_dev[hyp0_host[p] .. + hyp_len_host[p]) (length m) against the reference
@@ -622,6 +622,40 @@ typedef struct w2v2_resample_filter {
 } w2v2_resample_filter;
 int w2v2_resample(const float* in_dev, int32_t n, const int64_t* in0_host, const int64_t* in_len_host, const int32_t* filter_of_host,
                   const w2v2_resample_filter* filters, int32_t n_filters, float* out_dev, const int64_t* out0_host, void* stream);
+
+/* Waveform augmentation for fine-tuning (the same definitions in numpy: tests/augment_reference.py): reverberation
+ * and additive noise.  Model-free like w2v2_resample: many segments per call, addressed by host tables, each computed as if it were
+ * alone; enqueued on `stream` (the host tables are uploaded as there); launches are attributed to the `misc` profiling family;
+ * ranges that overlap each other or an input are the caller's error and are not detected.  Inputs are assumed finite: what a NaN or
+ * Inf does within its own segment is unspecified, and it never reaches another segment.
+ *
+ * w2v2_fir.  Segment i is x = in_dev[in0_host[i] .. + len_host[i]), zero outside, its filter h = taps_dev[taps0_host[i] .. +
+ * ntaps_host[i]), K = ntaps_host[i], d = delay_host[i] in [0, K); it writes out_dev[out0_host[i] .. + len_host[i]):
+ *     y[n] = sum_{k < K} h[k] x[n + d - k]        for n in [0, len)
+ * as ONE fp32 chain in ascending k from +0.0f, one fmaf per tap, zero pads included.  The bits of y[n] depend on the segment's
+ * samples, its taps, d and n alone -- not on the other segments, on where the segment lies in the buffers, or on the tiling: a block
+ * computes W2V2_FIR_TILE consecutive outputs counted from the segment's first sample and walks k in chunks of W2V2_FIR_CHUNK
+ * (csrc/augment.hip).  With match_power != 0, Px = sum x^2 and Py = sum y^2 over the segment in fp64 (chunks of 4096 samples from the
+ * segment's start; within a chunk 256 strided sums folded by a tree; the chunks folded the same way), g = (float)sqrt(Px / Py), g = 1
+ * when either sum is 0, and out = g * y, one fp32 multiply per sample.  Otherwise out = y and g = 1.  gain_dev (n floats, or NULL)
+ * receives g.
+ *
+ * w2v2_mix.  Segment i as above; v[n] = noise_dev[noise0_host[i] + (offset_host[i] + n) mod noise_len_host[i]].  Px = sum x^2 and
+ * Pv = sum v^2 over the len samples read, as above; g = (float)(sqrt(Px / Pv) * scale_host[i]), g = 0 when either sum is 0;
+ * out[n] = fmaf(g, v[n], x[n]), and x[n]'s own bits where g == 0.  scale = 10^(-snr_db / 20) gives that signal-to-noise ratio.
+ *
+ * W2V2_EINVAL with a message: a null pointer (gain_dev excepted), n < 1, a length (or noise length) outside [1, 2^31), ntaps outside
+ * [1, W2V2_FIR_MAX_TAPS], a delay outside [0, ntaps), an offset outside [0, noise_len), a scale that is negative or not finite, a
+ * negative in0 / taps0 / noise0 / out0. */
+#define W2V2_FIR_MAX_TAPS 65536
+#define W2V2_FIR_TILE 8192
+#define W2V2_FIR_CHUNK 2048
+int w2v2_fir(const float* in_dev, int32_t n, const int64_t* in0_host, const int64_t* len_host, const float* taps_dev,
+             const int64_t* taps0_host, const int32_t* ntaps_host, const int32_t* delay_host, float* out_dev, const int64_t* out0_host,
+             int32_t match_power, float* gain_dev, void* stream);
+int w2v2_mix(const float* in_dev, int32_t n, const int64_t* in0_host, const int64_t* len_host, const float* noise_dev,
+             const int64_t* noise0_host, const int64_t* noise_len_host, const int64_t* offset_host, const double* scale_host,
+             float* out_dev, const int64_t* out0_host, float* gain_dev, void* stream);
 
 /* ---- the training step (reference src/main.py:136-259) --------
  * Replaces what Keras' train_step does around the forward: training-mode forward, backward of every
