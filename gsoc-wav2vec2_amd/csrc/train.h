@@ -3,6 +3,7 @@
 #pragma once
 
 #include "common.h"
+#include "weight_grad_plan.h"
 
 namespace w2v2 {
 
@@ -251,6 +252,23 @@ int launch_spec_aug_fwd(const float* x, const uint8_t* mask, const float* embed,
 int launch_spec_aug_bwd(const float* dy, const uint8_t* mask, float* dx, float* dmasked, int64_t rows, int H, hipStream_t s);
 // dst (Kin, Nout) = A16[R rows]^T B16[R rows], bf16 operands, fp32 accumulate: the leftover rows of a weight gradient
 int launch_dw_tail_bf16(const uint16_t* A16, int64_t lda, const uint16_t* B16, int64_t ldb, float* dst, int R, int Kin, int Nout, hipStream_t s);
+// where a weight gradient puts its split-K slabs and who folds them
+struct WgSite {
+    float* slabs = nullptr;           // own slab scratch (TrainState::site_slabs[k]); null: the shared TrainState::slabs
+    int64_t slab_floats = 0;          // its size
+    FoldBatch* defer = nullptr;       // the slab fold joins this batch instead of running behind the GEMM
+    float* unpack3[3] = {nullptr, nullptr, nullptr};      // q|k|v: the fold writes the three (H, H) kernels straight from the packed (H, 3H) slabs
+    int unpackH = 0;
+};
+// every byte of scratch a weight gradient touches: the slabs (+ the fold's partial scratch behind them), the transposed copy of A
+// ((Kin, M) floats, the fp32 forms), the per-slab column sums of dY, the reduction scratch of the column-sum passes
+struct WgScratch {
+    float *slabs, *at, *cs_ws, *red_ws;
+};
+void weight_grad_knobs(int* dw_blocks, int* dw_uneven);      // W2V2_DW_BLOCKS, W2V2_DW_UNEVEN (tools/knob_sweep.sh): their one reader
+// executes weight_grad_plan(q) (weight_grad_plan.h); w2v2_train.hip
+int launch_weight_grad(Profiler* prof, const WgProblem& q, const WgPlan& p, const float* A, const float* dY, const uint16_t* A16, const uint16_t* dY16,
+                       float* dW, float* db, const WgScratch& w, const WgSite* site, hipStream_t s);
 int launch_axpby(const float* a, const float* b, float* y, int64_t n, float alpha, float beta, hipStream_t s);
 int launch_axpby_x(const float* a, const float* b, float* y, uint16_t* y16 /* optional bf16 shadow */, int64_t n, float alpha, float beta,
                    hipStream_t s);

@@ -843,6 +843,38 @@ int w2v2_op_gemm_bf16_route(const int64_t* q, int32_t* out) {
     for (int i = 0; i < 5; ++i) out[i] = v[i];
     return W2V2_OK;
 }
+static WgProblem wg_problem(const int64_t* q) {
+    return WgProblem{(int)q[0], (int)q[1], (int)q[2], (int)q[3], q[4] != 0, q[5] != 0, q[6] != 0, q[7] != 0, q[8] != 0, q[9] != 0, q[10] != 0, q[11] != 0,
+                     q[12], q[13], q[14], (int)q[15], (int)q[16]};
+}
+int w2v2_op_weight_grad_plan(const int64_t* q, int64_t* out) {
+    W2V2_REQUIRE(q && out && q[0] > 0 && q[1] > 0 && q[2] > 0 && q[0] <= INT32_MAX && q[1] <= INT32_MAX && q[2] <= INT32_MAX && q[12] >= 0 && q[13] >= 0 &&
+                     q[14] >= 0 && q[15] > 0,
+                 "op_weight_grad_plan: bad argument");
+    const WgPlan p = weight_grad_plan(wg_problem(q));
+    const int64_t v[18] = {p.refusal, p.form, p.kernel, p.kq, p.cap, p.S, p.Kp, p.kextra, p.validK, p.b_zero_row, p.Mq, p.R, p.tail, p.nslabs, p.dst, p.fold,
+                           p.bias, wg_max_slabs(q[1], q[2])};
+    for (int i = 0; i < 18; ++i) out[i] = v[i];
+    return W2V2_OK;
+}
+int w2v2_op_weight_grad(const int64_t* problem, const float* A, const float* dY, const uint16_t* A16, const uint16_t* dY16, float* dW, float* db,
+                        float* slabs, float* at, int64_t at_floats, float* cs_ws, float* red_ws, int64_t red_ws_floats, void* stream) {
+    int64_t unused[18];
+    if (int e = w2v2_op_weight_grad_plan(problem, unused)) return e;
+    const WgProblem q = wg_problem(problem);
+    W2V2_REQUIRE(q.precision == gemm_get_precision(), "op_weight_grad: the problem says precision %d, w2v2_op_set_precision set %d", q.precision, gemm_get_precision());
+    W2V2_REQUIRE(q.A == (A != nullptr) && q.dY == (dY != nullptr) && q.A16 == (A16 != nullptr) && q.dY16 == (dY16 != nullptr) && q.want_dW == (dW != nullptr) &&
+                     q.want_db == (db != nullptr) && !q.unpack,
+                 "op_weight_grad: the problem's operand flags disagree with the pointers (and the unpacking fold is the training step's)");
+    const WgPlan p = weight_grad_plan(q);
+    W2V2_REQUIRE(p.refusal == WGR_NONE, "%s", weight_grad_refusal_text(p.refusal));
+    W2V2_REQUIRE(p.dst != WG_TO_SLABS || slabs, "op_weight_grad: this plan writes slabs");
+    const bool copies = p.form == WG_DIV_F32_COPY || p.tail == WG_TAIL_COPY;
+    W2V2_REQUIRE(!copies || (at && at_floats >= (int64_t)q.Kin * q.M), "op_weight_grad: this plan needs Kin M floats for the transposed copy");
+    W2V2_REQUIRE(p.bias != WG_BIAS_FUSED || cs_ws, "op_weight_grad: this plan writes per-slab column sums");
+    W2V2_REQUIRE(p.bias == WG_BIAS_NONE || (red_ws && red_ws_floats >= colsum_ws_floats(q.M, q.Nout)), "op_weight_grad: reduction scratch too small");
+    return launch_weight_grad(nullptr, q, p, A, dY, A16, dY16, dW, db, WgScratch{slabs, at, cs_ws, red_ws}, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
 int w2v2_op_gemm_bf16_launches(int64_t* counts) {
     W2V2_REQUIRE(counts, "op_gemm_bf16_launches: null argument");
     gemm_bf16_launches(counts);
@@ -924,16 +956,16 @@ int w2v2_op_weight_grad_bf16(const uint16_t* x16, const uint16_t* dy16, float* s
     // gives the first e slabs one K tile more (GemmShadows::kextra -- how the training step cuts B T rows into any number of slabs).
     // variant 3 additionally promises that row `rows` of dy16 exists and is all-zero, which lets the last K tile be short.
     const bool sw = variant == 2 || variant == 3;
-    const int64_t units = (rows + 63) / 64, over_units = units - (int64_t)(rows_per_slab / 64) * nslabs;
-    const bool shape_ok = sw && over_units >= 0 && over_units < nslabs && (rows % 64 == 0 || variant == 3) && (over_units == 0 || nslabs > 1);
+    const WgUneven u = wg_uneven_slabs(rows, nslabs);
+    const bool shape_ok = sw && u.Kp == rows_per_slab && (u.validK == 0 || variant == 3);
     W2V2_REQUIRE(!sw || (shape_ok && gemm_bf16_swtr_ok(Kin, Nout, rows_per_slab, Kin, Nout, (int64_t)rows_per_slab * Kin, (int64_t)rows_per_slab * Nout)),
                  "op_weight_grad_bf16: variants 2 / 3 need whole 64-row K tiles (variant 3: a zero row behind dy16 instead), at most one extra K tile "
                  "per slab, Nout %% 256 == 0 and at least 192 rows per slab");
     GemmShadows x;
     x.transA = true; x.A16 = x16; x.B16p = dy16; x.force_kernel = sw ? 2 : variant;
     if (sw) {
-        x.kextra = (int)over_units;
-        x.validK = rows % 64 == 0 ? 0 : rows;
+        x.kextra = u.kextra;
+        x.validK = u.validK;
         x.b_zero_row = variant == 3;
     } else {
         x.validK = rows == (int64_t)rows_per_slab * nslabs ? 0 : rows;

@@ -102,29 +102,12 @@ struct TrainState {
     float* red_ws_side = nullptr;     // the side stream's own reduction scratch (red_ws belongs to the main stream's kernels)
     // Deferred folds (train.h: FoldBatch): the partial rows of a layer's gradients live until the layer's one fold launch, so each
     // deferred producer has its own scratch -- split-K slabs of the four weight gradients (0 = FFN down, 1 = FFN up, 2 = out-projection,
-    // 3 = q|k|v; site_slab_count + 1 slabs of the kernel's size each: ensure_site_scratch) and the per-block column sums of LayerNorm 2 / the FFN
+    // 3 = q|k|v; wg_max_slabs + 1 slabs of the kernel's size each: ensure_site_scratch) and the per-block column sums of LayerNorm 2 / the FFN
     // dropout backward / LayerNorm 1 (site_ws).  The attention backward's column partials already have theirs (attn_colpart).
     float* site_slabs[4] = {nullptr, nullptr, nullptr, nullptr};
     int64_t site_slab_floats[4] = {0, 0, 0, 0};
     float* site_ws[3] = {nullptr, nullptr, nullptr};
     int64_t red_ws_floats = 0;        // size of red_ws (and of each of red_ws_side / site_ws[k] once they exist)
-};
-
-// Slabs a weight gradient of `elems` = Kin x Nout elements can be cut into: weight_grad's rule is tiles x S <= 512 blocks for the bf16
-// kernels (tiles of at most 128 x 256) and <= 2048 for the fp32 one (128 x 128), S <= 32 -- plus one slab of fold scratch.  (Round 5
-// allocated 33 slabs for every site whatever its shape: 0.93 GB for base, 1.66 GB for large, where this rule gives 0.50 / 0.59 GB.)
-static int64_t site_slab_count(int64_t elems) {
-    const int64_t s = ((int64_t)2048 * 16384 + elems - 1) / elems;
-    return (s < 32 ? s : 32) + 1;
-}
-
-// where a weight gradient puts its split-K slabs and who folds them
-struct WgSite {
-    float* slabs = nullptr;           // own slab scratch (TrainState::site_slabs[k]); null: the shared TrainState::slabs
-    int64_t slab_floats = 0;          // its size
-    FoldBatch* defer = nullptr;       // the slab fold joins this batch instead of running behind the GEMM
-    float* unpack3[3] = {nullptr, nullptr, nullptr};      // q|k|v: the fold writes the three (H, H) kernels straight from the packed (H, 3H) slabs
-    int unpackH = 0;
 };
 
 static int t_alloc(TrainState* t, float** out, int64_t floats) {
@@ -218,10 +201,10 @@ static int ensure_persistent(w2v2_model* m) {
             if (int e = p_alloc(t, &l.W2T, H * F)) return e;
             l.keep = 1.f;
         }
-        t->slab_floats = 33 * (F * H > 3 * H * H ? F * H : 3 * H * H);      // 32 split-K slabs + the reduction scratch
+        t->slab_floats = WG_MAX_SLABS * (F * H > 3 * H * H ? F * H : 3 * H * H);      // 32 split-K slabs + the reduction scratch
         if (int e = p_alloc(t, &t->slabs, t->slab_floats)) return e;
         // (the per-site slab scratches of the deferred folds are allocated by the first backward that defers: ensure_site_scratch)
-        t->cs_floats = 34 * (F > 3 * H ? F : 3 * H);
+        t->cs_floats = (WG_MAX_SLABS + 1) * (F > 3 * H ? F : 3 * H);
         if (int e = p_alloc(t, &t->cs_ws, t->cs_floats)) return e;
         if (int e = p_alloc(t, &t->dwqkv, 3 * H * H + 3 * H)) return e;
         if (int e = p_alloc(t, &t->dummy, 2 * (H + C + F))) return e;       // sink for gradients of frozen LN params
@@ -242,10 +225,10 @@ static int ensure_site_scratch(w2v2_model* m, bool side, bool defer_cols, bool d
             if (int e = t_alloc(t, &t->site_ws[k], t->red_ws_floats)) return e;
     if (defer_slabs && !t->site_slabs[0]) {
         const int64_t H = m->cfg.hidden_size, F = m->cfg.intermediate_size;
-        const int64_t site_elems[4] = {F * H, H * F, H * H, 3 * H * H};
+        const int64_t site_dims[4][2] = {{F, H}, {H, F}, {H, H}, {H, 3 * H}};
         for (int k = 0; k < 4; ++k) {
-            // (+ 1: S slabs, a leftover-row slab and the fold's partial scratch behind them -- weight_grad's `nslabs + 1` -- always fit)
-            t->site_slab_floats[k] = (site_slab_count(site_elems[k]) + 1) * site_elems[k];
+            // (+ 1: the fold's partial scratch behind the slabs -- the plan's `nslabs + 1`)
+            t->site_slab_floats[k] = (wg_max_slabs(site_dims[k][0], site_dims[k][1]) + 1) * site_dims[k][0] * site_dims[k][1];
             if (int e = p_alloc(t, &t->site_slabs[k], t->site_slab_floats[k])) return e;
         }
     }
@@ -468,166 +451,99 @@ static bool is_trainable(w2v2_model* m, const std::string& name) {
     return it != m->index.end() && m->train->trainable[it->second];
 }
 
-// dW (Kin x Nout) = A^T (Kin x M) dY (M x Nout), db = column sums of dY.  A is (M x Kin) row-major.
-// A16 / dY16: bf16 shadows of A and dY (row-major, same shapes) or null: with both, the fast slabs read half the bytes
-// dy16_zero_row: the caller keeps row M of dY16 all-zero (TrainState's dY shadows are allocated that way) -- a row count that is not a
-// multiple of 64 can then take the 128 x 256 kernel's ragged form instead of the 128 x 128 kernel
-static int weight_grad(w2v2_model* m, const float* A, const float* dY, int M, int Kin, int Nout, float* dW,
-                       float* db, hipStream_t s, const uint16_t* A16 = nullptr, const uint16_t* dY16 = nullptr, bool dy16_zero_row = false,
-                       float* red_ws = nullptr, const WgSite* site = nullptr) {
-    TrainState* t = m->train;
-    if (!red_ws) red_ws = t->red_ws;       // (the side stream passes its own: TrainState::red_ws_side)
-    bool fused_bias = false;
-    // slab scratch: the shared one, or this site's own (S <= 32 slabs, a leftover-row slab and the fold's partial scratch behind them).
-    // The slab-count rule below keeps using TrainState::slab_floats either way, so S does not depend on the site.
-    float* const slabs = (site && site->slabs) ? site->slabs : t->slabs;
-    const int64_t slab_cap = (site && site->slabs) ? site->slab_floats : t->slab_floats;      // floats behind `slabs`: what the capacity checks look at
-    FoldBatch* const defer = (site && site->slabs) ? site->defer : nullptr;
-    const bool unpack = site && site->unpackH > 0;
-    // dW = sum of `nrows` slabs: behind the GEMM, or as a job of the layer's fold launch.  (`unpack`: even a single slab goes through the
-    // fold, which scatters the packed matrix into the three kernels)
-    auto fold_slabs = [&](int nrows) -> int {
-        if (defer && (unpack ? defer->add_tall(slabs, nrows, (int64_t)Kin * Nout, site->unpack3[0], site->unpackH, site->unpack3[1], site->unpack3[2])
-                             : defer->add_tall(slabs, nrows, (int64_t)Kin * Nout, dW)))
-            return W2V2_OK;
-        if (unpack) {           // behind the GEMM, but still one launch for the sum and the scatter into the three kernels
-            FoldBatch one;
-            W2V2_REQUIRE(one.add_tall(slabs, nrows, (int64_t)Kin * Nout, site->unpack3[0], site->unpackH, site->unpack3[1], site->unpack3[2]),
-                         "weight_grad: the unpacking fold does not fit this shape");
-            return one.flush(s);
-        }
-        // (the one-chunk partial scratch lives behind the slabs: every caller has checked that nrows + 1 slabs fit `slab_cap`)
-        return launch_colsum(slabs, dW, nrows, Kin * Nout, slabs + (int64_t)nrows * Kin * Nout, 0, s);
+// Runs a plan of weight_grad_plan.h: dW (Kin x Nout) = A^T (Kin x M) dY (M x Nout), db = column sums of dY, A (M x Kin) row-major,
+// A16 / dY16 the bf16 shadows of A and dY (same shapes) or null.  `w` is every byte of scratch it touches; `site` says who folds.
+namespace w2v2 {
+void weight_grad_knobs(int* dw_blocks, int* dw_uneven) {
+    *dw_blocks = tune_int("W2V2_DW_BLOCKS", WG_BLOCKS_BF16);
+    *dw_uneven = tune_int("W2V2_DW_UNEVEN", 1);
+}
+
+int launch_weight_grad(Profiler* prof, const WgProblem& q, const WgPlan& p, const float* A, const float* dY, const uint16_t* A16, const uint16_t* dY16,
+                       float* dW, float* db, const WgScratch& w, const WgSite* site, hipStream_t s) {
+    W2V2_REQUIRE(p.refusal == WGR_NONE, "%s", weight_grad_refusal_text(p.refusal));
+    const int M = q.M, Kin = q.Kin, Nout = q.Nout, S = p.S, Kp = p.Kp, Mq = p.Mq, R = p.R;
+    const int64_t elems = (int64_t)Kin * Nout;
+    float* const dst = p.dst == WG_TO_SLABS ? w.slabs : dW;
+    float* const tail_dst = dst + (int64_t)S * elems;      // slab S: the leftover rows [Mq, M)
+    // S slabs of Kp rows on the bf16 kernel the plan names, A transposed on its way in
+    auto slabs_bf16 = [&](const GemmShadows& x) -> int {
+        return launch_gemm_bf16_x(prof, A, Kin, (int64_t)Kp * Kin, dY, Nout, (int64_t)Kp * Nout, dst, Nout, elems, nullptr, nullptr, Kin, Nout, Kp, S, 0, x, s);
     };
-    // db = column sums of the fp32 dY, where no GEMM took them along
-    auto bias_colsum = [&]() -> int {
-        if (!db) return W2V2_OK;
-        W2V2_REQUIRE(dY, "weight_grad: the bias gradient needs the fp32 dY");
-        return launch_colsum(dY, db, M, Nout, red_ws, 0, s);
+    // `rows` rows from row `r0` through a transposed copy `at` (Kin, rows) and the fp32 GEMM, as nb slabs of kp rows
+    auto slabs_copy = [&](int r0, int rows, float* at, float* out, int kp, int nb, int64_t strideC) -> int {
+        if (int e = launch_transpose(A + (int64_t)r0 * Kin, at, rows, Kin, 1, s)) return e;
+        return launch_gemm_ex(prof, at, rows, nb == 1 ? 0 : kp, dY + (int64_t)r0 * Nout, Nout, nb == 1 ? 0 : (int64_t)kp * Nout, out, Nout,
+                              strideC, nullptr, nullptr, Kin, Nout, kp, nb, 0, s);
     };
-    // The whole weight gradient on the transposing-read kernel (both bf16 shadows; no fp32 operand is touched): S slabs of Kp rows as
-    // `x` describes them, their fold, the bias column sum -- for the uneven-slab and the ragged branch below
-    auto tr_slabs = [&](int S, int Kp, const GemmShadows& x) -> int {
-        W2V2_REQUIRE(S == 1 || (int64_t)(S + 1) * Kin * Nout <= slab_cap, "weight_grad: slab scratch too small");
-        if (int e = launch_gemm_bf16_x(m->prof, nullptr, Kin, (int64_t)Kp * Kin, nullptr, Nout, (int64_t)Kp * Nout, (S == 1 && !unpack) ? dW : slabs, Nout,
-                                       (int64_t)Kin * Nout, nullptr, nullptr, Kin, Nout, Kp, S, 0, x, s))
-            return e;
-        if (S > 1 || unpack)
-            if (int e = fold_slabs(S)) return e;
-        return bias_colsum();
-    };
-    if (dW) {
-        // dW (Kin, Nout) = A^T dY over the M = B T rows: few output tiles and a very long K, so the rows are cut into S slabs
-        // (one GEMM batch each) that a column sum folds.  precision mode 1 stages A^T from X directly (the bf16 GEMM's B path
-        // transposes in registers anyway); fp32 goes through a transposed copy.
-        const bool direct = gemm_get_precision() == 1 && Kin % 4 == 0 && Nout % 4 == 0;
-        const int kq = direct ? 64 : 32;        // K granularity of the fast kernel that will run
-        // The fast kernels need every slab to be a multiple of kq rows.  M need not be (T = 1499 at 480000 samples gives
-        // B T = 23984): the first Mq = kq floor(M / kq) rows go through the fast path in S equal slabs, S a divisor of
-        // Mq / kq, and the R = M - Mq < kq leftover rows form one more slab on the guarded kernel (0.2 % of the work).
-        // (Before this, such an M fell back to ONE guarded GEMM over all rows: 256 tiles, K = 23984.)
-        // (tiles as the kernel that will run counts them: with both bf16 shadows, whole rows and Nout % 256 == 0 the weight gradient
-        //  takes the 128 x 256 software-pipelined kernel, which has half as many tiles to spread over the 512 block slots)
-        const bool wide_tiles = direct && A16 && dY16 && Kin % 128 == 0 && Nout % 256 == 0 && (M % kq == 0 || (dy16_zero_row && M > kq));
-        const int64_t tiles = (int64_t)((Kin + 127) / 128) * (wide_tiles ? Nout / 256 : (Nout + 127) / 128);
-        // slabs cost a reduction pass each: the bf16 kernels are happiest with ONE block per resident slot (512),
-        // the fp32 one wants ~4 to balance its long tiles (183.8 vs 189.4 ms)
-        const int dwb = tune_int("W2V2_DW_BLOCKS", 512);      // 512 -> 40.0 ms per step, 1024 -> 40.5, 256 -> 47.0 (base, 32 x 246000)
-        const int64_t max_blocks = direct ? dwb : 2048;
-        int cap = 32;                                                   // most slabs worth having / that fit the scratch
-        while (cap > 1 && (tiles * cap > max_blocks || (int64_t)(cap + 2) * Kin * Nout > t->slab_floats)) --cap;
-        // (a site's own scratch is sized for the most slabs the line above can give its shape -- site_slab_count; should that bound ever
-        //  be wrong the count shrinks to what fits instead of writing past the end: correct, though no longer the shared scratch's count)
-        while (cap > 1 && site && site->slabs && (int64_t)(cap + 1) * Kin * Nout > site->slab_floats) --cap;
-        // S must divide the number of kq-row units; if M / kq has no useful divisor (a prime, say), give up to 15 more
-        // units to the leftover slab until one appears
-        // both bf16 shadows and whole 128 x 128 tiles: the LDS-DMA + transposing-read kernel; it has no fp32 dY in registers,
-        // so the bias gradient (a sum of the UNROUNDED dY) takes the column-sum pass below instead of riding along.  In this form
-        // the fp32 A / dY are not read at all (callers may pass null when nothing else needs them).
-        const bool tr_form = direct && A16 && dY16 && Kin % 128 == 0 && Nout % 128 == 0;
-        W2V2_REQUIRE(tr_form || (A && dY), "weight_grad: the fp32 operands are needed here (no bf16 shadows / shapes not whole 128-tiles)");
-        // The 128 x 256 transposed kernel: ANY slab count works there (GemmShadows::kextra: the first ceil(M / 64) mod S slabs run one
-        // K tile more; a short last K tile reads its missing rows from the zero row behind dY16), so take as many slabs as fit the block slots -- 7 x 72 tiles = 504 blocks for the FFN matrices where
-        // the divisor rule below stops at 6 x 72 = 432 (a sixth of the chip idle while the longest CUs run two 64-K-tile blocks).
-        if (wide_tiles && tr_form && tune_int("W2V2_DW_UNEVEN", 1) != 0) {
-            const int64_t units_all = (M + kq - 1) / kq;                   // (the last unit may be short: GemmShadows::b_zero_row)
-            const int S = (int)std::min<int64_t>(cap, units_all / 3);      // (a slab is at least three K tiles: the kernel's pipeline depth)
-            if (S >= 1) {
-                const int64_t q = units_all / S;
-                GemmShadows x;
-                x.transA = true; x.A16 = A16; x.B16p = dY16; x.kextra = (int)(units_all % S);
-                if (M % kq != 0) { x.validK = M; x.b_zero_row = true; }
-                return tr_slabs(S, (int)(q * kq), x);
-            }
-        }
-        // That kernel reads rows past M as zero (GemmShadows::validK), so any M splits into S slabs of ceil(M / 64 / S) K tiles with
-        // no leftover pass: the last slab is merely short.
-        const bool ragged = !tune_int("W2V2_NO_RAGGED_DW", 0);      // (tuning build: 1 = leftover rows on the tail kernel instead)
-        if (tr_form && ragged && M % kq != 0) {
-            const int64_t units_all = (M + kq - 1) / kq;
-            int S = (int)(units_all < cap ? units_all : cap);
-            int64_t per = (units_all + S - 1) / S;
-            while (S > 1 && (int64_t)(S - 1) * per >= units_all) { --S; per = (units_all + S - 1) / S; }     // (no empty slab)
-            GemmShadows x;
-            x.transA = true; x.A16 = A16; x.B16p = dY16; x.validK = M;
-            return tr_slabs(S, (int)(per * kq), x);
-        }
-        const int64_t units0 = M / kq;
-        int64_t units = units0;
-        int S = units0 > 0 ? 1 : 0;
-        for (int drop = 0; drop < 16 && units0 - drop > 0; ++drop) {
-            const int64_t u = units0 - drop;
-            int d = 1;
-            for (int cand = cap; cand >= 2; --cand)
-                if (u % cand == 0) { d = cand; break; }
-            if (d > S) { S = d; units = u; }
-            if (2 * d >= cap) break;                                    // good enough: stop giving rows away
-        }
-        const int Mq = (int)(units * kq), R = M - Mq;
-        const int nslabs = S + (R ? 1 : 0);
-        W2V2_REQUIRE(nslabs == 1 || (int64_t)(nslabs + 1) * Kin * Nout <= slab_cap, "weight_grad: slab scratch too small");
-        float* dst = (nslabs == 1 && !unpack) ? dW : slabs;
-        const int Kp = S ? Mq / S : 0;
-        if (S) {
-            if (direct) {
-                GemmShadows x;
-                x.transA = true;
-                if (tr_form) { x.A16 = A16; x.B16p = dY16; }
-                // otherwise the bias gradient rides along: the kernel's row-tile-0 blocks sum the dY columns they stage anyway
-                fused_bias = !tr_form && db != nullptr && (int64_t)(nslabs + 1) * Nout <= t->cs_floats;
-                if (fused_bias) { x.colsum = t->cs_ws; x.strideCS = Nout; }
-                if (int e = launch_gemm_bf16_x(m->prof, A, Kin, (int64_t)Kp * Kin, dY, Nout, (int64_t)Kp * Nout, dst, Nout,
-                                               (int64_t)Kin * Nout, nullptr, nullptr, Kin, Nout, Kp, S, 0, x, s))
-                    return e;
-            } else {
-                if (int e = launch_transpose(A, t->at, Mq, Kin, 1, s)) return e;          // at = (Kin, Mq)
-                if (int e = launch_gemm_ex(m->prof, t->at, Mq, S == 1 ? 0 : Kp, dY, Nout, S == 1 ? 0 : (int64_t)Kp * Nout, dst, Nout,
-                                           (int64_t)Kin * Nout, nullptr, nullptr, Kin, Nout, Kp, S, 0, s))
-                    return e;
-            }
-        }
-        if (R && tr_form) {                      // leftover rows [Mq, M) from the same shadows
-            if (int e = launch_dw_tail_bf16(A16 + (int64_t)Mq * Kin, Kin, dY16 + (int64_t)Mq * Nout, Nout, dst + (int64_t)S * Kin * Nout, R, Kin,
-                                            Nout, s))
-                return e;
-        } else if (R) {                          // leftover rows [Mq, M): transposed copy (Kin, R), guarded kernel, slab S
-            float* atr = t->at + (int64_t)Kin * Mq;
-            if (int e = launch_transpose(A + (int64_t)Mq * Kin, atr, R, Kin, 1, s)) return e;
-            if (int e = launch_gemm_ex(m->prof, atr, R, 0, dY + (int64_t)Mq * Nout, Nout, 0, dst + (int64_t)S * Kin * Nout, Nout, 0,
-                                       nullptr, nullptr, Kin, Nout, R, 1, 0, s))
-                return e;
-        }
-        // sum the slabs (rows = nslabs, cols = Kin * Nout); the one-chunk partial scratch lives behind the slabs
-        if (nslabs > 1 || unpack)
-            if (int e = fold_slabs(nslabs)) return e;
-        if (fused_bias) {
-            // per-slab column sums of dY are in cs_ws (S, Nout); the leftover rows add one more row, then one small fold
+    GemmShadows x;
+    x.transA = true;
+    switch (p.form) {
+        case WG_BIAS_ONLY: break;
+        case WG_UNEVEN_128x256:
+        case WG_RAGGED_128x128:
+        case WG_DIV_SHADOWS:        // (no fp32 operand is read: callers may pass null)
+            x.A16 = A16; x.B16p = dY16; x.kextra = p.kextra; x.validK = p.validK; x.b_zero_row = p.b_zero_row;
+            if (S)
+                if (int e = slabs_bf16(x)) return e;
             if (R)
-                if (int e = launch_colsum(dY + (int64_t)Mq * Nout, t->cs_ws + (int64_t)S * Nout, R, Nout, red_ws, 0, s)) return e;
-            if (int e = launch_colsum(t->cs_ws, db, nslabs, Nout, red_ws, 0, s)) return e;
+                if (int e = launch_dw_tail_bf16(A16 + (int64_t)Mq * Kin, Kin, dY16 + (int64_t)Mq * Nout, Nout, tail_dst, R, Kin, Nout, s)) return e;
+            break;
+        case WG_DIV_F32_REG:
+            if (p.bias == WG_BIAS_FUSED) { x.colsum = w.cs_ws; x.strideCS = Nout; }
+            if (S)
+                if (int e = slabs_bf16(x)) return e;
+            if (R)
+                if (int e = slabs_copy(Mq, R, w.at + (int64_t)Kin * Mq, tail_dst, R, 1, 0)) return e;
+            break;
+        case WG_DIV_F32_COPY:
+            if (S)
+                if (int e = slabs_copy(0, Mq, w.at, dst, Kp, S, elems)) return e;
+            if (R)
+                if (int e = slabs_copy(Mq, R, w.at + (int64_t)Kin * Mq, tail_dst, R, 1, 0)) return e;
+            break;
+        default: W2V2_REQUIRE(false, "weight_grad: unknown form %d", p.form);
+    }
+    // dW = sum of the slabs: as a job of the layer's fold launch, or behind the GEMM (the unpacking fold: still one launch for the sum and
+    // the scatter into the three kernels; the plain one: its one-chunk partial scratch lives behind the slabs, which the plan checked)
+    if (p.fold) {
+        FoldBatch* const defer = (site && site->slabs) ? site->defer : nullptr;
+        auto add = [&](FoldBatch& b) {
+            return q.unpack ? b.add_tall(w.slabs, p.nslabs, elems, site->unpack3[0], site->unpackH, site->unpack3[1], site->unpack3[2])
+                            : b.add_tall(w.slabs, p.nslabs, elems, dW);
+        };
+        if (defer && add(*defer)) {
+        } else if (q.unpack) {
+            FoldBatch one;
+            W2V2_REQUIRE(add(one), "weight_grad: the unpacking fold does not fit this shape");
+            if (int e = one.flush(s)) return e;
+        } else if (int e = launch_colsum(w.slabs, dW, p.nslabs, (int)elems, w.slabs + (int64_t)p.nslabs * elems, 0, s)) {
+            return e;
         }
     }
-    return fused_bias ? W2V2_OK : bias_colsum();
+    if (p.bias == WG_BIAS_FUSED) {      // per-slab column sums of dY are in cs_ws (S, Nout); the leftover rows add one more row, then one small fold
+        if (R)
+            if (int e = launch_colsum(dY + (int64_t)Mq * Nout, w.cs_ws + (int64_t)S * Nout, R, Nout, w.red_ws, 0, s)) return e;
+        return launch_colsum(w.cs_ws, db, p.nslabs, Nout, w.red_ws, 0, s);
+    }
+    if (p.bias == WG_BIAS_PASS) return launch_colsum(dY, db, M, Nout, w.red_ws, 0, s);
+    return W2V2_OK;
+}
+}  // namespace w2v2
+
+// The training step's weight gradients: the problem and the scratch from the model.  dy16_zero_row: the caller keeps row M of dY16
+// all-zero (TrainState's dY shadows are allocated that way).  red_ws: the side stream passes its own (TrainState::red_ws_side).
+static int weight_grad(w2v2_model* m, const float* A, const float* dY, int M, int Kin, int Nout, float* dW, float* db, hipStream_t s,
+                       const uint16_t* A16 = nullptr, const uint16_t* dY16 = nullptr, bool dy16_zero_row = false, float* red_ws = nullptr,
+                       const WgSite* site = nullptr) {
+    TrainState* t = m->train;
+    const bool own = site && site->slabs;
+    int dw_blocks, dw_uneven;
+    weight_grad_knobs(&dw_blocks, &dw_uneven);
+    const WgProblem q{M, Kin, Nout, gemm_get_precision(), A != nullptr, dY != nullptr, A16 != nullptr, dY16 != nullptr, dy16_zero_row, dW != nullptr,
+                      db != nullptr, site && site->unpackH > 0, t->slab_floats, own ? site->slab_floats : 0, t->cs_floats, dw_blocks, dw_uneven};
+    const WgScratch w{own ? site->slabs : t->slabs, t->at, t->cs_ws, red_ws ? red_ws : t->red_ws};
+    return launch_weight_grad(m->prof, q, weight_grad_plan(q), A, dY, A16, dY16, dW, db, w, site, s);
 }
 
 extern "C" {

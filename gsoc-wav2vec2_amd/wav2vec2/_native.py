@@ -204,6 +204,8 @@ PROTOTYPES = {
     "w2v2_op_gemm_bf16_launches": (C.c_int, [C.POINTER(_I64)]),
     "w2v2_op_attention_route": (C.c_int, [C.POINTER(_I32), C.POINTER(_I32)]),
     "w2v2_op_attention_launches": (C.c_int, [C.POINTER(_I64)]),
+    "w2v2_op_weight_grad_plan": (C.c_int, [C.POINTER(_I64), C.POINTER(_I64)]),
+    "w2v2_op_weight_grad": (C.c_int, [C.POINTER(_I64), _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _I64, _P]),
     "w2v2_op_split_planes": (C.c_int, [_P, _P, _I64, _I64, _I32, _P, _P]),
     "w2v2_op_split_weight": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P]),
     "w2v2_op_gemm_split_planes": (C.c_int, [_I32, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),

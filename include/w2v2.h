@@ -966,6 +966,29 @@ int w2v2_op_attention_route(const int32_t* problem, int32_t* out);
 /* Launches by this process so far per kernel of that list (host memory): counts[25], counts[k] for kernel k, counts[0] unused.  One
  * count per call of a pass (the backward's three kernels count once).  Diagnostic only, as w2v2_op_gemm_bf16_launches. */
 int w2v2_op_attention_launches(int64_t* counts);
+/* How the training step would compute a weight gradient dW (Kin, Nout) = A^T dY over M rows and the bias gradient db (csrc/
+ * weight_grad_plan.h).  Host only: touches no device and launches nothing.  problem[17], in order: M, Kin, Nout, precision
+ * (W2V2_PRECISION_*), the operands present (0 / 1) fp32 A, fp32 dY, A16, dY16, row M of dY16 is all-zero, dW wanted, db wanted, the fold
+ * unpacks q|k|v, floats of the shared slab scratch, of the site's own (0 = none), of the column-sum scratch, then W2V2_DW_BLOCKS and
+ * W2V2_DW_UNEVEN (512 and 1 outside the tools-only build).
+ *   out[0] != 0: refused (1 the fp32 operands are needed, 2 slab scratch too small, 3 the bias gradient needs the fp32 dY);
+ *   out[1] form: 0 bias only, 1 uneven slabs on the 128 x 256 transposed kernel, 2 ragged rows on the 128 x 128 transposing-read kernel,
+ *          3 divisor rule from both shadows, 4 divisor rule from fp32 operands transposed in registers, 5 divisor rule through a
+ *          transposed copy on the fp32 GEMM;
+ *   out[2] kernel of the slab GEMM, as w2v2_op_gemm_bf16_route numbers them (0: the fp32 GEMM, or no slab GEMM);
+ *   out[3] K granularity; out[4] most slabs allowed; out[5] S slabs of out[6] rows; out[7] kextra, out[8] validK, out[9] b_zero_row
+ *          (GemmShadows); out[10] rows on the slab kernel, out[11] leftover rows; out[12] their kernel (0 none, 1 the shadow tail,
+ *          2 transposed copy); out[13] slabs in all; out[14] the GEMMs write 1 dW, 2 slabs; out[15] a fold runs;
+ *   out[16] db: 0 none, 1 column sums fused into the GEMM, 2 a column-sum pass; out[17] slabs a site's scratch is sized for. */
+int w2v2_op_weight_grad_plan(const int64_t* problem, int64_t* out);
+/* Plans and runs that weight gradient on the caller's operands and scratch: dW (Kin, Nout) and db (Nout), either may be NULL.  The
+ * problem's operand flags must agree with the pointers, its precision with w2v2_op_set_precision, and it must not ask for the
+ * unpacking fold.  slabs: the scratch the problem sized (the site's when that is non-zero); at: at_floats >= Kin M floats where the
+ * plan takes a transposed copy; cs_ws: the problem's column-sum scratch; red_ws: red_ws_floats >= ceil(M / 128) Nout + 8 floats cover
+ * every column-sum pass.  With dy16_zero_row set, dy16 has M + 1 rows and row M holds zeros. */
+int w2v2_op_weight_grad(const int64_t* problem, const float* A_dev, const float* dY_dev, const uint16_t* A16_dev, const uint16_t* dY16_dev,
+                        float* dW_dev, float* db_dev, float* slabs_dev, float* at_dev, int64_t at_floats, float* cs_ws_dev, float* red_ws_dev,
+                        int64_t red_ws_floats, void* stream);
 
 /* The weight-gradient form of the same GEMM: C_z (M, N) = A_z^T B_z with A given TRANSPOSED, (K, M) fp32 row-major with
  * row stride lda (>= M), and per-batch strides on A, B and C (split-K: batch z covers rows [z K, (z+1) K) of both

@@ -10,6 +10,7 @@ import pytest
 import helpers as H
 from oracle import w2v2_oracle as O
 from oracle import w2v2_torch_train as TT
+from test_weight_grad_plan_cpu import plan as weight_grad_plan, problem as weight_grad_problem
 from wav2vec2 import _native as N
 from wav2vec2 import variables as V
 from wav2vec2.spec_augment import compute_mask_indices
@@ -764,9 +765,8 @@ def test_weight_gradient_slabs_with_awkward_row_counts(env, precision):
     _, torch, dev = env
     L2, Hh, F = 400 + 320 * 2052, cfg.hidden_size, cfg.intermediate_size
     assert cfg.num_frames(L2) == 2053
-    kq, blocks = (32, 2048) if precision == "fp32" else (64, 512)
-    for Kin, Nout in ((F, Hh), (Hh, F), (Hh, Hh)):
-        assert _weight_grad_slabs(2053, Kin, Nout, kq, blocks, 33 * max(F * Hh, 3 * Hh * Hh)) == 33
+    for Kin, Nout in ((F, Hh), (Hh, F), (Hh, Hh)):      # (64 x 128: no whole 128-tiles, so mode bf16 takes the fp32 operands too)
+        assert weight_grad_plan(weight_grad_problem(2053, Kin, Nout, int(precision != "fp32"), A=1, dY=1, shared=33 * max(F * Hh, 3 * Hh * Hh)))["nslabs"] == 33
     x2 = V.hash_normal("train/wave_2053", L2, 8).reshape(1, L2)
     res = []
     for flag in (False, True):
@@ -777,27 +777,6 @@ def test_weight_gradient_slabs_with_awkward_row_counts(env, precision):
         torch.cuda.synchronize()
     assert float(res[0].abs().max()) > 0 and bool(torch.isfinite(res[0]).all())
     assert torch.equal(res[0], res[1]), int((res[0] != res[1]).sum())
-
-
-def _weight_grad_slabs(M, Kin, Nout, kq, max_blocks, shared_slab_floats):
-    """Host mirror of weight_grad's slab rule (csrc/w2v2_train.hip) where the bf16 transposing-read form does not apply (fp32, or dims
-    that are not whole 128-tiles): S equal slabs of whole kq-row units, S a divisor of the unit count, plus one slab of leftover rows."""
-    tiles = -(-Kin // 128) * -(-Nout // 128)
-    cap = 32
-    while cap > 1 and (tiles * cap > max_blocks or (cap + 2) * Kin * Nout > shared_slab_floats):
-        cap -= 1
-    units0 = M // kq
-    S, units = (1 if units0 else 0), units0
-    for drop in range(16):
-        u = units0 - drop
-        if u <= 0:
-            break
-        d = next((cand for cand in range(cap, 1, -1) if u % cand == 0), 1)
-        if d > S:
-            S, units = d, u
-        if 2 * d >= cap:
-            break
-    return S + (1 if M - units * kq else 0)
 
 
 def test_bf16x3_training_matches_fp32_path(env):

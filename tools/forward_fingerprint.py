@@ -11,7 +11,8 @@ Runs a fixed matrix and prints one JSON object per entry:
   packed      predict_packed of three utterances of unequal length (cuts of the fixture's first row) in fp32 / bf16x3 / f16x2,
               same options
   train       one training forward + backward in fp32 / bf16 / bf16x3 with dropout 0 and 0.1, fixed seed, spec-augment off
-  train_plan  tiny_base, tiny_robust and base dims at 3 x 24080 samples (B T = 225, ragged): spec-augment on, a dropped layer,
+  train_plan  tiny_base, tiny_robust and base dims at 3 x 24080 and 9 x 24080 samples (B T = 225: one weight-gradient slab; 675:
+              three uneven slabs; both ragged): spec-augment on, a dropped layer,
               bf16_shadows off, defer_folds off / on, wgrad_stream on, only lm_head / only layer 0 trainable; each entry also holds
               Trainer.activation_storage() (`storage`, `storage_bytes`)
 
@@ -94,17 +95,18 @@ def train_plan_cases(cfg):
 
 def train_plan(emit):
     """Training forward + backward of tiny_base, tiny_robust (postnorm + group norm, prenorm + layer norm + mask) and base dims at a
-    ragged row count (3 x 24080 samples: B T = 225, H % 128 == 0) over train_plan_cases; each entry also records activation_storage()."""
+    ragged row count (3 and 9 x 24080 samples: B T = 225 and 675, H % 128 == 0) over train_plan_cases; each entry also records
+    activation_storage()."""
     import helpers as H
     import torch
     import wav2vec2
     from wav2vec2 import variables as V
     from wav2vec2.spec_augment import compute_mask_indices
     from wav2vec2.training import Trainer
-    for name in ("tiny_base", "tiny_robust", "base_sample_padded"):
-        if name == "base_sample_padded":
+    for name, batch in (("tiny_base", 0), ("tiny_robust", 0), ("base_sample_padded", 3), ("base_sample_padded", 9)):
+        if batch:
             cfg, mask = H.case_config(name), None
-            wave = V.hash_normal("fingerprint/train_plan", 3 * 24080, 8).reshape(3, 24080)
+            wave = V.hash_normal("fingerprint/train_plan", batch * 24080, 8).reshape(batch, 24080)
             m = wav2vec2.Wav2Vec2ForCTC(cfg, input_shape=wave.shape)
             m.set_weights(H.case_weights(name))
         else:
@@ -130,7 +132,7 @@ def train_plan(emit):
                 tr.backward(torch.sin(logits))
                 names, nbytes = tr.activation_storage()
                 tag = dict(opts, **{k: (v if isinstance(v, (str, bool)) else [float(x) for x in v]) for k, v in kw.items()})
-                emit(dict(fixture=name, form="train_plan", precision=precision, **tag), m, [], out=sha(logits), grads=sha(tr.grad_buffer()),
+                emit(dict(fixture=name, form="train_plan", precision=precision, batch=wave.shape[0], **tag), m, [], out=sha(logits), grads=sha(tr.grad_buffer()),
                      storage=sorted(names), storage_bytes=nbytes)
                 for k, v in defaults.items():
                     m.set_option(k, v)
